@@ -1,6 +1,8 @@
 """SVGPVAE_Hensman train steps/sec on MI355X (BASELINE.json metric) and the roofline-relevant side workloads.
 
     python bench.py --gpus 1 --steps 200 --warmup 20                      # BASELINE configs[1] (the metric)
+    python bench.py --gpus 1 --steps 200 --warmup 20 --full               # + parity gate, roofline, stages, CPU baseline
+    python bench.py --gpus 1 --steps 200 --warmup 20 --dump-outputs DIR   # + the last timed step's outputs as DIR/*.npy
     python bench.py --workload cfg3|sprites800|cfg5                       # BASELINE configs[2] / [3] / [4]
     python bench.py --gpus N --steps K --warmup W                         # N > 1: spawns the launcher below as a child
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
@@ -12,14 +14,25 @@ m=32 inducing points, L=16, GPLVM dim 8, N_train=4050, float64 like the referenc
 256 rows, the global batch is 256*N rows coupled through the sufficient-statistics all-reduces; `value` =
 N * steps / time = 256-row batches trained per second.  With N > 1 a `"scaling": "strong"` line (the 256-row global batch of
 the headline configuration split over the ranks; value = steps / time) is printed BEFORE the weak line, which stays last.
-Inputs are synthetic, generated once and resident in HBM before the timed region.
+Inputs are synthetic, generated once and resident in HBM before the timed region.  On them the GECO constraint is never met
+and the training state overflows after ~4 000 steps, so cfg2 / cfg3 restore the initial parameters, Adam moments and state
+every RESTART_EVERY = 2000 steps (four small device copies; see mnist_case).
 
-Timing: after W warm-up steps, R (`--repeats`, default 5) blocks of EXACTLY K steps, each bracketed by barrier +
-synchronize on both sides and reduced with MAX over ranks; the reported ms_per_step / value come from the MEDIAN block
-(a 20-step block is a 4 ms sample; one scheduling hiccup would move a single block by 10 %).
+Timing: after W warm-up steps, R (`--repeats`, default 1; 5 with --full) blocks of EXACTLY K steps, each bracketed by
+barrier + synchronize on both sides and reduced with MAX over ranks; the reported ms_per_step / value come from the MEDIAN
+block (a 20-step block is a 4 ms sample; one scheduling hiccup would move a single block by 10 %).
 
-Every workload prints ONE JSON line with `roofline` (dominant stage, HIP events on the launch stream, algorithmic
-work model of SURVEY 8d / DESIGN section 5) and `cpu_baseline` (the oracle timed on this host's cores; N=1 only).
+A plain run sets up, warms up, times ONE block of exactly K steps (`--repeats` defaults to 1) and prints ONE JSON line
+(`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` = milliseconds per timed step, ...).  Everything else
+moves behind `--full` (default --repeats 5): the ELBO parity gate against the oracle, `roofline` (dominant stage, HIP events
+on the launch stream, algorithmic work model of SURVEY 8d / DESIGN section 5), per-stage and per-exchange-point timings,
+`cpu_baseline` (the oracle timed on this host's cores; N=1 only) and, with several ranks, the strong-scaling line.
+
+`--dump-outputs DIR` writes what the timed path computed in its last timed step -- cfg2 / cfg3 / sprites800: the updated
+parameters (`param_<name>.npy`), their gradients (`grad_<name>.npy`) and the step's scalars (`scalar_<name>.npy`); cfg5: the
+statistics S_l, v_l and K_nm -- float64 (float32 where the result is float32), at most 64 MB in all: an array of more than
+2^20 elements is written as `<name>_sample.npy`, the elements at fixed positions drawn with np.random.RandomState(0).
+All inputs are seeded, so the same arguments give the same inputs in every run.
 """
 import argparse
 import ctypes as C
@@ -42,6 +55,7 @@ F64_PEAK_TFLOPS = 78.6     # MI355X FP64 vector = matrix peak (AMD datasheet; = 
                            # listed in MI355X_MICROARCH.md, which has no f64 row)
 F32_PEAK_TFLOPS = 157.3    # MI355X_MICROARCH.md: f32-input MFMA = f32 vector peak
 HBM_PEAK_GBS = 8000.0
+RESTART_EVERY = 2000       # cfg2 / cfg3: steps between two restores of the initial training state (mnist_case)
 
 
 # =====================================================================================================================
@@ -169,6 +183,36 @@ def emit(line):
     C.CDLL(None).fflush(None)
     sys.stdout.flush()
     print(json.dumps(line), flush=True)
+
+
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SAMPLE = 1 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: one `<name>.npy` per (name, tensor) in float64 (float32 for float32 results); more than DUMP_SAMPLE
+    elements -> `<name>_sample.npy`, the flattened tensor at DUMP_SAMPLE sorted positions drawn from RandomState(0)."""
+    os.makedirs(out_dir, exist_ok=True)
+    files, total = [], 0
+    for name, t in arrays:
+        t = torch.as_tensor(t).detach()
+        dt = np.float32 if t.dtype == torch.float32 else np.float64
+        if t.numel() > DUMP_SAMPLE:
+            idx = np.sort(np.random.RandomState(0).randint(0, t.numel(), DUMP_SAMPLE))
+            t, name = t.reshape(-1)[torch.from_numpy(idx).to(t.device)], name + "_sample"
+        a = t.cpu().numpy().astype(dt)
+        total += a.nbytes
+        files.append((name, a))
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES}-byte budget")
+    for name, a in files:
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+def step_arrays(params, grads, scalars):
+    """The arrays a caller of a training step receives: updated parameters, their gradients, the step's scalars."""
+    return ([("param_" + k, v) for k, v in params.items()] + [("grad_" + k, v) for k, v in grads.items()]
+            + [("scalar_" + k, torch.tensor(v, dtype=torch.float64)) for k, v in scalars.items()])
 
 
 # =====================================================================================================================
@@ -396,7 +440,7 @@ def run_mnist(args):
         if ctx["comm"] is None:      # both legs are RCCL; this only changes who enqueues the collective
             print(f"[bench] rank {rank}: in-library RCCL communicator unavailable ({ctx['why']}); "
                   f"using torch.distributed all_reduce between per-phase graphs", file=sys.stderr, flush=True)
-    modes = [args.scaling] if args.scaling else (["strong", "weak"] if multi else ["weak"])
+    modes = [args.scaling] if args.scaling else (["strong", "weak"] if multi and args.full else ["weak"])
     strong = None
     for mode in modes:
         # Without an explicit --scaling the strong case is BEST EFFORT: it must never cost the run its headline (weak)
@@ -466,16 +510,18 @@ def mnist_case(args, scaling, multi, dev, ctx, strict=True):
         comm_ranks = ctx["comm"].world_size
         launch = "one in-order stream: phases + in-library RCCL all-reduce x3"
 
-    # ---- parity gate: ONE explicit-eps step (no optimiser update) through the same exchange path the timed region
+    # ---- parity gate (--full): ONE explicit-eps step (no optimiser update) through the same exchange path the timed region
     # uses; its ELBO is checked against the oracle's efficient formulation on the GLOBAL batch (all ranks' rows are
     # regenerated on rank 0 from their seeds).  north_star: "1/2/4/8-GPU ELBO equal at the same global batch".
-    eng.bind(d_img, d_aux, d_eps)
-    eng.run(adam=False)
-    eng.synchronize()
-    gpu_elbo = eng.scalars()["elbo"]
-    eng.reset_state()
-    elbo_rel = None
-    if rank == 0 and not args.no_parity_gate:
+    # reset_state() afterwards: the timed region starts from the same state with or without it.
+    gpu_elbo, elbo_rel = None, None
+    if args.full:
+        eng.bind(d_img, d_aux, d_eps)
+        eng.run(adam=False)
+        eng.synchronize()
+        gpu_elbo = eng.scalars()["elbo"]
+        eng.reset_state()
+    if rank == 0 and args.full and not args.no_parity_gate:
         want = oracle_elbo(params, *global_rows())
         elbo_rel = abs(gpu_elbo - want) / abs(want)
         assert elbo_rel < 1e-3, f"ELBO parity failed at {world} rank(s): GPU {gpu_elbo} oracle {want}"
@@ -488,6 +534,26 @@ def mnist_case(args, scaling, multi, dev, ctx, strict=True):
     if multi:
         dist.barrier()
 
+    # ---- restarts: on the synthetic batch the GECO constraint (reconstruction error <= kappa^2) is never met, so the Lagrange
+    # multiplier grows by ~e^0.09 per step, and the squared gradients (~1e-3 x the multiplier) overflow Adam's second moment after
+    # ~4 000 steps.  Every RESTART_EVERY steps (counted from here: probe, warm-up and timed steps alike) the step first restores the
+    # initial parameters, Adam moments and state on the engine's stream -- four small copies -- so that any --steps times finite
+    # steps.  A run of at most RESTART_EVERY steps in all is not touched.
+    eng.synchronize()
+    init = [t.clone() for t in (eng.theta, eng.adam_m, eng.adam_v, eng.state)]
+    eng.stream.wait_stream(torch.cuda.current_stream(dev))
+    done = [0]
+
+    def restarting(fn):
+        def one():
+            if done[0] and done[0] % RESTART_EVERY == 0:
+                with torch.cuda.stream(eng.stream):
+                    for dst, src in zip((eng.theta, eng.adam_m, eng.adam_v, eng.state), init):
+                        dst.copy_(src)
+            fn()
+            done[0] += 1
+        return one
+
     # ---- timed region: eps drawn on device every step (tf.random.normal, SVGPVAE_model.py:901)
     eng.bind(d_img, d_aux, None)
     if use_graph:
@@ -495,35 +561,41 @@ def mnist_case(args, scaling, multi, dev, ctx, strict=True):
         # this box in an untimed probe (config 2: 14 launches per step keep the host far ahead and eager wins by ~2.5 %;
         # config 3: the replayed graph overlaps the two branches of its step slightly better and wins by ~3 %)
         eng.capture("step", adam=True)
-        cand = {"hipGraph replay": (lambda: eng.replay("step")), "eager phases": (lambda: eng.run(adam=True))}
+        cand = {"hipGraph replay": restarting(lambda: eng.replay("step")), "eager phases": restarting(lambda: eng.run(adam=True))}
         probe = {}
-        for name, fn in cand.items():
-            probe[name] = min(timed_blocks(fn, eng.synchronize, max(20, args.steps // 4), 5, 3, False, dev))
+        for name, fn in cand.items():      # bounded: the probe is part of every run's set-up time
+            probe[name] = min(timed_blocks(fn, eng.synchronize, min(max(20, args.steps // 4), 250), 5, 3, False, dev))
         launch = min(probe, key=probe.get)
         step = cand[launch]
         launch += " (faster of hipGraph replay / eager phases in an untimed probe)"
     elif launch is not None:
-        step = lambda: eng.run(adam=True)
+        step = restarting(lambda: eng.run(adam=True))
     elif not args.no_graph and multi:
         # one hipGraph per phase, torch.distributed (RCCL) all-reduces (not captured) in between
         eng.capture_phases("step", adam=True)
-        step = lambda: eng.run_phase_graphs("step")
+        step = restarting(lambda: eng.run_phase_graphs("step"))
         launch = "per-phase hipGraphs + torch.distributed RCCL all-reduce x3"
         comm_ranks = dist.get_world_size()
     else:
-        step = lambda: eng.run(adam=True)
+        step = restarting(lambda: eng.run(adam=True))
         launch = "eager phases" + (" + torch.distributed RCCL all-reduce x3" if multi else "")
     blocks = timed_blocks(step, eng.synchronize, args.steps, args.warmup, args.repeats, multi, dev)
     el = float(np.median(blocks))
     sc = eng.scalars()
-    assert math.isfinite(sc["elbo"]) and sc["adam_t"] >= args.steps * args.repeats, sc
+    assert math.isfinite(sc["elbo"]) and done[0] >= args.steps * args.repeats and sc["adam_t"] == (done[0] - 1) % RESTART_EVERY + 1, sc
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step_arrays(eng.params, eng.grads(), sc))
+    if rank == 0 and not args.full:
+        return mnist_line(args, cfg3, scaling, world, B, blocks, el, launch, comm_ranks, eng, elbo_rel)
+    if not args.full:
+        return None
     # per-exchange-point microseconds (HIP events around pack + grouped collective + unpack, svgp_comm_timing): a few extra
     # steps after the timed region, the maximum over ranks of the per-point medians
     def collectives():
         eng.comm.timing(True)
         samples = []
         for _ in range(10):
-            eng.run(adam=True)
+            restarting(lambda: eng.run(adam=True))()
             eng.synchronize()
             samples.append(eng.comm.timing_read())
         eng.comm.timing(False)
@@ -544,7 +616,7 @@ def mnist_case(args, scaling, multi, dev, ctx, strict=True):
             flag = bool(eng.base["split_grad_exchange"])
             eng.set_split_grad_exchange(not flag)
             eng.bind(d_img, d_aux, None)
-            ob = timed_blocks(lambda: eng.run(adam=True), eng.synchronize, max(20, args.steps // 3), 5, 3, multi, dev)
+            ob = timed_blocks(restarting(lambda: eng.run(adam=True)), eng.synchronize, max(20, args.steps // 3), 5, 3, multi, dev)
             other = {"split_grad_exchange": not flag, "ms_per_step": float(np.median(ob)) / max(20, args.steps // 3) * 1e3,
                      "collectives_us": collectives()}
             eng.set_split_grad_exchange(flag)
@@ -557,27 +629,7 @@ def mnist_case(args, scaling, multi, dev, ctx, strict=True):
 
     if rank == 0:
         step_flops = sum(r["flops"] for r in stage_rows)
-        name = ("BASELINE configs[1]: rotated-MNIST SVGPVAE_Hensman, m=32 inducing, L=16, GPLVM dim 8, batch 256 per "
-                "GPU, N_train=4050, GECO + clip_qs, float64") if not cfg3 else \
-               ("BASELINE configs[2]: rotated-MNIST SVGPVAE_Hensman, m=256 inducing, L=16, GPLVM dim 32 (SURVEY F9), "
-                "batch 1024 per GPU, N_train=4050, GECO + clip_qs, float64, large-m GEMM path")
-        line = {
-            "metric": "SVGPVAE train steps/sec, rotated MNIST (N=4050, M=32, L=16)" if not cfg3 else
-                      "SVGPVAE train steps/sec, rotated MNIST (N=4050, M=256, L=16, batch 1024)",
-            "value": world * args.steps / el if scaling == "weak" else args.steps / el,
-            "unit": f"steps/s ({B}-row batches, whole job)" if scaling == "weak" else
-                    f"steps/s ({B * world}-row global batches)",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": el / args.steps * 1e3,
-            "higher_is_better": True, "scaling": scaling, "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "repeats": args.repeats, "block_ms": [round(x * 1e3, 3) for x in blocks], "timing": "median block",
-            "config": {"workload": name, "global_batch": B * world, "rows_per_gpu": B, "launch": launch,
-                       "parallelism": f"dp{world}", "rccl_ranks": comm_ranks,
-                       "single_stat_block": int(eng.base["single_stat_block"]),
-                       "scaling_note": ("weak: rows per GPU fixed, the global batch (and so c = N_train / b_global of "
-                                        "SVGPVAE_model.py:328) grows with N" if scaling == "weak" else
-                                        "strong: global batch fixed, rows per GPU = global / N")},
-            "elbo_rel_err_gpu_vs_oracle": elbo_rel,
-        }
+        line = mnist_line(args, cfg3, scaling, world, B, blocks, el, launch, comm_ranks, eng, elbo_rel)
         if scaling == "strong" and elbo_rel is not None:
             line["elbo_within_1e-8_of_oracle"] = bool(elbo_rel < 1e-8)
         top = stage_rows[0]
@@ -620,6 +672,31 @@ def mnist_case(args, scaling, multi, dev, ctx, strict=True):
         line["elbo"] = gpu_elbo
         return line
     return None
+
+
+def mnist_line(args, cfg3, scaling, world, B, blocks, el, launch, comm_ranks, eng, elbo_rel):
+    """The result line's headline part (every run); --full adds the rest in mnist_case."""
+    name = ("BASELINE configs[1]: rotated-MNIST SVGPVAE_Hensman, m=32 inducing, L=16, GPLVM dim 8, batch 256 per "
+            "GPU, N_train=4050, GECO + clip_qs, float64") if not cfg3 else \
+           ("BASELINE configs[2]: rotated-MNIST SVGPVAE_Hensman, m=256 inducing, L=16, GPLVM dim 32 (SURVEY F9), "
+            "batch 1024 per GPU, N_train=4050, GECO + clip_qs, float64, large-m GEMM path")
+    return {
+        "metric": "SVGPVAE train steps/sec, rotated MNIST (N=4050, M=32, L=16)" if not cfg3 else
+                  "SVGPVAE train steps/sec, rotated MNIST (N=4050, M=256, L=16, batch 1024)",
+        "value": world * args.steps / el if scaling == "weak" else args.steps / el,
+        "unit": f"steps/s ({B}-row batches, whole job)" if scaling == "weak" else
+                f"steps/s ({B * world}-row global batches)",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": el / args.steps * 1e3,
+        "higher_is_better": True, "scaling": scaling, "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+        "repeats": args.repeats, "block_ms": [round(x * 1e3, 3) for x in blocks], "timing": "median block",
+        "config": {"workload": name, "global_batch": B * world, "rows_per_gpu": B, "launch": launch,
+                   "parallelism": f"dp{world}", "rccl_ranks": comm_ranks,
+                   "single_stat_block": int(eng.base["single_stat_block"]),
+                   "scaling_note": ("weak: rows per GPU fixed, the global batch (and so c = N_train / b_global of "
+                                    "SVGPVAE_model.py:328) grows with N" if scaling == "weak" else
+                                    "strong: global batch fixed, rows per GPU = global / N")},
+        "elbo_rel_err_gpu_vs_oracle": elbo_rel,
+    }
 
 
 # =====================================================================================================================
@@ -669,7 +746,7 @@ def run_sprites(args):
         comm = RcclComm(0, 1, RcclComm.unique_id())
     # several ranks and no explicit --scaling: the strong line first (the configuration's own 500 frames cut in whole 50-frame
     # character groups -- one ELBO at every rank count, checked against the oracle), then the weak line, which stays last
-    modes = [args.scaling] if args.scaling else (["strong", "weak"] if multi and world <= 10 else ["weak"])
+    modes = [args.scaling] if args.scaling else (["strong", "weak"] if multi and world <= 10 and args.full else ["weak"])
     for scaling in modes:
         sprites_case(args, scaling, multi, comm, comm_why)
     if multi:
@@ -718,7 +795,15 @@ def sprites_case(args, scaling, multi, comm, comm_why):
     step = lambda: eng.step(d_img, d_ids, None, adam=True, b_global=b_global)
     blocks = timed_blocks(step, eng.stream.synchronize, args.steps, args.warmup, args.repeats, multi, dev)
     el = float(np.median(blocks))
-    # ---- stage times: HIP events recorded on the engine's stream at the stage boundaries of one more step
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step_arrays(eng.params, eng.grads, eng.scalars()))
+    if not args.full:
+        sc = eng.scalars()
+        assert math.isfinite(sc["elbo"]), sc
+        if rank == 0:
+            emit(sprites_line(args, scaling, world, b, b_global, m, k_se, blocks, el, eng, comm, comm_why))
+        return
+    # ---- stage times (--full): HIP events recorded on the engine's stream at the stage boundaries of one more step
     eng.trace = []
     step()
     eng.stream.synchronize()
@@ -761,28 +846,7 @@ def sprites_case(args, scaling, multi, comm, comm_why):
     if rank == 0:
         nets, gp = sprites_flops(b, L_, m)
         ms = el / args.steps * 1e3
-        line = {
-            "metric": f"SVGPVAE train steps/sec, SPRITES 64x64 (m={m}, L=64, 500 frames per GPU)" if scaling == "weak" else
-                      f"SVGPVAE train steps/sec, SPRITES 64x64 (m={m}, L=64, {b_global} frames per step over all GPUs)",
-            "value": world * args.steps / el if scaling == "weak" else args.steps / el,
-            "unit": "steps/s (500-frame batches, whole job)" if scaling == "weak" else f"steps/s ({b_global}-frame global batches)",
-            "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms, "higher_is_better": True, "scaling": scaling,
-            "vs_baseline": None, "dtype": eng.dtype_name, "data": "synthetic",
-            "repeats": args.repeats, "block_ms": [round(x * 1e3, 3) for x in blocks], "timing": "median block",
-            "config": {"workload": f"BASELINE configs[3] shape: SPRITES SVGPVAE_Hensman + GPLVM, {b} frames per GPU "
-                                   f"(10 characters x 50), L=64, L_action=8, L_character=16, m={m}, jitter 0.01, "
-                                   + ("SE x SE kernel (--K_SE; full-rank K_mm)" if k_se else "cosine-normalised linear x linear kernel")
-                                   + ", GECO, gradient clip 1e6",
-                       "global_batch": b_global, "rows_per_gpu": b, "parallelism": f"dp{world}",
-                       "rccl_ranks": None if (comm is None or comm_why is not None) else comm.world_size,
-                       "comm_fallback": comm_why,
-                       "exchange": None if comm is None else (
-                           "channel-sharded, one grouped RCCL launch per point, symmetric blocks tile-packed: reduce-scatter "
-                           "S,v | all-gather Sigma^-1,M2,t,u | reduce-scatter A2,ud,td | all-gather Ssym,vbar,KL | all-reduce "
-                           "gradients" if eng.chan_shard else "all-reduce x3"),
-                       "launch": "eager stream" + ("" if comm is None else " + in-library RCCL collectives")},
-        }
+        line = sprites_line(args, scaling, world, b, b_global, m, k_se, blocks, el, eng, comm, comm_why)
         peak = F64_PEAK_TFLOPS          # the dominant stage groups are the float64 GP factor stages in both precisions
         top = max(stages, key=stages.get)
         gflops = {"gp_fwd": gp / 3, "gp_bwd": 2 * gp / 3, "nets_fwd": nets / 3, "nets_bwd": 2 * nets / 3}
@@ -827,6 +891,32 @@ def sprites_case(args, scaling, multi, comm, comm_why):
             if world == 1 and scaling == "weak":
                 line["cpu_baseline"] = cb
         emit(line)
+
+
+def sprites_line(args, scaling, world, b, b_global, m, k_se, blocks, el, eng, comm, comm_why):
+    """The result line's headline part (every run); --full adds the rest in sprites_case."""
+    return {
+        "metric": f"SVGPVAE train steps/sec, SPRITES 64x64 (m={m}, L=64, 500 frames per GPU)" if scaling == "weak" else
+                  f"SVGPVAE train steps/sec, SPRITES 64x64 (m={m}, L=64, {b_global} frames per step over all GPUs)",
+        "value": world * args.steps / el if scaling == "weak" else args.steps / el,
+        "unit": "steps/s (500-frame batches, whole job)" if scaling == "weak" else f"steps/s ({b_global}-frame global batches)",
+        "n_gpus": world,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": el / args.steps * 1e3, "higher_is_better": True,
+        "scaling": scaling, "vs_baseline": None, "dtype": eng.dtype_name, "data": "synthetic",
+        "repeats": args.repeats, "block_ms": [round(x * 1e3, 3) for x in blocks], "timing": "median block",
+        "config": {"workload": f"BASELINE configs[3] shape: SPRITES SVGPVAE_Hensman + GPLVM, {b} frames per GPU "
+                               f"(10 characters x 50), L=64, L_action=8, L_character=16, m={m}, jitter 0.01, "
+                               + ("SE x SE kernel (--K_SE; full-rank K_mm)" if k_se else "cosine-normalised linear x linear kernel")
+                               + ", GECO, gradient clip 1e6",
+                   "global_batch": b_global, "rows_per_gpu": b, "parallelism": f"dp{world}",
+                   "rccl_ranks": None if (comm is None or comm_why is not None) else comm.world_size,
+                   "comm_fallback": comm_why,
+                   "exchange": None if comm is None else (
+                       "channel-sharded, one grouped RCCL launch per point, symmetric blocks tile-packed: reduce-scatter "
+                       "S,v | all-gather Sigma^-1,M2,t,u | reduce-scatter A2,ud,td | all-gather Ssym,vbar,KL | all-reduce "
+                       "gradients" if eng.chan_shard else "all-reduce x3"),
+                   "launch": "eager stream" + ("" if comm is None else " + in-library RCCL collectives")},
+    }
 
 
 def cpu_worker_sprites(m, k_se=False):
@@ -901,6 +991,14 @@ def run_cfg5(args):
 
     blocks = timed_blocks(step, torch.cuda.synchronize, args.steps, args.warmup, args.repeats, multi, dev)
     el = float(np.median(blocks))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, [("S", S), ("v", v), ("K_nm", K)])
+    if not args.full:
+        if rank == 0:
+            emit(cfg5_line(args, world, n, m, L_, D, blocks, el, comm, comm_why))
+        if multi:
+            dist.destroy_process_group()
+        return
 
     def ev_time(fn, reps=5):         # SS.* launch on torch's current stream: torch events see them
         fn(); torch.cuda.synchronize()
@@ -927,20 +1025,8 @@ def run_cfg5(args):
     if rank == 0:
         alg_flops = float(L_) * n * m * m          # symmetric count (L N m^2)
         knm_bytes = 4.0 * (n * m + n * D + m * D)
-        line = {
-            "metric": "SVGP statistics pass rows/sec (N=2^20 frames, m=2048, L=16, fp32; K_nm build + S_l, v_l)",
-            "value": world * n * args.steps / el, "unit": "rows/s (whole job)", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": el / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f32", "data": "synthetic", "repeats": args.repeats,
-            "block_ms": [round(x * 1e3, 3) for x in blocks], "timing": "median block",
-            "config": {"workload": f"BASELINE configs[4], one GPU's shard: {n} rows x m={m} inducing, L={L_}, "
-                                   f"periodic x linear kernel (D={D}), float32: features, materialised K_nm (5a), "
-                                   f"S_l / v_l statistics (5b)" + (", RCCL all-reduce of S, v" if comm is not None else ""),
-                       "rows_per_gpu": n, "parallelism": f"dp{world}",
-                       "rccl_ranks": None if (comm is None or comm_why is not None) else comm.world_size,
-                       "comm_fallback": comm_why},
-            "probe_rel_err_S": err,
-        }
+        line = cfg5_line(args, world, n, m, L_, D, blocks, el, comm, comm_why)
+        line["probe_rel_err_S"] = err
         t_s, src_s = committed_traffic("k_stats_mfma_f32", per_pass_of="k_stats_reduce_f32")
         line["roofline"] = roofline_of(alg_flops, 4.0 * (n * m + 2 * n * L_ + L_ * m * m), us_stats, F32_PEAK_TFLOPS,
                                        kernel="stream_stats_f32 (k_stats_mfma_f32 + v_l + reduction)",
@@ -956,6 +1042,23 @@ def run_cfg5(args):
         emit(line)
     if multi:
         dist.destroy_process_group()
+
+
+def cfg5_line(args, world, n, m, L_, D, blocks, el, comm, comm_why):
+    """The result line's headline part (every run); --full adds the rest in run_cfg5."""
+    return {
+        "metric": "SVGP statistics pass rows/sec (N=2^20 frames, m=2048, L=16, fp32; K_nm build + S_l, v_l)",
+        "value": world * n * args.steps / el, "unit": "rows/s (whole job)", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": el / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f32", "data": "synthetic", "repeats": args.repeats,
+        "block_ms": [round(x * 1e3, 3) for x in blocks], "timing": "median block",
+        "config": {"workload": f"BASELINE configs[4], one GPU's shard: {n} rows x m={m} inducing, L={L_}, "
+                               f"periodic x linear kernel (D={D}), float32: features, materialised K_nm (5a), "
+                               f"S_l / v_l statistics (5b)" + (", RCCL all-reduce of S, v" if comm is not None else ""),
+                   "rows_per_gpu": n, "parallelism": f"dp{world}",
+                   "rccl_ranks": None if (comm is None or comm_why is not None) else comm.world_size,
+                   "comm_fallback": comm_why},
+    }
 
 
 def cfg5_inputs(rank, n, m, L_, M, n_obj=400):
@@ -1058,7 +1161,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=None)
     ap.add_argument("--warmup", type=int, default=None)
-    ap.add_argument("--repeats", type=int, default=5, help="blocks of --steps steps; the median block is reported")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="blocks of --steps steps; the median block is reported (default 1; 5 with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: parity gate, roofline, per-stage and per-exchange timings, "
+                         "CPU baseline, the strong-scaling line with several ranks")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (at most 64 MB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-parity-gate", action="store_true")
     ap.add_argument("--no-graph", action="store_true")
@@ -1115,6 +1224,7 @@ def main():
     dflt = {"cfg2": (300, 30), "cfg3": (30, 5), "sprites800": (3, 1), "cfg5": (3, 1)}[args.workload]
     args.steps = dflt[0] if args.steps is None else args.steps
     args.warmup = dflt[1] if args.warmup is None else args.warmup
+    args.repeats = (5 if args.full else 1) if args.repeats is None else args.repeats
     if args.workload in ("sprites800", "cfg5") and args.repeats > 3:
         args.repeats = 3
 

@@ -185,7 +185,7 @@ def test_bench_multi_gpu_code_path_at_world_size_one():
     for ex, port in (("rccl", 29531), ("torch", 29532)):
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr",
                "127.0.0.1", "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "20",
-               "--warmup", "3", "--no-cpu-baseline", "--force-dist", "--exchange", ex]
+               "--warmup", "3", "--no-cpu-baseline", "--force-dist", "--exchange", ex, "--full"]
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
         assert r.returncode == 0, r.stderr[-2000:]
         line = json.loads(r.stdout.strip().splitlines()[-1])
@@ -202,7 +202,7 @@ def test_bench_multi_gpu_code_path_at_world_size_one():
     # a rank whose library communicator cannot be created: the collective decision sends every rank to the torch.distributed form
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", "29534", os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "3",
-           "--no-cpu-baseline", "--force-dist"]
+           "--no-cpu-baseline", "--force-dist", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root, env=dict(os.environ, SVGP_BENCH_FAIL_LIBCOMM="1"))
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
@@ -211,7 +211,7 @@ def test_bench_multi_gpu_code_path_at_world_size_one():
     # config 3 (channel-sharded sequence: five grouped points) through the same code path
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", "29533", os.path.join(root, "bench.py"), "--gpus", "1", "--workload", "cfg3", "--steps", "5",
-           "--warmup", "2", "--repeats", "1", "--no-cpu-baseline", "--force-dist"]
+           "--warmup", "2", "--repeats", "1", "--no-cpu-baseline", "--force-dist", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
@@ -230,7 +230,7 @@ def test_bench_launches_its_own_ranks_and_prints_the_strong_line_first():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--force-dist", "--steps", "20", "--warmup", "5",
-                        "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, cwd=root, env=env)
+                        "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=900, cwd=root, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     assert "torch.distributed.run --nnodes=1 --nproc-per-node=1 --master-addr 127.0.0.1" in r.stderr
     lines = [json.loads(x) for x in r.stdout.splitlines() if x.lstrip().startswith("{") and '"metric"' in x]
@@ -267,7 +267,7 @@ def test_bench_multi_rank_paths_of_the_eight_gpu_configs_with_one_rank(workload,
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--force-dist", "--workload", workload, "--steps", "2",
-           "--warmup", "1", "--repeats", "1", "--no-cpu-baseline"] + extra
+           "--warmup", "1", "--repeats", "1", "--no-cpu-baseline", "--full"] + extra
     for fail in (False, True):
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=root,
                            env=dict(env, SVGP_BENCH_FAIL_LIBCOMM="1") if fail else env)
