@@ -85,8 +85,10 @@ typedef struct {
                            /* -- decoder + GP parameters + scalar sums as soon as the kernel-matrix reverse pass is done (they   */
                            /* do not depend on the encoder's reverse pass; svgp_mnist_train_step_dp issues it on a side        */
                            /* stream), the encoder's part behind its reverse pass -- so that one of the three small-message    */
-                           /* latencies hides under the encoder's reverse pass.  0 (default): one all-reduce.  (The field sits */
-                           /* in the padding in front of N_train: the struct's size and every other offset are unchanged.)    */
+                           /* latencies hides under the encoder's reverse pass.  0 (default): one all-reduce.  Any other value */
+                           /* is refused (svgp_check_cfg): an uninitialised field must not switch only some ranks to the two  */
+                           /* messages (mismatched collectives hang).  (The field sits in the padding in front of N_train:     */
+                           /* the struct's size and every other offset are unchanged.)                                         */
     double  N_train;       /* mainSVGP.N_train                                                  */
     double  jitter;        /* mainSVGP.jitter                                                   */
     double  kappa_squared; /* GECO kappa^2                                                      */
@@ -220,7 +222,8 @@ int svgp_gp_posterior_fwd(const svgp_mnist_cfg*, const double* eps, double* ws, 
 /* mnistVAE.decode + squared reconstruction error (VAE_utils.py:154-162, SVGPVAE_model.py:905-918) */
 int svgp_mnist_decoder_fwd(const svgp_mnist_cfg*, const double* theta, const double* images,
                            double* ws, void* stream);
-/* reverse of the decoder; writes zbar and decoder weight-gradient partials */
+/* reverse of the decoder; writes zbar and decoder weight-gradient partials.  One launch up to L = 21; from L = 22 its LDS would
+ * exceed a workgroup's 160 KB and it issues svgp_mnist_decoder_bwd_data + _weights (threads 256, n_types 3) instead */
 int svgp_mnist_decoder_bwd(const svgp_mnist_cfg*, const double* theta, const double* images,
                            double* ws, const double* state, void* stream);
 /* The reverse pass of the decoder in two halves (tf.gradients of VAE_utils.py:128-141,154-162; MNIST_experiment.py:202-205).

@@ -47,6 +47,9 @@ int svgp_check_cfg(const svgp_mnist_cfg* c) {
     SVGP_REQUIRE(c->kl_form == 0 || c->kl_form == 1, SVGP_ERR_INVALID, "kl_form=%d (0 or 1)", c->kl_form);
     SVGP_REQUIRE(c->clip_pv >= 0 && c->clip_pv <= 2, SVGP_ERR_INVALID, "clip_pv=%d (0, 1 or 2)", c->clip_pv);
     SVGP_REQUIRE(c->gemm_f32 >= 0 && c->gemm_f32 <= 2, SVGP_ERR_INVALID, "gemm_f32=%d (0, 1 or 2)", c->gemm_f32);
+    // every rank must take the same exchange schedule: a stray non-zero value would switch only some ranks to two messages
+    SVGP_REQUIRE(c->split_grad_exchange == 0 || c->split_grad_exchange == 1, SVGP_ERR_INVALID,
+                 "split_grad_exchange=%d (0 or 1)", c->split_grad_exchange);
     SVGP_REQUIRE(!(c->kl_form && c->m > SVGP_M_MAX), SVGP_ERR_UNSUPPORTED,
                  "kl_form=1 (moving-ball SVGP) is implemented for m <= %d inducing points (m=%d)", SVGP_M_MAX, c->m);
     SVGP_REQUIRE(!(c->kl_form && c->b != c->b_global), SVGP_ERR_UNSUPPORTED,

@@ -14,6 +14,7 @@ typedef double real;
 #define SVGP_MAX_PART 256      // max workgroups that write weight-gradient partials (= CUs)
 #define SVGP_M_MAX 64          // up to here the m x m stages stay LDS-resident (gp_kernels.hip)
 #define SVGP_M_LIMIT 2048      // beyond SVGP_M_MAX: global-memory matrices + batched MFMA GEMMs (gp_large.hip)
+#define SVGP_LDS_MAX_BYTES (160 * 1024)   // dynamic LDS one workgroup may declare on gfx950
 #define SVGP_CHOL_INVERSE_MIN_M 512   // spd inverse: fused 32-block Gauss-Jordan sweep below, potrf + potri from here on
 #define SVGP_LOG_2PI 1.8378770664093453
 

@@ -422,6 +422,14 @@ extern "C" int svgp_mnist_decoder_bwd(const svgp_mnist_cfg* c, const double* the
     SVGP_REQUIRE(theta && images && ws && state, SVGP_ERR_INVALID, "NULL device pointer");
     const int64_t n_dec = pl.n_vae - pl.n_enc;
     const size_t lds = (size_t)(c->L * 128 + n_dec + 2 * DEC_NWE + 64 + 128 + 512 + 1568 + 784 + 1568 + 512 + 128 + VAE_SCRATCH) * sizeof(real);
+    if (lds > SVGP_LDS_MAX_BYTES) {
+        // L >= 22: the dense weights and their gradient (2 L 128 reals) no longer fit one workgroup's LDS next to the rest.  The two
+        // halves write the same zbar and the same partial slots (ws.part_dec, svgp_n_part of them), each within the LDS up to L = 64
+        // (the split the m <= 64 training step takes anyway; its weight half runs on 256 threads there too)
+        int rc = svgp_mnist_decoder_bwd_data(c, theta, images, ws, state, stream);
+        if (rc) return rc;
+        return svgp_mnist_decoder_bwd_weights(c, images, ws, state, 256, 3, stream);
+    }
     int rc = set_dyn_lds(k_decoder_bwd, lds);
     if (rc) return rc;
     hipLaunchKernelGGL(k_decoder_bwd, dim3(svgp_n_part(c)), dim3(VAE_NT), lds, (hipStream_t)stream, c->b, c->L,

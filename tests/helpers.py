@@ -84,3 +84,112 @@ def relerr(a, b):
     a = torch.as_tensor(a, dtype=DT).cpu().reshape(-1)
     b = torch.as_tensor(b, dtype=DT).cpu().reshape(-1)
     return float((a - b).abs().max() / (b.abs().max() + 1e-300))
+
+
+# ---------------------------------------------------------------- one training step of the HIP engine against the oracle
+# Tolerances (float64 end to end): forward intermediates 1e-9 relative to the tensor's max-abs, scalars 1e-9 relative,
+# gradients 1e-7 relative to the tensor's max-abs (tests/test_gpu_parity.py).
+FWD_TOL, GRAD_TOL, SCALAR_TOL = 1e-9, 1e-7, 1e-9
+
+FIELD_SHAPES = lambda b, m, L: dict(
+    qnet_mu=(b, L), qnet_var_raw=(b, L), qnet_var=(b, L), K=(m, m), Kn=(b, m), knn=(b,), S=(L, m, m), v=(L, m),
+    Ki=(m, m), ldK=(1,), Si=(L, m, m), t=(L, m), G=(L, m, m), A=(L, m, m), Aji=(L, m, m), mu_hat=(L, m),
+    u=(L, m), M2=(L, m, m), KL=(L,), q=(b,), p_m=(b, L), p_v=(b, L), e=(b, L), d=(b, L), z=(b, L),
+    recon=(b, 784))
+
+
+def _run_once(eng, images, aux, eps, adam=False):
+    dev = eng.device
+    eng.bind(images.to(dev), aux.to(dev), None if eps is None else eps.to(dev))
+    eng.run(adam=adam)
+    eng.synchronize()
+
+
+def _compare_step(params, images, aux, eps, *, geco, clip_qs=True, N_train=4050.0, jitter=1e-6, beta=0.001,
+                  K_obj_normalize=False, C_ma=0.0, lagrange=1.0, alpha=0.0, kappa2=0.020, label="",
+                  FWD_TOL=FWD_TOL, GRAD_TOL=GRAD_TOL, self_consistency=False, b_max=None, eng=None):
+    """One step (no Adam) of a fresh engine -- built for b_max >= b rows of capacity when b_max is given -- or of `eng`, an
+    engine of the same shape and settings built earlier (params are loaded into it), against the float64 oracle.
+    Returns (list of failures, engine)."""
+    b, L = eps.shape
+    m = params["inducing_index_points"].shape[0]
+    if eng is None:
+        eng = engine_for(params, b if b_max is None else b_max, geco=geco, clip_qs=clip_qs, N_train=N_train, jitter=jitter,
+                         beta=beta, K_obj_normalize=K_obj_normalize, kappa_squared=kappa2)
+    else:
+        eng.load_params(params)
+    if eng.cfg.b != b:
+        eng.set_batch_size(b)
+    eng.set_scalars(c_ma=C_ma, lagrange=lagrange, alpha=alpha)
+    _run_once(eng, images, aux, eps)
+    bad = []
+    ref = oracle_stages(params, images, aux, eps, N_train=N_train, jitter=jitter, clip_qs=clip_qs, geco=geco,
+                        beta=beta, K_obj_normalize=K_obj_normalize)
+    fwd_tol = {name: FWD_TOL for name in FIELD_SHAPES(b, m, L)}
+    p2 = img2 = None
+    if self_consistency:
+        # ill-conditioned cases: the yardstick is the oracle's own response to a one-ulp perturbation of its real inputs
+        # (what any two backward-stable float64 evaluations of these formulas may differ by; tests/test_gpu_fullsize.py);
+        # the HIP result must sit within 20x of it, forward fields, scalars and gradients alike
+        gen = torch.Generator().manual_seed(17)
+        ulp = lambda t: t * (1.0 + 2.0 ** -52 * (torch.randint(0, 2, t.shape, generator=gen).to(DT) * 2 - 1))
+        p2 = {k: ulp(v) for k, v in params.items()}
+        p2["inducing_index_points"][:, 0] = params["inducing_index_points"][:, 0]
+        img2 = ulp(images)
+        ref2 = oracle_stages(p2, img2, aux, eps, N_train=N_train, jitter=jitter, clip_qs=clip_qs, geco=geco,
+                             beta=beta, K_obj_normalize=K_obj_normalize)
+        fwd_tol = {name: max(FWD_TOL, 20 * relerr(ref2[name], ref[name])) for name in fwd_tol}
+    for name, shp in FIELD_SHAPES(b, m, L).items():
+        if name == "M2" and m > 64:
+            # the large-m path evaluates k^T M2 k as w^T Si w and does not form M2 = Ki A Ki (gp_large.hip, "W form"): its
+            # channel-independent rows W = Kn Ki K sit behind the b rows of K_nm and are compared instead
+            W = eng.ws[eng.wl.Kn + b * m:eng.wl.Kn + 2 * b * m].view(b, m)
+            want = ref["Kn"] @ ref["Ki"] @ ref["K"]
+            err = relerr(W, want)
+            if not err < fwd_tol["M2"]:
+                bad.append(f"{label} fwd W: rel {err:.3e} (tol {fwd_tol['M2']:.1e})")
+            continue
+        err = relerr(eng.ws_view(name, shp), ref[name])
+        if not err < fwd_tol[name]:
+            bad.append(f"{label} fwd {name}: rel {err:.3e} (tol {fwd_tol[name]:.1e})")
+    out, grads = O.loss_and_grads(params, images, aux, eps, beta=beta, C_ma=torch.tensor(C_ma, dtype=DT),
+                                  lagrange_mult=torch.tensor(lagrange, dtype=DT), alpha=alpha,
+                                  kappa=math.sqrt(kappa2), clipping_qs=clip_qs, GECO=geco, jitter=jitter,
+                                  N_train=N_train, L=L, formulation="efficient", K_obj_normalize=K_obj_normalize)
+    sc = eng.scalars()
+    out_ulp = g_ulp = None
+    if self_consistency:
+        out_ulp, g_ulp = O.loss_and_grads(p2, img2, aux, eps, beta=beta, C_ma=torch.tensor(C_ma, dtype=DT),
+                                          lagrange_mult=torch.tensor(lagrange, dtype=DT), alpha=alpha,
+                                          kappa=math.sqrt(kappa2), clipping_qs=clip_qs, GECO=geco, jitter=jitter,
+                                          N_train=N_train, L=L, formulation="efficient",
+                                          K_obj_normalize=K_obj_normalize)
+    for key, idx in (("elbo", 0), ("recon_loss", 1), ("kl_term", 2), ("inside_elbo", 3), ("ce_term", 4),
+                     ("inside_recon", 10), ("inside_kl", 11)):
+        want = float(out[idx])
+        stol = SCALAR_TOL * max(1.0, abs(want))
+        if out_ulp is not None:
+            stol = max(stol, 20 * abs(float(out_ulp[idx]) - want))
+        if not abs(sc[key] - want) <= stol:
+            bad.append(f"{label} scalar {key}: got {sc[key]!r} want {want!r} (tol {stol:.1e})")
+    if geco:
+        for key, idx in (("c_ma", 13), ("lagrange", 14)):
+            want = float(out[idx])
+            if not abs(sc[key] - want) <= SCALAR_TOL * max(1.0, abs(want)):
+                bad.append(f"{label} scalar {key}: got {sc[key]!r} want {want!r}")
+    tol = {k: GRAD_TOL for k in grads}
+    if self_consistency:
+        # ill-conditioned cases: the oracle's literal and efficient formulations (same mathematics, float64)
+        # disagree by far more than GRAD_TOL; the HIP result must sit within 5x of that self-disagreement
+        _, g_lit = O.loss_and_grads(params, images, aux, eps, beta=beta, C_ma=torch.tensor(C_ma, dtype=DT),
+                                    lagrange_mult=torch.tensor(lagrange, dtype=DT), alpha=alpha,
+                                    kappa=math.sqrt(kappa2), clipping_qs=clip_qs, GECO=geco, jitter=jitter,
+                                    N_train=N_train, L=L, formulation="literal", K_obj_normalize=K_obj_normalize)
+        # ... or within 20x of the oracle's response to the one-ulp input perturbation above
+        tol = {k: max(GRAD_TOL, 5 * relerr(g_lit[k], grads[k]), 20 * relerr(g_ulp[k], grads[k])) for k in grads}
+    g = eng.grads()
+    for k, want in grads.items():
+        err = relerr(g[k], want)
+        if not err < tol[k]:
+            bad.append(f"{label} grad {k}: rel {err:.3e} (max|want| {float(want.abs().max()):.3e})")
+    return bad, eng

@@ -76,6 +76,21 @@ def test_bad_shapes_are_rejected_with_a_message():
         _lib.call("svgp_mnist_param_layout_get", C.byref(cfg), C.byref(_lib.ParamLayout()))
 
 
+@pytest.mark.parametrize("field,value,message", [
+    ("L", 0, "bad shape"), ("L", 65, "64 latent channels"), ("M", 129, "M=129"), ("m", 2049, "m <= 2048"),
+    ("kl_form", 2, "kl_form=2"), ("split_grad_exchange", 2, "split_grad_exchange=2")])
+def test_each_out_of_range_field_is_rejected_with_a_message(field, value, message):
+    """One field just past what svgp_check_cfg accepts, the rest a valid config-2 shape; refused by both layout calls."""
+    kw = dict(b=256, b_global=256, m=32, L=16, M=8, n_obj=400, N_train=4050.0, jitter=1e-6)
+    _lib.call("svgp_mnist_ws_layout_get", C.byref(_lib.MnistCfg(**kw)), C.byref(_lib.WsLayout()))
+    kw[field] = value
+    cfg = _lib.MnistCfg(**kw)
+    with pytest.raises(svgp_vae_amd.SvgpError, match=message):
+        _lib.call("svgp_mnist_param_layout_get", C.byref(cfg), C.byref(_lib.ParamLayout()))
+    with pytest.raises(svgp_vae_amd.SvgpError, match=message):
+        _lib.call("svgp_mnist_ws_layout_get", C.byref(cfg), C.byref(_lib.WsLayout()))
+
+
 def test_null_pointers_are_rejected_before_any_launch():
     cfg = _lib.MnistCfg(b=4, b_global=4, m=8, L=2, M=2, n_obj=0, N_train=10.0, jitter=1e-6)
     with pytest.raises(svgp_vae_amd.SvgpError, match="NULL"):

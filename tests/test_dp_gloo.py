@@ -267,7 +267,9 @@ def _worker(rank, world, port, b_global, geco, ret):
                            N_train=300.0, jitter=1e-6, geco=geco, beta=0.001, lagrange=1.7)
         DataParallelStep(be).step()
         if rank == 0:
-            ret.put(be.block("gradC").clone())
+            # by value (numpy): a torch tensor would travel as a shared-memory handle that the parent can only open while this
+            # process is still alive, and it exits right after destroy_process_group
+            ret.put(be.block("gradC").clone().numpy())
     finally:
         dist.destroy_process_group()
 
@@ -296,7 +298,16 @@ def test_dp_schedule_reproduces_single_process(world, b_global, geco):
     procs = [ctx.Process(target=_worker, args=(r, world, port, b_global, geco, ret)) for r in range(world)]
     for p in procs:
         p.start()
-    got = ret.get()
+    import time
+    t0 = time.time()
+    while ret.empty():                           # a failed worker must fail the test, not hang it on the queue
+        if any(p.exitcode not in (None, 0) for p in procs) or time.time() - t0 > 300:
+            for q in procs:
+                if q.is_alive():
+                    q.terminate()
+            pytest.fail(f"worker exit codes {[p.exitcode for p in procs]}")
+        time.sleep(0.05)
+    got = torch.from_numpy(ret.get())
     for p in procs:
         p.join(timeout=120)
         assert p.exitcode == 0
