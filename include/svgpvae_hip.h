@@ -21,6 +21,8 @@
  *     what is created once and then only read -- the dlopen'd RCCL entry points (svgp_comm_*) -- and one pair of
  *     library-owned side streams + events per (device, caller stream), created at the first m > 64 step (or with
  *     SVGP_SIDE_STREAMS=1) on that stream and used only by calls that pass that stream.
+ *   - the SVGP_* environment variables named below are schedule switches: same bits, another launch order.  They are read
+ *     once per call of an exported entry point; DESIGN.md section 6.4 lists all of them with values and defaults.
  */
 #ifndef SVGPVAE_HIP_H
 #define SVGPVAE_HIP_H
@@ -437,8 +439,8 @@ int svgp_gp_factor_bwd_channels_part(const svgp_mnist_cfg*, int l0, int nl, int 
  * grouped RCCL launch (ncclGroupStart / End): [S | v] reduce-scatter, [Sigma^-1 | M2 | t | u] all-gather, [A2 | ud | td]
  * reduce-scatter, [Ssym | vbar | KL] all-gather, gradient all-reduce.  The (L,m,m) members are symmetric and travel
  * TILE-PACKED (svgp_sym_pack: lower triangle in 32 x 32 tiles, 52 % of the square at m = 800; SURVEY 8e "halve via
- * symmetry") with SVGP_DP_PACK=1, off with 0; default: from m >= 512.  The tail of the forward factor stage and the early half of the
- * reverse one run on the library's side stream beside the all-gather, the row stage, the networks and the reverse
+ * symmetry") with SVGP_DP_PACK=1, off with 0; default: svgp_dp_pack_default(m).  The tail of the forward factor stage and the early
+ * half of the reverse one run on the library's side stream beside the all-gather, the row stage, the networks and the reverse
  * statistics (as in the single-GPU step; SVGP_SIDE_STREAMS=0 puts them in line).                                      */
 int svgp_mnist_train_step_dp(const svgp_mnist_cfg*, void* comm, double* theta, const double* images,
                              const double* aux, const double* eps, double* ws, double* state,
@@ -456,6 +458,8 @@ int svgp_comm_timing_read(void* comm, float* us, int cap, int* n);
  * holds (x_ij + x_ji) / 2 (for products that are symmetric only up to rounding, M2 = Ki A Ki); else x_ij of the lower
  * tiles.  svgp_sym_unpack writes both triangles of the square matrices.  src / dst strides: m * m and packed_elems.   */
 int64_t svgp_sym_packed_elems(int m);
+/* 1 where the packed exchange is the default for this m (the single definition of the rule; SVGP_DP_PACK overrides it). */
+int svgp_dp_pack_default(int m);
 int svgp_sym_pack(int m, int L, int avg, const double* src, double* dst, void* stream);
 int svgp_sym_unpack(int m, int L, const double* src, double* dst, void* stream);
 

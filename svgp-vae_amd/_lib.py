@@ -259,6 +259,7 @@ NON_STATUS = {"svgp_version": ([], C.c_int), "svgp_last_error": ([], C.c_char_p)
               "svgp_struct_sizeof": ([C.c_int], C.c_int),
               "svgp_comm_unique_id_bytes": ([], C.c_int),
               "svgp_sym_packed_elems": ([C.c_int], C.c_int64),
+              "svgp_dp_pack_default": ([C.c_int], C.c_int),
               "svgp_stream_feature_elems": ([C.c_void_p, C.c_int64], C.c_int64),
               "svgp_stream_stats_workspace_elems": ([C.c_int64, C.c_int, C.c_int], C.c_int64),
               "svgp_spd_inverse_workspace_elems": ([C.c_int, C.c_int], C.c_size_t),
@@ -305,6 +306,32 @@ def load_library(path=None):
     if path is None:
         _lib = lib
     return lib
+
+
+class Schedule:
+    """The schedule switches as the host code needs them -- the only reader of a schedule variable in this package (the library's
+    own is csrc/sched.hpp; DESIGN.md "Schedule switches" has the table of names, values, defaults and the comparing tests).
+    Read from the environment when constructed, so build one per engine / per step, not per process.  A switch is ON unless
+    its value starts with "0".
+
+    SVGP_SIDE_STREAMS, by first character:
+      "0"   no side stream anywhere: every launch on the caller's stream                          -> side_off
+      "1"   additionally opts in to the library's m <= 64 fork (csrc/api.hip); here as unset
+      "2"   SPRITES step only: ONE side stream, the early reverse half behind the forward tail    -> side_single
+      unset the large-m side branches on (SPRITES: two side streams), the m <= 64 fork off"""
+
+    def __init__(self):
+        env = os.environ
+        on = lambda name: not env.get(name, "").startswith("0")
+        side = env.get("SVGP_SIDE_STREAMS", "")
+        self.side_off = side.startswith("0")
+        self.side_single = side.startswith("2")
+        self.kbar_branch = on("SVGP_KBAR_BRANCH")
+        self.stream_probe = on("SVGP_STREAM_PROBE")
+        pack = env.get("SVGP_DP_PACK")
+        self.dp_pack = None if pack is None else not pack.startswith("0")      # None: the library's default for m
+        # m <= 64 data parallelism: the statistics keep their row partials on the wire; "0": one block per channel (engine.py)
+        self.dp_stat_partials = env.get("SVGP_DP_STAT_PARTIALS") != "0"
 
 
 def check(rc, lib=None):

@@ -209,7 +209,7 @@ int streams_overlap(hipStream_t a, hipStream_t b, bool* out) {
     return SVGP_OK;
 }
 
-int side_get(hipStream_t main, Side** out) {
+int side_get(hipStream_t main, const SvgpSched& sc, Side** out) {
     int dev = 0;
     SVGP_CHECK_HIP(hipGetDevice(&dev));
     std::lock_guard<std::mutex> lk(g_side_mu);
@@ -221,8 +221,7 @@ int side_get(hipStream_t main, Side** out) {
         // the probe above.  Not under stream capture (the probe synchronises) and not with SVGP_STREAM_PROBE=0: then the first two.
         hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
         (void)hipStreamIsCapturing(main, &cap);
-        const char* ev = getenv("SVGP_STREAM_PROBE");
-        const bool probe = cap == hipStreamCaptureStatusNone && !(ev && ev[0] == '0');
+        const bool probe = cap == hipStreamCaptureStatusNone && sc.stream_probe;
         hipStream_t cand[12];
         int n_cand = 0, picked = 0;
         while (picked < 2 && n_cand < (probe ? 12 : 2)) {
@@ -276,9 +275,9 @@ bool side_take_konly(Side* sd, const void* ws) { std::lock_guard<std::mutex> lk(
 // comm.hip (channel-sharded step, branch 1) / cholesky.hip (look-ahead of the blocked factorisation, branch 0): side branch k
 // of the caller's stream.  _fork: the branch continues after everything issued on the caller's stream so far (re-forking an
 // open branch just adds that dependency); _join: the caller's stream continues after everything issued on the branch.
-int svgp_side_branch_fork(void* main_stream, void** side_stream_out, int k) {
+int svgp_side_branch_fork(const SvgpSched& sc, void* main_stream, void** side_stream_out, int k) {
     Side* sd = nullptr;
-    int rc = side_get((hipStream_t)main_stream, &sd);
+    int rc = side_get((hipStream_t)main_stream, sc, &sd);
     if (rc) return rc;
     rc = side_fork(sd, k, (hipStream_t)main_stream);
     if (rc) return rc;
@@ -286,56 +285,28 @@ int svgp_side_branch_fork(void* main_stream, void** side_stream_out, int k) {
     return SVGP_OK;
 }
 int svgp_side_branch_join(void* main_stream, int k) {
+    int dev = 0;
+    SVGP_CHECK_HIP(hipGetDevice(&dev));
     Side* sd = nullptr;
-    int rc = side_get((hipStream_t)main_stream, &sd);
-    if (rc) return rc;
+    {
+        std::lock_guard<std::mutex> lk(g_side_mu);
+        auto it = g_side.find(std::make_pair(dev, (hipStream_t)main_stream));
+        if (it == g_side.end()) return SVGP_OK;                 // never forked: nothing to join
+        sd = it->second;
+    }
     return side_join(sd, k, (hipStream_t)main_stream);
 }
 
 namespace {
-// m <= 64 (round 6): the decoder's reverse pass as the data half (the chain to zbar) in phase 1 and the weight half as riders of
-// the reverse factor launch in phase 2 (vae_dev.hpp).  SVGP_DEC_SPLIT=0: the one-kernel form of rounds 1-5.
-// Read per call (tests compare the two forms in one process); a caller must not change it between phase 1 and phase 2 of a step.
-bool dec_split_on() {
-    const char* e = getenv("SVGP_DEC_SPLIT");
-    return !(e && e[0] == '0');
-}
-// m <= 64 (round 6): kernel-matrix VJP + encoder reverse pass in one launch.  SVGP_ENC_KM_MERGE=0: two launches.
-bool enc_km_merge_on() {
-    const char* e = getenv("SVGP_ENC_KM_MERGE");
-    return !(e && e[0] == '0');
-}
-bool sum_merge_on() {
-    const char* e = getenv("SVGP_SUM_MERGE");
-    return !(e && e[0] == '0');
-}
-// m <= 64, phases issued back to back with nothing exchanged in between (round 6): the reverse statistics ride in the reverse factor
-// launch (svgp_gp_stats_factor_bwd_wgrad).  SVGP_STAT_MERGE=0: their own launch at the end of phase 1.
-bool stat_merge_on() {
-    const char* e = getenv("SVGP_STAT_MERGE");
-    return !(e && e[0] == '0');
-}
-// m <= 32 (round 6): the deferred (A_hat + jI)^-1 rides in the decoder's data-reverse launch instead of the forward row-stage launch
-// (svgp_mnist_decoder_bwd_data_pre_aji).  SVGP_AJI_DEC=0: svgp_gp_posterior_fwd_with_aji.
-bool aji_dec_on() {
-    const char* e = getenv("SVGP_AJI_DEC");
-    return !(e && e[0] == '0');
-}
-bool kbar_branch_on() {
-    const char* e = getenv("SVGP_KBAR_BRANCH");
-    return !(e && e[0] == '0');
-}
-bool konly_on() {      // (read per call: tests compare the two orders in one process)
-    const char* e = getenv("SVGP_KONLY_BRANCH");
-    return !(e && e[0] == '0');
-}
+// The schedule switches this function consults (sched.hpp) are read once per exported call and arrive in `sc`; a caller must not
+// change SVGP_DEC_SPLIT between phase 1 and phase 2 of a step.
 // `defer`: the caller issues all four phases back to back on one stream (svgp_mnist_train_step), so a
 // branch forked in one phase may be joined in a later one; otherwise every phase joins before returning
 // (each phase may be captured into its own graph, with a collective in between).  defer == 2: ... and NOTHING is exchanged
 // between the phases (the single-GPU step), so a stage may move across a phase boundary.
 int step_phase_impl(const svgp_mnist_cfg* c, int phase, double* theta, const double* images, const double* aux,
                     const double* eps, double* ws, double* state, double* adam_m, double* adam_v, void* stream,
-                    int defer) {
+                    int defer, const SvgpSched& sc) {
     int rc = svgp_check_cfg(c);
     if (rc) return rc;
     SVGP_REQUIRE(theta && images && aux && ws && state, SVGP_ERR_INVALID, "NULL device pointer");
@@ -345,26 +316,25 @@ int step_phase_impl(const svgp_mnist_cfg* c, int phase, double* theta, const dou
     // kernel-matrix reverse pass || encoder reverse pass branch hides ~20 us, which pays only in the
     // per-phase-graph replay form (phase 2: 110 -> 100 us) and loses in the eager in-order form
     // (261 -> 283 us per step), so it is opt-in: SVGP_SIDE_STREAMS=1.
-    const char* fk = getenv("SVGP_SIDE_STREAMS");
-    const bool fork2 = fk && fk[0] == '1';
+    const bool fork2 = sc.side_small_m;
     // Large-m path: the tail of the forward factor stage ((A_hat + jI)^-1, its log det, KL: a whole batched inverse that only
     // the reverse factor stage and the final ELBO need) runs on side stream 1, beside the row stage, the decoder and the
     // reverse statistics.  That hides ~140 us at config 3 for ~10 us of signalling, so it is on unless SVGP_SIDE_STREAMS=0.
     // Not with cfg.titsias: svgp_gp_titsias_fwd inverts its own batch through the SAME inverse scratch (ws.scr_inv) on the
     // caller's stream, and the early reverse half would only multiply zero seeds.
     const bool large = c->m > SVGP_M_MAX;
-    const bool fork1 = large && !c->titsias && !(fk && fk[0] == '0');
+    const bool fork1 = large && !c->titsias && !sc.side_off;
     Side* sd = nullptr;
     if (fork2 || large) {
-        rc = side_get(ms, &sd);
+        rc = side_get(ms, sc, &sd);
         if (rc) return rc;
     }
     hipStream_t s2 = fork2 ? sd->s[0] : ms;
 #define RUN(call) do { rc = (call); if (rc) return rc; } while (0)
-    const bool ksplit = phase == 0 && fork1 && defer && c->m < SVGP_CHOL_INVERSE_MIN_M && konly_on();
-    const bool sum_rides = phase == 2 && !large && !fork2 && !c->titsias && enc_km_merge_on() && sum_merge_on();
-    const bool aji_in_dec = phase == 1 && c->m <= 32 && !c->titsias && dec_split_on() && aji_dec_on();
-    const bool stat_rides = defer == 2 && !large && !c->titsias && c->L <= 56 && dec_split_on() && stat_merge_on();
+    const bool ksplit = phase == 0 && fork1 && defer && c->m < SVGP_CHOL_INVERSE_MIN_M && sc.konly_branch;
+    const bool sum_rides = phase == 2 && !large && !fork2 && !c->titsias && sc.enc_km_merge && sc.sum_merge;
+    const bool aji_in_dec = phase == 1 && c->m <= 32 && !c->titsias && sc.dec_split && sc.aji_dec;
+    const bool stat_rides = defer == 2 && !large && !c->titsias && c->L <= 56 && sc.dec_split && sc.stat_merge;
     switch (phase) {
     case 0:
         RUN(svgp_mnist_encoder_kernel_matrix_fwd(c, theta, images, aux, ws, stream));   // one launch for the two
@@ -407,7 +377,7 @@ int step_phase_impl(const svgp_mnist_cfg* c, int phase, double* theta, const dou
         }
         if (c->titsias) RUN(svgp_gp_titsias_fwd(c, ws, state, stream));
         // m <= 64 with the split on: the `_pre` forms read the effective up-convolution weights phase 0 of this step left in ws.dec_weff
-        if (!large && dec_split_on()) {
+        if (!large && sc.dec_split) {
             RUN(svgp_mnist_decoder_fwd_pre(c, theta, images, ws, stream));
             if (aji_in_dec) RUN(svgp_mnist_decoder_bwd_data_pre_aji(c, theta, images, ws, state, stream));
             else RUN(svgp_mnist_decoder_bwd_data_pre(c, theta, images, ws, state, stream));
@@ -434,7 +404,7 @@ int step_phase_impl(const svgp_mnist_cfg* c, int phase, double* theta, const dou
             RUN(side_join(sd, 1, ms));                                  // (a no-op unless phase 1 left the branch open)
             // round 6: the single-matrix chain of the gradient of Ki (five ~9 us launches) on the branch that has just been joined,
             // beside the channel block on the caller's stream; SVGP_KBAR_BRANCH=0: one after the other
-            if (kbar_branch_on()) {
+            if (sc.kbar_branch) {
                 RUN(side_fork(sd, 1, ms));
                 RUN(svgp_gp_factor_bwd_late_b_kbar(c, ws, state, (void*)sd->s[1]));
                 RUN(svgp_gp_factor_bwd_late_b_channels(c, ws, state, stream));
@@ -444,8 +414,8 @@ int step_phase_impl(const svgp_mnist_cfg* c, int phase, double* theta, const dou
             RUN(svgp_gp_factor_bwd_late_b(c, ws, state, stream));
         } else {
             // channel sum Kbar: inside the next launch; m <= 64: + the decoder's weight gradients as riders (phase 1 ran the data half)
-            if (stat_rides) RUN(svgp_gp_stats_factor_bwd_wgrad(c, images, ws, state, stream));
-            else if (!large && dec_split_on()) RUN(svgp_gp_factor_bwd_nofinal_wgrad(c, images, ws, state, stream));
+            if (stat_rides) RUN(svgp_gp_stats_factor_bwd_wgrad_sched(c, images, ws, state, stream, sc));
+            else if (!large && sc.dec_split) RUN(svgp_gp_factor_bwd_nofinal_wgrad(c, images, ws, state, stream));
             else RUN(svgp_gp_factor_bwd_nofinal(c, ws, state, stream));
         }
         // m <= 64 (round 6): pass 2 of the reverse row stage (the sums over channels, consumed by the kernel-matrix VJP only) rides in the
@@ -463,7 +433,7 @@ int step_phase_impl(const svgp_mnist_cfg* c, int phase, double* theta, const dou
         }
         if (sum_rides) {
             RUN(svgp_mnist_encoder_bwd_km_sum(c, theta, images, aux, ws, state, stream));
-        } else if (!large && !fork2 && enc_km_merge_on()) {
+        } else if (!large && !fork2 && sc.enc_km_merge) {
             RUN(svgp_mnist_encoder_bwd_km(c, theta, images, aux, ws, stream));
         } else {
             if (fork2) RUN(side_fork(sd, 0, ms));
@@ -498,14 +468,14 @@ int step_phase_impl(const svgp_mnist_cfg* c, int phase, double* theta, const dou
 extern "C" int svgp_mnist_step_phase(const svgp_mnist_cfg* c, int phase, double* theta, const double* images,
                                      const double* aux, const double* eps, double* ws, double* state,
                                      double* adam_m, double* adam_v, void* stream) {
-    return step_phase_impl(c, phase, theta, images, aux, eps, ws, state, adam_m, adam_v, stream, 0);
+    return step_phase_impl(c, phase, theta, images, aux, eps, ws, state, adam_m, adam_v, stream, 0, sched_read());
 }
 
 // internal (comm.hip): one phase of a step whose phases are all issued back to back on one stream
 int svgp_mnist_step_phase_deferred(const svgp_mnist_cfg* c, int phase, double* theta, const double* images,
                                    const double* aux, const double* eps, double* ws, double* state, double* adam_m,
-                                   double* adam_v, void* stream) {
-    return step_phase_impl(c, phase, theta, images, aux, eps, ws, state, adam_m, adam_v, stream, 1);
+                                   double* adam_v, void* stream, const SvgpSched& sc) {
+    return step_phase_impl(c, phase, theta, images, aux, eps, ws, state, adam_m, adam_v, stream, 1, sc);
 }
 
 extern "C" int svgp_mnist_train_step(const svgp_mnist_cfg* c, double* theta, const double* images,
@@ -514,8 +484,9 @@ extern "C" int svgp_mnist_train_step(const svgp_mnist_cfg* c, double* theta, con
     SVGP_REQUIRE(c && c->b == c->b_global, SVGP_ERR_INVALID,
                  "svgp_mnist_train_step is the single-GPU form (b == b_global); use svgp_mnist_step_phase "
                  "with all-reduces between phases for data parallelism");
+    const SvgpSched sc = sched_read();
     for (int ph = 0; ph < 4; ++ph) {
-        int rc = step_phase_impl(c, ph, theta, images, aux, eps, ws, state, adam_m, adam_v, stream, 2);
+        int rc = step_phase_impl(c, ph, theta, images, aux, eps, ws, state, adam_m, adam_v, stream, 2, sc);
         if (rc) return rc;
     }
     return SVGP_OK;
@@ -528,7 +499,7 @@ extern "C" int svgp_mnist_train_step(const svgp_mnist_cfg* c, double* theta, con
 // itself for callers that own their side streams (sprites.py).
 extern "C" int svgp_side_streams_prepare(void* stream) {
     Side* sd = nullptr;
-    return side_get((hipStream_t)stream, &sd);
+    return side_get((hipStream_t)stream, sched_read(), &sd);
 }
 extern "C" int svgp_streams_overlap(void* a, void* b, int* out) {
     SVGP_REQUIRE(out, SVGP_ERR_INVALID, "out is NULL");

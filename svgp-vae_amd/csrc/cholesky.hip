@@ -20,12 +20,6 @@ __device__ __forceinline__ real wave_sum_c(real x) {
     return x;
 }
 
-// Lower Cholesky of the 64 x 64 block in Ls (identity-padded beyond n; 256 threads), unblocked right-looking with the
-// matrix in REGISTERS: thread (ti = tid >> 4, tj = tid & 15) owns the 16 elements (ti + 16 a, tj + 16 b).  Per column k the
-// owners of that column publish it (64 values) through a double-buffered LDS vector -- one barrier per column and 16 FMAs
-// per thread; the first version kept the matrix in LDS (3 barriers, 4 LDS accesses per update, an integer division per
-// element): 113 us per diagonal block at m = 800 against the GEMMs' 40-90 us per block step.
-// Ls lower triangle <- L, strict upper triangle <- 0.  A non-positive pivot yields NaN (sqrt), as LAPACK's failure would.
 // 1 / sqrt(x): v_rsq_f64 (about 2^-26) + two Newton steps y <- y + y/2 (1 - x y^2); sqrt(x) = x * (1 / sqrt(x)).  The library
 // sqrt() and the IEEE division each expand to a chain of ~25 dependent float64 instructions, and one of each sat on the
 // critical path of every column of the diagonal-block factorisation.  A non-positive x gives NaN / inf, as sqrt would.
@@ -37,62 +31,17 @@ __device__ __forceinline__ real fast_rsqrt(real x) {
     y = fma(real(0.5) * y, e, y);
     return y;
 }
-// rdiag[k] receives 1 / L_kk (the triangular inverse multiplies by it instead of dividing)
-// (Loading the thread's 16 elements straight from global memory instead of through the LDS image was measured slower:
-// 79 against 58 us per launch of the diagonal-block kernel at m = 800, batch 65.)
-__device__ __forceinline__ void chol64_lds(real (*Ls)[CLD], real (*colk)[CB], real* rdiag) {
-    const int tid = threadIdx.x, ti = tid >> 4, tj = tid & 15;
-    real r[4][4];
-    __syncthreads();                                  // the caller has just filled Ls
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) r[a][b] = Ls[ti + 16 * a][tj + 16 * b];
-#pragma unroll
-    for (int k = 0; k < CB; ++k) {
-        const int kb = k >> 4, kr = k & 15;          // compile-time after unrolling
-        real* ck = colk[k & 1];
-        if (tj == kr) {
-#pragma unroll
-            for (int a = 0; a < 4; ++a) ck[ti + 16 * a] = r[a][kb];
-        }
-        __syncthreads();
-        const real rd = fast_rsqrt(ck[k]), sd = ck[k] * rd;
-        if (tid == 0) rdiag[k] = rd;
-        real li[4], lj[4];
-#pragma unroll
-        for (int a = 0; a < 4; ++a) li[a] = (ti + 16 * a > k) ? ck[ti + 16 * a] * rd : real(0);
-#pragma unroll
-        for (int b = 0; b < 4; ++b) lj[b] = (tj + 16 * b > k) ? ck[tj + 16 * b] * rd : real(0);
-#pragma unroll
-        for (int a = 0; a < 4; ++a)
-#pragma unroll
-            for (int b = 0; b < 4; ++b) r[a][b] -= li[a] * lj[b];
-        if (tj == kr) {                               // the finished column k
-#pragma unroll
-            for (int a = 0; a < 4; ++a) {
-                const int i = ti + 16 * a;
-                r[a][kb] = i == k ? sd : (i > k ? li[a] : r[a][kb]);
-            }
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
-            const int i = ti + 16 * a, j = tj + 16 * b;
-            Ls[i][j] = j <= i ? r[a][b] : real(0);
-        }
-    __syncthreads();
-}
 
-// The same factorisation on ONE wave with a matrix row per lane (64 float64 registers): per column k every lane publishes its
+// Lower Cholesky of the 64 x 64 block in Ls (identity-padded beyond n), unblocked right-looking on ONE wave of the 256-thread
+// workgroup with a matrix row per lane (64 float64 registers).  Ls lower triangle <- L, strict upper triangle <- 0; rdiag[k]
+// receives 1 / L_kk (the triangular inverse multiplies by it instead of dividing).  A non-positive pivot yields NaN (sqrt), as
+// LAPACK's failure would.  Per column k every lane publishes its
 // a_ik through the LDS vector, reads the column back as wave-uniform (broadcast) LDS loads and applies
 // a_ij -= (a_ik / a_kk) a_jk to its row -- no workgroup barrier (LDS operations of one wave complete in order), the next
 // column's element is updated and published first so its LDS round trip hides behind the rest of the row update.
-// 2016 FMAs per lane in all (4 cycles each) against 64 x (barrier + LDS round trip + rsqrt chain + 16 FMAs) of chol64_lds:
-// DIAGTIMES in DESIGN.md section 11.  The other three waves wait at the closing barrier.
+// 2016 FMAs per lane in all (4 cycles each).  The other three waves wait at the closing barrier.
+// (tried: four waves with 4 x 4 register tiles and one barrier per column -- 64 x (barrier + LDS round trip + rsqrt chain + 16
+// FMAs), 475 ns per column, 30 us per block at m = 800; removed)
 #define CHOL_PIN8(r, a) asm volatile("" : "+v"(r[a]), "+v"(r[a + 1]), "+v"(r[a + 2]), "+v"(r[a + 3]), "+v"(r[a + 4]), "+v"(r[a + 5]), \
                                         "+v"(r[a + 6]), "+v"(r[a + 7]) :: "memory")
 // column k (a template parameter: #pragma unroll gives up on a body this large, and a rolled loop would index the row dynamically).
@@ -184,10 +133,6 @@ __device__ __forceinline__ void chol64_wave(real (*Ls)[CLD], real (*colk)[CB], r
     }
     __syncthreads();
 }
-__device__ __forceinline__ void chol64(real (*Ls)[CLD], real (*colk)[CB], real* rdiag, int onewave) {
-    if (onewave) chol64_wave(Ls, colk, rdiag);
-    else chol64_lds(Ls, colk, rdiag);
-}
 
 // X = L^-1 for the lower-triangular 64 x 64 block in Ls (identity-padded), by halves:
 //   X11 = L11^-1 (wave 0), X22 = L22^-1 (wave 1): lane j solves L x = e_j with x in registers, x_i = ((i == j) - sum_{k<i} l_ik x_k) / l_ii
@@ -252,7 +197,6 @@ struct DiagArgs {
     real* Linv;       // (batch, nblk, 64, 64): slot r0 / 64 receives L_kk^-1 (identity-padded)
     int nblk;
     real* logdet;     // (batch): += 2 sum log diag  (= when first)
-    int onewave;      // chol64_wave instead of chol64_lds
 };
 // one workgroup per matrix: Cholesky of the diagonal block + inverse of its factor + log det contribution
 // dynamic LDS (DIAG_LDS_BYTES: two padded 64 x 64 blocks + the column buffer = 67.6 KB, above the 64 KB a kernel gets
@@ -271,7 +215,7 @@ __global__ __launch_bounds__(256) void k_chol_diag(DiagArgs g) {
         const int i = e / CB, j = e % CB;
         Ls[i][j] = (i < n && j < n) ? A[(size_t)i * g.lda + j] : (i == j ? real(1) : real(0));     // identity pad
     }
-    chol64(Ls, colk, rdiag, g.onewave);
+    chol64_wave(Ls, colk, rdiag);
     real lg = (threadIdx.x < n) ? log(Ls[threadIdx.x][threadIdx.x]) : real(0);
     lg = wave_sum_c(lg);
     if (threadIdx.x == 0) g.logdet[l] = (g.first ? real(0) : g.logdet[l]) + real(2) * lg;
@@ -318,7 +262,6 @@ struct Diag2Args {
     real* Linv;       // (batch, nblk, 64, 64)
     real* Linv2;      // (batch, nblk2, 128, 128): slot r0 / 128
     real* logdet;
-    int onewave;
 };
 // Two 64 x 64 blocks of LDS (68 KB, as k_chol_diag), not four: a workgroup with 135 KB needs a CU with no GEMM workgroup on it
 // (66.5 KB each, two per CU), and inside a training step the chip is full of them on the other streams and on the look-ahead
@@ -339,7 +282,7 @@ __global__ __launch_bounds__(256) void k_chol_diag2(Diag2Args g) {
     real* Xb = g.Linv2 + ((size_t)l * g.nblk2 + g.r0 / (2 * CB)) * (4 * CB * CB);        // 128 x 128, ld 128
     // ---- first 64-block: P = A11 -> L11, Q = X11
     for (int e = threadIdx.x; e < CB * CB; e += blockDim.x) P[e / CB][e % CB] = A[(size_t)(e / CB) * g.lda + e % CB];
-    chol64(P, colk, rdiag, g.onewave);
+    chol64_wave(P, colk, rdiag);
     real lg = (threadIdx.x < CB) ? log(P[threadIdx.x][threadIdx.x]) : real(0);
     lg = wave_sum_c(lg);
     if (threadIdx.x == 0) g.logdet[l] = (g.first ? real(0) : g.logdet[l]) + real(2) * lg;
@@ -389,7 +332,7 @@ __global__ __launch_bounds__(256) void k_chol_diag2(Diag2Args g) {
             Q[i][j] = a22 - acc[u][e];
         }
     // ---- second 64-block: Q -> L22, P = X22
-    chol64(Q, colk, rdiag, g.onewave);
+    chol64_wave(Q, colk, rdiag);
     lg = (threadIdx.x < n2) ? log(Q[threadIdx.x][threadIdx.x]) : real(0);
     lg = wave_sum_c(lg);
     if (threadIdx.x == 0) g.logdet[l] += real(2) * lg;
@@ -526,10 +469,7 @@ extern "C" size_t svgp_potri_workspace_elems(int m, int batch) {
 // svgp_spd_inverse_batched): instead of the whole strict upper triangle only the `ZBAND` columns right of the diagonal are
 // zeroed -- what a tile of at most ZBAND x ZBAND that touches the diagonal can read of it.
 #define ZBAND 128
-static bool potrf_wide_steps(int m) {
-    static const int wide_on = [] { const char* e = getenv("SVGP_POTRF_BLOCK"); return (e && atoi(e) == 64) ? 0 : 1; }();
-    return wide_on && m >= 512;
-}
+static bool potrf_wide_steps(int m) { return m >= 512; }
 static int potrf_impl(int m, int batch, double* A, int lda, long long strideA, double* logdet, double* work, void* stream, int band) {
     SVGP_REQUIRE(m >= 1 && batch >= 0 && lda >= m, SVGP_ERR_INVALID, "bad m / batch / lda (m=%d batch=%d lda=%d)", m, batch, lda);
     if (batch == 0) return SVGP_OK;
@@ -548,20 +488,16 @@ static int potrf_impl(int m, int batch, double* A, int lda, long long strideA, d
     Diag2Args d2;
     d2.m = m; d2.lda = lda; d2.batch = batch; d2.sA = strideA; d2.A = A; d2.Linv = Linv; d2.Linv2 = Linv2; d2.nblk = nblk;
     d2.nblk2 = nblk2; d2.logdet = logdet;
-    // diagonal blocks on one wave with a row per lane (chol64_wave); SVGP_CHOL_WAVE=0: the four-wave register-tiled form
-    static const int onewave = [] { const char* e = getenv("SVGP_CHOL_WAVE"); return (e && e[0] == '0') ? 0 : 1; }();
-    d.onewave = d2.onewave = onewave;
     // Block steps of W = 128 rows from m >= 512 (k_chol_diag2: half the dependent launches, K = 128 products; the triangular inverse
     // of svgp_spd_inverse_batched then starts from 128-blocks: 512 x 16 inverse 557 -> 522 us), 64 below
-    // (SVGP_POTRF_BLOCK=64 forces the 64-wide steps).
     const int W = potrf_wide_steps(m) ? 2 * CB : CB, nstep = (m + W - 1) / W;   // (256 x 17: 243 -> 255 us, 512 x 16: 553 -> 561 with the wide steps)
     // Look-ahead (right-looking with the trailing update split): after panel k is solved, ONLY block column k + 1 is updated on
     // the caller's stream -- that is all the next diagonal block and the next panel solve need -- and the rest of the trailing
     // update (columns k + 2 ..) runs on a side branch beside them: a block step costs max(trailing update, column update +
-    // diagonal block + panel solve) instead of their sum.  SVGP_POTRF_LOOKAHEAD=0: everything in line.  Same operations on the
-    // same values.
-    static const int la_on = [] { const char* e = getenv("SVGP_POTRF_LOOKAHEAD"); return (e && e[0] == '0') ? 0 : 1; }();
-    const bool la = la_on && m >= 640;            // (below, the fork / join per block step costs more than it hides: 512 x 16 553 -> 578 us)
+    // diagonal block + panel solve) instead of their sum.  Same operations on the same values as
+    // the in-line order.
+    const bool la = m >= 640;                     // (below, the fork / join per block step costs more than it hides: 512 x 16 553 -> 578 us)
+    const SvgpSched sc = sched_read();            // (SVGP_STREAM_PROBE, when this call is the first to fork a branch of `stream`)
     void* side = stream;
     bool side_open = false;
     struct JoinGuard {           // an error return inside the loop must not leave the look-ahead branch forked
@@ -609,7 +545,7 @@ static int potrf_impl(int m, int batch, double* A, int lda, long long strideA, d
         RUNC(svgp_dgemm_tri_batched(1, 0, 1, rem, nb1, nbk, -1.0, Pn, W, (long long)m * W, Pn, W, (long long)m * W, 1.0,
                                     trail, lda, strideA, batch, stream));
         // columns k + 2 ..: on the side branch (forked here: after the panel solve and, through stream order, after the join)
-        RUNC(svgp_side_branch_fork(stream, &side, 0));
+        RUNC(svgp_side_branch_fork(sc, stream, &side, 0));
         side_open = true;
         RUNC(svgp_dgemm_tri_batched(1, 0, 1, rem2, rem2, nbk, -1.0, Pn + (size_t)nb1 * W, W, (long long)m * W,
                                     Pn + (size_t)nb1 * W, W, (long long)m * W, 1.0, trail + (size_t)nb1 * lda + nb1, lda, strideA,
@@ -753,9 +689,8 @@ static int potri_impl(int m, int batch, double* A, const double* linv_blocks, co
     }
     // A^-1 = X^T X, X lower triangular: the contraction starts at max(first row, first column) of the tile; the result is
     // symmetric, so only the tiles that touch the lower triangle are computed and stored mirrored (as LAPACK's potri returns one
-    // triangle): 28 instead of 49 tiles per matrix at m = 800 (SVGP_POTRI_FULL=1: both triangles computed)
-    static const int potri_full = [] { const char* e = getenv("SVGP_POTRI_FULL"); return (e && e[0] == '1') ? 1 : 0; }();
-    RUNC(svgp_dgemm_tri_batched(potri_full ? (2 | 4) : (1 | 2 | 4 | 16), 1, 0, m, m, m, 1.0, X, m, mm, X, m, mm, 0.0, A, m, mm, batch,
+    // triangle): 28 instead of 49 tiles per matrix at m = 800 (tried: both triangles computed; removed)
+    RUNC(svgp_dgemm_tri_batched(1 | 2 | 4 | 16, 1, 0, m, m, m, 1.0, X, m, mm, X, m, mm, 0.0, A, m, mm, batch,
                                 stream));
     return SVGP_OK;
 }

@@ -334,15 +334,18 @@ struct Point {
 // (measured with a 1-rank communicator at m = 256, L = 16: the pack / unpack launches cost ~100 us per step, the 44 % of 8.4 MB
 // they take off each of the four points is worth ~15 us apiece on xGMI; at m = 800, L = 64 a point is 328 MB)
 bool dp_pack_default(int m) { return m >= 512; }
+}  // namespace
+extern "C" int svgp_dp_pack_default(int m) { return dp_pack_default(m) ? 1 : 0; }
+namespace {
 // Whatever way svgp_mnist_train_step_dp returns, an RCCL group it opened is closed and a side branch it forked is joined
 // (an error inside a group left ncclGroup depth above zero -- every later RCCL call of the thread deferred --, an
 // error behind the fork an unjoined branch, which under stream capture is an unjoined capture).
 struct DpGuard {
-    void* comm; void* stream;
+    void* comm; void* stream; const SvgpSched& sc;
     bool group = false, forked = false;
     int begin_group() { int rc = svgp_comm_group_begin(comm); group = rc == SVGP_OK; return rc; }
     int end_group() { group = false; return svgp_comm_group_end(comm); }
-    int fork(void** side) { int rc = svgp_side_branch_fork(stream, side); forked = rc == SVGP_OK; return rc; }
+    int fork(void** side) { int rc = svgp_side_branch_fork(sc, stream, side); forked = rc == SVGP_OK; return rc; }
     int join() { forked = false; return svgp_side_branch_join(stream); }
     ~DpGuard() {
         if (group) (void)svgp_comm_group_end(comm);
@@ -362,7 +365,8 @@ extern "C" int svgp_mnist_train_step_dp(const svgp_mnist_cfg* c, void* comm, dou
     const int G = cm->nranks, L = c->L, m = c->m;
     const bool sharded = m > SVGP_M_MAX && L % G == 0 && !c->titsias && !c->kl_form;
     Point pt{cm, (hipStream_t)stream, -1};
-    DpGuard guard{comm, stream};
+    const SvgpSched sc = sched_read();
+    DpGuard guard{comm, stream, sc};
     if (cm->timing) cm->npoints = 0;
 #define RUN(call) do { rc = (call); if (rc) return rc; } while (0)
     if (!sharded && c->split_grad_exchange) {
@@ -374,30 +378,30 @@ extern "C" int svgp_mnist_train_step_dp(const svgp_mnist_cfg* c, void* comm, dou
         RUN(svgp_mnist_param_layout_get(c, &pl));
         const int64_t off2[2] = {wl.statA, wl.statB}, len2[2] = {wl.statA_len, wl.statB_len};
         for (int ph = 0; ph < 2; ++ph) {
-            RUN(svgp_mnist_step_phase_deferred(c, ph, theta, images, aux, eps, ws, state, adam_m, adam_v, stream));
+            RUN(svgp_mnist_step_phase_deferred(c, ph, theta, images, aux, eps, ws, state, adam_m, adam_v, stream, sc));
             RUN(pt.begin());
             RUN(svgp_allreduce_sum_f64(comm, ws + off2[ph], len2[ph], stream));
             RUN(pt.end());
         }
-        RUN(svgp_mnist_step_phase_deferred(c, 4, theta, images, aux, eps, ws, state, adam_m, adam_v, stream));
+        RUN(svgp_mnist_step_phase_deferred(c, 4, theta, images, aux, eps, ws, state, adam_m, adam_v, stream, sc));
         void* side = stream;
         RUN(guard.fork(&side));
         Point pts{cm, (hipStream_t)side, -1};
         RUN(pts.begin());
         RUN(svgp_allreduce_sum_f64(comm, ws + wl.gradC + pl.n_enc, wl.gradC_len - pl.n_enc, side));
         RUN(pts.end());
-        RUN(svgp_mnist_step_phase_deferred(c, 5, theta, images, aux, eps, ws, state, adam_m, adam_v, stream));
+        RUN(svgp_mnist_step_phase_deferred(c, 5, theta, images, aux, eps, ws, state, adam_m, adam_v, stream, sc));
         RUN(pt.begin());
         RUN(svgp_allreduce_sum_f64(comm, ws + wl.gradC, pl.n_enc, stream));
         RUN(pt.end());
         RUN(guard.join());
-        RUN(svgp_mnist_step_phase_deferred(c, 3, theta, images, aux, eps, ws, state, adam_m, adam_v, stream));
+        RUN(svgp_mnist_step_phase_deferred(c, 3, theta, images, aux, eps, ws, state, adam_m, adam_v, stream, sc));
         return SVGP_OK;
     }
     if (!sharded) {
         const int64_t off[3] = {wl.statA, wl.statB, wl.gradC}, len[3] = {wl.statA_len, wl.statB_len, wl.gradC_len};
         for (int ph = 0; ph < 4; ++ph) {
-            RUN(svgp_mnist_step_phase_deferred(c, ph, theta, images, aux, eps, ws, state, adam_m, adam_v, stream));
+            RUN(svgp_mnist_step_phase_deferred(c, ph, theta, images, aux, eps, ws, state, adam_m, adam_v, stream, sc));
             if (ph < 3) {
                 RUN(pt.begin());
                 RUN(svgp_allreduce_sum_f64(comm, ws + off[ph], len[ph], stream));
@@ -411,10 +415,8 @@ extern "C" int svgp_mnist_train_step_dp(const svgp_mnist_cfg* c, void* comm, dou
     cc.rep_weight = 1.0;                         // Kbar = this rank's channel-window share: every share counts
     const int nl = L / G, l0 = cm->rank * nl;
     const int64_t mm = (int64_t)m * m, Lmm = (int64_t)L * mm, Lm = (int64_t)L * m;
-    const char* ev_pack = getenv("SVGP_DP_PACK");
-    const bool pack = ev_pack ? ev_pack[0] != '0' : dp_pack_default(m);
-    const char* ev_side = getenv("SVGP_SIDE_STREAMS");
-    const bool fork = !(ev_side && ev_side[0] == '0');
+    const bool pack = sc.dp_pack < 0 ? dp_pack_default(m) : sc.dp_pack != 0;
+    const bool fork = !sc.side_off;
     const int64_t pe = svgp_sym_packed_elems(m);
     SVGP_REQUIRE(!pack || wl.xpack_len >= (int64_t)L * pe, SVGP_ERR_INVALID,
                  "the packed exchange needs the workspace's wire buffer: lay the workspace out with cfg.single_stat_block = 1");
@@ -430,8 +432,7 @@ extern "C" int svgp_mnist_train_step_dp(const svgp_mnist_cfg* c, void* comm, dou
     // the channel-independent block of the forward factor stage ((K + jI)^-1, Kn Ki, q, W, P^T -- every rank computes it, and with
     // L / G channels per rank it is most of the stage) on the side branch from here on, beside the statistics, exchange point 1
     // and the window's channel inverses; joined where u = Ki mu needs it (as svgp_mnist_train_step does on one GPU, api.hip)
-    const char* ev_k = getenv("SVGP_KONLY_BRANCH");
-    const bool ksplit = fork && m < SVGP_CHOL_INVERSE_MIN_M && !(ev_k && ev_k[0] == '0');
+    const bool ksplit = fork && m < SVGP_CHOL_INVERSE_MIN_M && sc.konly_branch;
     void* side0 = stream;
     if (ksplit) RUN(guard.fork(&side0));
     RUN(svgp_gp_stats_fwd(&cc, ws, stream));         // (issued first: the branch's 15 launches would hold the caller's stream back)
@@ -499,8 +500,7 @@ extern "C" int svgp_mnist_train_step_dp(const svgp_mnist_cfg* c, void* comm, dou
         // round 6 (as svgp_mnist_train_step does on one GPU, api.hip): the single-matrix chain of the gradient of Ki -- five small launches
         // that every rank runs in full, while the channel block covers its L / G channels only -- on the branch that has just been
         // joined, beside the channel block.  SVGP_KBAR_BRANCH=0: one launch after the other.
-        const char* ev_kb = getenv("SVGP_KBAR_BRANCH");
-        if (!(ev_kb && ev_kb[0] == '0')) {
+        if (sc.kbar_branch) {
             RUN(svgp_big_factor_bwd(&cc, wl, ws, state, stream, l0, nl, 6));
             void* side2 = stream;
             RUN(guard.fork(&side2));
@@ -531,7 +531,7 @@ extern "C" int svgp_mnist_train_step_dp(const svgp_mnist_cfg* c, void* comm, dou
     RUN(pt.begin());
     RUN(svgp_allreduce_sum_f64(comm, ws + wl.gradC, wl.gradC_len, stream));
     RUN(pt.end());
-    RUN(svgp_mnist_step_phase_deferred(&cc, 3, theta, images, aux, eps, ws, state, adam_m, adam_v, stream));
+    RUN(svgp_mnist_step_phase_deferred(&cc, 3, theta, images, aux, eps, ws, state, adam_m, adam_v, stream, sc));
 #undef RUN
     return SVGP_OK;
 }

@@ -7,6 +7,7 @@
 #include <cstring>
 
 #include "../../include/svgpvae_hip.h"
+#include "sched.hpp"
 
 typedef double real;
 
@@ -39,7 +40,7 @@ void svgp_set_error(const char* fmt, ...);
     } while (0)
 
 // api.hip: fork / join of the library-owned side branch of a caller stream (one per (device, stream))
-int svgp_side_branch_fork(void* main_stream, void** side_stream_out, int k = 1);
+int svgp_side_branch_fork(const SvgpSched& sc, void* main_stream, void** side_stream_out, int k = 1);
 // cholesky.hip: svgp_potrf_batched that zeroes only the 128 columns right of the diagonal (library-internal consumers)
 int svgp_potri_batched_wide(int m, int batch, double* A, const double* potrf_work, double* work, void* stream);
 int svgp_potrf_batched_band(int m, int batch, double* A, int lda, long long strideA, double* logdet, double* work, void* stream);
@@ -52,7 +53,10 @@ int svgp_dgemm_splitk_rows2(int ta, int tb, int M, int N, int K, double alpha, d
 int svgp_gp_factor_fwd_part(const svgp_mnist_cfg* c, double* ws, void* stream, int part);
 int svgp_mnist_step_phase_deferred(const svgp_mnist_cfg* c, int phase, double* theta, const double* images,
                                    const double* aux, const double* eps, double* ws, double* state, double* adam_m,
-                                   double* adam_v, void* stream);
+                                   double* adam_v, void* stream, const SvgpSched& sc);
+// gp_kernels.hip: svgp_gp_stats_factor_bwd_wgrad with the caller's reading of the schedule switches
+int svgp_gp_stats_factor_bwd_wgrad_sched(const svgp_mnist_cfg* c, const double* images, double* ws, const double* state,
+                                         void* stream, const SvgpSched& sc);
 
 // Loss seeds of the reverse passes.  `flags` = cfg.geco | cfg.titsias << 1 (SVGP_LOSS_FLAGS).
 //   seed_T : d(minimised objective)/d(KL_term): GECO -1 (SVGPVAE_model.py:913), beta-ELBO -beta/L (:925); also

@@ -1931,7 +1931,7 @@ static FactBwdArgs make_fb(const svgp_mnist_cfg* c, const svgp_mnist_ws_layout& 
 }
 
 static int factor_bwd_impl(const svgp_mnist_cfg* c, double* ws, const double* state, bool with_final, void* stream,
-                           const double* images_for_wgrad = nullptr, bool with_stats = false);
+                           const double* images_for_wgrad = nullptr, bool with_stats = false, bool stat_four = false);
 extern "C" int svgp_gp_factor_bwd(const svgp_mnist_cfg* c, double* ws, const double* state, void* stream) {
     return factor_bwd_impl(c, ws, state, true, stream);
 }
@@ -1949,13 +1949,17 @@ extern "C" int svgp_gp_factor_bwd_nofinal_wgrad(const svgp_mnist_cfg* c, const d
 }
 // ... and, when nothing is exchanged between the reverse statistics and the reverse factor stage (one GPU), svgp_gp_stats_bwd as
 // P L leading workgroups of that launch too: channel l starts when its own P row partials are there (ws.flags[8 + l])
-extern "C" int svgp_gp_stats_factor_bwd_wgrad(const svgp_mnist_cfg* c, const double* images, double* ws, const double* state,
-                                              void* stream) {
+int svgp_gp_stats_factor_bwd_wgrad_sched(const svgp_mnist_cfg* c, const double* images, double* ws, const double* state,
+                                         void* stream, const SvgpSched& sc) {
     SVGP_REQUIRE(c && c->m <= SVGP_M_MAX, SVGP_ERR_UNSUPPORTED,
                  "the merged reverse statistics + factor launch exists for the LDS-resident stage (m <= %d)", SVGP_M_MAX);
     SVGP_REQUIRE(c->L <= 56, SVGP_ERR_UNSUPPORTED, "ws.flags holds 56 channel counters (L = %d)", c->L);
     SVGP_REQUIRE(images, SVGP_ERR_INVALID, "NULL device pointer");
-    return factor_bwd_impl(c, ws, state, false, stream, images, true);
+    return factor_bwd_impl(c, ws, state, false, stream, images, true, sc.stat_four);
+}
+extern "C" int svgp_gp_stats_factor_bwd_wgrad(const svgp_mnist_cfg* c, const double* images, double* ws, const double* state,
+                                              void* stream) {
+    return svgp_gp_stats_factor_bwd_wgrad_sched(c, images, ws, state, stream, sched_read());
 }
 // m > 64: the two halves of svgp_gp_factor_bwd (gp_large.hip svgp_big_factor_bwd).  _early needs only forward quantities, the
 // loss seeds in `state` and (A_hat + jI)^-1: it may run on another stream, ordered after svgp_gp_factor_fwd_aji_tail, beside
@@ -2022,7 +2026,7 @@ extern "C" int svgp_gp_factor_bwd_late(const svgp_mnist_cfg* c, double* ws, cons
     return svgp_big_factor_bwd(c, wl, ws, state, stream, 0, c->L, 2);
 }
 static int factor_bwd_impl(const svgp_mnist_cfg* c, double* ws, const double* state, bool with_final, void* stream,
-                           const double* images_for_wgrad, bool with_stats) {
+                           const double* images_for_wgrad, bool with_stats, bool stat_four) {
     GET_LAYOUTS();
     SVGP_REQUIRE(ws && state, SVGP_ERR_INVALID, "NULL device pointer");
     if (c->m > SVGP_M_MAX) return svgp_big_factor_bwd(c, wl, ws, state, stream, 0, c->L);
@@ -2032,7 +2036,7 @@ static int factor_bwd_impl(const svgp_mnist_cfg* c, double* ws, const double* st
     size_t lds = mat_lds_pad(m, 4 + keep) + (size_t)(6 * m) * sizeof(real), lds_w = 0;
     bool five = false;
     if (images_for_wgrad) {
-        static const int n_types = [] { const char* e = getenv("SVGP_DEC_RIDER_TYPES"); return (e && e[0] >= '1' && e[0] <= '3') ? e[0] - '0' : 3; }();
+        const int n_types = 3;
         a.wg = svgp_make_dec_wgrad_args(c, wl, images_for_wgrad, ws, state, n_types);
         a.n_riders = a.wg.n_slots * a.wg.n_types;
         lds_w = (size_t)svgp_vae::dec_wgrad_lds(SVGP_BLOCK, c->L, n_types) * sizeof(real);
@@ -2044,7 +2048,7 @@ static int factor_bwd_impl(const svgp_mnist_cfg* c, double* ws, const double* st
         a.n_stat = a.P * c->L;
         a.wait_n = a.P;
         // (SVGP_STAT_FOUR=1: the four-matrix form also where five fit -- what 32 < m <= 64 runs; tests compare the two)
-        five = !c->kl_form && m * m <= 4 * SVGP_BLOCK && !getenv("SVGP_STAT_FOUR");
+        five = !c->kl_form && m * m <= 4 * SVGP_BLOCK && !stat_four;
         if (five) lds = mat_lds_pad(m, 5 + keep) + (size_t)(6 * m) * sizeof(real);
         if (images_for_wgrad && lds_w > lds) lds = lds_w;
         a.flags = reinterpret_cast<unsigned long long*>(ws + wl.flags);

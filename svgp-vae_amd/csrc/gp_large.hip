@@ -484,10 +484,6 @@ __global__ __launch_bounds__(256) void k_big_gemv_fb(FbArgs a, const real* __res
 }
 
 inline unsigned nblk(long long n) { return (unsigned)((n + 255) / 256); }
-inline bool x0_epilogue_on() {
-    const char* e = getenv("SVGP_X0_EPILOGUE");
-    return !(e && e[0] == '0');
-}
 
 }  // namespace
 
@@ -597,7 +593,7 @@ int svgp_big_stats(const svgp_mnist_cfg* c, const svgp_mnist_ws_layout& wl, doub
         // Round 6: the product's epilogue writes X0 = A2 - g3/2 SW in SW's place (mm2) -- what the late reverse factor half needs
         // of SW; the rank-one part of X is applied after the Sigma^-1 sandwiches (FbArgs.rank1_late), so the 1 GB pass k_big_fb_sibar
         // (0.42 ms at m = 800, L = 64) is gone.  -g3/2 is a device scalar (the loss seeds live in the state vector): written by
-        // k_big_recip, read by the epilogue.  SVGP_X0_EPILOGUE=0: plain SW + the pass (A / B measurements).
+        // k_big_recip, read by the epilogue.  (tried: plain SW + the pass; removed)
         if (!c->titsias && c->b == c->b_global && c->b < 3 * m) {
             real* mhalf_g3 = s.ldtmp + c->L + 8;       // (slots L + 1 .. L + 15 of the log-det scratch are free)
             hipLaunchKernelGGL(k_big_recip, dim3(nblk((long long)b * L)), dim3(256), 0, st, b * L, ws + wl.qnet_var, s.wst,
@@ -607,7 +603,7 @@ int svgp_big_stats(const svgp_mnist_cfg* c, const svgp_mnist_ws_layout& wl, doub
             ep.E = ws + wl.A2; ep.lde = m; ep.se = (long long)m * m; ep.g1 = 1.0; ep.alpha_dev = mhalf_g3;
             ep.e_sym = 1;                              // A2 = Kn^T diag(g_pv) Kn: a mirrored-store product
             RUNC(svgp_dgemm_symout_batched(c->gemm_f32 != 0, 1, 0, m, b, 1.0, s.W, m, 0, s.W, m, 0, 0.0, s.mm2, m, (long long)m * m, L,
-                                           stream, s.wst, L, 1, x0_epilogue_on() ? &ep : nullptr));
+                                           stream, s.wst, L, 1, &ep));
         }
     }
     // (K_mm + jI)^-1 and its log det (SVGPVAE_model.py:239,270,273) are formed by svgp_big_factor_fwd, in the same
@@ -769,7 +765,7 @@ int svgp_big_factor_bwd(const svgp_mnist_cfg* c, const svgp_mnist_ws_layout& wl,
     const bool sw_rows = c->b == c->b_global && c->b < 3 * m;
     // X0 = A2 - g3/2 SW sits in mm2 in SW's place (epilogue of the SW product, svgp_big_stats mode 1; all L channels: the row form
     // exists for b == b_global, i.e. without a channel window).  mm2 is only read here: the stage can be repeated on a workspace.
-    const bool x0_ready = has_sw && sw_rows && l0 == 0 && nl == c->L && x0_epilogue_on();
+    const bool x0_ready = has_sw && sw_rows && l0 == 0 && nl == c->L;
     a.rank1_late = x0_ready ? 1 : 0; a.t = ws + wl.t + ov; a.vbar = ws + wl.vbar + ov;
     if (has_sw && !sw_rows && (part == 0 || part == 1 || part == 3)) {
         GEMM(0, 1, m, m, m, 1.0, ws + wl.S + om, m, mm, s.PT, m, 0, 0.0, s.mm1, m, mm, L);        // T = S P   (P = (P^T)^T)

@@ -46,35 +46,10 @@ __device__ __forceinline__ const real* act_row(const SpK& a, int n) {
     return a.table + (size_t)((long long)a.aux[(size_t)n * (1 + a.Lc)]) * a.La;
 }
 
-__global__ __launch_bounds__(256) void k_sprites_kernel_fwd(SpK a, real* __restrict__ K, real* __restrict__ Kn,
-                                                            real* __restrict__ knn) {
-    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long long nbm = (long long)a.b * a.m, nmm = (long long)a.m * a.m;
-    const int D = a.La + a.Lc;
-    const real la = a.se[0], sa = a.se[1], lc = a.se[2], sc = a.se[3];
-    real ca, cb, d2;
-    if (idx < nbm) {
-        const int n = (int)(idx / a.m), j = (int)(idx % a.m);
-        const real* z = a.ip + (size_t)j * D;
-        Kn[idx] = grp_k(a.kind, act_row(a, n), z, a.La, la, sa, ca, cb, d2) *
-                  grp_k(a.kind, a.aux + (size_t)n * (1 + a.Lc) + 1, z + a.La, a.Lc, lc, sc, ca, cb, d2);
-    } else if (idx < nbm + nmm) {
-        const long long o = idx - nbm;
-        const real* zi = a.ip + (size_t)(o / a.m) * D;
-        const real* zj = a.ip + (size_t)(o % a.m) * D;
-        K[o] = grp_k(a.kind, zi, zj, a.La, la, sa, ca, cb, d2) * grp_k(a.kind, zi + a.La, zj + a.La, a.Lc, lc, sc, ca, cb, d2);
-    } else if (idx < nbm + nmm + a.b) {
-        const int n = (int)(idx - nbm - nmm);
-        const real* xa = act_row(a, n);
-        const real* xc = a.aux + (size_t)n * (1 + a.Lc) + 1;
-        knn[n] = grp_k(a.kind, xa, xa, a.La, la, sa, ca, cb, d2) * grp_k(a.kind, xc, xc, a.Lc, lc, sc, ca, cb, d2);
-    }
-}
-
-// The same values by 16 x 16 output tiles: the 16 + 16 feature rows of a tile are staged in LDS with coalesced loads (the element-wise
-// kernel above reads 2 D per-lane doubles with a row stride between the lanes for every entry: 165 us for the 1.04 M entries of the
-// SPRITES shape), and the norms of the cosine-normalised kernel are formed once per row instead of once per entry -- by the same
-// expressions, so the entries are bit-identical to k_sprites_kernel_fwd's (which stays for k_nn and as the reference form).
+// K_nm, K_mm and k_nn by 16 x 16 output tiles: the 16 + 16 feature rows of a tile are staged in LDS with coalesced loads, and the
+// norms of the cosine-normalised kernel are formed once per row instead of once per entry.
+// (tried: one thread per entry, 2 D per-lane doubles read with a row stride between the lanes -- 165 us for the 1.04 M entries of
+// the SPRITES shape; removed)
 // blocks [0, nbt nmt): tiles of K_nm; [.., + nmt nmt): tiles of K_mm; the rest: k_nn, 256 entries each.
 __global__ __launch_bounds__(256) void k_sprites_kernel_fwd_tiles(SpK a, int nbt, int nmt, real* __restrict__ K, real* __restrict__ Kn,
                                                                   real* __restrict__ knn) {
@@ -568,15 +543,9 @@ extern "C" int svgp_sprites_kernel_matrix_fwd(const svgp_sprites_kcfg* c, const 
     int rc = make_spk(c, aux, ip, table, se, a);
     if (rc) return rc;
     SVGP_REQUIRE(K && Kn && knn, SVGP_ERR_INVALID, "NULL pointer");
-    static const int tiles_on = [] { const char* e = getenv("SVGP_SPRITES_KFWD_TILES"); return (e && e[0] == '0') ? 0 : 1; }();
-    if (tiles_on) {
-        const int nbt = (a.b + 15) / 16, nmt = (a.m + 15) / 16;
-        hipLaunchKernelGGL(k_sprites_kernel_fwd_tiles, dim3((unsigned)(nbt * nmt + nmt * nmt) + nb256(a.b)), dim3(256), 0,
-                           (hipStream_t)stream, a, nbt, nmt, K, Kn, knn);
-    } else {
-        const long long tot = (long long)a.b * a.m + (long long)a.m * a.m + a.b;
-        hipLaunchKernelGGL(k_sprites_kernel_fwd, dim3(nb256(tot)), dim3(256), 0, (hipStream_t)stream, a, K, Kn, knn);
-    }
+    const int nbt = (a.b + 15) / 16, nmt = (a.m + 15) / 16;
+    hipLaunchKernelGGL(k_sprites_kernel_fwd_tiles, dim3((unsigned)(nbt * nmt + nmt * nmt) + nb256(a.b)), dim3(256), 0,
+                       (hipStream_t)stream, a, nbt, nmt, K, Kn, knn);
     SVGP_LAUNCH_CHECK();
     return SVGP_OK;
 }
@@ -631,9 +600,8 @@ extern "C" int svgp_sprites_kernel_matrix_bwd(const svgp_sprites_kcfg* c, const 
     real* d_xa = scratch;
     real* part_se = scratch + (size_t)a.b * a.La;
     hipStream_t st = (hipStream_t)stream;
-    static const int tiles_on = [] { const char* e = getenv("SVGP_SPRITES_KBWD_TILES"); return (e && e[0] == '0') ? 0 : 1; }();
-    const int bk = tiles_on ? sprites_bwd_bucket(a.La, a.Lc) : 0;
-    if (bk) {                                             // the tiled form
+    const int bk = sprites_bwd_bucket(a.La, a.Lc);
+    if (bk) {                                             // the tiled form (else: feature groups outside the two template buckets)
         int s0, s1;
         sprites_bwd_splits(a, &s0, &s1);
         const int NV = bk == 1 ? 8 + 16 + 4 : 16 + 32 + 4;

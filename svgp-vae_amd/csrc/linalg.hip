@@ -700,20 +700,17 @@ static int gemm_launch(int prec, int tri, int ta, int tb, int M, int N, int K, d
     int wt = (blocks128 >= 192 && cost4 <= cost2) ? 4 : (blocks64 < 256 ? 1 : 2);
     // mixed tiling (k_gemm_mixed, float64): an extent with a remainder of at most 64 modulo 128 gets 128-tiles + one row / column
     // of 32- or 64-wide edge tiles
-    static const int mixed_on = [] { const char* e = getenv("SVGP_GEMM_MIXED"); return (e && e[0] == '0') ? 0 : 1; }();
     const int rem_m = M % 128, rem_n = N % 128;
     const bool edge_m = rem_m > 0 && rem_m <= 64, edge_n = rem_n > 0 && rem_n <= 64;
     // (short contractions -- the K = 128 panel solves / column updates of the blocked Cholesky -- are prologue / epilogue bound and
     // rarely fill two workgroups per CU with 128-tiles: 672 x 128 x 128 x 65 48.2 -> 38.8 us with the 64-tiles, 544: 46.3 -> 34.5;
     // potrf 800 x 65 1.32 -> 1.13 ms, SPRITES m = 800 step 25.45 -> 25.10 ms)
-    static const int shortk_on = [] { const char* e = getenv("SVGP_GEMM_SHORTK"); return (e && e[0] == '0') ? 0 : 1; }();
-    const bool short_k = shortk_on && K <= 256 && blocks128 < 1024;
-    const bool mixed = mixed_on && prec == 0 && M >= 128 && N >= 128 && blocks128 >= 192 && (edge_m || edge_n) && !short_k;
+    const bool short_k = K <= 256 && blocks128 < 1024;
+    const bool mixed = prec == 0 && M >= 128 && N >= 128 && blocks128 >= 192 && (edge_m || edge_n) && !short_k;
     if (short_k && prec == 0 && wt == 4 && blocks64 >= 512) wt = 2;       // (640 x 128 x 128 x 65: 38.9 -> 37.0 us, 512: 39.0 -> 32.5)
     int edge_w = ((edge_m && rem_m > 32) || (edge_n && rem_n > 32)) ? 2 : 1;
     if (mixed) wt = 4;
     // 128 a + 96 b decomposition of both extents (E = 3) when neither is small: least padding, then most 128-tiles
-    static const int t96_on = [] { const char* e = getenv("SVGP_GEMM_T96"); return (e && e[0] == '0') ? 0 : 1; }();
     auto cut = [](int X, int& a, int& b) {
         int best = 1 << 30;
         for (int bb = 0; bb <= 3; ++bb) {
@@ -724,12 +721,11 @@ static int gemm_launch(int prec, int tri, int ta, int tb, int M, int N, int K, d
     };
     int am = 0, bm = 0, an = 0, bn = 0;
     cut(M, am, bm); cut(N, an, bn);
-    const bool t96 = t96_on && mixed_on && prec == 0 && M >= 192 && N >= 192 && blocks128 >= 192 && (bm > 0 || bn > 0);
+    const bool t96 = prec == 0 && M >= 192 && N >= 192 && blocks128 >= 192 && (bm > 0 || bn > 0);
     if (t96) { wt = 4; edge_w = 3; }
     // rectangular tiles (float64): 128 x 64 where 128-tiles leave fewer than two workgroups per CU, 64 x 32 where 64-tiles do
-    static const int rect_on = [] { const char* e = getenv("SVGP_GEMM_RECT"); return (e && e[0] == '0') ? 0 : 1; }();
     int rwm = 0, rwn = 0;
-    if (rect_on && prec == 0 && !mixed && !t96 && !(tri & 1)) {
+    if (prec == 0 && !mixed && !t96 && !(tri & 1)) {
         if (wt == 4 && blocks128 < 512 && M % 128 == 0 && N % 64 == 0) { rwm = 4; rwn = 2; }
         else if (wt == 2 && blocks64 < 512 && M % 64 == 0 && N % 32 == 0) { rwm = 2; rwn = 1; }
     }

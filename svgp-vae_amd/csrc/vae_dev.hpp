@@ -391,21 +391,6 @@ struct UpConv3 {
         __syncthreads();
     }
 
-    // out = elu(conv(up(in)) + bias): four output-parity classes, each a 4-tap MFMA gather-GEMM on the low-res input
-    static __device__ void fwd_mfma(const real* in, const real* We, const real* bias, real* out) {
-#pragma unroll
-        for (int cls = 0; cls < 4; ++cls) {
-            const int opy = cls >> 1, opx = cls & 1;
-            const int by = opy - PAD, bx = opx - PAD, py = by & 1, px = bx & 1, dY = (by - py) / 2, dX = (bx - px) / 2;
-            const int oy[4] = {dY, dY, dY + 1, dY + 1}, ox[4] = {dX, dX + 1, dX, dX + 1};
-            int wo[4];
-#pragma unroll
-            for (int t = 0; t < 4; ++t) wo[t] = ((py * 2 + px) * 4 + t) * CIN * COUT;
-            gg_fwd<4, false, true, CIN, COUT, NT>(in, HS, HS, HOUT / 2, HOUT / 2, 1, 1, oy, ox, wo, We, COUT, bias, out, HOUT, 2, 2,
-                                              opy, opx);
-        }
-    }
-
     // din (HS x HS x CIN) from dpre (HOUT x HOUT x COUT): one 16-tap gather-GEMM with input stride 2 over dpre
     static __device__ void bwd_data_mfma(const real* dpre, const real* We, real* din) {
         int oy[16], ox[16], wo[16];

@@ -7,7 +7,6 @@ Counterpart of the reference's graph construction + `sess.run([optim_step, ...])
 torch.distributed only; every kernel is in libsvgpvae_hip.so.
 """
 import ctypes as C
-import os
 
 import numpy as np
 import torch
@@ -207,11 +206,10 @@ def _gloo_reduce_scatter(out, chunks, r, group):
 
 
 def dp_pack_enabled(m):
-    """Whether the channel-sharded exchange moves its (L,m,m) blocks tile-packed: SVGP_DP_PACK=0/1, default from m >= 512
-    (the rule of svgp_mnist_train_step_dp)."""
-    import os
-    e = os.environ.get("SVGP_DP_PACK")
-    return (e[0] != "0") if e else m >= 512
+    """Whether the channel-sharded exchange moves its (L,m,m) blocks tile-packed: SVGP_DP_PACK=0/1, default: the library's rule
+    (svgp_dp_pack_default, what svgp_mnist_train_step_dp applies)."""
+    pack = _lib.Schedule().dp_pack
+    return bool(_lib.load_library().svgp_dp_pack_default(m)) if pack is None else pack
 
 
 class RcclComm:
@@ -350,7 +348,7 @@ def concurrent_streams(main, n, device):
     svgp_streams_overlap; measured round 4: a side stream that shares the caller's queue hides nothing).  Candidates come from
     torch's stream pool and are probed with the library's spin / no-op test; if fewer than n concurrent ones exist, the first
     candidates fill up.  SVGP_STREAM_PROBE=0: the first n candidates."""
-    probe = os.environ.get("SVGP_STREAM_PROBE", "1")[0] != "0"
+    probe = _lib.Schedule().stream_probe
     flag = C.c_int(0)
 
     def overlap(a, b):
@@ -398,7 +396,7 @@ class MnistStepEngine:
                          # Every rank must be built with the SAME b_max (the partial count is a function of the capacity);
                          # attach_comm / run check the block lengths across ranks.
                          # (single_stat_block on one rank: the kernel configuration of a multi-rank step, bench.py --force-comm)
-                         single_stat_block=int((world_size > 1 and (m > 64 or os.environ.get("SVGP_DP_STAT_PARTIALS") == "0"))
+                         single_stat_block=int((world_size > 1 and (m > 64 or not _lib.Schedule().dp_stat_partials))
                                                if single_stat_block is None else single_stat_block),
                          # row-sharded data parallelism: the gradient all-reduce in two parts, the first one (decoder + GP parameters
                          # + scalar sums) beside the encoder's reverse pass (include/svgpvae_hip.h: cfg.split_grad_exchange); off by
@@ -621,7 +619,7 @@ class MnistStepEngine:
         xp = [self.ws[self.wl.xpack:self.wl.xpack + L * pe]]            # ONE wire buffer: every point moves one symmetric block
         sym = lambda k, avg=False, pre=False: SymBlock(m, L, avg, xp[k], pre) if pack else None
         plain = lambda kind, *fields: [ExchangeOp(kind, fld(n, per)) for n, per in fields]
-        fork = os.environ.get("SVGP_SIDE_STREAMS", "1")[0] != "0"
+        fork = not _lib.Schedule().side_off
         side = self._side_stream() if fork else self.stream
         wptr = lambda name, packed_k=None: (xp[packed_k].data_ptr() + 8 * l0 * pe) if packed_k is not None else \
             (self.ws.data_ptr() + 8 * (getattr(self.wl, name) + l0 * mm))

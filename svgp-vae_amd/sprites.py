@@ -22,7 +22,6 @@ runs every product of the large-m GP block on the float32 MFMA (float64 storage)
 products.  The m x m factorisations / inverses, the scalar epilogue, Adam and the master parameters stay float64.
 """
 import ctypes as C
-import os
 import math
 
 import numpy as np
@@ -130,8 +129,8 @@ class SpritesStepEngine:
         # stream: the first part of the early reverse half runs beside the forward tail (SVGP_SIDE_STREAMS=2: behind it).
         # Measured on one box, m = 800: one stream 31.8 ms, two 30.4, three 30.1 per step (round 2).  The two are picked by the
         # concurrency probe (engine.concurrent_streams): streams that share a hardware queue with self.stream hide nothing.
-        mode = os.environ.get("SVGP_SIDE_STREAMS")
-        picked = [] if mode == "0" else concurrent_streams(self.stream, 1 if mode == "2" else 2, self.dev)
+        sched = _lib.Schedule()
+        picked = [] if sched.side_off else concurrent_streams(self.stream, 1 if sched.side_single else 2, self.dev)
         self.side = picked[0] if picked else None
         self.side2 = picked[1] if len(picked) > 1 else None
         call("svgp_side_streams_prepare", self.stream.cuda_stream)     # the library's own branches (Cholesky look-ahead) of the three
@@ -488,8 +487,8 @@ class SpritesStepEngine:
                 return r_, aux_
 
             # the step opens with two independent chains of small launches: representation network -> auxiliary data -> kernel
-            # matrices, and the encoder; the first goes to the side stream (SVGP_SPRITES_ENC_SIDE=0 / one stream: in line)
-            if self.side is not None and os.environ.get("SVGP_SPRITES_ENC_SIDE") != "0":
+            # matrices, and the encoder; the first goes to the side stream (one stream: in line)
+            if self.side is not None:
                 self.side.wait_stream(self.stream)
                 with torch.cuda.stream(self.side):
                     r, aux = repr_and_kernel_matrices(self.side)
@@ -620,7 +619,7 @@ class SpritesStepEngine:
                 # there for the second inverse + early half with that work ready (kernel trace, round 5)
                 call("svgp_gp_factor_bwd_late_a", cp, ws, st, s)
                 self.stream.wait_stream(self.side)
-                if os.environ.get("SVGP_KBAR_BRANCH") != "0":
+                if _lib.Schedule().kbar_branch:
                     # round 6 (as csrc/api.hip does for the MNIST step): the single-matrix chain of the gradient of Ki on the branch that
                     # has just been joined, beside the channel block
                     self.side.wait_stream(self.stream)
@@ -642,7 +641,7 @@ class SpritesStepEngine:
             # most of the time): kernel-matrix reverse pass -> representation network, and encoder head -> encoder.  Both need
             # only the reverse row stage above, so the encoder chain goes to the side stream (idle since the reverse factor stage)
             # with its own weight-gradient scratch: 1.12 -> 0.65 ms for this tail at m = 800.  SVGP_SIDE_STREAMS=0: in line.
-            enc_side = self.side is not None and os.environ.get("SVGP_SPRITES_ENC_SIDE") != "0"
+            enc_side = self.side is not None
 
             def encoder_bwd(sx, scratch):
                 d_enc = torch.empty(b, 2 * L, **f64)

@@ -1,7 +1,7 @@
 """Development probe: the convolution entry points (conv_taps.hip) on the spritesVAE layer shapes at 500 frames.
 Descriptors, effective / transposed weights and outputs are built once; each C entry point is then timed alone with HIP events
 over back-to-back launches -> algorithmic TFLOP/s (2 * taps * Ci * Co * output pixels; up layers: the four 2x2 parity classes).
-    python tools/conv_probe.py [frames] [f32]          SVGP_CONV_DIRECT=0: the workgroup-tiled kernels only"""
+    python tools/conv_probe.py [frames] [f32]"""
 import os, sys
 sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
 import torch
