@@ -306,30 +306,43 @@ int svgp_gp_posterior_fwd_with_aji(const svgp_mnist_cfg*, const double* eps, dou
  * svgp_gp_stats_bwd, so the second batched inverse of the step runs beside them (svgp_mnist_step_phase does this on a
  * library-owned side stream unless SVGP_SIDE_STREAMS=0). */
 int svgp_gp_factor_fwd_aji_tail(const svgp_mnist_cfg*, double* ws, void* stream);
-/* m > 64: svgp_gp_factor_bwd in two halves.  _early (T1 = S Ki, Ki S Ki, T1 A_hat, Abar, Gbar = K Abar, Z = Sigma^-1 Gbar,
- * Gbar K: 5.5 of the stage's 8 m^3 L products) needs forward quantities, the loss seeds of `state` and (A_hat + jI)^-1 only --
- * no reverse statistic -- and may run on the stream of svgp_gp_factor_fwd_aji_tail, behind it; _late needs _early, A2 / ud /
- * td (svgp_gp_stats_bwd and their exchange).  _early + _late == svgp_gp_factor_bwd, operation for operation. */
+/* m > 64: the pieces of the two factor stages.  A piece is what a caller may issue on its own, on another stream, before or
+ * after a join; an entry point runs its pieces in the order of the table, and the entry points of one stage that together hold
+ * every piece once == the stage itself, operation for operation.
+ *
+ *   forward   computes                                               entry points that contain it
+ *   K         (K + jI)^-1, its log det, Kn Ki, q, W, P^T            svgp_gp_factor_fwd, _defer_aji
+ *   SIG       Sigma^-1, t, G, A_hat (+ A_hat + jI), mu              svgp_gp_factor_fwd, _defer_aji
+ *   KL        u = Ki mu, the trace terms of KL_l                    svgp_gp_factor_fwd, _defer_aji
+ *   TAIL      (A_hat + jI)^-1, its log det, KL_l                    svgp_gp_factor_fwd, _aji_tail
+ *
+ *   reverse   computes                                               entry points that contain it (svgp_gp_factor_bwd and ...)
+ *   SW        SW = P^T S P, unless svgp_gp_stats_bwd formed it      _early, _early_a
+ *   EARLY_B   H = G (Ki - (A_hat + jI)^-1), H G^T, channel sums     _early, _early_b
+ *   LATE_A    the vector chain ubar, mubar, tbar (+ X block *)      _late, _late_a
+ *   CHANNELS  (X block otherwise,) Ssym, the channel sum of Sg      _late, _late_b, _late_b_channels
+ *   KBAR      K Pbar^T, Kib, Ki Kib Ki, Pbar^T Ki (five launches)   _late, _late_b, _late_b_kbar
+ *   FINAL     the assembly of Kbar                                  _late, _late_b, _late_b_final
+ *   (*) X block = X, vbar, Si X, -(Si X) Si: in LATE_A when the statistic SW is formed by svgp_gp_stats_bwd (all rows local,
+ *       b < 3 m) or with cfg.titsias -- the row form -- and in CHANNELS otherwise.
+ *
+ * What a piece needs: SW forward quantities only, not even (A_hat + jI)^-1 -- it may run beside _aji_tail on a third stream;
+ * EARLY_B also the loss seeds of `state` and (A_hat + jI)^-1, no reverse statistic -- it may run on the stream of _aji_tail,
+ * behind it; the late pieces A2 / ud / td (svgp_gp_stats_bwd and their exchange).  LATE_A reads nothing the early half writes:
+ * a caller that runs the early half on another stream issues it BEFORE joining that stream.  KBAR reads nothing of CHANNELS
+ * and may run beside it on another stream; FINAL follows both.
+ * WRITE SET of _late_a: the scratch vectors ubar / mubar / tbar always; in the row form also ws.vbar, the Ssym slot
+ * (it parks Si X there) and scratch matrix 1 (X, then -(Si X) Si) -- none of which the early half touches IN THAT FORM (it then
+ * skips its own T = S P in scratch matrix 1).  The form is a function of cfg.b / cfg.b_global / cfg.titsias alone and is
+ * evaluated by svgp_gp_stats_bwd, _early and _late_a independently: a caller must not change those fields between the three
+ * calls of one step (svgp_mnist_step_phase / _train_step never do; row-form X0 itself is left in scratch matrix 2 by
+ * svgp_gp_stats_bwd, so the stage may be repeated on a workspace). */
 int svgp_gp_factor_bwd_early(const svgp_mnist_cfg*, double* ws, const double* state, void* stream);
 int svgp_gp_factor_bwd_late(const svgp_mnist_cfg*, double* ws, const double* state, void* stream);
-/* _early = _early_a + _early_b: _early_a (T1, Ki S Ki, T1 A_hat) does not even need (A_hat + jI)^-1 and may run beside
- * svgp_gp_factor_fwd_aji_tail on a third stream; _early_b (Abar, Gbar, Z, Gbar K) is ordered behind both. */
 int svgp_gp_factor_bwd_early_a(const svgp_mnist_cfg*, double* ws, const double* state, void* stream);
 int svgp_gp_factor_bwd_early_b(const svgp_mnist_cfg*, double* ws, const double* state, void* stream);
-/* _late = _late_a + _late_b: _late_a (the vector chain; with the statistic SW formed by svgp_gp_stats_bwd -- all rows local,
- * b < 3 m -- also X, vbar, Si X and -(Si X) Si) reads nothing the early half writes, so a caller that runs the early half on
- * another stream issues it BEFORE joining that stream; _late_b follows the join.
- * WRITE SET of _late_a: the scratch vectors ubar / mubar / tbar always; in the row form (cfg.b == cfg.b_global,
- * cfg.b < 3 m, or cfg.titsias) also ws.vbar, the Ssym slot (it parks Si X there) and scratch matrix 1 (X, then -(Si X) Si) --
- * none of which the early half touches IN THAT FORM (it then skips its own T = S P in scratch matrix 1).  The form is a function
- * of cfg.b / cfg.b_global / cfg.titsias alone and is evaluated by svgp_gp_stats_bwd, _early and _late_a independently: a caller
- * must not change those fields between the three calls of one step (svgp_mnist_step_phase / _train_step never do; row-form X0
- * itself is left in scratch matrix 2 by svgp_gp_stats_bwd, so the stage may be repeated on a workspace). */
 int svgp_gp_factor_bwd_late_a(const svgp_mnist_cfg*, double* ws, const double* state, void* stream);
 int svgp_gp_factor_bwd_late_b(const svgp_mnist_cfg*, double* ws, const double* state, void* stream);
-/* _late_b in three pieces (round 6): _channels (the channel block: X sandwiches unless _late_a took them, Ssym, the channel sum) and _kbar
- * (the single-matrix chain of the gradient of Ki: K Pbar^T, Kib, Ki Kib Ki, Pbar^T Ki -- five small launches that read nothing of
- * _channels) may run on two streams; _final assembles Kbar and follows both.  _late_b == _channels; _kbar; _final. */
 int svgp_gp_factor_bwd_late_b_channels(const svgp_mnist_cfg*, double* ws, const double* state, void* stream);
 int svgp_gp_factor_bwd_late_b_kbar(const svgp_mnist_cfg*, double* ws, const double* state, void* stream);
 int svgp_gp_factor_bwd_late_b_final(const svgp_mnist_cfg*, double* ws, const double* state, void* stream);
@@ -429,9 +442,9 @@ int svgp_allgather_f64(void* comm, double* buf, int64_t count_per_rank, void* st
  * call; with l0 = 0, nl = L they are svgp_gp_factor_fwd / svgp_gp_factor_bwd                                            */
 int svgp_gp_factor_fwd_channels(const svgp_mnist_cfg*, int l0, int nl, double* ws, void* stream);
 int svgp_gp_factor_bwd_channels(const svgp_mnist_cfg*, int l0, int nl, double* ws, const double* state, void* stream);
-/* ... and their parts, the split of the two-stream step on a channel window: forward part 0 = the whole stage, 1 = without
- * the (A_hat + jI)^-1 tail (svgp_gp_factor_fwd_defer_aji), 2 = the tail (svgp_gp_factor_fwd_aji_tail); reverse part 0 = the
- * whole stage, 1 = early half, 2 = late half, 3 / 4 = the two parts of the early half (svgp_gp_factor_bwd_early_a / _b).  */
+/* ... and their pieces (the table at svgp_gp_factor_bwd_early) on a channel window, the split of the two-stream step.
+ * Forward `part`: 0 = K SIG KL TAIL, 1 = K SIG KL, 2 = TAIL.  Reverse `part`: 0 = all six, 1 = SW EARLY_B, 2 = LATE_A
+ * CHANNELS KBAR FINAL, 3 = SW, 4 = EARLY_B.  Any other value: SVGP_ERR_INVALID.                                          */
 int svgp_gp_factor_fwd_channels_part(const svgp_mnist_cfg*, int l0, int nl, int part, double* ws, void* stream);
 int svgp_gp_factor_bwd_channels_part(const svgp_mnist_cfg*, int l0, int nl, int part, double* ws, const double* state,
                                      void* stream);

@@ -77,6 +77,9 @@ class PearceBufs(C.Structure):
 STATE = dict(C_MA=0, LAGRANGE=1, ALPHA=2, ADAM_T=3, LR=4, BETA=5, ELBO=6, RECON_LOSS=7, KL_TERM=8,
              INSIDE_ELBO=9, CE_TERM=10, INSIDE_RECON=11, INSIDE_KL=12, RNG_CTR=13)
 STATE_LEN = 16
+# the public `part` integers of svgp_gp_factor_fwd_channels_part / svgp_gp_factor_bwd_channels_part (include/svgpvae_hip.h)
+FWD_PART = dict(ALL=0, HEAD=1, TAIL=2)
+BWD_PART = dict(ALL=0, EARLY=1, LATE=2, EARLY_A=3, EARLY_B=4)
 
 _P = C.c_void_p
 _CFG = C.POINTER(MnistCfg)

@@ -349,16 +349,16 @@ int step_phase_impl(const svgp_mnist_cfg* c, int phase, double* theta, const dou
         if (ksplit) RUN(side_fork(sd, 1, ms));
         RUN(svgp_gp_stats_fwd(c, ws, stream));
         if (ksplit) {
-            RUN(svgp_gp_factor_fwd_part(c, ws, (void*)sd->s[1], 5));
+            RUN(svgp_gp_factor_fwd_pieces(c, ws, (void*)sd->s[1], SVGP_FWD_K));
             side_mark_konly(sd, ws);
         }
         if (c->titsias) RUN(svgp_gp_titsias_stats(c, ws, stream));
         break;
     case 1:
         if (large && side_take_konly(sd, ws)) {                // the channel block; then what needs the branch's (K + jI)^-1 too
-            RUN(svgp_gp_factor_fwd_part(c, ws, stream, 6));
+            RUN(svgp_gp_factor_fwd_pieces(c, ws, stream, SVGP_FWD_SIG));
             RUN(side_join(sd, 1, ms));
-            RUN(svgp_gp_factor_fwd_part(c, ws, stream, 7));
+            RUN(svgp_gp_factor_fwd_pieces(c, ws, stream, SVGP_FWD_KL));
         } else
         RUN(svgp_gp_factor_fwd_defer_aji(c, ws, stream));      // m <= 64: (A_hat + jI)^-1 finishes inside the row-stage launch
         // m > 64: the tail of the stage and the early half of the REVERSE factor stage (no reverse statistic needed; phase 2 then

@@ -436,7 +436,7 @@ extern "C" int svgp_mnist_train_step_dp(const svgp_mnist_cfg* c, void* comm, dou
     void* side0 = stream;
     if (ksplit) RUN(guard.fork(&side0));
     RUN(svgp_gp_stats_fwd(&cc, ws, stream));         // (issued first: the branch's 15 launches would hold the caller's stream back)
-    if (ksplit) RUN(svgp_big_factor_fwd(&cc, wl, ws, side0, l0, nl, 5));
+    if (ksplit) RUN(svgp_big_factor_fwd(&cc, wl, ws, side0, l0, nl, SVGP_FWD_K));
     // ---- point 1: reduce-scatter [S | v] over the channels
     RUN(pt.begin());
     if (pack) RUN(svgp_sym_pack(m, L, 0, ws + wl.S, xp0, stream));
@@ -448,11 +448,11 @@ extern "C" int svgp_mnist_train_step_dp(const svgp_mnist_cfg* c, void* comm, dou
     RUN(pt.end());
     // window factor stage without its tail
     if (ksplit) {
-        RUN(svgp_big_factor_fwd(&cc, wl, ws, stream, l0, nl, 6));
+        RUN(svgp_big_factor_fwd(&cc, wl, ws, stream, l0, nl, SVGP_FWD_SIG));
         RUN(guard.join());
-        RUN(svgp_big_factor_fwd(&cc, wl, ws, stream, l0, nl, 7));
+        RUN(svgp_big_factor_fwd(&cc, wl, ws, stream, l0, nl, SVGP_FWD_KL));
     } else {
-        RUN(svgp_big_factor_fwd(&cc, wl, ws, stream, l0, nl, 1));
+        RUN(svgp_big_factor_fwd(&cc, wl, ws, stream, l0, nl, SVGP_FWD_HEAD));
     }
     // ---- point 2: all-gather [Sigma^-1 | t | u]
     RUN(pt.begin());
@@ -480,8 +480,8 @@ extern "C" int svgp_mnist_train_step_dp(const svgp_mnist_cfg* c, void* comm, dou
     // (the row stage is issued first: the branch's ~25 launches take the host ~100 us to enqueue, during which the caller's stream
     // would have nothing to run; the branch has that much slack)
     RUN(svgp_gp_posterior_fwd(&cc, eps, ws, state, stream));
-    RUN(svgp_big_factor_fwd(&cc, wl, ws, side, l0, nl, 2));
-    if (fork) RUN(svgp_big_factor_bwd(&cc, wl, ws, state, side, l0, nl, 1));
+    RUN(svgp_big_factor_fwd(&cc, wl, ws, side, l0, nl, SVGP_FWD_TAIL));
+    if (fork) RUN(svgp_big_factor_bwd(&cc, wl, ws, state, side, l0, nl, SVGP_BWD_EARLY));
     RUN(svgp_mnist_decoder_fwd(&cc, theta, images, ws, stream));
     RUN(svgp_mnist_decoder_bwd(&cc, theta, images, ws, state, stream));
     RUN(svgp_gp_stats_bwd(&cc, ws, state, stream));
@@ -501,17 +501,17 @@ extern "C" int svgp_mnist_train_step_dp(const svgp_mnist_cfg* c, void* comm, dou
         // that every rank runs in full, while the channel block covers its L / G channels only -- on the branch that has just been
         // joined, beside the channel block.  SVGP_KBAR_BRANCH=0: one launch after the other.
         if (sc.kbar_branch) {
-            RUN(svgp_big_factor_bwd(&cc, wl, ws, state, stream, l0, nl, 6));
+            RUN(svgp_big_factor_bwd(&cc, wl, ws, state, stream, l0, nl, SVGP_BWD_LATE_A));
             void* side2 = stream;
             RUN(guard.fork(&side2));
-            RUN(svgp_big_factor_bwd(&cc, wl, ws, state, side2, l0, nl, 9));
-            RUN(svgp_big_factor_bwd(&cc, wl, ws, state, stream, l0, nl, 8));
+            RUN(svgp_big_factor_bwd(&cc, wl, ws, state, side2, l0, nl, SVGP_BWD_KBAR));
+            RUN(svgp_big_factor_bwd(&cc, wl, ws, state, stream, l0, nl, SVGP_BWD_CHANNELS));
             RUN(guard.join());
-            RUN(svgp_big_factor_bwd(&cc, wl, ws, state, stream, l0, nl, 10));
+            RUN(svgp_big_factor_bwd(&cc, wl, ws, state, stream, l0, nl, SVGP_BWD_FINAL));
         } else
-        RUN(svgp_big_factor_bwd(&cc, wl, ws, state, stream, l0, nl, 2));
+        RUN(svgp_big_factor_bwd(&cc, wl, ws, state, stream, l0, nl, SVGP_BWD_LATE));
     } else {
-        RUN(svgp_big_factor_bwd(&cc, wl, ws, state, stream, l0, nl, 0));
+        RUN(svgp_big_factor_bwd(&cc, wl, ws, state, stream, l0, nl, SVGP_BWD_ALL));
     }
     // ---- point 4: all-gather [Ssym | vbar | KL]
     RUN(pt.begin());

@@ -49,8 +49,8 @@ int svgp_side_branch_join(void* main_stream, int k = 1);
 int svgp_dgemm_splitk_rows2(int ta, int tb, int M, int N, int K, double alpha, double alpha2, int row2, const double* A, int lda,
                             const double* B, int ldb, double beta, double* C, int ldc, double* scratch, long long scratch_elems,
                             void* stream);
-// gp_kernels.hip: parts 5 / 6 / 7 of the large-m forward factor stage (see gp_large.hip svgp_big_factor_fwd)
-int svgp_gp_factor_fwd_part(const svgp_mnist_cfg* c, double* ws, void* stream, int part);
+// gp_kernels.hip: a piece set (SVGP_FWD_*, below) of the large-m forward factor stage on all channels, with the entry points' checks
+int svgp_gp_factor_fwd_pieces(const svgp_mnist_cfg* c, double* ws, void* stream, unsigned pieces);
 int svgp_mnist_step_phase_deferred(const svgp_mnist_cfg* c, int phase, double* theta, const double* images,
                                    const double* aux, const double* eps, double* ws, double* state, double* adam_m,
                                    double* adam_v, void* stream, const SvgpSched& sc);
@@ -169,12 +169,35 @@ int svgp_dgemm_epi_batched(int f32c, int ta, int tb, int M, int N, int K, double
 // large-m implementations (gp_large.hip)
 int svgp_big_stats(const svgp_mnist_cfg* c, const svgp_mnist_ws_layout& wl, double* ws, const double* state, int mode,
                    void* stream);
+// The pieces of the two factor stages: what a caller may issue on its own (on another stream, before or after a join).  A call runs
+// the pieces of its set in the order listed here; the data dependencies between pieces of different calls are the caller's business
+// (gp_large.hip has them at the two functions).
+enum : unsigned {
+    SVGP_FWD_K = 1,         // channel-independent block: (K + jI)^-1, log det, Kn Ki, q, W, P^T -- needs the kernel matrices only
+    SVGP_FWD_SIG = 2,       // channel block up to mu: Sigma^-1, t, G, A_hat (+ A_hat + jI), mu
+    SVGP_FWD_KL = 4,        // u = Ki mu and the trace partials: needs K and SIG
+    SVGP_FWD_TAIL = 8,      // (A_hat + jI)^-1, its log det, KL_l: only the reverse factor stage and the final ELBO need it
+    SVGP_FWD_HEAD = SVGP_FWD_K | SVGP_FWD_SIG | SVGP_FWD_KL,
+    SVGP_FWD_ALL = SVGP_FWD_HEAD | SVGP_FWD_TAIL,
+};
+enum : unsigned {
+    SVGP_BWD_SW = 1,        // T = S P, SW = P^T T (only when SW is not formed over the rows by the reverse statistics)
+    SVGP_BWD_EARLY_B = 2,   // H, HG, the three channel sums: needs (A_hat + jI)^-1
+    SVGP_BWD_LATE_A = 4,    // the vector chain; + the X block when it reads nothing EARLY_B writes (SW from the rows, or no SW)
+    SVGP_BWD_CHANNELS = 8,  // the X block otherwise; Ssym; the channel sum Sgs
+    SVGP_BWD_KBAR = 16,     // the single-matrix chain of the gradient of Ki (five launches that read nothing of CHANNELS)
+    SVGP_BWD_FINAL = 32,    // the closing assembly of Kbar
+    SVGP_BWD_EARLY = SVGP_BWD_SW | SVGP_BWD_EARLY_B,
+    SVGP_BWD_LATE_B = SVGP_BWD_CHANNELS | SVGP_BWD_KBAR | SVGP_BWD_FINAL,
+    SVGP_BWD_LATE = SVGP_BWD_LATE_A | SVGP_BWD_LATE_B,
+    SVGP_BWD_ALL = SVGP_BWD_EARLY | SVGP_BWD_LATE,
+};
 int svgp_big_factor_fwd(const svgp_mnist_cfg* c, const svgp_mnist_ws_layout& wl, double* ws, void* stream, int l0, int nl,
-                        int part = 0);
+                        unsigned pieces = SVGP_FWD_ALL);
 int svgp_big_posterior_fwd(const svgp_mnist_cfg* c, const svgp_mnist_ws_layout& wl, const double* eps, double* ws,
                            double* state, void* stream);
 int svgp_big_factor_bwd(const svgp_mnist_cfg* c, const svgp_mnist_ws_layout& wl, double* ws, const double* state,
-                        void* stream, int l0, int nl, int part = 0);
+                        void* stream, int l0, int nl, unsigned pieces = SVGP_BWD_ALL);
 int svgp_big_posterior_bwd(const svgp_mnist_cfg* c, const svgp_mnist_ws_layout& wl, double* ws, const double* state,
                            void* stream);
 

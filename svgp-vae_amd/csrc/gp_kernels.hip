@@ -1800,68 +1800,61 @@ extern "C" int svgp_gp_factor_fwd(const svgp_mnist_cfg* c, double* ws, void* str
 extern "C" int svgp_gp_factor_fwd_defer_aji(const svgp_mnist_cfg* c, double* ws, void* stream) {
     return factor_fwd_impl(c, ws, 1, stream);
 }
+// The exported pieces of the large-m factor stages (gp_large.hip; the piece sets SVGP_FWD_* / SVGP_BWD_* of common.hpp): layouts,
+// pointer checks, m > 64 (`need_big`: the message, with one %d), the channel window if the caller has one, the call.
+// fwd: the forward stage (no `state`).
+static int big_factor(const svgp_mnist_cfg* c, double* ws, const double* state, bool fwd, void* stream, unsigned pieces,
+                      const char* need_big, bool window = false, int l0 = 0, int nl = 0) {
+    GET_LAYOUTS();
+    SVGP_REQUIRE(ws && (fwd || state), SVGP_ERR_INVALID, "NULL device pointer");
+    SVGP_REQUIRE(c->m > SVGP_M_MAX, SVGP_ERR_UNSUPPORTED, need_big, SVGP_M_MAX);
+    if (window) SVGP_REQUIRE(l0 >= 0 && nl >= 1 && l0 + nl <= c->L, SVGP_ERR_INVALID, "channel window [%d, %d) outside 0..%d", l0, l0 + nl, c->L);
+    else nl = c->L;
+    return fwd ? svgp_big_factor_fwd(c, wl, ws, stream, l0, nl, pieces) : svgp_big_factor_bwd(c, wl, ws, state, stream, l0, nl, pieces);
+}
+static const char NEED_BIG_TAIL[] = "for m <= %d the deferred inverse rides in svgp_gp_posterior_fwd_with_aji / svgp_gp_stats_bwd_with_aji";
+static const char NEED_BIG_FWD[] = "the split forward factor stage exists for m > %d";
+static const char NEED_BIG_BWD[] = "the split reverse factor stage exists for m > %d";
+static const char NEED_BIG_WIN[] = "channel windows exist for the large-m path (m > %d); below it the factor stage is L small workgroups";
+static const char NEED_BIG_WIN_PART[] = "channel windows exist for the large-m path (m > %d)";
 // m > 64: the tail that svgp_gp_factor_fwd_defer_aji leaves out -- (A_hat_l + jI)^-1, its log det, KL_l; may run on another
 // stream than the stages that follow (it shares no buffer with the row stage, the decoder and the reverse statistics)
 extern "C" int svgp_gp_factor_fwd_aji_tail(const svgp_mnist_cfg* c, double* ws, void* stream) {
-    GET_LAYOUTS();
-    SVGP_REQUIRE(ws, SVGP_ERR_INVALID, "NULL device pointer");
-    SVGP_REQUIRE(c->m > SVGP_M_MAX, SVGP_ERR_UNSUPPORTED,
-                 "for m <= %d the deferred inverse rides in svgp_gp_posterior_fwd_with_aji / svgp_gp_stats_bwd_with_aji", SVGP_M_MAX);
-    return svgp_big_factor_fwd(c, wl, ws, stream, 0, c->L, 2);
+    return big_factor(c, ws, nullptr, true, stream, SVGP_FWD_TAIL, NEED_BIG_TAIL);
 }
-// internal (api.hip): one part of the large-m forward factor stage (gp_large.hip svgp_big_factor_fwd: 5 = the channel-independent
-// block, 6 = the channel block up to mu, 7 = u and the KL terms)
-int svgp_gp_factor_fwd_part(const svgp_mnist_cfg* c, double* ws, void* stream, int part) {
-    GET_LAYOUTS();
-    SVGP_REQUIRE(ws, SVGP_ERR_INVALID, "NULL device pointer");
-    SVGP_REQUIRE(c->m > SVGP_M_MAX && c->m < SVGP_CHOL_INVERSE_MIN_M && part >= 5 && part <= 7, SVGP_ERR_UNSUPPORTED,
-                 "the split forward factor stage exists for %d < m < %d", SVGP_M_MAX, SVGP_CHOL_INVERSE_MIN_M);
-    return svgp_big_factor_fwd(c, wl, ws, stream, 0, c->L, part);
+// internal (api.hip): K, SIG or KL of the large-m forward factor stage on its own, on all channels
+int svgp_gp_factor_fwd_pieces(const svgp_mnist_cfg* c, double* ws, void* stream, unsigned pieces) {
+    SVGP_REQUIRE(c && c->m < SVGP_CHOL_INVERSE_MIN_M, SVGP_ERR_UNSUPPORTED, "the split forward factor stage exists for %d < m < %d",
+                 SVGP_M_MAX, SVGP_CHOL_INVERSE_MIN_M);
+    return big_factor(c, ws, nullptr, true, stream, pieces, NEED_BIG_FWD);
 }
 // channel windows of the factor stages (large-m path): see svgp_big_factor_fwd
 extern "C" int svgp_gp_factor_fwd_channels(const svgp_mnist_cfg* c, int l0, int nl, double* ws, void* stream) {
-    GET_LAYOUTS();
-    SVGP_REQUIRE(ws, SVGP_ERR_INVALID, "NULL device pointer");
-    SVGP_REQUIRE(c->m > SVGP_M_MAX, SVGP_ERR_UNSUPPORTED,
-                 "channel windows exist for the large-m path (m > %d); below it the factor stage is L small workgroups", SVGP_M_MAX);
-    SVGP_REQUIRE(l0 >= 0 && nl >= 1 && l0 + nl <= c->L, SVGP_ERR_INVALID, "channel window [%d, %d) outside 0..%d", l0, l0 + nl, c->L);
-    return svgp_big_factor_fwd(c, wl, ws, stream, l0, nl);
+    return big_factor(c, ws, nullptr, true, stream, SVGP_FWD_ALL, NEED_BIG_WIN, true, l0, nl);
 }
 extern "C" int svgp_gp_factor_bwd_channels(const svgp_mnist_cfg* c, int l0, int nl, double* ws, const double* state,
                                            void* stream) {
-    GET_LAYOUTS();
-    SVGP_REQUIRE(ws && state, SVGP_ERR_INVALID, "NULL device pointer");
-    SVGP_REQUIRE(c->m > SVGP_M_MAX, SVGP_ERR_UNSUPPORTED,
-                 "channel windows exist for the large-m path (m > %d); below it the factor stage is L small workgroups", SVGP_M_MAX);
-    SVGP_REQUIRE(l0 >= 0 && nl >= 1 && l0 + nl <= c->L, SVGP_ERR_INVALID, "channel window [%d, %d) outside 0..%d", l0, l0 + nl, c->L);
-    return svgp_big_factor_bwd(c, wl, ws, state, stream, l0, nl);
+    return big_factor(c, ws, state, false, stream, SVGP_BWD_ALL, NEED_BIG_WIN, true, l0, nl);
 }
 
-// ... and their parts (the split of the two-stream step on a window): forward part 0 = whole stage, 1 = without the
-// (A_hat + jI)^-1 tail, 2 = the tail; reverse part 0 = whole stage, 1 = early half, 2 = late half, 3 / 4 = the two parts of the
-// early half (svgp_gp_factor_bwd_early_a / _b)
+// ... and their parts (the split of the two-stream step on a window).  The public `part` integers mean what these two tables say,
+// and nothing else in the library reads them.  The range check comes first: it needs no device.
+static const unsigned FWD_PART[] = {SVGP_FWD_ALL, SVGP_FWD_HEAD /* no (A_hat + jI)^-1 tail */, SVGP_FWD_TAIL};
+static const unsigned BWD_PART[] = {SVGP_BWD_ALL, SVGP_BWD_EARLY, SVGP_BWD_LATE, SVGP_BWD_SW /* _early_a */, SVGP_BWD_EARLY_B};
 extern "C" int svgp_gp_factor_fwd_channels_part(const svgp_mnist_cfg* c, int l0, int nl, int part, double* ws, void* stream) {
-    GET_LAYOUTS();
-    SVGP_REQUIRE(ws, SVGP_ERR_INVALID, "NULL device pointer");
-    SVGP_REQUIRE(c->m > SVGP_M_MAX, SVGP_ERR_UNSUPPORTED, "channel windows exist for the large-m path (m > %d)", SVGP_M_MAX);
-    SVGP_REQUIRE(l0 >= 0 && nl >= 1 && l0 + nl <= c->L, SVGP_ERR_INVALID, "channel window [%d, %d) outside 0..%d", l0, l0 + nl, c->L);
     SVGP_REQUIRE(part >= 0 && part <= 2, SVGP_ERR_INVALID, "forward part %d (0, 1 or 2)", part);
-    return svgp_big_factor_fwd(c, wl, ws, stream, l0, nl, part);
+    return big_factor(c, ws, nullptr, true, stream, FWD_PART[part], NEED_BIG_WIN_PART, true, l0, nl);
 }
 extern "C" int svgp_gp_factor_bwd_channels_part(const svgp_mnist_cfg* c, int l0, int nl, int part, double* ws,
                                                 const double* state, void* stream) {
-    GET_LAYOUTS();
-    SVGP_REQUIRE(ws && state, SVGP_ERR_INVALID, "NULL device pointer");
-    SVGP_REQUIRE(c->m > SVGP_M_MAX, SVGP_ERR_UNSUPPORTED, "channel windows exist for the large-m path (m > %d)", SVGP_M_MAX);
-    SVGP_REQUIRE(l0 >= 0 && nl >= 1 && l0 + nl <= c->L, SVGP_ERR_INVALID, "channel window [%d, %d) outside 0..%d", l0, l0 + nl, c->L);
     SVGP_REQUIRE(part >= 0 && part <= 4, SVGP_ERR_INVALID, "reverse part %d (0..4)", part);
-    return svgp_big_factor_bwd(c, wl, ws, state, stream, l0, nl, part);
+    return big_factor(c, ws, state, false, stream, BWD_PART[part], NEED_BIG_WIN_PART, true, l0, nl);
 }
 
 static int factor_fwd_impl(const svgp_mnist_cfg* c, double* ws, int defer_aji, void* stream) {
     GET_LAYOUTS();
     SVGP_REQUIRE(ws, SVGP_ERR_INVALID, "NULL device pointer");
-    if (c->m > SVGP_M_MAX) return svgp_big_factor_fwd(c, wl, ws, stream, 0, c->L, defer_aji ? 1 : 0);
+    if (c->m > SVGP_M_MAX) return svgp_big_factor_fwd(c, wl, ws, stream, 0, c->L, defer_aji ? SVGP_FWD_HEAD : SVGP_FWD_ALL);
     FactArgs a;
     a.defer_aji = defer_aji; a.kl_form = c->kl_form; a.P = svgp_stat_parts(c);
     a.b = c->b; a.m = c->m; a.L = c->L; a.c = c->N_train / (double)c->b_global; a.jitter = c->jitter;
@@ -1961,75 +1954,39 @@ extern "C" int svgp_gp_stats_factor_bwd_wgrad(const svgp_mnist_cfg* c, const dou
                                               void* stream) {
     return svgp_gp_stats_factor_bwd_wgrad_sched(c, images, ws, state, stream, sched_read());
 }
-// m > 64: the two halves of svgp_gp_factor_bwd (gp_large.hip svgp_big_factor_bwd).  _early needs only forward quantities, the
-// loss seeds in `state` and (A_hat + jI)^-1: it may run on another stream, ordered after svgp_gp_factor_fwd_aji_tail, beside
-// the row stage, the networks and the reverse statistics; _late follows svgp_gp_stats_bwd (and its exchange) and _early.
+// m > 64: svgp_gp_factor_bwd piece by piece (the table in include/svgpvae_hip.h; what each piece needs: gp_large.hip svgp_big_factor_bwd)
 extern "C" int svgp_gp_factor_bwd_early(const svgp_mnist_cfg* c, double* ws, const double* state, void* stream) {
-    GET_LAYOUTS();
-    SVGP_REQUIRE(ws && state, SVGP_ERR_INVALID, "NULL device pointer");
-    SVGP_REQUIRE(c->m > SVGP_M_MAX, SVGP_ERR_UNSUPPORTED, "the split reverse factor stage exists for m > %d", SVGP_M_MAX);
-    return svgp_big_factor_bwd(c, wl, ws, state, stream, 0, c->L, 1);
+    return big_factor(c, ws, state, false, stream, SVGP_BWD_EARLY, NEED_BIG_BWD);
 }
-// _early in two parts: _early_a (T1, Ki S Ki, T1 A_hat) needs no (A_hat + jI)^-1 and may run BESIDE svgp_gp_factor_fwd_aji_tail
-// (a third stream); _early_b (Abar, Gbar, Z, Gbar K) needs both.  The gp_large.hip fb_part hazard: _early_b overwrites the trace
-// partials the tail's last kernel reads -- it is ordered behind the tail anyway (it needs (A_hat + jI)^-1).
 extern "C" int svgp_gp_factor_bwd_early_a(const svgp_mnist_cfg* c, double* ws, const double* state, void* stream) {
-    GET_LAYOUTS();
-    SVGP_REQUIRE(ws && state, SVGP_ERR_INVALID, "NULL device pointer");
-    SVGP_REQUIRE(c->m > SVGP_M_MAX, SVGP_ERR_UNSUPPORTED, "the split reverse factor stage exists for m > %d", SVGP_M_MAX);
-    return svgp_big_factor_bwd(c, wl, ws, state, stream, 0, c->L, 3);
+    return big_factor(c, ws, state, false, stream, SVGP_BWD_SW, NEED_BIG_BWD);
 }
 extern "C" int svgp_gp_factor_bwd_early_b(const svgp_mnist_cfg* c, double* ws, const double* state, void* stream) {
-    GET_LAYOUTS();
-    SVGP_REQUIRE(ws && state, SVGP_ERR_INVALID, "NULL device pointer");
-    SVGP_REQUIRE(c->m > SVGP_M_MAX, SVGP_ERR_UNSUPPORTED, "the split reverse factor stage exists for m > %d", SVGP_M_MAX);
-    return svgp_big_factor_bwd(c, wl, ws, state, stream, 0, c->L, 4);
-}
-// _late = _late_a + _late_b: _late_a reads nothing the early half writes and may be issued BEFORE the caller's stream joins the branch
-// the early half runs on; _late_b follows the join
-extern "C" int svgp_gp_factor_bwd_late_a(const svgp_mnist_cfg* c, double* ws, const double* state, void* stream) {
-    GET_LAYOUTS();
-    SVGP_REQUIRE(ws && state, SVGP_ERR_INVALID, "NULL device pointer");
-    SVGP_REQUIRE(c->m > SVGP_M_MAX, SVGP_ERR_UNSUPPORTED, "the split reverse factor stage exists for m > %d", SVGP_M_MAX);
-    return svgp_big_factor_bwd(c, wl, ws, state, stream, 0, c->L, 6);
-}
-extern "C" int svgp_gp_factor_bwd_late_b(const svgp_mnist_cfg* c, double* ws, const double* state, void* stream) {
-    GET_LAYOUTS();
-    SVGP_REQUIRE(ws && state, SVGP_ERR_INVALID, "NULL device pointer");
-    SVGP_REQUIRE(c->m > SVGP_M_MAX, SVGP_ERR_UNSUPPORTED, "the split reverse factor stage exists for m > %d", SVGP_M_MAX);
-    return svgp_big_factor_bwd(c, wl, ws, state, stream, 0, c->L, 7);
-}
-// _late_b = _late_b_channels (the channel block: X sandwiches, Ssym, Sgs) + _late_b_kbar (the single-matrix chain of the gradient of Ki:
-// five small launches that read nothing of the channel block and may run beside it on another stream) + _late_b_final (round 6)
-extern "C" int svgp_gp_factor_bwd_late_b_channels(const svgp_mnist_cfg* c, double* ws, const double* state, void* stream) {
-    GET_LAYOUTS();
-    SVGP_REQUIRE(ws && state, SVGP_ERR_INVALID, "NULL device pointer");
-    SVGP_REQUIRE(c->m > SVGP_M_MAX, SVGP_ERR_UNSUPPORTED, "the split reverse factor stage exists for m > %d", SVGP_M_MAX);
-    return svgp_big_factor_bwd(c, wl, ws, state, stream, 0, c->L, 8);
-}
-extern "C" int svgp_gp_factor_bwd_late_b_kbar(const svgp_mnist_cfg* c, double* ws, const double* state, void* stream) {
-    GET_LAYOUTS();
-    SVGP_REQUIRE(ws && state, SVGP_ERR_INVALID, "NULL device pointer");
-    SVGP_REQUIRE(c->m > SVGP_M_MAX, SVGP_ERR_UNSUPPORTED, "the split reverse factor stage exists for m > %d", SVGP_M_MAX);
-    return svgp_big_factor_bwd(c, wl, ws, state, stream, 0, c->L, 9);
-}
-extern "C" int svgp_gp_factor_bwd_late_b_final(const svgp_mnist_cfg* c, double* ws, const double* state, void* stream) {
-    GET_LAYOUTS();
-    SVGP_REQUIRE(ws && state, SVGP_ERR_INVALID, "NULL device pointer");
-    SVGP_REQUIRE(c->m > SVGP_M_MAX, SVGP_ERR_UNSUPPORTED, "the split reverse factor stage exists for m > %d", SVGP_M_MAX);
-    return svgp_big_factor_bwd(c, wl, ws, state, stream, 0, c->L, 10);
+    return big_factor(c, ws, state, false, stream, SVGP_BWD_EARLY_B, NEED_BIG_BWD);
 }
 extern "C" int svgp_gp_factor_bwd_late(const svgp_mnist_cfg* c, double* ws, const double* state, void* stream) {
-    GET_LAYOUTS();
-    SVGP_REQUIRE(ws && state, SVGP_ERR_INVALID, "NULL device pointer");
-    SVGP_REQUIRE(c->m > SVGP_M_MAX, SVGP_ERR_UNSUPPORTED, "the split reverse factor stage exists for m > %d", SVGP_M_MAX);
-    return svgp_big_factor_bwd(c, wl, ws, state, stream, 0, c->L, 2);
+    return big_factor(c, ws, state, false, stream, SVGP_BWD_LATE, NEED_BIG_BWD);
+}
+extern "C" int svgp_gp_factor_bwd_late_a(const svgp_mnist_cfg* c, double* ws, const double* state, void* stream) {
+    return big_factor(c, ws, state, false, stream, SVGP_BWD_LATE_A, NEED_BIG_BWD);
+}
+extern "C" int svgp_gp_factor_bwd_late_b(const svgp_mnist_cfg* c, double* ws, const double* state, void* stream) {
+    return big_factor(c, ws, state, false, stream, SVGP_BWD_LATE_B, NEED_BIG_BWD);
+}
+extern "C" int svgp_gp_factor_bwd_late_b_channels(const svgp_mnist_cfg* c, double* ws, const double* state, void* stream) {
+    return big_factor(c, ws, state, false, stream, SVGP_BWD_CHANNELS, NEED_BIG_BWD);
+}
+extern "C" int svgp_gp_factor_bwd_late_b_kbar(const svgp_mnist_cfg* c, double* ws, const double* state, void* stream) {
+    return big_factor(c, ws, state, false, stream, SVGP_BWD_KBAR, NEED_BIG_BWD);
+}
+extern "C" int svgp_gp_factor_bwd_late_b_final(const svgp_mnist_cfg* c, double* ws, const double* state, void* stream) {
+    return big_factor(c, ws, state, false, stream, SVGP_BWD_FINAL, NEED_BIG_BWD);
 }
 static int factor_bwd_impl(const svgp_mnist_cfg* c, double* ws, const double* state, bool with_final, void* stream,
                            const double* images_for_wgrad, bool with_stats, bool stat_four) {
     GET_LAYOUTS();
     SVGP_REQUIRE(ws && state, SVGP_ERR_INVALID, "NULL device pointer");
-    if (c->m > SVGP_M_MAX) return svgp_big_factor_bwd(c, wl, ws, state, stream, 0, c->L);
+    if (c->m > SVGP_M_MAX) return svgp_big_factor_bwd(c, wl, ws, state, stream, 0, c->L, SVGP_BWD_ALL);
     FactBwdArgs a = make_fb(c, wl, ws, state);
     const int m = c->m;
     const int keep = m * m <= 4 * SVGP_BLOCK ? 1 : 0;          // + the LDS accumulator of Kbar_l

@@ -614,13 +614,20 @@ int svgp_big_stats(const svgp_mnist_cfg* c, const svgp_mnist_ws_layout& wl, doub
 // Channel window [l0, l0 + nl): the factor stage of those channels only (all of them: l0 = 0, nl = L).  With the batch
 // sharded over ranks and the statistics reduce-SCATTERED over channels, every rank factors L / G channels instead of all
 // L redundantly; (K_mm + jI)^-1, q_n and W are channel-independent and computed by every caller.
-// part: 0 = the whole stage; 1 = without its tail -- (A_hat_l + jI)^-1, its log det and the KL_l scalars, which only the
-// reverse factor stage and the final ELBO need; 2 = that tail alone.  The training step issues the tail on a side stream
-// (api.hip, sprites.py) so that the second batched inverse of the step runs beside the row stage, the decoder and the
-// reverse statistics instead of in front of them.  The tail touches A (read), Aji, KL, the inverse workspace, s.ldtmp and
-// the trace partials in fb_part -- nothing the stages between the two factor stages use.
+// `pieces` (SVGP_FWD_*, common.hpp) -- the same operations on the same values in whichever calls they are issued:
+//   K    the CHANNEL-INDEPENDENT block -- (K + jI)^-1 and its log det, Kn Ki, q, W, P^T: functions of the kernel matrices only, not
+//        of the encoder's output -- which the training step issues on a side branch as soon as the kernel matrices exist, beside
+//        the encoder's tail, the forward statistics and the channel inverses (api.hip, comm.hip);
+//   SIG  the channel block up to mu (Sigma^-1, t, G, A_hat);
+//   KL   what needs both (u = Ki mu, the KL terms);
+//   TAIL (A_hat_l + jI)^-1, its log det and the KL_l scalars, which only the reverse factor stage and the final ELBO need.  The
+//        training step issues it on a side stream (api.hip, sprites.py) so that the second batched inverse of the step runs beside
+//        the row stage, the decoder and the reverse statistics instead of in front of them.  It touches A (read), Aji, KL, the
+//        inverse workspace, s.ldtmp and the trace partials in fb_part -- nothing the stages between the two factor stages use.
+// K, SIG and KL in one call: the (K + jI) inverse rides in the channel matrices' launches.  One of them alone: an inverse of its
+// own, which exists for m < SVGP_CHOL_INVERSE_MIN_M.  The sets the schedules use are the ones accepted.
 int svgp_big_factor_fwd(const svgp_mnist_cfg* c, const svgp_mnist_ws_layout& wl, double* ws, void* stream, int l0, int nl,
-                        int part) {
+                        unsigned pieces) {
     const int b = c->b, m = c->m, L = nl;
     const long long mm = (long long)m * m;
     const real cc = c->N_train / (double)c->b_global;
@@ -630,19 +637,12 @@ int svgp_big_factor_fwd(const svgp_mnist_cfg* c, const svgp_mnist_ws_layout& wl,
     real *K = ws + wl.K, *Ki = ws + wl.Ki, *Si = ws + wl.Si + om, *G = ws + wl.G + om, *A = ws + wl.A + om, *Aji = ws + wl.Aji + om;
     real *t = ws + wl.t + ov, *mu = ws + wl.mu_hat + ov, *u = ws + wl.u + ov, *v = ws + wl.v + ov, *Kn = ws + wl.Kn;
     real* klp = ws + wl.fb_part;                 // (L, KL_NCH, 2) trace partials (fb_part is free until the reverse factor stage)
-    if (part == 2) goto aji_tail;
-    {
-    // part 5 = the CHANNEL-INDEPENDENT block alone -- (K + jI)^-1 and its log det, Kn Ki, q, W, P^T: functions of the kernel
-    // matrices only, not of the encoder's output -- which the training step issues on a side branch as soon as the kernel
-    // matrices exist, beside the encoder's tail, the forward statistics and the channel inverses (api.hip, comm.hip); part 6 = the
-    // channel block up to mu (Sigma^-1, t, G, A_hat); part 7 = what needs both (u = Ki mu, the KL terms).  1 = 5 + 6 + 7 in one
-    // call, with the (K + jI) inverse riding in the channel matrices' launches.  Same operations on the same values either way.
-    const bool split = part == 5 || part == 6 || part == 7;
-    SVGP_REQUIRE(!split || m < SVGP_CHOL_INVERSE_MIN_M, SVGP_ERR_INVALID, "the split forward factor stage exists for m < %d",
+    const bool alone = pieces == SVGP_FWD_K || pieces == SVGP_FWD_SIG || pieces == SVGP_FWD_KL;
+    SVGP_REQUIRE(alone || pieces == SVGP_FWD_HEAD || pieces == SVGP_FWD_TAIL || pieces == SVGP_FWD_ALL, SVGP_ERR_INVALID,
+                 "forward factor stage: piece set 0x%x is not one of K, SIG, KL, K|SIG|KL, TAIL, all", pieces);
+    SVGP_REQUIRE(!alone || m < SVGP_CHOL_INVERSE_MIN_M, SVGP_ERR_INVALID, "the split forward factor stage exists for m < %d",
                  SVGP_CHOL_INVERSE_MIN_M);
-    const bool do_k = !split || part == 5, do_sig = !split || part == 6, do_kl = !split || part == 7;
-    // the blocked inverse's workspace is (pivots | ping-pong copy) per matrix: the channel batch takes the head, (K + jI) the tail
-    real* inv_k = s.inv + (size_t)c->L * (2 * 32 * 32 + (size_t)mm);
+    const bool do_k = pieces & SVGP_FWD_K, do_sig = pieces & SVGP_FWD_SIG;
     if (do_sig) {
         hipLaunchKernelGGL(k_big_add_diag, dim3(nblk(mm * L)), dim3(256), 0, st, m, L, cc, c->jitter, K, ws + wl.S + om, 0LL, Si);
         SVGP_LAUNCH_CHECK();
@@ -653,18 +653,23 @@ int svgp_big_factor_fwd(const svgp_mnist_cfg* c, const svgp_mnist_ws_layout& wl,
                            0LL, Ki);
         SVGP_LAUNCH_CHECK();
     }
-    if (split) {
-        if (part == 5) RUNC(svgp_spd_inverse_fused(m, 1, Ki, ws + wl.ldK, 0, nullptr, nullptr, inv_k, stream));
-        if (part == 6) RUNC(svgp_spd_inverse_fused(m, L, Si, s.ldtmp, 0, nullptr, nullptr, s.inv, stream));
-    } else if (m < SVGP_CHOL_INVERSE_MIN_M) {
-        RUNC(svgp_spd_inverse_fused(m, L, Si, s.ldtmp, 1, Ki, ws + wl.ldK, s.inv, stream));
-    } else if (Ki == Si + (size_t)L * mm) {
-        // one batch of L + 1: Ki sits right behind Si in the workspace (api.hip); its log det is the last entry
-        RUNC(svgp_spd_inverse_batched(m, L + 1, Si, s.ldtmp, s.inv, stream));
-        SVGP_CHECK_HIP(hipMemcpyAsync(ws + wl.ldK, s.ldtmp + L, sizeof(real), hipMemcpyDeviceToDevice, st));
-    } else {
-        RUNC(svgp_spd_inverse_batched(m, 1, Ki, ws + wl.ldK, s.inv, stream));
-        RUNC(svgp_spd_inverse_batched(m, L, Si, s.ldtmp, s.inv, stream));
+    if (do_k && do_sig) {
+        if (m < SVGP_CHOL_INVERSE_MIN_M) {
+            RUNC(svgp_spd_inverse_fused(m, L, Si, s.ldtmp, 1, Ki, ws + wl.ldK, s.inv, stream));
+        } else if (Ki == Si + (size_t)L * mm) {
+            // one batch of L + 1: Ki sits right behind Si in the workspace (api.hip); its log det is the last entry
+            RUNC(svgp_spd_inverse_batched(m, L + 1, Si, s.ldtmp, s.inv, stream));
+            SVGP_CHECK_HIP(hipMemcpyAsync(ws + wl.ldK, s.ldtmp + L, sizeof(real), hipMemcpyDeviceToDevice, st));
+        } else {
+            RUNC(svgp_spd_inverse_batched(m, 1, Ki, ws + wl.ldK, s.inv, stream));
+            RUNC(svgp_spd_inverse_batched(m, L, Si, s.ldtmp, s.inv, stream));
+        }
+    } else if (do_k) {
+        // the blocked inverse's workspace is (pivots | ping-pong copy) per matrix: the channel batch takes the head, (K + jI) the tail
+        real* inv_k = s.inv + (size_t)c->L * (2 * 32 * 32 + (size_t)mm);
+        RUNC(svgp_spd_inverse_fused(m, 1, Ki, ws + wl.ldK, 0, nullptr, nullptr, inv_k, stream));
+    } else if (do_sig) {
+        RUNC(svgp_spd_inverse_fused(m, L, Si, s.ldtmp, 0, nullptr, nullptr, s.inv, stream));
     }
     if (do_sig) {
         GEMV(1.0, Si, mm, v, t, L);                                                                  // t = Si v
@@ -678,7 +683,7 @@ int svgp_big_factor_fwd(const svgp_mnist_cfg* c, const svgp_mnist_ws_layout& wl,
         }
         GEMV(cc, K, 0, t, mu, L);                                                                    // mu = c K t
     }
-    if (do_kl) {
+    if (pieces & SVGP_FWD_KL) {
         GEMV(1.0, Ki, 0, mu, u, L);                                                                  // u = Ki mu
         hipLaunchKernelGGL(k_big_kl_terms, dim3(KL_NCH, L), dim3(256), 0, st, m, Ki, A, mu, u, klp);
         SVGP_LAUNCH_CHECK();
@@ -692,13 +697,12 @@ int svgp_big_factor_fwd(const svgp_mnist_cfg* c, const svgp_mnist_ws_layout& wl,
         GEMM(0, 1, b, m, m, 1.0, s.KnKi, m, 0, K, m, 0, 0.0, s.W, m, 0, 1);
         GEMM(0, 1, m, m, m, 1.0, K, m, 0, Ki, m, 0, 0.0, s.PT, m, 0, 1);
     }
-    if (part == 1 || split) return SVGP_OK;
+    if (pieces & SVGP_FWD_TAIL) {
+        // (Aji holds A_hat + jI: written by the product A = K G above; the tail inverts it in place)
+        RUNC(svgp_spd_inverse_batched(m, L, Aji, s.ldtmp, s.inv, stream));
+        hipLaunchKernelGGL(k_big_kl, dim3(nblk(L)), dim3(256), 0, st, m, L, ws + wl.ldK, s.ldtmp, klp, ws + wl.KL + l0);
+        SVGP_LAUNCH_CHECK();
     }
-aji_tail:
-    // (Aji holds A_hat + jI: written by the product A = K G above; the tail inverts it in place)
-    RUNC(svgp_spd_inverse_batched(m, L, Aji, s.ldtmp, s.inv, stream));
-    hipLaunchKernelGGL(k_big_kl, dim3(nblk(L)), dim3(256), 0, st, m, L, ws + wl.ldK, s.ldtmp, klp, ws + wl.KL + l0);
-    SVGP_LAUNCH_CHECK();
     return SVGP_OK;
 }
 
@@ -733,15 +737,23 @@ int svgp_big_posterior_fwd(const svgp_mnist_cfg* c, const svgp_mnist_ws_layout& 
 // channel window [l0, l0 + nl) as in svgp_big_factor_fwd; Kbar then holds rep_weight x the window's share of the gradient of
 // K_mm plus this rank's row-local share (the shares of the ranks add up in the gradient exchange: kernel_matrix_bwd is linear
 // in Kbar and takes it unweighted on this path).
-// part: 0 = the whole stage; 1 = its EARLY half (3 + 4: its two parts separately); 2 = its LATE half (6 + 7: see there).  The early half --
-//   D = Ki - Aji, H = G D (= Z' = Sigma^-1 K D), HG = H G^T (= Sigma^-1 K D K Sigma^-1), the channel sums of H, HG and A_hat
-// -- depends on forward quantities only (the scalar gK/2 of Abar = gK/2 D is applied where the products are consumed),
-// not on the reverse statistics B2, ud, td.  The training step issues it on the side stream right behind the forward stage's
-// tail, under the row stage, the networks and the reverse statistics; the late half (ubar ... Sigma^-1 Sibar Sigma^-1, the
-// Ki-gradient, Kbar) stays on the critical path.  Same operations on the same values either way.  Buffers: H in mm0, HG in mm3, then X in mm1, Sigma^-1 X in mm0 and Sg0 in mm1; SW in mm2 (its m-space form: T in mm1, early).
-// Part 3 (needs no (A_hat + jI)^-1: can run beside the forward tail) is the statistic SW (see there).
+// `pieces` (SVGP_BWD_*, common.hpp) -- the same operations on the same values in whichever calls they are issued:
+//   SW, EARLY_B  the EARLY half --
+//        D = Ki - Aji, H = G D (= Z' = Sigma^-1 K D), HG = H G^T (= Sigma^-1 K D K Sigma^-1), the channel sums of H, HG and A_hat
+//        -- depends on forward quantities only (the scalar gK/2 of Abar = gK/2 D is applied where the products are consumed), not
+//        on the reverse statistics B2, ud, td.  The training step issues it on the side stream right behind the forward stage's
+//        tail, under the row stage, the networks and the reverse statistics.  SW (the statistic SW, see there) needs not even
+//        (A_hat + jI)^-1: it can run beside the forward tail.
+//   LATE_A, CHANNELS, KBAR, FINAL  the LATE half (ubar ... Sigma^-1 Sibar Sigma^-1, the Ki-gradient, Kbar) stays on the critical
+//        path.  LATE_A (round 5) = what reads NOTHING the early half writes: a caller with the early half on a side branch issues
+//        LATE_A, THEN joins, then the rest: at m = 800 the caller's stream waited 0.8 ms at the join with 2.3 ms of its own work ready
+//        (kernel trace).  Round 6: the rest in three -- CHANNELS = the channel block (X sandwiches if they are not LATE_A's, Ssym, the
+//        channel sum Sgs), KBAR = the single-matrix chain of the gradient of Ki (K Pbar^T, Kib, Ki Kib Ki, Pbar^T Ki: five small
+//        launches that read nothing of CHANNELS) and FINAL = the closing assembly of Kbar; a caller with a free side branch runs
+//        KBAR beside CHANNELS.
+// Buffers: H in mm0, HG in mm3, then X in mm1, Sigma^-1 X in mm0 and Sg0 in mm1; SW in mm2 (its m-space form: T in mm1, early).
 int svgp_big_factor_bwd(const svgp_mnist_cfg* c, const svgp_mnist_ws_layout& wl, double* ws, const double* state,
-                        void* stream, int l0, int nl, int part) {
+                        void* stream, int l0, int nl, unsigned pieces) {
     const int m = c->m, L = nl;
     const long long mm = (long long)m * m;
     const real cc = c->N_train / (double)c->b_global;
@@ -758,7 +770,7 @@ int svgp_big_factor_bwd(const svgp_mnist_cfg* c, const svgp_mnist_ws_layout& wl,
     // SW_l = W^T diag(p_l) W = P^T S_l P -- forward quantities only.  Over the rows (a statistics product with contraction b) when ALL
     // rows of the batch are local (b == b_global) and that is the cheaper form (m^2 b against 3 m^3 per channel): at the end of the
     // reverse statistics (svgp_big_stats, mode 1).  From S_l otherwise -- under data parallelism S_l is the all-reduced statistic, so SW needs no exchange of
-    // its own (3 m^3 L / G flops per rank on the window): early half, first part (3), which needs not even (A_hat + jI)^-1 and can
+    // its own (3 m^3 L / G flops per rank on the window): the piece SW, which needs not even (A_hat + jI)^-1 and can
     // run beside the forward tail.  mm2; T = S P in mm1 (free until the late half).
     const bool has_sw = !c->titsias;
     a.SW = has_sw ? s.mm2 : nullptr;
@@ -767,12 +779,11 @@ int svgp_big_factor_bwd(const svgp_mnist_cfg* c, const svgp_mnist_ws_layout& wl,
     // exists for b == b_global, i.e. without a channel window).  mm2 is only read here: the stage can be repeated on a workspace.
     const bool x0_ready = has_sw && sw_rows && l0 == 0 && nl == c->L;
     a.rank1_late = x0_ready ? 1 : 0; a.t = ws + wl.t + ov; a.vbar = ws + wl.vbar + ov;
-    if (has_sw && !sw_rows && (part == 0 || part == 1 || part == 3)) {
+    if ((pieces & SVGP_BWD_SW) && has_sw && !sw_rows) {
         GEMM(0, 1, m, m, m, 1.0, ws + wl.S + om, m, mm, s.PT, m, 0, 0.0, s.mm1, m, mm, L);        // T = S P   (P = (P^T)^T)
         GEMM_SYM(0, 0, m, m, 1.0, s.PT, m, 0, s.mm1, m, mm, 0.0, s.mm2, m, mm, L);                // SW = P^T T
     }
-    if (part == 3) return SVGP_OK;
-    if (part == 0 || part == 1 || part == 4) {
+    if (pieces & SVGP_BWD_EARLY_B) {
         real* G = ws + wl.G + om;
         // H = G D = Si K (Ki - Aji) = Z', D = D^T read as [j][k].  Small m (launch-bound, config 3): D = Ki - Aji is formed while the
         // B operand is staged (one launch less: 1.307 -> 1.299 ms).  Large m: a pass materialises D first -- the second operand
@@ -790,19 +801,11 @@ int svgp_big_factor_bwd(const svgp_mnist_cfg* c, const svgp_mnist_ws_layout& wl,
                            (const real*)s.mm3, s.HGs, (const real*)A, s.Asum);
         SVGP_LAUNCH_CHECK();
     }
-    if (part == 1 || part == 4) return SVGP_OK;
-    // Round 6: part 7 in three pieces -- 8 = the channel block (X sandwiches if they are not part 6's, Ssym, the channel sum Sgs), 9 = the
-    // single-matrix chain of the gradient of Ki (K Pbar^T, Kib, Ki Kib Ki, Pbar^T Ki: five small launches that read nothing of 8) and
-    // 10 = the closing assembly of Kbar.  7 = 8 + 9 + 10; a caller with a free side branch runs 9 beside 8.
-    const bool run_8 = part != 9 && part != 10, run_9 = part != 8 && part != 10, run_10 = part != 8 && part != 9;
-    if (run_8) {
-    // The late half in two parts (round 5): 6 = what reads NOTHING the early half writes, 7 = the rest (2 = 6 + 7).  The vector chain
-    // always belongs to part 6; X, vbar and the two full products Si X, -(Si X) Si do when the statistic SW comes from the reverse
-    // statistics on the caller's stream (`sw_rows`: SPRITES) and not from the early half -- then Si X goes to the Ssym slot (free
-    // until the tile-pair kernel below writes it) instead of mm0, where the early half keeps H until it is summed.  A caller with
-    // the early half on a side branch issues part 6, THEN joins, then part 7: at m = 800 the caller's stream waited 0.8 ms at the join
-    // with 2.3 ms of its own work ready (kernel trace).
-    const bool do_a = part != 7 && part != 8, do_b = part != 6, x_early = sw_rows || !has_sw;
+    // The X block -- X, vbar and the two full products Si X, -(Si X) Si -- belongs to LATE_A when the statistic SW comes from the
+    // reverse statistics on the caller's stream (`sw_rows`: SPRITES) and not from the early half -- then Si X goes to the Ssym slot
+    // (free until the tile-pair kernel below writes it) instead of mm0, where the early half keeps H until it is summed -- and to
+    // CHANNELS otherwise.
+    const bool x_early = sw_rows || !has_sw;
     real* six = x_early ? ws + wl.Ssym + om : s.mm0;
     auto x_block = [&]() -> int {
         if (!x0_ready) {
@@ -819,7 +822,7 @@ int svgp_big_factor_bwd(const svgp_mnist_cfg* c, const svgp_mnist_ws_layout& wl,
         GEMM(0, 1, m, m, m, -1.0, six, m, mm, Si, m, mm, 0.0, s.mm1, m, mm, L);            // Sg0 (mm1: X is consumed)
         return SVGP_OK;
     };
-    if (do_a) {
+    if (pieces & SVGP_BWD_LATE_A) {
         // ubar = ud + gK/2 mu;  mubar = Ki ubar + gK/2 u;  tbar = td + c K mubar: two launches (k_big_gemv_fb)
         hipLaunchKernelGGL(k_big_gemv_fb<1>, dim3((m + 15) / 16, L), dim3(256), (size_t)m * sizeof(real), st, a, (const real*)Ki);
         SVGP_LAUNCH_CHECK();
@@ -827,34 +830,32 @@ int svgp_big_factor_bwd(const svgp_mnist_cfg* c, const svgp_mnist_ws_layout& wl,
         SVGP_LAUNCH_CHECK();
         if (x_early) RUNC(x_block());
     }
-    if (part == 6) return SVGP_OK;
-    if (do_b && !x_early) RUNC(x_block());
-    hipLaunchKernelGGL(k_big_fb_ssym, dim3(ntp, ntp, L), dim3(256), 0, st, a);
-    SVGP_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_big_sum_channels, dim3(nblk(mm)), dim3(256), 0, st, (int)mm, L, real(1), s.mm1, s.Sgs);
-    SVGP_LAUNCH_CHECK();
+    if (pieces & SVGP_BWD_CHANNELS) {
+        if (!x_early) RUNC(x_block());
+        hipLaunchKernelGGL(k_big_fb_ssym, dim3(ntp, ntp, L), dim3(256), 0, st, a);
+        SVGP_LAUNCH_CHECK();
+        hipLaunchKernelGGL(k_big_sum_channels, dim3(nblk(mm)), dim3(256), 0, st, (int)mm, L, real(1), s.mm1, s.Sgs);
+        SVGP_LAUNCH_CHECK();
     }
-    if (part == 8) return SVGP_OK;
     // The gradient of Ki is needed for the channel sum only (Ki is shared): Kib = rep_weight (gK/2 sum A + sum ubar mu^T) + Qs + Pbar K,
     // then Ki Kib Ki once.  Pbar, Qs: this rank's row sums from svgp_big_stats (mode 1).
     FinArgs f;
     f.m = m; f.L = L; f.Ltot = c->L; f.geco = SVGP_LOSS_FLAGS(c); f.b_global = c->b_global; f.c = cc; f.N_train = c->N_train;
     f.rep_weight = c->rep_weight; f.state = state;
     f.Asum = s.Asum; f.ubar = s.vec0; f.mu = a.mu; f.Qs = s.Qs; f.PbarK = s.tA; f.Zs = s.Zs; f.mubar = s.vec1; f.t = ws + wl.t + ov;
-    f.Sgs = s.Sgs; f.HGs = s.HGs; f.Ki = Ki; f.KiPbar = s.Pbar; f.KiKibKi = s.tA; f.Kib = s.tB; f.Kbar = ws + wl.Kbar;
-    f.rank1_late = a.rank1_late; f.vbar = a.vbar;
-    if (run_9) {
-    GEMM(0, 0, m, m, m, 1.0, K, m, 0, s.Pbar, m, 0, 0.0, s.tA, m, 0, 1);                // K Pbar^T = (Pbar K)^T   (s.Pbar holds Pbar^T)
-    hipLaunchKernelGGL(k_big_fb_kib, dim3(nblk(mm)), dim3(256), 0, st, f);             // Kib (tB)
-    SVGP_LAUNCH_CHECK();
-    GEMM(0, 0, m, m, m, 1.0, Ki, m, 0, s.tB, m, 0, 0.0, s.tC, m, 0, 1);                 // Ki Kib             (tC)
-    GEMM(0, 1, m, m, m, 1.0, s.tC, m, 0, Ki, m, 0, 0.0, s.tA, m, 0, 1);                 // Ki Kib Ki          (tA)
-    GEMM(0, 1, m, m, m, 1.0, s.Pbar, m, 0, Ki, m, 0, 0.0, s.tB, m, 0, 1);               // Pbar^T Ki = (Ki Pbar)^T   (tB)
+    f.Sgs = s.Sgs; f.HGs = s.HGs; f.Ki = Ki; f.KiPbar = s.tB; f.KiKibKi = s.tA; f.Kib = s.tB; f.Kbar = ws + wl.Kbar;
+    f.rank1_late = a.rank1_late; f.vbar = a.vbar;      // (KiPbar: KBAR's last product, read by FINAL only)
+    if (pieces & SVGP_BWD_KBAR) {
+        GEMM(0, 0, m, m, m, 1.0, K, m, 0, s.Pbar, m, 0, 0.0, s.tA, m, 0, 1);                // K Pbar^T = (Pbar K)^T   (s.Pbar holds Pbar^T)
+        hipLaunchKernelGGL(k_big_fb_kib, dim3(nblk(mm)), dim3(256), 0, st, f);             // Kib (tB)
+        SVGP_LAUNCH_CHECK();
+        GEMM(0, 0, m, m, m, 1.0, Ki, m, 0, s.tB, m, 0, 0.0, s.tC, m, 0, 1);                 // Ki Kib             (tC)
+        GEMM(0, 1, m, m, m, 1.0, s.tC, m, 0, Ki, m, 0, 0.0, s.tA, m, 0, 1);                 // Ki Kib Ki          (tA)
+        GEMM(0, 1, m, m, m, 1.0, s.Pbar, m, 0, Ki, m, 0, 0.0, s.tB, m, 0, 1);               // Pbar^T Ki = (Ki Pbar)^T   (tB)
     }
-    f.KiPbar = s.tB;
-    if (run_10) {
-    hipLaunchKernelGGL(k_big_fb_final, dim3(nblk(mm)), dim3(256), 0, st, f);
-    SVGP_LAUNCH_CHECK();
+    if (pieces & SVGP_BWD_FINAL) {
+        hipLaunchKernelGGL(k_big_fb_final, dim3(nblk(mm)), dim3(256), 0, st, f);
+        SVGP_LAUNCH_CHECK();
     }
     return SVGP_OK;
 }

@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import STATE, STATE_LEN, MnistCfg, ParamLayout, WsLayout, call
+from ._lib import BWD_PART, FWD_PART, STATE, STATE_LEN, MnistCfg, ParamLayout, WsLayout, call
 
 VAE_PARAM_NAMES = ("enc_c1_w", "enc_c1_b", "enc_c2_w", "enc_c2_b", "enc_c3_w", "enc_c3_b", "enc_d_w", "enc_d_b",
                    "dec_d_w", "dec_d_b", "dec_c1_w", "dec_c1_b", "dec_c2_w", "dec_c2_b", "dec_c3_w", "dec_c3_b")
@@ -210,6 +210,44 @@ def dp_pack_enabled(m):
     (svgp_dp_pack_default, what svgp_mnist_train_step_dp applies)."""
     pack = _lib.Schedule().dp_pack
     return bool(_lib.load_library().svgp_dp_pack_default(m)) if pack is None else pack
+
+
+class ShardedExchange:
+    """Exchange points 1-4 of the channel-sharded step (the sequence of svgp_mnist_train_step_dp) on the flat workspace `ws` with
+    layout `wl`: each point is ONE grouped launch of a symmetric (L, m, m) block -- tile-packed (SymBlock) from m >= 512,
+    dp_pack_enabled -- and its (L, m) / (L,) companions.  l0, nl: the rank's channel window."""
+
+    def __init__(self, ws, wl, m, L, rank, world_size):
+        self.m, self.nl = m, L // world_size
+        self.l0 = rank * self.nl
+        pack = dp_pack_enabled(m)
+        pe = int(_lib.load_library().svgp_sym_packed_elems(m))
+        if pack and wl.xpack_len < L * pe:
+            raise _lib.SvgpError("the packed exchange needs the workspace's wire buffer: build the engine with world_size > 1 "
+                                 "(cfg.single_stat_block) or set SVGP_DP_PACK=0")
+        xp = ws[wl.xpack:wl.xpack + L * pe] if pack else None      # ONE wire buffer: every point moves one symmetric block
+        fld = lambda name, per: ws[getattr(wl, name):getattr(wl, name) + L * per]       # an (L, per) field
+
+        def point(kind, block, vecs, prepacked=False):
+            sym = SymBlock(m, L, False, xp, prepacked) if pack else None
+            return [ExchangeOp(kind, fld(block, m * m), sym)] + [ExchangeOp(kind, fld(n, per)) for n, per in vecs]
+        # (round 4: M2 = Ki A Ki is neither formed nor exchanged -- the row stage evaluates k^T M2 k as w^T Si w, gp_large.hip;
+        # KL_l comes out of the forward stage's tail, joined before point 4)
+        self._points = (point("reduce_scatter", "S", (("v", m),)),
+                        point("allgather", "Si", (("t", m), ("u", m)), prepacked=True),
+                        point("reduce_scatter", "A2", (("ud", m), ("td", m))),
+                        point("allgather", "Ssym", (("vbar", m), ("KL", 1))))
+        self._si = ws.data_ptr() + 8 * (wl.Si + self.l0 * m * m)
+        self._si_wire = xp.data_ptr() + 8 * self.l0 * pe if pack else None
+
+    def point(self, k):
+        """The list of ExchangeOp of exchange point k = 1..4."""
+        return self._points[k - 1]
+
+    def pack_window(self, stream):
+        """The rank's Sigma^-1 window in wire format: BEFORE the caller forks the side branch that reads the window."""
+        if self._si_wire is not None:
+            call("svgp_sym_pack", self.m, self.nl, 0, self._si, self._si_wire, stream)
 
 
 class RcclComm:
@@ -607,50 +645,35 @@ class MnistStepEngine:
         cp, th, ws, st, s = C.byref(cfg), self.theta.data_ptr(), self.ws.data_ptr(), self.state.data_ptr(), \
             self.stream.cuda_stream
         im, ax, ep = images.data_ptr(), aux.data_ptr(), (eps.data_ptr() if eps is not None else None)
-        L, m, G = self.base["L"], self.base["m"], self.world_size
-        nl, l0 = L // G, self.rank * (L // G)
-        fld = lambda name, per: self.ws[getattr(self.wl, name):getattr(self.wl, name) + L * per]
-        mm = m * m
-        pack = dp_pack_enabled(m)
-        pe = int(self.lib.svgp_sym_packed_elems(m))
-        if pack and self.wl.xpack_len < L * pe:
-            raise _lib.SvgpError("the packed exchange needs the workspace's wire buffer: build the engine with world_size > 1 "
-                            "(cfg.single_stat_block) or set SVGP_DP_PACK=0")
-        xp = [self.ws[self.wl.xpack:self.wl.xpack + L * pe]]            # ONE wire buffer: every point moves one symmetric block
-        sym = lambda k, avg=False, pre=False: SymBlock(m, L, avg, xp[k], pre) if pack else None
-        plain = lambda kind, *fields: [ExchangeOp(kind, fld(n, per)) for n, per in fields]
+        plan = ShardedExchange(self.ws, self.wl, self.base["m"], self.base["L"], self.rank, self.world_size)
+        l0, nl = plan.l0, plan.nl
         fork = not _lib.Schedule().side_off
         side = self._side_stream() if fork else self.stream
-        wptr = lambda name, packed_k=None: (xp[packed_k].data_ptr() + 8 * l0 * pe) if packed_k is not None else \
-            (self.ws.data_ptr() + 8 * (getattr(self.wl, name) + l0 * mm))
         with torch.cuda.stream(self.stream):
             call("svgp_mnist_encoder_kernel_matrix_fwd", cp, th, im, ax, ws, s)
             call("svgp_gp_stats_fwd", cp, ws, s)
-        yield [ExchangeOp("reduce_scatter", fld("S", mm), sym(0))] + plain("reduce_scatter", ("v", m))
+        yield plan.point(1)
         with torch.cuda.stream(self.stream):
-            call("svgp_gp_factor_fwd_channels_part", cp, l0, nl, 1, ws, s)            # without the (A_hat + jI)^-1 tail
-            if pack:      # the window in wire format BEFORE the side branch starts reading it
-                call("svgp_sym_pack", m, nl, 0, wptr("Si"), wptr("Si", 0), s)
+            call("svgp_gp_factor_fwd_channels_part", cp, l0, nl, FWD_PART["HEAD"], ws, s)
+            plan.pack_window(s)
             # the tail and the early reverse half go to the side branch, beside the all-gather, the row stage, the decoder and
             # the reverse statistics: FORKED here, ISSUED behind the collective (below) -- enqueued first, the branch's GEMMs
             # fill the chip and the collective's kernel waits for a slot
             side.wait_stream(self.stream)
-        # (round 4: M2 = Ki A Ki is no longer formed or exchanged -- the row stage evaluates k^T M2 k as w^T Si w, gp_large.hip)
-        yield [ExchangeOp("allgather", fld("Si", mm), sym(0, pre=True))] + plain("allgather", ("t", m), ("u", m))
+        yield plan.point(2)
         with torch.cuda.stream(self.stream):
             call("svgp_gp_posterior_fwd", cp, ep, ws, st, s)              # (first: the caller's stream must not wait for the host)
-            call("svgp_gp_factor_fwd_channels_part", cp, l0, nl, 2, ws, side.cuda_stream)
+            call("svgp_gp_factor_fwd_channels_part", cp, l0, nl, FWD_PART["TAIL"], ws, side.cuda_stream)
             if fork:
-                call("svgp_gp_factor_bwd_channels_part", cp, l0, nl, 1, ws, st, side.cuda_stream)
+                call("svgp_gp_factor_bwd_channels_part", cp, l0, nl, BWD_PART["EARLY"], ws, st, side.cuda_stream)
             call("svgp_mnist_decoder_fwd", cp, th, im, ws, s)
             call("svgp_mnist_decoder_bwd", cp, th, im, ws, st, s)
             call("svgp_gp_stats_bwd", cp, ws, st, s)
-        yield [ExchangeOp("reduce_scatter", fld("A2", mm), sym(0))] + plain("reduce_scatter", ("ud", m), ("td", m))
+        yield plan.point(3)
         with torch.cuda.stream(self.stream):
             self.stream.wait_stream(side)
-            call("svgp_gp_factor_bwd_channels_part", cp, l0, nl, 2 if fork else 0, ws, st, s)
-        # (KL_l comes out of the tail, joined above)
-        yield [ExchangeOp("allgather", fld("Ssym", mm), sym(0))] + plain("allgather", ("vbar", m), ("KL", 1))
+            call("svgp_gp_factor_bwd_channels_part", cp, l0, nl, BWD_PART["LATE" if fork else "ALL"], ws, st, s)
+        yield plan.point(4)
         with torch.cuda.stream(self.stream):
             call("svgp_gp_posterior_bwd", cp, ws, st, s)
             call("svgp_kernel_matrix_bwd_partials", cp, th, ax, ws, s)

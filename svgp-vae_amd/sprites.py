@@ -28,9 +28,9 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import STATE, STATE_LEN, MnistCfg, SpritesKcfg, WsLayout, call
+from ._lib import BWD_PART, FWD_PART, STATE, STATE_LEN, MnistCfg, SpritesKcfg, WsLayout, call
 from .conv import ConvLayer, DeferredSums
-from .engine import ExchangeOp, SymBlock, concurrent_streams, dp_pack_enabled
+from .engine import ExchangeOp, ShardedExchange, concurrent_streams
 
 _F64 = torch.float64
 ENC_STRIDES = (1, 2, 1, 2, 1, 2)
@@ -502,23 +502,11 @@ class SpritesStepEngine:
             call("svgp_gp_stats_fwd", cp, ws, s)
             if self.svgp.titsias:
                 call("svgp_gp_titsias_stats", cp, ws, s)
-        mm_, G_, r_ = self.m * self.m, self.world_size, self.rank
-        nl = L // G_ if self.chan_shard else L
-        fld = lambda name, per: self.ws[getattr(self.wl, name):getattr(self.wl, name) + L * per]       # an (L, per) field
-        plain = lambda kind, *fields: [ExchangeOp(kind, fld(n_, per)) for n_, per in fields]
-        # channel-sharded exchange (the sequence of svgp_mnist_train_step_dp): five points, each ONE grouped RCCL launch; the
-        # symmetric (L,m,m) members travel tile-packed (engine.SymBlock) from m >= 512
-        pack = self.chan_shard and dp_pack_enabled(self.m)
-        pe = int(_lib.load_library().svgp_sym_packed_elems(self.m))
-        if pack and self.wl.xpack_len < L * pe:
-            raise _lib.SvgpError("the packed exchange needs the workspace's wire buffer (world_size > 1) or SVGP_DP_PACK=0")
-        xp = [self.ws[self.wl.xpack:self.wl.xpack + L * pe]] if pack else [None]     # ONE wire buffer per exchange point
-        sym = lambda k, avg=False, pre=False: SymBlock(self.m, L, avg, xp[k], pre) if pack else None
-        l0 = r_ * nl
-        wptr = lambda name, k=None: (xp[k].data_ptr() + 8 * l0 * pe) if k is not None else \
-            (self.ws.data_ptr() + 8 * (getattr(self.wl, name) + l0 * mm_))
+        # channel-sharded exchange (the sequence of svgp_mnist_train_step_dp): five points, each ONE grouped RCCL launch
+        plan = ShardedExchange(self.ws, self.wl, self.m, L, self.rank, self.world_size) if self.chan_shard else None
         if self.chan_shard:
-            yield [ExchangeOp("reduce_scatter", fld("S", mm_), sym(0))] + plain("reduce_scatter", ("v", self.m))
+            l0, nl = plan.l0, plan.nl
+            yield plan.point(1)
         else:
             yield [ExchangeOp("allreduce", self.ws[self.wl.statA:self.wl.statA + self.wl.statA_len])]
         eps_ptr = None if eps is None else eps.contiguous().data_ptr()
@@ -531,16 +519,15 @@ class SpritesStepEngine:
         with torch.cuda.stream(self.stream):
             self._mark("gp_fwd_factor")
             if self.chan_shard:
-                call("svgp_gp_factor_fwd_channels_part", cp, l0, nl, 1, ws, s)         # without the (A_hat + jI)^-1 tail
-                if pack:   # the window in wire format BEFORE the side branch starts reading it
-                    call("svgp_sym_pack", self.m, nl, 0, wptr("Si"), wptr("Si", 0), s)
+                call("svgp_gp_factor_fwd_channels_part", cp, l0, nl, FWD_PART["HEAD"], ws, s)
+                plan.pack_window(s)
                 sd = self.side if self.side is not None else self.stream
                 sd.wait_stream(self.stream)
 
                 def side_work():
-                    call("svgp_gp_factor_fwd_channels_part", cp, l0, nl, 2, ws, sd.cuda_stream)
+                    call("svgp_gp_factor_fwd_channels_part", cp, l0, nl, FWD_PART["TAIL"], ws, sd.cuda_stream)
                     if self.side is not None:
-                        call("svgp_gp_factor_bwd_channels_part", cp, l0, nl, 1, ws, st, sd.cuda_stream)
+                        call("svgp_gp_factor_bwd_channels_part", cp, l0, nl, BWD_PART["EARLY"], ws, st, sd.cuda_stream)
             elif self.m > 64 and self.side is not None and not self.svgp.titsias:
                 # (not with titsias: svgp_gp_titsias_fwd inverts through the same scratch, ws.scr_inv, on the main stream)
                 call("svgp_gp_factor_fwd_defer_aji", cp, ws, s)
@@ -561,8 +548,7 @@ class SpritesStepEngine:
             else:
                 call("svgp_gp_factor_fwd", cp, ws, s)
         if self.chan_shard:
-            # (round 4: M2 = Ki A Ki is neither formed nor exchanged -- the row stage evaluates k^T M2 k as w^T Si w)
-            yield [ExchangeOp("allgather", fld("Si", mm_), sym(0, pre=True))] + plain("allgather", ("t", self.m), ("u", self.m))
+            yield plan.point(2)
         with torch.cuda.stream(self.stream):
             call("svgp_gp_posterior_fwd", cp, eps_ptr, ws, st, s)
             if side_work is not None:
@@ -604,7 +590,7 @@ class SpritesStepEngine:
             self._mark("gp_bwd_stats")
             call("svgp_gp_stats_bwd", cp, ws, st, s)
         if self.chan_shard:
-            yield [ExchangeOp("reduce_scatter", fld("A2", mm_), sym(0))] + plain("reduce_scatter", ("ud", self.m), ("td", self.m))
+            yield plan.point(3)
         else:
             yield [ExchangeOp("allreduce", self.ws[self.wl.statB:self.wl.statB + self.wl.statB_len])]
         with torch.cuda.stream(self.stream):
@@ -612,7 +598,7 @@ class SpritesStepEngine:
             if self.chan_shard:
                 if self.side is not None:
                     self.stream.wait_stream(self.side)
-                call("svgp_gp_factor_bwd_channels_part", cp, l0, nl, 2 if self.side is not None else 0, ws, st, s)
+                call("svgp_gp_factor_bwd_channels_part", cp, l0, nl, BWD_PART["LATE" if self.side is not None else "ALL"], ws, st, s)
             elif self.m > 64 and self.side is not None and not self.svgp.titsias:
                 # the part of the late half that reads nothing the side branch writes -- the vector chain and, with all rows local, X and
                 # the two full products Si X, (Si X) Si: 2.3 ms at m = 800 -- BEFORE the join: the caller's stream used to wait 0.8 ms
@@ -631,8 +617,8 @@ class SpritesStepEngine:
                     call("svgp_gp_factor_bwd_late_b", cp, ws, st, s)
             else:
                 call("svgp_gp_factor_bwd", cp, ws, st, s)
-        if self.chan_shard:      # (KL_l comes out of the tail, joined above)
-            yield [ExchangeOp("allgather", fld("Ssym", mm_), sym(0))] + plain("allgather", ("vbar", self.m), ("KL", 1))
+        if self.chan_shard:
+            yield plan.point(4)
         with torch.cuda.stream(self.stream):
             call("svgp_gp_posterior_bwd", cp, ws, st, s)
             if self.svgp.titsias:

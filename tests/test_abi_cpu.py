@@ -99,6 +99,21 @@ def test_null_pointers_are_rejected_before_any_launch():
         _lib.call("svgp_mnist_step_phase", C.byref(cfg), 7, 1, 1, 1, None, 1, 1, None, None, None)
 
 
+@pytest.mark.parametrize("sym,n_parts,extra", [("svgp_gp_factor_fwd_channels_part", 3, ()),
+                                               ("svgp_gp_factor_bwd_channels_part", 5, (None,))])
+def test_public_part_range_of_the_channel_window_entry_points(sym, n_parts, extra):
+    """The public `part` integers (forward 0..2, reverse 0..4) are checked before anything else: a value outside is refused with
+    the number in the message; one inside gets as far as the next check, the NULL workspace pointer.  No launch either way."""
+    cfg = _lib.MnistCfg(b=64, b_global=64, m=128, L=4, M=8, n_obj=400, N_train=4050.0, jitter=1e-6)
+    assert set(_lib.FWD_PART.values()) == set(range(3)) and set(_lib.BWD_PART.values()) == set(range(5))
+    for part in (-1, n_parts, n_parts + 1, 10):
+        with pytest.raises(svgp_vae_amd.SvgpError, match=f"part {part} "):
+            _lib.call(sym, C.byref(cfg), 0, 4, part, None, *extra, None)
+    for part in range(n_parts):
+        with pytest.raises(svgp_vae_amd.SvgpError, match="NULL device pointer"):
+            _lib.call(sym, C.byref(cfg), 0, 4, part, None, *extra, None)
+
+
 def test_newer_entry_points_validate_their_arguments():
     """Argument checks of the streaming / communicator / Titsias entry points happen before any device call."""
     fake = C.c_void_p(4096)                                     # never dereferenced: every case fails validation first
