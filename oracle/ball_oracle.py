@@ -173,7 +173,8 @@ def train_trajectory(params, vids, epsilons, *, beta, titsias, jitter, clipping_
 def pearce_elbo_graphs(p, vid_batch, beta, type_elbo, l_x, l_y, lt, epsilon, ran_ind=None, con_tf=None):
     """build_pearce_elbo_graphs for type_elbo in {GPVAE_Pearce, VAE, NP}.  l_x / l_y: the length scales of the two
     full-data GPs (trainable under GP_joint, else equal to lt); lt: the constant model length scale the NP context
-    likelihoods use (:152-153).  ran_ind (batch,tmax) long permutations, con_tf = number of context frames (:121-137;
+    likelihoods use (:152-153), or a pair (lt_x, lt_y) of equal values so that autograd can tell the two coordinates'
+    context likelihoods apart.  ran_ind (batch,tmax) long permutations, con_tf = number of context frames (:121-137;
     injected instead of drawn).  Returns (elbo, elbo_recon, elbo_prior_kl, full_p_mu, full_p_var, qnet_mu, qnet_var, pred)."""
     from .pearce_vae_oracle import build_1d_gp
     batch, tmax, px, py = vid_batch.shape
@@ -185,8 +186,9 @@ def pearce_elbo_graphs(p, vid_batch, beta, type_elbo, l_x, l_y, lt, epsilon, ran
         con_T = T[con_ind]
         con_lm = torch.gather(qnet_mu, 1, con_ind[:, :, None].expand(-1, -1, 2))
         con_lv = torch.gather(qnet_var, 1, con_ind[:, :, None].expand(-1, -1, 2))
-        con_lhood = build_1d_gp(con_T, con_lm[:, :, 0], con_lv[:, :, 0], batch_T, lt)[2] + \
-            build_1d_gp(con_T, con_lm[:, :, 1], con_lv[:, :, 1], batch_T, lt)[2]
+        lt_x, lt_y = lt if isinstance(lt, (tuple, list)) else (lt, lt)
+        con_lhood = build_1d_gp(con_T, con_lm[:, :, 0], con_lv[:, :, 0], batch_T, lt_x)[2] + \
+            build_1d_gp(con_T, con_lm[:, :, 1], con_lv[:, :, 1], batch_T, lt_y)[2]
     p_mx, p_vx, lhx = build_1d_gp(batch_T, qnet_mu[:, :, 0], qnet_var[:, :, 0], batch_T, l_x)
     p_my, p_vy, lhy = build_1d_gp(batch_T, qnet_mu[:, :, 1], qnet_var[:, :, 1], batch_T, l_y)
     full_p_mu, full_p_var = torch.stack([p_mx, p_my], 2), torch.stack([p_vx, p_vy], 2)
@@ -208,10 +210,19 @@ def pearce_elbo_graphs(p, vid_batch, beta, type_elbo, l_x, l_y, lt, epsilon, ran
 PEARCE_PARAM_ORDER = ("encW1", "encB1", "encW2", "encB2", "decW1", "decB1", "decW2", "decB2", "l_x", "l_y")
 
 
-def pearce_loss_and_grads(params, vid_batch, epsilon, *, beta, type_elbo, lt, ran_ind=None, con_tf=None):
+def pearce_loss_and_grads(params, vid_batch, epsilon, *, beta, type_elbo, lt, ran_ind=None, con_tf=None,
+                          context_lt_grads=False):
+    """context_lt_grads (NP only): also return d loss / d lt of the x and of the y context likelihood as grads["ctx_l_x"],
+    grads["ctx_l_y"] -- the model constant is no trained parameter, but its reverse pass is computed all the same."""
     leaf = {k: v.detach().clone().requires_grad_(True) for k, v in params.items()}
+    order = list(PEARCE_PARAM_ORDER)
+    if context_lt_grads:
+        leaf["ctx_l_x"] = torch.tensor(float(lt), dtype=DT, requires_grad=True)
+        leaf["ctx_l_y"] = torch.tensor(float(lt), dtype=DT, requires_grad=True)
+        lt = (leaf["ctx_l_x"], leaf["ctx_l_y"])
+        order += ["ctx_l_x", "ctx_l_y"]
     out = pearce_elbo_graphs(leaf, vid_batch, beta, type_elbo, leaf["l_x"], leaf["l_y"], lt, epsilon, ran_ind, con_tf)
     loss = -out[0].mean()
-    gs = torch.autograd.grad(loss, [leaf[k] for k in PEARCE_PARAM_ORDER], allow_unused=True)
-    grads = {k: (torch.zeros_like(leaf[k]) if g is None else g) for k, g in zip(PEARCE_PARAM_ORDER, gs)}
+    gs = torch.autograd.grad(loss, [leaf[k] for k in order], allow_unused=True)
+    grads = {k: (torch.zeros_like(leaf[k]) if g is None else g) for k, g in zip(order, gs)}
     return tuple(o.detach() for o in out), loss.detach(), grads

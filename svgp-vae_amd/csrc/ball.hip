@@ -112,7 +112,7 @@ __global__ void k_ball_head_fwd(int B, int T, int clip, const real* __restrict__
     o.mu[c][e] = h[(size_t)r * 4 + c] + bias[c];
     const real vr = exp(h[(size_t)r * 4 + 2 + c] + bias[2 + c]);
     o.var_raw[c][e] = vr;
-    o.var[c][e] = clip ? fmin(fmax(vr, 1e-6), 1e3) : vr;
+    o.var[c][e] = clip ? clip_keep_nan(vr, 1e-6, 1e3) : vr;
 }
 struct HeadBwdPtrs { const real* var_raw[2]; const real* ybar[2]; const real* s2bar[2]; };
 __global__ void k_ball_head_bwd(int B, int T, int clip, HeadBwdPtrs p, real* __restrict__ dh) {

@@ -271,6 +271,10 @@ __device__ __forceinline__ real svgp_philox_normal(unsigned long long ctr, unsig
 
 __device__ __forceinline__ real recip_no_nan(real x) { return x == real(0) ? real(0) : real(1) / x; }
 
+// tf.clip_by_value / torch.clamp: a NaN stays a NaN (fmin / fmax alone return the other operand, which would turn a NaN
+// gradient into -thr and a NaN encoder variance into the lower bound); bit-identical to fmin(fmax(x, lo), hi) otherwise
+__device__ __forceinline__ real clip_keep_nan(real x, real lo, real hi) { return x != x ? x : fmin(fmax(x, lo), hi); }
+
 // mnistSVGP.kernel_matrix arguments (SVGPVAE_model.py:427-476), shared by gp_kernels.hip and the encoder launch that
 // carries the kernel-matrix build in its spare workgroups
 struct SvgpKernArgs {

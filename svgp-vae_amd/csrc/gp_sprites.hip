@@ -473,7 +473,7 @@ __global__ void k_enc_head_fwd(int b, int L, int clip, const real* __restrict__ 
     else {
         const real vr = exp(v);
         var_raw[(size_t)n * L + j - L] = vr;
-        var[(size_t)n * L + j - L] = clip ? fmin(fmax(vr, 1e-3), 10.0) : vr;
+        var[(size_t)n * L + j - L] = clip ? clip_keep_nan(vr, 1e-3, 10.0) : vr;
     }
 }
 __global__ void k_enc_head_bwd(int b, int L, int clip, const real* __restrict__ var_raw, const real* __restrict__ ybar,
@@ -518,7 +518,7 @@ __global__ void k_sqerr_bwd(long long tot, int geco, real inv_bglobal, real inv_
 }
 __global__ void k_clip(long long tot, real thr, real* __restrict__ g) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < tot) g[i] = fmin(fmax(g[i], -thr), thr);
+    if (i < tot) g[i] = clip_keep_nan(g[i], -thr, thr);
 }
 
 inline unsigned nb256(long long n) { return (unsigned)((n + 255) / 256); }

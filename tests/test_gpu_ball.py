@@ -7,31 +7,10 @@ import torch
 from oracle import ball_oracle as BO
 from oracle import pearce_vae_oracle as PO
 from tests import helpers as H
+from tests.ball_cases import _engine, _pearce_engine, _problem
 
 pytestmark = pytest.mark.gpu
 DT = torch.float64
-
-
-def _problem(batch, T, px, hidden, m, seed=0, lt=2.0):
-    g = torch.Generator().manual_seed(seed)
-    vid = PO.make_video_batch(tmax=T, px=px, py=px, lt=lt, batch=batch, r=max(2, px // 10), generator=g, dtype=DT)
-    p = {k: v.to(DT) for k, v in PO.init_mlp_params(px, px, hidden=hidden, seed=seed).items()}
-    # non-zero biases so that their gradients / updates are exercised from a generic point
-    for k in ("encB1", "encB2", "decB1", "decB2"):
-        p[k] = 0.05 * torch.randn(*p[k].shape, dtype=DT, generator=g)
-    for c in "xy":
-        p[f"ip_{c}"] = BO.BallSVGP.initial_inducing_points(m, False, 1, T, 1, T) + 0.1 * torch.randn(m, dtype=DT, generator=g)
-        p[f"l_{c}"] = torch.tensor(lt + (0.3 if c == "y" else 0.0), dtype=DT)
-    eps = torch.randn(batch, T, 2, dtype=DT, generator=g)
-    return p, vid, eps
-
-
-def _engine(p, batch, T, px, hidden, m, *, titsias, jitter, clip_qs, beta, fixed_ip=False, fixed_gp=False, **kw):
-    from svgp_vae_amd import ball
-    mk = lambda n: ball.SVGP(titsias, m, fixed_ip, 1, T, 2.0, fixed_gp, n, jitter, 1, T, 2.0)
-    flat = {k: (v.reshape(-1) if k.startswith(("encB", "decB", "l_")) else v) for k, v in p.items()}
-    return ball.BallStepEngine(mk("x"), mk("y"), batch=batch, tmax=T, px=px, py=px, hidden=hidden, clip_qs=clip_qs,
-                               beta=beta, params=flat, **kw)
 
 
 CASES = {
@@ -143,13 +122,6 @@ def test_unsupported_shapes_fail_loudly():
 # ---------------------------------------------------------------------------------------------------------
 # Pearce baseline (BASELINE configs[0]: BALL_experiment.py --elbo VAE; also GPVAE_Pearce and NP)
 # ---------------------------------------------------------------------------------------------------------
-def _pearce_engine(p, type_elbo, lt, GP_joint, batch, T, px, hidden, beta, **kw):
-    from svgp_vae_amd import ball
-    flat = {k: (v.reshape(-1) if k.startswith(("encB", "decB", "l_")) else v) for k, v in p.items()}
-    return ball.PearceStepEngine(type_elbo, lt, 0.5, GP_joint, 2.0, batch=batch, tmax=T, px=px, py=px, hidden=hidden,
-                                 beta=beta, params=flat, **kw)
-
-
 PEARCE_CASES = {
     "vae_small": dict(shape=(5, 12, 8, 16), type_elbo="VAE", lt=0.001, joint=False),
     "pearce_small_joint": dict(shape=(5, 12, 8, 16), type_elbo="GPVAE_Pearce", lt=2.0, joint=True),
