@@ -188,7 +188,8 @@ int         svgp_version(void);
 const char* svgp_last_error(void);
 /* sizeof() of the ABI structs as compiled into the library, so a binding can verify its own mirror of a struct at load
  * time (a stale mirror shifts every later field silently): which = 0 svgp_mnist_cfg, 1 svgp_mnist_param_layout,
- * 2 svgp_mnist_ws_layout, 3 svgp_stream_kdesc, 4 svgp_conv_desc, 5 svgp_sprites_kcfg, 6 svgp_pearce_bufs; -1 otherwise. */
+ * 2 svgp_mnist_ws_layout, 3 svgp_stream_kdesc, 4 svgp_conv_desc, 5 svgp_sprites_kcfg, 6 svgp_pearce_bufs,
+ * 7 svgp_sum_job, 8 svgp_casale_cfg, 9 svgp_casale_layout; -1 otherwise. */
 int         svgp_struct_sizeof(int which);
 
 int svgp_mnist_param_layout_get(const svgp_mnist_cfg* cfg, svgp_mnist_param_layout* out);
@@ -786,6 +787,90 @@ int svgp_svigp_bwd(int b, int b_global, int m, int L, int n_pix, double N_train,
 int svgp_svigp_assemble(int b, int b_global, int m, int L, int n_pix, double N_train, const double* noise,
                         const double* part_sums, int n_part, const double* ws, double* out, void* stream);
 int svgp_scale_by_device_scalar(long long n, const double* f, double* x, void* stream);
+
+/* ---- Casale GP-VAE baseline on rotated MNIST (casale.hip): MNIST_experiment.py --elbo GPVAE_Casale ---------------------
+ * casaleGP.V_matrix / taylor_coeff (GPVAE_Casale_model.py:278-351) and the GP prior term of forward_pass_Casale (:134-142)
+ * in H x H space, H = M Q.  The reference forms K_inv = (I - V (alpha I + V^T V)^-1 V^T) / alpha (N x N) and the Taylor
+ * coefficients a (L,N), B (L,N,H), c (L); with K_inv V = V P and V^T A = U the same number is
+ *   G = V^T V   P = (alpha I + G)^-1   W = V^T Z   U = P W   A = (Z - V U) / alpha            (A^T = a)
+ *   GP_prior_term = sum(zb * A[idx]) - sum(A[idx] * (V[idx] U)) + L sum((V[idx] P) * V[idx])
+ *                   + alpha/2 (-||A||_F^2 + L ((N - H) / alpha + tr P))
+ * for the batch rows idx = [lo, hi) of the sorted train set, Z (N,L) the latent sample of all rows and zb (hi-lo, L) the
+ * batch's own.  V[i, k Q + r] = ov[obj_idx[i], k] L_W[ang_idx[i], r] (ov row-normalised with cfg.normalize_obj), L_W the
+ * Cholesky factor of K_W = ExpSinSquared(amplitude, l_GP, 2 pi) on the Q sorted unique train angles, no jitter (:301-302).
+ * Rows are sorted by object: obj_idx is non-decreasing.  gp = [l_GP, amplitude, alpha, object_vectors (n_obj, M)], the
+ * suffix of theta (svgp_casale_layout: th_l_GP).
+ *   svgp_casale_v_fwd  : K_W, L_W (one workgroup) and V
+ *   svgp_casale_gp_fwd : svgp_casale_v_fwd, then G, W (svgp_dgemm_splitk), P (svgp_spd_inverse_batched), U,
+ *                        V[idx] P (svgp_dgemm_batched), one row kernel (V U, A and the row partials of the four sums) and
+ *                        the scalar epilogue -> ws[terms] = [sum zb A, -sum A (V U), L sum (V P) V, ||A||^2, tr P, tr K_inv,
+ *                        sum(c), GP_prior_term]
+ *   svgp_casale_gp_bwd : reverse pass of seed * GP_prior_term: Zbar (N,L), zbbar (hi-lo,L), Vbar, the deterministic VJP of
+ *                        the V build into ovbar (n_obj,M) and L_W (row-chunk partials, fixed order, no float atomics), the
+ *                        Cholesky VJP Phi(L^T Lbar) with two triangular solves and the kernel VJP (one workgroup)
+ *                        -> ws[grad_gp] = [l_GP, amplitude, alpha | object_vectors]; zero where cfg.train_gp / train_ov is 0
+ *   svgp_casale_sample / _seeds : the two samples of a step from ONE encoder pass over all N rows (encode, :86-91: clip
+ *                        [1e-3, 10]; forward_pass_Casale, :123-131: clip [1e-3, 100], log_var) and the combined seed w.r.t.
+ *                        (mu, var_raw) of all N rows for svgp_mnist_encoder_bwd with cfg.clip_qs = 0
+ *   svgp_casale_vae_sample / _vae_seeds : the plain-VAE objective of the `VAE` regime (SVGPVAE_model.py:718-782), batch rows
+ *   svgp_casale_finalize : out (8) = [elbo, recon_loss, GP_prior_term, log_var, KL_term, 0, 0, 0] (:150-153); mode 1: the
+ *                        plain-VAE scalars [elbo_VAE, recon_loss, 0, 0, KL_term] with the decoder's sigma_vae (mode 0 ignores
+ *                        it); state[ADAM_T] += did_adam
+ *   svgp_casale_predict_var : predict_test_set_Casale (:158-203): mean = K_*n A is one GEMM; var_i = k_ii - (|k_i|^2 -
+ *                        r_i . (P r_i)) / alpha from K_*n (T,N), R = K_*n V and RP = R P (T,H each), one wave per test row;
+ *                        the caller spreads var over the channels as the reference does (:194, sic: var[(i L + l) mod T])
+ *   svgp_scale_f64     : x *= f
+ * Refused: Q > 32, H > 2048, M > 128, L > 64 (SVGP_ERR_UNSUPPORTED); a batch range outside [0, N], NULL pointers
+ * (SVGP_ERR_INVALID).  Plain launches on `stream`. */
+typedef struct {
+    int32_t N;             /* train rows                                                                    */
+    int32_t n_obj;         /* rows of the object_vectors table                                              */
+    int32_t Q;             /* unique train angles                                                           */
+    int32_t M;             /* object-vector dimension; H = M Q                                              */
+    int32_t L;             /* latent channels                                                               */
+    int32_t b_cap;         /* largest batch (rows of the batch-sized fields)                                */
+    int32_t normalize_obj; /* object_kernel_normalize                                                       */
+    int32_t train_gp;      /* 0: l_GP, amplitude, alpha fixed (fixed_gp_params)                             */
+    int32_t train_ov;      /* 1: object_vectors trainable (--ov_joint)                                      */
+} svgp_casale_cfg;
+/* theta offsets (encoder, decoder, l_GP, amplitude, alpha, object_vectors: the reference's creation order) and workspace
+ * offsets (float64 elements) of every intermediate */
+typedef struct {
+    int64_t th_l_GP, th_amplitude, th_alpha, th_ov, n_enc, n_vae, n_total;
+    int64_t K_W, L_W;                     /* (Q,Q) each                                                     */
+    int64_t V, G, P, W, U, VU, A, VPb;    /* (N,H) (H,H) (H,H) (H,L) (H,L) (N,L) (N,L) (b,H)                */
+    int64_t Z, zb, qvar_b;                /* (N,L) (b,L) (b,L): the two samples, the batch's clipped variance */
+    int64_t part, terms, lv_part, n_lv;   /* (N,4) row partials; (8); per-workgroup log_var / KL partials   */
+    int64_t Abar, Cm, Zbar, zbbar, Vbar;  /* (N,L) (N,L) (N,L) (b,L) (N,H)                                  */
+    int64_t Ubar, Pbar, Wbar, T, Mbar;    /* (H,L) (H,H) (H,L) (H,H) (H,H): Mbar holds Mbar + Mbar^T        */
+    int64_t part_alpha, trM;              /* (N) row partials of alphabar; (1) tr Mbar                      */
+    int64_t LWbar_part, n_chunk, LWbar, KWbar; /* (n_chunk,Q,Q) partials over row chunks; (Q,Q); (Q,Q)      */
+    int64_t grad_gp;                      /* (3 + n_obj M) = [l_GP, amplitude, alpha | object_vectors]      */
+    int64_t logdet, scr_inv, scr_splitk, scr_splitk_len;
+    int64_t total;
+} svgp_casale_layout;
+int svgp_casale_layout_get(const svgp_casale_cfg*, svgp_casale_layout* out);
+int svgp_casale_v_fwd(const svgp_casale_cfg*, const double* gp, const double* angles, const int32_t* obj_idx,
+                      const int32_t* ang_idx, double* ws, void* stream);
+int svgp_casale_gp_fwd(const svgp_casale_cfg*, const double* gp, const double* angles, const int32_t* obj_idx,
+                       const int32_t* ang_idx, const double* Z, const double* zb, int lo, int hi, double* ws, void* stream);
+int svgp_casale_gp_bwd(const svgp_casale_cfg*, const double* gp, const double* angles, const int32_t* obj_idx,
+                       const int32_t* ang_idx, const double* Z, const double* zb, int lo, int hi, double seed, double* ws,
+                       void* stream);
+int svgp_casale_sample(const svgp_casale_cfg*, int clip, int lo, int hi, const double* mu, const double* var_raw,
+                       const double* eps_full, const double* eps_batch, double* z_dec, double* ws, void* stream);
+int svgp_casale_seeds(const svgp_casale_cfg*, int clip, int lo, int hi, const double* var_raw, const double* eps_full,
+                      const double* eps_batch, const double* dec_zbar, double c_logvar, double* ybar, double* s2bar,
+                      double* ws, void* stream);
+int svgp_casale_vae_sample(const svgp_casale_cfg*, int b, const double* mu, const double* var_raw, const double* eps,
+                           double* z_dec, double* ws, void* stream);
+int svgp_casale_vae_seeds(const svgp_casale_cfg*, int b, double scale, const double* mu, const double* var_raw,
+                          const double* eps, const double* dec_zbar, double* ybar, double* s2bar, void* stream);
+int svgp_casale_finalize(const svgp_casale_cfg*, int mode, int b, double beta, double sigma_vae, const double* dec_sums,
+                         int did_adam, double* ws, double* out, double* state, void* stream);
+int svgp_casale_predict_var(int T, int N, int H, const double* K_tn, const double* k_tt, const double* R, const double* RP,
+                            const double* alpha, double* var, void* stream);
+int svgp_scale_f64(long long n, double f, double* x, void* stream);
 
 /* ---- runtime helpers: HIP graphs and events without going through torch ---------------------*/
 int svgp_stream_create(void** stream_out);

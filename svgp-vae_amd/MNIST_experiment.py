@@ -1,5 +1,5 @@
 """Rotated-MNIST experiment driver with the reference's CLI (MNIST_experiment.py:1115-1174 flags and
-defaults) for `--elbo SVGPVAE_Hensman | SVGPVAE_Titsias | SVIGP_Hensman`, running every step on the HIP library.
+defaults) for `--elbo SVGPVAE_Hensman | SVGPVAE_Titsias | SVIGP_Hensman | GPVAE_Casale`, running every step on the HIP library.
 
     python -m svgp_vae_amd.MNIST_experiment --elbo SVGPVAE_Hensman --ip_joint --GP_joint --ov_joint \
         --clip_qs --GECO --PCA --mnist_data_path "MNIST data/"
@@ -11,7 +11,9 @@ generation MSE on the test set (:457-486) and `pics/test_metrics.txt` lines `epo
 (:509-510).  Plotting / pandas logging of the reference are not reproduced.
 `--elbo SVIGP_Hensman` mirrors run_experiment_rotated_mnist_SVIGP_Hensman (:544-760): deep SVIGP with free variational
 parameters, same loaders / inducing-point init, per-epoch train MSE and the conditional-generation MSE on the test set.
-Other --elbo values (VAE, CVAE, GPVAE_Casale*) are baselines outside this build.
+`--elbo GPVAE_Casale` mirrors run_experiment_rotated_mnist_Casale (:786-1110): Casale's GP-VAE with the three optimisation
+regimes of `--opt_regime` (joint / GP / VAE), one Adam state, conditional generation on the test set every 5 epochs.
+Other --elbo values (VAE, CVAE, GPVAE_Casale_batch) are baselines outside this build.
 """
 import argparse
 import json
@@ -64,7 +66,8 @@ def build_parser():
     # additions of this build
     p.add_argument('--train_file', type=str, default=None,
                    help="pickle used as the train set instead of train_data<dataset>.p (absent from the reference checkout)")
-    p.add_argument('--eval_every', type=int, default=10, help="reference: every 10 epochs")
+    p.add_argument('--eval_every', type=int, default=None,
+                   help="evaluation period in epochs; default: the reference's 10, and 5 for GPVAE_Casale")
     p.add_argument('--seed', type=int, default=0, help="seed of the Keras-style weight init and numpy")
     p.add_argument('--epsilon_seed', type=int, default=None,
                    help="reproducible N(0,1) draws of SVGPVAE_model.py:901: batch i of epoch e uses "
@@ -76,6 +79,12 @@ def build_parser():
                    help="rank 0 writes the per-step log (elbo, recon_loss, C_ma, lagrange_mult), the evaluation series and the "
                         "final flat parameter vector to this file")
     return p
+
+
+def _eval_every(args, default):
+    """--eval_every, or the calling driver's reference period when the flag was not given."""
+    given = getattr(args, "eval_every", None)
+    return default if given is None else given
 
 
 def run_experiment_rotated_mnist_SVGPVAE(args, args_dict=None, ctx=None):
@@ -178,7 +187,7 @@ def run_experiment_rotated_mnist_SVGPVAE(args, args_dict=None, ctx=None):
         return eng.scalars()
 
     def on_epoch_end(epoch, log):
-        if not ((epoch + 1) % args.eval_every == 0 or epoch + 1 == nr_epochs):
+        if not ((epoch + 1) % _eval_every(args, 10) == 0 or epoch + 1 == nr_epochs):
             return
         if root:       # parameters are replicated: rank 0 evaluates alone (collective-free stage calls), the others wait
             # eval-set reconstruction through the posterior (forward only, no optimiser step)
@@ -280,7 +289,7 @@ def run_experiment_rotated_mnist_SVIGP_Hensman(args, args_dict=None):
         mse = float(np.sum(losses) / N_train)
         log["epoch"].append(epoch); log["elbo"].append(float(np.mean(elbos))); log["recon_loss"].append(mse)
         log["epoch_time"].append(time.time() - t0)
-        if (epoch + 1) % args.eval_every == 0 or epoch + 1 == nr_epochs:
+        if (epoch + 1) % _eval_every(args, 10) == 0 or epoch + 1 == nr_epochs:
             print(f"Epoch {epoch}, mean ELBO per batch: {np.mean(elbos)}")
             print(f"MSE loss on train set for epoch {epoch} : {mse}")
             cg = [float(eng.predict(d_test_img[lo:hi], d_test_aux[lo:hi])[1]) for lo, hi in batches(N_test, args.batch_size)]
@@ -299,6 +308,97 @@ def run_experiment_rotated_mnist_SVIGP_Hensman(args, args_dict=None):
     return log
 
 
+def run_experiment_rotated_mnist_Casale(args, args_dict=None):
+    """MNIST_experiment.py:786-1110.  Returns a dict of the logged series (per-step ELBO included)."""
+    from .GPVAE_Casale_model import CasaleStepEngine, _angles_mask, casaleGP, sort_train_data
+    np.random.seed(args.seed)
+    n = len(args.dataset)
+    GPLVM_ending = "" if args.M == 8 else "_{}".format(args.M)                                # :819
+    ending = args.dataset + GPLVM_ending + ".p"
+    load = lambda path: pickle.load(open(path, "rb"))
+    train = sort_train_data(load(args.train_file or (args.mnist_data_path + "train_data" + ending)), dataset=args.dataset)
+    mask_path = args.mnist_data_path + "train_ids_mask" + ending
+    # the mask is a function of the train rows; a stored one is only used when it fits them
+    train_ids_mask = load(mask_path) if os.path.exists(mask_path) and not args.train_file else _angles_mask(train["aux_data"][:, 1:])
+    te = load(args.mnist_data_path + "test_data" + ending)
+    N_train, N_test = len(train["images"]), len(te["images"])
+    if int(np.sum(train_ids_mask)) != N_train:
+        raise ValueError(f"train_ids_mask selects {int(np.sum(train_ids_mask))} (object, angle) pairs for {N_train} train rows")
+    chkpnt_dir = None
+    if args.save:
+        stamp = time.strftime("%d_%m_%Y__at__%H_%M_%S")
+        chkpnt_dir = os.path.join(args.base_dir, args.expid, f"{args.elbo}_{args.beta}__on__{stamp}") + "/"
+        os.makedirs(chkpnt_dir + "pics/", exist_ok=True)
+        json.dump({k: v for k, v in (args_dict or vars(args)).items() if not callable(v)}, open(chkpnt_dir + "args.json", "wt"))
+    VAE = mnistVAE(L=args.L, seed=args.seed)                                                   # :846
+    if args.PCA:                                                                               # :849-855
+        object_vectors_init = load(args.mnist_data_path + "pca_ov_init{}{}.p".format(args.dataset, GPLVM_ending))
+    else:
+        assert args.ov_joint, "If --ov_joint is not used, at least PCA initialization must be utilized."
+        object_vectors_init = np.random.normal(0, 1.5, n * 400 * args.M).reshape(n * 400, args.M)
+    GP = casaleGP(fixed_gp_params=not args.GP_joint, object_vectors_init=object_vectors_init,
+                  object_kernel_normalize=args.object_kernel_normalize, ov_joint=args.ov_joint)   # :848, :857 (sic)
+    train_aux = train["aux_data"][:, :3]                       # [global id, object id, angle]: the step reads nothing else
+    eng = CasaleStepEngine(VAE, GP, train["images"], train_aux, batch_size=args.batch_size, beta=args.beta,
+                           clipping_qs=args.clip_qs)
+    print(f"Number of train params: {eng.n_total}")
+    nr_epochs, training_regime = parse_opt_regime(args.opt_regime)                              # :978
+    train_batches = batches(N_train, args.batch_size)
+    every = _eval_every(args, 5)                                                                # :1067
+    L = args.L
+    d_test_img = torch.tensor(te["images"], dtype=torch.float64, device=eng.dev).contiguous()
+    log = dict(epoch=[], regime=[], elbo=[], recon_loss=[], step_elbo=[], cgen_mse=[], epoch_time=[])
+    start, recon_images_cgen = time.time(), None
+    for epoch in range(nr_epochs):
+        regime, t0 = training_regime[epoch], time.time()
+        elbos, losses = [], []
+        for i, (lo, hi) in enumerate(train_batches):                                            # :1018-1025
+            eps_f = eps_b = None
+            if args.epsilon_seed is not None:
+                eps_f = np.random.RandomState(1000 * epoch + i + args.epsilon_seed).randn(N_train, L)
+                eps_b = np.random.RandomState(500000 + 1000 * epoch + i + args.epsilon_seed).randn(hi - lo, L)
+            eng.step(regime, lo, hi, eps_full=eps_f, eps_batch=eps_b, adam=True)
+            sc = eng.scalars()
+            elbos.append(sc["elbo"]); losses.append(sc["recon_loss"])
+        mse = float(np.sum(losses) / N_train)
+        log["epoch"].append(epoch); log["regime"].append(regime); log["elbo"].append(float(np.mean(elbos)))
+        log["recon_loss"].append(mse); log["step_elbo"].extend(elbos); log["epoch_time"].append(time.time() - t0)
+        print(f"Epoch {epoch}, opt regime {regime}, mean ELBO per batch: {np.mean(elbos)}")
+        print(f"Epoch {epoch}, opt regime {regime}, MSE loss on train set: {mse}")
+        print(f"Time elapsed for epoch {epoch}, opt regime {regime}: {time.time() - t0}", flush=True)
+        if (epoch + 1) % every == 0:                                                            # :1067-1098
+            eps_f = eps_t = None
+            if args.epsilon_seed is not None:
+                eps_f = np.random.RandomState(900000 + epoch + args.epsilon_seed).randn(N_train, L)
+                eps_t = np.random.RandomState(950000 + epoch + args.epsilon_seed).randn(N_test, L)
+            recon_images_cgen, cgen = eng.predict(d_test_img, te["aux_data"], eps_full=eps_f, epsilon=eps_t)
+            cgen = float(cgen)
+            log["cgen_mse"].append((epoch, cgen))
+            print(f"Conditional generation MSE loss on test set for epoch {epoch}: {cgen}", flush=True)
+            if chkpnt_dir:
+                with open(chkpnt_dir + "pics/test_metrics.txt", "a") as f:
+                    f.write("{},{}\n".format(epoch + 1, round(cgen, 4)))
+                if args.save_model_weights:
+                    eng.synchronize()
+                    torch.save({"theta": eng.theta.cpu(), "adam_m": eng.adam_m.cpu(), "adam_v": eng.adam_v.cpu(),
+                                "state": eng.state.cpu()}, chkpnt_dir + f"model_{int(eng.scalars()['adam_t'])}.pt")
+    log["total_time"] = time.time() - start
+    print("Running time for {} epochs: {}".format(nr_epochs, round(log["total_time"], 2)))
+    if log["cgen_mse"]:
+        best = sorted(log["cgen_mse"], key=lambda x: x[1])[0]
+        print("Best cgen MSE on test set throughout training at epoch {}: {}".format(best[0], best[1]))
+    if chkpnt_dir and recon_images_cgen is not None:
+        with open(chkpnt_dir + "cgen_images.p", "wb") as f:
+            pickle.dump(recon_images_cgen.cpu().numpy(), f)
+    log["chkpnt_dir"] = chkpnt_dir
+    if args.log_json:
+        eng.synchronize()
+        out = {k: v for k, v in log.items()}
+        out["theta"] = eng.theta.cpu().tolist()
+        json.dump(out, open(args.log_json, "wt"))
+    return log
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
     if args.elbo in ("SVGPVAE_Hensman", "SVGPVAE_Titsias"):
@@ -310,7 +410,9 @@ def main(argv=None):
             ctx.close()
     if args.elbo == "SVIGP_Hensman":
         return run_experiment_rotated_mnist_SVIGP_Hensman(args, vars(args))
-    raise NotImplementedError(f"--elbo {args.elbo}: only SVGPVAE_Hensman / SVGPVAE_Titsias / SVIGP_Hensman are built "
+    if args.elbo == "GPVAE_Casale":
+        return run_experiment_rotated_mnist_Casale(args, vars(args))
+    raise NotImplementedError(f"--elbo {args.elbo}: only SVGPVAE_Hensman / SVGPVAE_Titsias / SVIGP_Hensman / GPVAE_Casale are built "
                               f"(see DESIGN.md section 9)")
 
 

@@ -74,6 +74,23 @@ class PearceBufs(C.Structure):
                                           "dl_part")]
 
 
+class CasaleCfg(C.Structure):
+    """svgp_casale_cfg (include/svgpvae_hip.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("N", "n_obj", "Q", "M", "L", "b_cap", "normalize_obj", "train_gp", "train_ov")]
+
+
+CASALE_FIELDS = ("th_l_GP", "th_amplitude", "th_alpha", "th_ov", "n_enc", "n_vae", "n_total",
+                 "K_W", "L_W", "V", "G", "P", "W", "U", "VU", "A", "VPb", "Z", "zb", "qvar_b",
+                 "part", "terms", "lv_part", "n_lv", "Abar", "Cm", "Zbar", "zbbar", "Vbar",
+                 "Ubar", "Pbar", "Wbar", "T", "Mbar", "part_alpha", "trM", "LWbar_part", "n_chunk", "LWbar", "KWbar",
+                 "grad_gp", "logdet", "scr_inv", "scr_splitk", "scr_splitk_len", "total")
+
+
+class CasaleLayout(C.Structure):
+    """svgp_casale_layout (include/svgpvae_hip.h)."""
+    _fields_ = [(n, C.c_int64) for n in CASALE_FIELDS]
+
+
 STATE = dict(C_MA=0, LAGRANGE=1, ALPHA=2, ADAM_T=3, LR=4, BETA=5, ELBO=6, RECON_LOSS=7, KL_TERM=8,
              INSIDE_ELBO=9, CE_TERM=10, INSIDE_RECON=11, INSIDE_KL=12, RNG_CTR=13)
 STATE_LEN = 16
@@ -241,6 +258,17 @@ SIGNATURES = {
     "svgp_svigp_assemble": [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _P, _P, C.c_int, _P, _P, _P],
     "svgp_scale_by_device_scalar": [C.c_longlong, _P, _P, _P],
     "svgp_ball_rasterize": [C.c_longlong, C.c_int, C.c_int, C.c_double, _P, _P, _P],
+    "svgp_casale_layout_get": [C.POINTER(CasaleCfg), C.POINTER(CasaleLayout)],
+    "svgp_casale_gp_fwd": [C.POINTER(CasaleCfg), _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, _P, _P],
+    "svgp_casale_gp_bwd": [C.POINTER(CasaleCfg), _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_double, _P, _P],
+    "svgp_casale_sample": [C.POINTER(CasaleCfg), C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P],
+    "svgp_casale_seeds": [C.POINTER(CasaleCfg), C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.c_double, _P, _P, _P, _P],
+    "svgp_casale_vae_sample": [C.POINTER(CasaleCfg), C.c_int, _P, _P, _P, _P, _P, _P],
+    "svgp_casale_vae_seeds": [C.POINTER(CasaleCfg), C.c_int, C.c_double, _P, _P, _P, _P, _P, _P, _P],
+    "svgp_casale_finalize": [C.POINTER(CasaleCfg), C.c_int, C.c_int, C.c_double, C.c_double, _P, C.c_int, _P, _P, _P, _P],
+    "svgp_casale_predict_var": [C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P],
+    "svgp_casale_v_fwd": [C.POINTER(CasaleCfg), _P, _P, _P, _P, _P, _P],
+    "svgp_scale_f64": [C.c_longlong, C.c_double, _P, _P],
     "svgp_stream_create": [C.POINTER(_P)],
     "svgp_stream_destroy": [_P],
     "svgp_stream_sync": [_P],
@@ -302,7 +330,8 @@ def load_library(path=None):
         fn.argtypes = argtypes
         fn.restype = restype
     # the ctypes mirrors must have the layout the library was compiled with (svgp_struct_sizeof)
-    for which, cls in enumerate((MnistCfg, ParamLayout, WsLayout, StreamKdesc, ConvDesc, SpritesKcfg, PearceBufs, SumJob)):
+    for which, cls in enumerate((MnistCfg, ParamLayout, WsLayout, StreamKdesc, ConvDesc, SpritesKcfg, PearceBufs, SumJob,
+                                 CasaleCfg, CasaleLayout)):
         if lib.svgp_struct_sizeof(which) != C.sizeof(cls):
             raise SvgpError(f"{p}: sizeof({cls.__name__}) is {lib.svgp_struct_sizeof(which)} in the library but "
                             f"{C.sizeof(cls)} in the binding; rebuild the library or update _lib.py")

@@ -29,6 +29,8 @@ extern "C" int svgp_struct_sizeof(int which) {
     case 5: return (int)sizeof(svgp_sprites_kcfg);
     case 6: return (int)sizeof(svgp_pearce_bufs);
     case 7: return (int)sizeof(svgp_sum_job);
+    case 8: return (int)sizeof(svgp_casale_cfg);
+    case 9: return (int)sizeof(svgp_casale_layout);
     default: return -1;
     }
 }
