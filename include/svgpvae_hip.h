@@ -872,6 +872,22 @@ int svgp_casale_predict_var(int T, int N, int H, const double* K_tn, const doubl
                             const double* alpha, double* var, void* stream);
 int svgp_scale_f64(long long n, double f, double* x, void* stream);
 
+/* ---- bias analysis of the inducing mean vector (bias.hip): MNIST_experiment.py --bias_analysis, supplement C.4 ----------
+ * The mean vector of channel l, c K_mm (Sigma_l + jI)^-1 K_mb (y_l / noise_l) with c = N_train / b (SVGPVAE_model.py:345-370),
+ * is ws[mu_hat] (L, m) of every step.  The reference appends it to a host list every step and averages the list at the end
+ * of the epoch (MNIST_experiment.py:325-363, utils.py:922-948); here the sum stays on the device.
+ * svgp_mean_vectors_accumulate: acc (L m + 1) doubles, zeroed by the caller at the start of the epoch:
+ *   acc[i] += mu_hat[i] for i < L m, acc[L m] += 1 (the number of accumulated steps).  One thread per element, no atomics:
+ *   after k calls acc[:L m] is the left-to-right float64 sum of the k inputs, bit for bit (the reference's `+=` order).
+ * svgp_mean_vectors_bias: out (1 + L) doubles from acc and the whole-train-set vectors full (L, m), B = acc[L m]:
+ *   out[1 + l] = sum_j |acc[l][j] / B - full[l][j]|   (a true division, utils.py:944-946)
+ *   out[0]     = (sum_l out[1 + l]) / L               (np.mean, :948)
+ *   One launch of one workgroup with a fixed summation order: the same bits on every run.  B = 0 gives NaN / infinity
+ *   through the arithmetic; nothing traps.
+ * Both: L < 1, m < 1 or a NULL pointer -> SVGP_ERR_INVALID, m > 2048 -> SVGP_ERR_UNSUPPORTED, before any launch.         */
+int svgp_mean_vectors_accumulate(int L, int m, const double* mu_hat, double* acc, void* stream);
+int svgp_mean_vectors_bias(int L, int m, const double* acc, const double* full, double* out, void* stream);
+
 /* ---- runtime helpers: HIP graphs and events without going through torch ---------------------*/
 int svgp_stream_create(void** stream_out);
 /* HIP maps streams onto a small pool of hardware queues (GPU_MAX_HW_QUEUES) in creation order; two streams on one queue run

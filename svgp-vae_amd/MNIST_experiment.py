@@ -9,6 +9,12 @@ inverted `fixed_*` flags (:96-98), the un-shuffled epoch loop with ragged last b
 carry / first-step alpha=0 (kept on device), and every 10 epochs: eval-set reconstruction MSE, conditional
 generation MSE on the test set (:457-486) and `pics/test_metrics.txt` lines `epoch,recon MSE,cgen MSE`
 (:509-510).  Plotting / pandas logging of the reference are not reproduced.
+`--bias_analysis` (:172-179, 325-363; supplement C.4) prints `Bias for epoch {epoch}: {bias}` after every epoch: the distance
+between the epoch's average of the per-step inducing mean vectors and the ones of the whole train set; `--save_latents`
+(:181-187, 531-541; needs `--save`) pickles the latent samples of the whole train set after the last epoch to
+`latents_train_full.p`.  Both are wired for the two SVGPVAE objectives only.
+Accepted without effect: `--test_set_metrics` (it selects the split of the reference's pandas rows, which this build does not
+write), `--show_pics` (no plots) and `--ram` (the reference's TensorFlow memory fraction).
 `--elbo SVIGP_Hensman` mirrors run_experiment_rotated_mnist_SVIGP_Hensman (:544-760): deep SVIGP with free variational
 parameters, same loaders / inducing-point init, per-epoch train MSE and the conditional-generation MSE on the test set.
 `--elbo GPVAE_Casale` mirrors run_experiment_rotated_mnist_Casale (:786-1110): Casale's GP-VAE with the three optimisation
@@ -25,7 +31,8 @@ import numpy as np
 import torch
 
 from .SVGPVAE_model import _runtime, bacthing_predict_SVGPVAE_rotated_mnist, batching_encode_SVGPVAE, mnistSVGP
-from .utils import batches, generate_init_inducing_points, import_rotated_mnist, parse_opt_regime
+from .utils import (batches, generate_init_inducing_points, import_rotated_mnist, latent_samples_SVGPVAE,
+                    parse_opt_regime)
 from .VAE_utils import mnistVAE
 
 
@@ -92,11 +99,23 @@ def run_experiment_rotated_mnist_SVGPVAE(args, args_dict=None, ctx=None):
 
     Data parallel (svgp_vae_amd/dp.py): launched as `python -m torch.distributed.run --nproc-per-node G -m
     svgp_vae_amd.MNIST_experiment ...`, every rank takes a contiguous row range of every batch (incl. the ragged last one),
-    c = N_train / b_global, the engines all-reduce statistics and gradients; rank 0 alone evaluates, prints and writes files."""
+    c = N_train / b_global, the engines all-reduce statistics and gradients; rank 0 alone evaluates, prints and writes files.
+
+    --bias_analysis: the mean vectors of every optimiser step (ws[mu_hat] of its forward pass, i.e. at the parameters before
+    the update; the ragged last batch included) are summed on the device by one extra launch behind the step, outside the
+    captured graph and without a read-back; at the end of every epoch rank 0 computes the mean vectors of the whole train
+    set at the parameters after the last update (c = N_train / N) and the bias of utils.py:922-948, prints it and appends
+    (epoch, bias) to log["bias"].  DEVIATION: the reference fills its list only in the GECO branch (:329-342) and fails on
+    the empty list without --GECO; this build collects under both objectives.
+    --save_latents: after the last epoch rank 0 writes the latent samples (N, L) of the whole train set to
+    chkpnt_dir + "latents_train_full.p" and returns the device tensor as log["_latents"]; with --epsilon_seed s the draw is
+    numpy.random.RandomState(1000 nr_epochs + s).randn(N, L), otherwise it is made on the device."""
     from .dp import DistContext, attach_library_comm, run_sharded_epochs
     if args.elbo not in ("SVGPVAE_Hensman", "SVGPVAE_Titsias"):
         raise NotImplementedError(f"--elbo {args.elbo}: only SVGPVAE_Hensman / SVGPVAE_Titsias are built "
                                   f"(see DESIGN.md section 9)")
+    if args.save_latents and not args.save:
+        raise ValueError("--save_latents writes latents_train_full.p into the checkpoint directory, which exists only with --save")
     ctx = (ctx or DistContext()).init()
     root = ctx.rank == 0
     np.random.seed(args.seed)                    # every rank: the same initial parameters (they are never broadcast)
@@ -182,11 +201,27 @@ def run_experiment_rotated_mnist_SVGPVAE(args, args_dict=None, ctx=None):
                 eng.capture(("train", b), adam=True)
                 graphs[b] = True
             eng.replay(("train", b))
+        if args.bias_analysis:         # :341-342: this step's mean vectors into the epoch's sum; a launch of its own behind the graph
+            eng.mean_vectors_accumulate()
         # the reference fetches elbo / recon_loss / C_ma / lagrange_mult every step (:334-340); one 128-byte read-back
         eng.synchronize()
         return eng.scalars()
 
+    def on_epoch_start(epoch):
+        if args.bias_analysis:         # :325-326
+            eng.mean_vectors_begin()
+
+    def bias_of_epoch(epoch, log):
+        """:357-363: the whole-train-set mean vectors at the parameters the epoch ends with, against the average of the steps'."""
+        if root:
+            bias, _ = eng.mean_vectors_bias(eng.mean_vectors_full(d_train_img, d_train_aux))
+            log.setdefault("bias", []).append((epoch, bias))
+            print("Bias for epoch {}: {}".format(epoch, bias), flush=True)
+        ctx.barrier()
+
     def on_epoch_end(epoch, log):
+        if args.bias_analysis:
+            bias_of_epoch(epoch, log)
         if not ((epoch + 1) % _eval_every(args, 10) == 0 or epoch + 1 == nr_epochs):
             return
         if root:       # parameters are replicated: rank 0 evaluates alone (collective-free stage calls), the others wait
@@ -228,8 +263,22 @@ def run_experiment_rotated_mnist_SVGPVAE(args, args_dict=None, ctx=None):
     nr_epochs, training_regime = parse_opt_regime(args.opt_regime)
     start = time.time()
 
-    log = run_sharded_epochs(ctx, train_batches, nr_epochs, local_step, N_train=N_train, on_epoch_end=on_epoch_end)
+    log = run_sharded_epochs(ctx, train_batches, nr_epochs, local_step, N_train=N_train, on_epoch_end=on_epoch_end,
+                             on_epoch_start=on_epoch_start)
     log.setdefault("eval_mse", []); log.setdefault("cgen_mse", [])
+    if args.bias_analysis:
+        log.setdefault("bias", [])
+    latents = None
+    if args.save_latents:              # :181-187, 531-541
+        if root:
+            N = d_train_img.shape[0]
+            eps = None
+            if getattr(args, "epsilon_seed", None) is not None:
+                eps = torch.as_tensor(np.random.RandomState(1000 * nr_epochs + args.epsilon_seed).randn(N, args.L))
+            latents = latent_samples_SVGPVAE(d_train_img, d_train_aux, VAE, SVGP_, clipping_qs=args.clip_qs, epsilon=eps)
+            with open(chkpnt_dir + "latents_train_full.p", "wb") as f:
+                pickle.dump(latents.cpu().numpy(), f)
+        ctx.barrier()
     log["world_size"], log["rank"] = ctx.world, ctx.rank
     log["rccl_ranks"] = eng.comm.world_size if eng.comm is not None else 0
     log["total_time"] = time.time() - start
@@ -238,6 +287,8 @@ def run_experiment_rotated_mnist_SVGPVAE(args, args_dict=None, ctx=None):
         json.dump(dict({k: v for k, v in log.items()}, theta=eng.theta.cpu().tolist(), adam_t=eng.scalars()["adam_t"],
                        param_order=list(eng.shapes)), open(args.log_json, "wt"))
     log["_engine"] = eng                     # (the final parameters / optimiser state for callers; not serialised)
+    if latents is not None:
+        log["_latents"] = latents            # (N, L) device tensor of --save_latents; not serialised
     return log
 
 

@@ -12,6 +12,7 @@ Mirrored names (reference file:line):
   forward_pass_SVGPVAE(data_batch, beta, vae, svgp, C_ma, lagrange_mult, alpha, kappa,
                        clipping_qs=False, GECO=False, ...) -> 16-tuple            :823-936
   batching_encode_SVGPVAE(data_batch, vae, clipping_qs=False, ...)                :939-968
+  batching_encode_SVGPVAE_full(train_images, vae, clipping_qs=False)              :971-986
 Additional (no reference counterpart - TF's tf.gradients + AdamOptimizer live in the driver):
   gradients_SVGPVAE(...) and train_step_SVGPVAE(...).
 
@@ -346,6 +347,14 @@ def batching_encode_SVGPVAE(data_batch, vae, clipping_qs=False, repr_nn=None, se
     if clipping_qs:
         var = torch.clamp(var, 1e-3, 10.0)
     return mu, var, aux_data
+
+
+def batching_encode_SVGPVAE_full(train_images, vae, clipping_qs=False):
+    """SVGPVAE_model.py:971-986: (qnet_mu, qnet_var) of all the given images at once."""
+    mu, var = vae.encode(train_images)
+    if clipping_qs:
+        var = torch.clamp(var, 1e-3, 10.0)
+    return mu, var
 
 
 def bacthing_predict_SVGPVAE_rotated_mnist(test_data_batch, vae, svgp, qnet_mu, qnet_var, aux_data_train,

@@ -730,6 +730,84 @@ class MnistStepEngine:
         with torch.cuda.stream(self.stream):
             DataParallelStep(_GraphAdapter(self, key), group).step()
 
+    # ------------------------------------------------------------------ bias analysis (MNIST_experiment.py:325-363, supplement C.4)
+    def mean_vectors_begin(self):
+        """Start of an epoch (:325-326): empties the device-side sum of the per-step mean vectors, [sum (L, m) | step count]."""
+        if self.comm is not None and self.channel_sharded():
+            raise _lib.SvgpError("bias analysis needs every channel's mu_hat on this rank; the channel-sharded data-parallel "
+                                 "step (m > 64, L divisible by the rank count) leaves only the rank's own channels in ws[mu_hat]")
+        with torch.cuda.stream(self.stream):
+            if getattr(self, "_mv_acc", None) is None:
+                self._mv_acc = torch.empty(self.base["L"] * self.base["m"] + 1, dtype=torch.float64, device=self.device)
+            self._mv_acc.zero_()
+        self._mv_steps = 0
+
+    def mean_vectors_accumulate(self):
+        """Behind a step (:341-342): adds the ws[mu_hat] that step's factor stage wrote -- the mean vectors at the parameters
+        before its update -- to the sum.  One launch on self.stream, no host synchronisation."""
+        if getattr(self, "_mv_acc", None) is None:
+            raise ValueError("mean_vectors_accumulate() before mean_vectors_begin()")
+        call("svgp_mean_vectors_accumulate", self.base["L"], self.base["m"], self.ws.data_ptr() + 8 * int(self.wl.mu_hat),
+             self._mv_acc.data_ptr(), self.stream.cuda_stream)
+        self._mv_steps += 1
+
+    def _full_pass(self, images, aux, eps=None, clip_qs=None):
+        """Encoder, kernel matrices, statistics and factor stage over ALL the given rows as one batch (b = b_global = N, so
+        c = N_train / N), through collective-free calls; with eps (N, L) also the row stage z = p_m + eps sqrt(p_v).  No
+        decoder, no reverse pass, no optimiser: theta, the Adam moments and the state vector are only read.  clip_qs: None =
+        the engine's own setting.  Returns clones of ws[mu_hat] (L, m) and, with eps, ws[z] (N, L); the batch configuration is
+        restored."""
+        N, L, m = images.shape[0], self.base["L"], self.base["m"]
+        if N > self.b_max:
+            raise ValueError(f"{N} rows exceed the engine's capacity b_max={self.b_max}")
+        saved, bound = (self.cfg.b, self.cfg.b_global), self._bound
+        img = images.to(self.device, torch.float64).contiguous()
+        ax = aux.to(self.device, torch.float64).contiguous()
+        d_eps = None if eps is None else eps.to(self.device, torch.float64).contiguous()
+        self.set_batch_size(N, N)
+        if clip_qs is not None:
+            self.cfg.clip_qs = int(bool(clip_qs))          # (set_batch_size below rebuilds cfg from the engine's settings)
+        self.bind(img, ax, d_eps)
+        cfg, ws, s = C.byref(self.cfg), self.ws.data_ptr(), self.stream.cuda_stream
+        with torch.cuda.stream(self.stream):
+            self.phase(0)
+            call("svgp_gp_factor_fwd", cfg, ws, s)
+            mu_hat = self.ws_view("mu_hat", (L, m)).clone()
+            z = None
+            if d_eps is not None:
+                call("svgp_gp_posterior_fwd", cfg, d_eps.data_ptr(), ws, self.state.data_ptr(), s)
+                z = self.ws_view("z", (N, L)).clone()
+        self.synchronize()
+        self.set_batch_size(*saved)
+        self._bound = bound
+        return mu_hat, z
+
+    def mean_vectors_full(self, images, aux):
+        """End of an epoch (:357-360, :172-179): the mean vectors (L, m) of the whole train set at the current parameters,
+        mean_vector_bias_analysis(train_aux, means[:, l], vars[:, l]) for every channel at once."""
+        return self._full_pass(images, aux)[0]
+
+    def latent_samples_full(self, images, aux, eps, clip_qs=None):
+        """utils.py:975-1008: z = p_m + eps sqrt(p_v) (N, L) with the posterior of every channel at the rows themselves,
+        approximate_posterior_params(aux, aux, mu_l, var_l)."""
+        return self._full_pass(images, aux, eps, clip_qs)[1]
+
+    def mean_vectors_bias(self, full):
+        """compute_bias_variance_mean_estimators (utils.py:922-948) of the steps accumulated since mean_vectors_begin() against
+        `full` (L, m): (bias, per-channel sums (L,))."""
+        if getattr(self, "_mv_acc", None) is None or self._mv_steps == 0:
+            raise ValueError("no step has been accumulated since mean_vectors_begin()")
+        L, m = self.base["L"], self.base["m"]
+        full = full.to(self.device, torch.float64).contiguous()
+        if full.shape != (L, m):
+            raise ValueError(f"full has shape {tuple(full.shape)}, expected {(L, m)}")
+        self.stream.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(self.stream):
+            out = torch.empty(1 + L, dtype=torch.float64, device=self.device)
+            call("svgp_mean_vectors_bias", L, m, self._mv_acc.data_ptr(), full.data_ptr(), out.data_ptr(), self.stream.cuda_stream)
+        self.synchronize()
+        return float(out[0]), out[1:].clone()
+
     def synchronize(self):
         self.stream.synchronize()
 

@@ -7,6 +7,9 @@
   gauss_cross_entropy(mu1, var1, mu2, var2)              utils.py:483-504 (element-wise; inside the step it is fused
                                                          into the HIP per-sample kernel, this is the stand-alone form)
   Make_Video_batch / build_video_batch_graph / MSE_rotation   utils.py:59-121,138-192,195-245 (moving ball; ball.py)
+  compute_bias_variance_mean_estimators(arr_batch, arr_full)  utils.py:922-948 (host; the driver's --bias_analysis keeps the
+                                                         sum on the device: engine.mean_vectors_*)
+  latent_samples_SVGPVAE(train_images, train_aux_data, vae, svgp, clipping_qs)   utils.py:975-1008
 """
 import pickle
 import random
@@ -89,6 +92,55 @@ def gauss_cross_entropy(mu1, var1, mu2, var2):
     call("svgp_gauss_cross_entropy", mu1.numel(), mu1.data_ptr(), var1.data_ptr(), mu2.data_ptr(), var2.data_ptr(),
          out.data_ptr(), s)
     return out
+
+
+def _host_array(t):
+    """A contiguous numpy copy of an array or a tensor (any device)."""
+    return np.array(t.detach().cpu().numpy() if hasattr(t, "detach") else t)
+
+
+def compute_bias_variance_mean_estimators(arr_batch, arr_full):
+    """utils.py:922-948 (Supplementary C.4): arr_batch (B, L, m), the mean vectors of the B steps of an epoch, arr_full (L, m),
+    the ones of the whole train set -- arrays, tensors or lists of them.  Returns mean_l sum_j |(sum_b arr_batch[b][l][j]) / B -
+    arr_full[l][j]|, on the host with the reference's operation order (steps added left to right, np.sum, np.mean), so the
+    result is the reference's to the bit.  The inputs are not modified (the reference adds into arr_batch[0]).  The variance
+    is a TODO of the reference."""
+    batch = [[_host_array(x) for x in step] for step in arr_batch]
+    full = [_host_array(x) for x in arr_full]
+    B, L, m = len(batch), len(batch[0]), batch[0][0].shape[0]
+    assert L == len(full)
+    assert m == full[0].shape[0]
+    avg_arr_batch = [0] * L
+    for l in range(L):
+        for b in range(B):
+            if b == 0:
+                avg_arr_batch[l] = batch[b][l]
+            else:
+                avg_arr_batch[l] += batch[b][l]
+    avg_arr_batch = [x / B for x in avg_arr_batch]
+    bias = [np.sum(np.abs(x - y)) for x, y in zip(avg_arr_batch, full)]
+    return np.mean(bias)
+
+
+def latent_samples_SVGPVAE(train_images, train_aux_data, vae, svgp, clipping_qs=False, epsilon=None):
+    """utils.py:975-1008: latent samples z = p_m + epsilon sqrt(p_v) (N, L) of the given rows, p_m / p_v from
+    svgp.approximate_posterior_params(aux, aux, qnet_mu[:, l], qnet_var[:, l]) per channel -- here one pass over all L
+    channels on the engine bound to (vae, svgp), c = N_train / N.  epsilon (N, L): the N(0,1) draw of :1005 as an input;
+    None: drawn on the device by torch's generator (the engine's own counter-based generator belongs to the training
+    trajectory and is left alone).  Returns a device tensor."""
+    import math
+
+    import torch
+    from .SVGPVAE_model import _runtime
+    N = train_images.shape[0]
+    rt = svgp._rt
+    if rt is None or rt.eng.b_max < N:        # as in bacthing_predict_SVGPVAE_rotated_mnist: a larger engine, same training state
+        rt = _runtime(vae, svgp, clipping_qs if rt is None else rt.key[0], False if rt is None else rt.key[1],
+                      math.sqrt(0.020) if rt is None else rt.key[2], N)
+    eng = rt.eng
+    if epsilon is None:
+        epsilon = torch.randn(N, vae.L, dtype=torch.float64, device=eng.device)
+    return eng.latent_samples_full(train_images, train_aux_data, epsilon, clip_qs=clipping_qs)
 
 
 def __getattr__(name):
