@@ -633,6 +633,12 @@ int svgp_conv_taps_wgrad_fused_f32(const svgp_conv_desc* d, int ncls, const floa
                                    float* part, float* part_b, int nwg, int part_stride, float* dw, float* db,
                                    void* stream);
 int svgp_upconv_fold_wgrad_f32(int Ci, int Co, const float* ge, float* g, void* stream);
+/* Which kernels a convolution call runs, as text: one line per launch, zero fill or partial-sum job, in order, with the
+ * kernel instance (template values), grid, LDS bytes and by-value scalars.  pass 0: svgp_conv_taps_fwd; pass 1:
+ * svgp_conv_taps_wgrad_fused (has_out: out != NULL).  elem_size: 4 or 8.  The same plan the launchers execute; makes no GPU
+ * call and needs no device.  SVGP_ERR_INVALID when `cap` bytes do not hold the text. */
+int svgp_conv_route(const svgp_conv_desc* d, int ncls, int pass, int has_out, int nwg, int part_stride, int elem_size,
+                    char* buf, int cap);
 int svgp_elu_bwd_bias_f32(long long npix, int C, const float* out, float* dout, float* part, float* db, void* stream);
 
 /* ---- SPRITES pieces (gp_sprites.hip) ----------------------------------------------------------------------

@@ -225,6 +225,7 @@ SIGNATURES = {
                                         C.POINTER(SumJob), C.c_int, C.POINTER(C.c_int), _P],
     "svgp_conv_taps_wgrad_fused_jobs_f32": [C.POINTER(ConvDesc), C.c_int, _P, _P, _P, _P, _P, C.c_int, C.c_int, _P, _P,
                                             C.POINTER(SumJob), C.c_int, C.POINTER(C.c_int), _P],
+    "svgp_conv_route": [C.POINTER(ConvDesc), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_int],
     "svgp_sum_partials_multi": [C.POINTER(SumJob), C.c_int, _P],
     "svgp_sum_partials_multi_f32": [C.POINTER(SumJob), C.c_int, _P],
     "svgp_transpose_taps": [C.c_int, C.c_int, C.c_int, _P, _P, _P],

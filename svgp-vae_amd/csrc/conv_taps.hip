@@ -1,18 +1,13 @@
-// Generic NHWC float64 convolution as a "tap-table" gather-GEMM on the f64 MFMA (gfx950):
+// NHWC convolutions (float64 / float32) as "tap-table" gather-GEMMs on the MFMA (gfx950):
 //
 //   out[n][y*osy+ooy][x*osx+oox][co] = act( bias[co] + sum_t sum_ci in[n][y*sy+oy_t][x*sx+ox_t][ci] * W_t[ci][co] )
 //
-// for (y,x) in an Hs x Ws iteration space; reads outside the input are zero.  One descriptor = one
-// "class"; up to 4 classes per launch (blockIdx.z = image * ncls + class).  With suitable tap tables this
-// one kernel is: Conv2D 3x3 / 2x2, stride 1 / 2, 'same' / 'valid' (Keras padding) forward; UpSampling2D(2)+
-// Conv2D as four parity classes with pre-summed effective weights (2.25x fewer MACs); and every data
-// gradient (transposed weights; parity classes for stride 2).  `svgp_conv_taps_wgrad` is the matching weight
-// gradient: dW_t[ci][co] = sum_{n,y,x} in[...][ci] * dout[...][co].
-// Reference layers: spritesVAE / sprites_representation_network (VAE_utils.py:275-391).
-//
-// Mapping: a wave owns one 16-pixel row segment; A[i=pixel][k=ci] from an LDS halo tile (pixel stride
-// Ci4+2 doubles -> conflict-free 16-pixel fetch), B[k=ci][j=co] from LDS weights, one
-// v_mfma_f64_16x16x4 per (tap, 4 input channels).  Workgroup = 4 waves = 16 x 8 output pixels.
+// for (y,x) in an Hs x Ws iteration space; reads outside the input are zero.  One descriptor = one "class", up to 4 classes per
+// call; what tap tables express is described at svgp_conv_desc (include/svgpvae_hip.h).  Reference layers: spritesVAE /
+// sprites_representation_network (VAE_utils.py:275-391).
+// Twelve kernel families serve this one formula: the generic kernels (a workgroup stages a halo tile in LDS), the direct
+// 16-input-channel kernels (k_conv16_*) and the thin-layer kernels (k_convS_*).  Which of them a call runs is decided by
+// conv_fwd_plan / conv_wgrad_plan at the end of this file; DESIGN.md section 5.1 has the table predicate -> family -> instances.
 #include "common.hpp"
 
 
@@ -1681,29 +1676,6 @@ __global__ __launch_bounds__(256) void k_convS_wgrad(svgp_conv_desc d, int nwg, 
     }
 }
 
-size_t fwd_lds(const svgp_conv_desc& d) {
-    int oy0 = d.oy[0], oy1 = d.oy[0], ox0 = d.ox[0], ox1 = d.ox[0];
-    for (int t = 1; t < d.nt; ++t) {
-        oy0 = oy0 < d.oy[t] ? oy0 : d.oy[t]; oy1 = oy1 > d.oy[t] ? oy1 : d.oy[t];
-        ox0 = ox0 < d.ox[t] ? ox0 : d.ox[t]; ox1 = ox1 > d.ox[t] ? ox1 : d.ox[t];
-    }
-    const int Ci4 = (d.Ci + 3) & ~3, ps = Ci4 + 2;
-    const int hh = (CT_TH - 1) * d.sy + (oy1 - oy0) + 1, hw = (CT_TW - 1) * d.sx + (ox1 - ox0) + 1;
-    return (size_t)hh * hw * ps;
-}
-
-size_t fwd_lds_all(const svgp_conv_desc* d, int ncls) {      // halo tile over the union of the classes' tap ranges
-    int oy0 = d[0].oy[0], oy1 = oy0, ox0 = d[0].ox[0], ox1 = ox0;
-    for (int c = 0; c < ncls; ++c)
-        for (int t = 0; t < d[c].nt; ++t) {
-            oy0 = oy0 < d[c].oy[t] ? oy0 : d[c].oy[t]; oy1 = oy1 > d[c].oy[t] ? oy1 : d[c].oy[t];
-            ox0 = ox0 < d[c].ox[t] ? ox0 : d[c].ox[t]; ox1 = ox1 > d[c].ox[t] ? ox1 : d[c].ox[t];
-        }
-    const int Ci4 = (d[0].Ci + 3) & ~3, ps = Ci4 + 2;
-    const int hh = (CT_TH - 1) * d[0].sy + (oy1 - oy0) + 1, hw = (CT_TW - 1) * d[0].sx + (ox1 - ox0) + 1;
-    return (size_t)hh * hw * ps;
-}
-
 int check_desc(const svgp_conv_desc* d, int ncls) {
     SVGP_REQUIRE(d && ncls >= 1 && ncls <= 4, SVGP_ERR_INVALID, "need 1..4 conv classes");
     for (int c = 0; c < ncls; ++c) {
@@ -1720,26 +1692,27 @@ int check_desc(const svgp_conv_desc* d, int ncls) {
 
 }  // namespace
 
-// ---- host side of the direct kernels
-static bool conv16_nt_ok(int nt) { return nt == 1 || nt == 2 || nt == 3 || nt == 4 || nt == 6 || nt == 9 || nt == 16; }
-static bool conv16_direct_ok(const svgp_conv_desc* d, int ncls, bool same_nt) {
-    for (int c = 0; c < ncls; ++c) {
-        if (d[c].Ci != 16 || !conv16_nt_ok(d[c].nt)) return false;
-        if (same_nt && (d[c].nt != d[0].nt || (d[c].nt != 4 && d[c].nt != 9))) return false;
-    }
-    return true;
-}
+// ---- host side of the direct kernels: conv_fwd_plan / conv_wgrad_plan choose among the kernel families (pure host arithmetic;
+// the table is DESIGN.md section 5.1), conv_run executes a plan, svgp_conv_route prints one.
 // SVGP_CONV_ROWS is the library's one TEST HOOK (not a schedule switch, hence not in sched.hpp): an odd rows-per-wave count gives
 // k_conv16_wgrad_grid a short last block, the path tests/test_gpu_conv.py checks in a child interpreter.  Read once per process.
-static int conv16_rows(const svgp_conv_desc& d) {            // output rows per wave (rolling kernels) / per strip / 4 (others)
+static int conv16_rows(int Hs) {                             // output rows per wave (rolling kernels) / per strip / 4 (others)
     static const int forced = [] { const char* e = getenv("SVGP_CONV_ROWS"); return e ? atoi(e) : 0; }();
     int rw = forced > 0 ? forced : 8;
-    const int q4 = (d.Hs + 3) / 4;
+    const int q4 = (Hs + 3) / 4;
     return rw < q4 ? rw : (q4 < 1 ? 1 : q4);
 }
-// Tap table = full NR x NC grid with consecutive row offsets?  `g` receives the descriptor with its taps in grid order
-// (row-major; g.oy[k * NC] = row offset k, g.ox[c] = column offset c).
-static bool conv16_grid(const svgp_conv_desc& d, svgp_conv_desc* g, int* NR, int* NC) {
+
+// One classification of a descriptor's tap table; every host predicate and halo / LDS size formula reads this.
+struct TapGrid {
+    int oy0, oy1, ox0, ox1;      // bounding box of the tap offsets
+    bool grid, cols;             // full NR x NC grid with consecutive row offsets; ... and consecutive column offsets
+    int NR, NC;                  // 0 unless grid
+    svgp_conv_desc g;            // grid: the descriptor with its taps in grid order (row-major; g.oy[k * NC] = row offset k,
+                                 // g.ox[c] = column offset c)
+    bool is(int nr, int nc) const { return NR == nr && NC == nc; }
+};
+static void tap_grid(const svgp_conv_desc& d, TapGrid& G) {
     int ys[16], xs[16], ny = 0, nx = 0;
     for (int t = 0; t < d.nt; ++t) {
         int k = 0;
@@ -1749,399 +1722,405 @@ static bool conv16_grid(const svgp_conv_desc& d, svgp_conv_desc* g, int* NR, int
         while (k < nx && xs[k] != d.ox[t]) ++k;
         if (k == nx) xs[nx++] = d.ox[t];
     }
-    if (ny * nx != d.nt) return false;
     for (int a = 0; a < ny; ++a) for (int b2 = a + 1; b2 < ny; ++b2) if (ys[b2] < ys[a]) { int v = ys[a]; ys[a] = ys[b2]; ys[b2] = v; }
     for (int a = 0; a < nx; ++a) for (int b2 = a + 1; b2 < nx; ++b2) if (xs[b2] < xs[a]) { int v = xs[a]; xs[a] = xs[b2]; xs[b2] = v; }
-    for (int k = 1; k < ny; ++k) if (ys[k] != ys[0] + k) return false;
-    *g = d;
-    for (int k = 0; k < ny; ++k)
-        for (int c = 0; c < nx; ++c) {
+    G.oy0 = ys[0]; G.oy1 = ys[ny - 1]; G.ox0 = xs[0]; G.ox1 = xs[nx - 1];
+    G.grid = ny * nx == d.nt && G.oy1 - G.oy0 == ny - 1;
+    G.g = d;
+    for (int k = 0; k < ny && G.grid; ++k)
+        for (int c = 0; c < nx && G.grid; ++c) {
             int t = 0;
             while (t < d.nt && !(d.oy[t] == ys[k] && d.ox[t] == xs[c])) ++t;
-            if (t == d.nt) return false;
-            g->oy[k * nx + c] = ys[k]; g->ox[k * nx + c] = xs[c]; g->woff[k * nx + c] = d.woff[t];
+            if (t == d.nt) { G.grid = false; break; }
+            G.g.oy[k * nx + c] = ys[k]; G.g.ox[k * nx + c] = xs[c]; G.g.woff[k * nx + c] = d.woff[t];
         }
-    *NR = ny; *NC = nx;
+    G.NR = G.grid ? ny : 0; G.NC = G.grid ? nx : 0;
+    G.cols = G.grid && G.ox1 - G.ox0 == nx - 1;
+}
+// elements of the generic kernels' halo tile (CT_TH x CT_TW outputs) for a tap bounding box
+static size_t halo_elems(const svgp_conv_desc& d, const TapGrid& t) {
+    const int hh = (CT_TH - 1) * d.sy + (t.oy1 - t.oy0) + 1, hw = (CT_TW - 1) * d.sx + (t.ox1 - t.ox0) + 1;
+    return (size_t)hh * hw * (((d.Ci + 3) & ~3) + 2);
+}
+
+// One launch, zero fill of `part` or partial-sum job of a call; a plan is their ordered list.  CONV_TEXT alone fixes the order of a
+// step's values v[]: the template values of the instance (after T), then the by-value scalars in the order of the kernel's
+// parameter list.  plan_step fills them in that order, the run_* functions hand them on, svgp_conv_route prints them with it.
+enum ConvKernel {
+    CK_conv16_thin_fwd, CK_conv16_fwd_roll, CK_conv16_fwd, CK_convS_fwd_ring, CK_convS_fwd, CK_conv_taps_fwd, CK_convS_wgrad_ring, CK_convS_wgrad,
+    CK_conv_taps_wgrad, CK_conv16_wgrad_grid, CK_conv16_wgrad_roll, CK_conv16_wgrad, CK_elu_bwd_colsum, CK_zero_part, CK_sum_partials
+};
+static const char* const CONV_TEXT[] = {
+    "conv16_thin_fwd<%d,%d,%d> ntask=%d nseg=%d nrb=%d RW=%d",                              // <NR,NC,CT>
+    "conv16_fwd_roll<%d,%d,%d,%d,%d> strips=%d RW=%d nseg=%d ntask=%d",                     // <NR,NC,SH,PF,FULL>
+    "conv16_fwd<%d> strips=%d R=%d nseg=%d",                                                // <NT>
+    "convS_fwd_ring<%d,%d,%d,%d,%d> ntask=%d nseg=%d nrb=%d RW=%d",                         // <NR,NC,S,CI,FULL>
+    "convS_fwd<%d> ntask=%d nseg=%d RW=%d",                                                 // <KS>
+    "conv_taps_fwd<%d,%d> nchunk=%d",                                                       // <CI4,NT>
+    "convS_wgrad_ring<%d,%d,%d,%d,%d,%d> nwg=%d RW=%d",                                     // <NR,NC,S,CT,ACT,MODE>
+    "convS_wgrad<%d,%d> nwg=%d RW=%d",                                                      // <NB,MODE>
+    "conv_taps_wgrad nwg=%d",
+    "conv16_wgrad_grid<%d,%d,%d,%d,%d> nwg=%d RW=%d",                                       // <NR,NC,SY,SX,ACT>
+    "conv16_wgrad_roll<%d,%d> nwg=%d RW=%d lpw=%d",                                         // <NT,SY>
+    "conv16_wgrad<%d> nwg=%d R=%d lpw=%d",                                                  // <NT>
+    "elu_bwd_colsum C=%d",
+    "zero_part rows=%d",                                                                    // rows of part_stride elements
+    "sum_partials ng=%d len=%d stride=%d accumulate=%d bias=%d"};                           // bias 0: part -> dw, 1: part_b -> db
+struct ConvStep {
+    int kernel, cls;             // ConvKernel; the class of a one-descriptor launch, -1: every class (ConvLaunch)
+    bool grid_order;             // the kernel receives TapGrid::g instead of the descriptor as given
+    int nt, v[11];               // nt template values, then the scalars
+    int gx, gy, gz;              // grid (256 threads per workgroup everywhere)
+    size_t lds;                  // dynamic LDS bytes
+    int a(int i) const { return v[nt + i]; }
+};
+struct ConvPlan { int n; ConvStep s[8]; TapGrid tg[4]; };         // the steps of a call; the tap classification of each class
+typedef std::initializer_list<int> ints;
+static ConvStep& plan_step(ConvPlan& P, int kernel, int cls, bool grid_order, int gx, int nt, ints v) {
+    ConvStep& s = P.s[P.n++];
+    s = ConvStep{kernel, cls, grid_order, nt, {}, gx, 1, 1, 0};
+    std::copy(v.begin(), v.end(), s.v);
+    return s;
+}
+static bool step_is(const ConvStep& s, ints t) { return (int)t.size() == s.nt && std::equal(t.begin(), t.end(), s.v); }
+static void plan_sums(ConvPlan& P, int ng, int part_stride, int ng_b, int Cb) {       // weights from `part`, bias from `part_b`
+    plan_step(P, CK_sum_partials, -1, false, 0, 0, {ng, part_stride, part_stride, 0, 0});
+    if (ng_b) plan_step(P, CK_sum_partials, -1, false, 0, 0, {ng_b, Cb, 16, 0, 1});
+}
+static const int ELU_NBLK = 1024;       // 4 workgroups per CU keep the HBM queues full
+static bool plan_elu_bias(ConvPlan& P, const svgp_conv_desc& d) {       // dpre and the bias gradient by their own pass over dout
+    if ((long long)d.n * d.Ho * d.Wo < 1) return false;
+    plan_step(P, CK_elu_bwd_colsum, 0, false, ELU_NBLK, 0, {d.Co});
+    plan_step(P, CK_sum_partials, -1, false, 0, 0, {ELU_NBLK, d.Co, d.Co, 0, 1});
     return true;
 }
-
-template <typename T>
-static int conv16_fwd_launch(const svgp_conv_desc* d, int ncls, const T* in, const T* w, const T* bias, T* out,
-                             void* stream) {
-    for (int c = 0; c < ncls; ++c) {
-        const svgp_conv_desc& dc = d[c];
-        SVGP_REQUIRE(!dc.act || bias, SVGP_ERR_INVALID, "bias is NULL but act != 0");
-        const int RW = conv16_rows(dc), R = 4 * RW, strips = (dc.Hs + R - 1) / R, nseg = (dc.Ws + 15) / 16;
-        const int ntask = dc.n * strips * nseg;
-        const dim3 grid((unsigned)ntask);
-        const dim3 grid_p((unsigned)(ntask < 1024 ? ntask : 1024));        // persistent form: <= 4 workgroups per CU
-        svgp_conv_desc g;
-        int NR = 0, NC = 0;
-        bool done = false;
-        if (dc.Ws >= 16 && conv16_grid(dc, &g, &NR, &NC)) {
-#define C16R(NR_, NC_, SH_, PF_)                                                                                              \
-            if (!done && NR == NR_ && NC == NC_ && dc.sy == SH_) {                                                          \
-                if (dc.Ws % 16 == 0 && dc.Co == 16)                                                                         \
-                    hipLaunchKernelGGL((k_conv16_fwd_roll<T, NR_, NC_, SH_, PF_, true>), grid_p, dim3(256), 0,                \
-                                       (hipStream_t)stream, g, strips, RW, nseg, ntask, in, w, bias, out);                  \
-                else                                                                                                        \
-                    hipLaunchKernelGGL((k_conv16_fwd_roll<T, NR_, NC_, SH_, PF_, false>), grid_p, dim3(256), 0,               \
-                                       (hipStream_t)stream, g, strips, RW, nseg, ntask, in, w, bias, out);                  \
-                done = true;                                                                                                \
-            }
-            C16R(3, 3, 1, true) C16R(3, 3, 2, true) C16R(2, 2, 1, true) C16R(2, 2, 2, true) C16R(4, 4, 2, false)
-            C16R(1, 1, 1, true) C16R(1, 2, 1, true) C16R(2, 1, 1, true)
-#undef C16R
-        }
-        if (!done) {
-#define C16F(NT_) hipLaunchKernelGGL((k_conv16_fwd<T, NT_>), grid, dim3(256), 0, (hipStream_t)stream, dc, strips, R, nseg, in, w, \
-                                     bias, out)
-            switch (dc.nt) {
-            case 1: C16F(1); break;
-            case 2: C16F(2); break;
-            case 3: C16F(3); break;
-            case 4: C16F(4); break;
-            case 6: C16F(6); break;
-            case 9: C16F(9); break;
-            default: C16F(16); break;
-            }
-#undef C16F
-        }
-        SVGP_LAUNCH_CHECK();
-    }
-    return SVGP_OK;
-}
-
-// ---- thin layers (k_convS_*)
-static bool convS_fwd_ok(const svgp_conv_desc* d, int ncls) {
-    for (int c = 0; c < ncls; ++c)
-        if (d[c].Ci >= 16 || d[c].nt * d[c].Ci > 32) return false;
+static bool all_classes(const svgp_conv_desc* d, int ncls, bool (*pred)(const svgp_conv_desc&)) {
+    for (int c = 0; c < ncls; ++c) if (!pred(d[c])) return false;
     return true;
 }
-template <typename T>
-static int convS_fwd_launch(const svgp_conv_desc* d, int ncls, const T* in, const T* w, const T* bias, T* out, void* stream) {
-    for (int c = 0; c < ncls; ++c) {
-        const svgp_conv_desc& dc = d[c];
-        SVGP_REQUIRE(!dc.act || bias, SVGP_ERR_INVALID, "bias is NULL but act != 0");
-        // 3 input channels, width a multiple of 16, full grid of consecutive offsets: k_convS_fwd_ring
-        if (dc.Ci == 3 && dc.Ws % 16 == 0 && dc.sy == dc.sx) {
-            svgp_conv_desc g;
-            int NR = 0, NC = 0;
-            bool ok = conv16_grid(dc, &g, &NR, &NC);
-            for (int x = 1; ok && x < NC; ++x) ok = g.ox[x] == g.ox[0] + x;
-            const int S = dc.sy;
-            ok = ok && ((NR == 3 && NC == 3 && S == 1) || (NR == 2 && NC == 2 && S == 2));
-            if (ok) {
-                int RW = 12;
-                if (RW > (g.Hs + 2) / 3 * 3) RW = (g.Hs + 2) / 3 * 3;
-                const int nrb = (g.Hs + RW - 1) / RW, nseg = g.Ws / 16, ntask = g.n * nrb * nseg, nwg = (ntask + 3) / 4;
-                const dim3 grid((unsigned)(nwg < 1024 ? nwg : 1024));
-#define CSFR(NR_, NC_, S_, FULL_) hipLaunchKernelGGL((k_convS_fwd_ring<T, NR_, NC_, S_, 3, FULL_>), grid, dim3(256), 0,         \
-                                                     (hipStream_t)stream, g, ntask, nseg, nrb, RW, in, w, bias, out)
-                if (S == 1) { if (g.Co == 16) CSFR(3, 3, 1, true); else CSFR(3, 3, 1, false); }
-                else { if (g.Co == 16) CSFR(2, 2, 2, true); else CSFR(2, 2, 2, false); }
-#undef CSFR
-                SVGP_LAUNCH_CHECK();
-                continue;
-            }
-        }
-        const int RW = conv16_rows(dc), strips = (dc.Hs + 4 * RW - 1) / (4 * RW), nseg = (dc.Ws + 15) / 16;
-        const int ntask = dc.n * strips * nseg, KS = (dc.nt * dc.Ci + 3) / 4;
-        const dim3 grid((unsigned)(ntask < 2048 ? ntask : 2048));
-#define CSF(KS_) hipLaunchKernelGGL((k_convS_fwd<T, KS_>), grid, dim3(256), 0, (hipStream_t)stream, dc, ntask, nseg, RW, in, w, bias, out)
-        switch (KS) {
-        case 1: CSF(1); break;
-        case 2: CSF(2); break;
-        case 3: CSF(3); break;
-        case 4: CSF(4); break;
-        case 5: CSF(5); break;
-        case 6: CSF(6); break;
-        case 7: CSF(7); break;
-        default: CSF(8); break;
-        }
-#undef CSF
-        SVGP_LAUNCH_CHECK();
-    }
-    return SVGP_OK;
+static bool conv16_ok(const svgp_conv_desc& d) {
+    return d.Ci == 16 && (d.nt == 1 || d.nt == 2 || d.nt == 3 || d.nt == 4 || d.nt == 6 || d.nt == 9 || d.nt == 16);
+}
+static bool convS_ok(const svgp_conv_desc& d) { return d.Ci < 16 && d.nt * d.Ci <= 32; }
+static bool plain_placement(const svgp_conv_desc& d) {
+    return d.sy == 1 && d.sx == 1 && d.osy == 1 && d.osx == 1 && d.ooy == 0 && d.oox == 0;
+}
+// 3 input channels, width a multiple of 16, 3 x 3 stride 1 or 2 x 2 stride 2 grid of consecutive offsets: the k_convS_*_ring forms
+static bool convS_ring_ok(const svgp_conv_desc& d, const TapGrid& t) {
+    return d.Ci == 3 && d.Ws % 16 == 0 && d.sy == d.sx && t.cols && ((t.is(3, 3) && d.sy == 1) || (t.is(2, 2) && d.sy == 2));
+}
+// the forward ring kernels: tasks of one wave each, RW = 12 rows clipped to whole ring periods, segments of segw columns
+static void plan_ring_fwd(ConvPlan& P, int kernel, int c, const svgp_conv_desc& d, int segw, int nt, int t0, int t1, int t2,
+                          int t3 = 0, int t4 = 0) {
+    const int per = (d.Hs + 2) / 3 * 3, RW = 12 > per ? per : 12;
+    const int nrb = (d.Hs + RW - 1) / RW, nseg = (d.Ws + segw - 1) / segw, ntask = d.n * nrb * nseg, nwg = (ntask + 3) / 4;
+    ConvStep& s = plan_step(P, kernel, c, true, nwg < 1024 ? nwg : 1024, nt, {t0, t1, t2, t3, t4});
+    s.v[nt] = ntask; s.v[nt + 1] = nseg; s.v[nt + 2] = nrb; s.v[nt + 3] = RW;
 }
 
-template <typename T>
-static int conv_taps_fwd_impl(const svgp_conv_desc* d, int ncls, const T* in, const T* w, const T* bias, T* out,
-                              void* stream) {
+// ---- the launches of svgp_conv_taps_fwd, in priority order (after the checks of the descriptors)
+static int conv_fwd_plan(const svgp_conv_desc* d, int ncls, int elem_size, ConvPlan& P) {
     int rc = check_desc(d, ncls);
     if (rc) return rc;
-    SVGP_REQUIRE(in && w && out, SVGP_ERR_INVALID, "NULL device pointer");
-    ConvLaunch L;
-    L.ncls = ncls;
+    P.n = 0;
     for (int c = 0; c < ncls; ++c) {
-        L.d[c] = d[c];
-        SVGP_REQUIRE(!d[c].act || bias, SVGP_ERR_INVALID, "bias is NULL but act != 0");
         SVGP_REQUIRE(d[c].n == d[0].n && d[c].Hs == d[0].Hs && d[c].Ws == d[0].Ws && d[c].sy == d[0].sy &&
                          d[c].sx == d[0].sx && d[c].Hi == d[0].Hi && d[c].Wi == d[0].Wi && d[c].Ci == d[0].Ci &&
                          d[c].Co == d[0].Co && d[c].act == d[0].act,
                      SVGP_ERR_INVALID, "the classes of one launch share the input geometry (n, Hs, Ws, strides, Ci, Co, act)");
+        tap_grid(d[c], P.tg[c]);
     }
+    const svgp_conv_desc& d0 = d[0];
     // 16 -> 3 channels, 3 x 3 grid of consecutive offsets, stride 1, plain output placement: the taps in the MFMA row index
-    {
-        svgp_conv_desc g;
-        int NR = 0, NC = 0;
-        bool ok = ncls == 1 && d[0].Ci == 16 && d[0].Co == 3 && d[0].sy == 1 && d[0].sx == 1 &&
-                  d[0].osy == 1 && d[0].osx == 1 && d[0].ooy == 0 && d[0].oox == 0 && conv16_grid(d[0], &g, &NR, &NC) && NR == 3 &&
-                  NC == 3;
-        for (int x = 1; ok && x < NC; ++x) ok = g.ox[x] == g.ox[0] + x;
-        if (ok) {
-            int RW = 12;                                                      // whole ring periods
-            if (RW > (g.Hs + 2) / 3 * 3) RW = (g.Hs + 2) / 3 * 3;
-            const int nrb = (g.Hs + RW - 1) / RW, nseg = (g.Ws + 13) / 14, ntask = g.n * nrb * nseg;   // tasks of one wave each
-            const int nwg = (ntask + 3) / 4;
-            hipLaunchKernelGGL((k_conv16_thin_fwd<T, 3, 3, 3>), dim3((unsigned)(nwg < 1024 ? nwg : 1024)), dim3(256), 0,
-                               (hipStream_t)stream, g, ntask, nseg, nrb, RW, in, w, bias, out);
-            SVGP_LAUNCH_CHECK();
-            return SVGP_OK;
-        }
+    if (ncls == 1 && d0.Ci == 16 && d0.Co == 3 && plain_placement(d0) && P.tg[0].is(3, 3) && P.tg[0].cols) {
+        plan_ring_fwd(P, CK_conv16_thin_fwd, 0, d0, 14, 3, 3, 3, 3);
+        return SVGP_OK;
     }
-    if (conv16_direct_ok(d, ncls, false)) return conv16_fwd_launch<T>(d, ncls, in, w, bias, out, stream);
-    if (convS_fwd_ok(d, ncls)) return convS_fwd_launch<T>(d, ncls, in, w, bias, out, stream);
+    const bool c16 = all_classes(d, ncls, conv16_ok);
+    if (c16 || all_classes(d, ncls, convS_ok)) {
+        for (int c = 0; c < ncls; ++c) {
+            const svgp_conv_desc& dc = d[c];
+            const TapGrid& t = P.tg[c];
+            const int RW = conv16_rows(dc.Hs), R = 4 * RW, strips = (dc.Hs + R - 1) / R, nseg = (dc.Ws + 15) / 16;
+            const int ntask = dc.n * strips * nseg;
+            // the rolling instances; all but the 4 x 4 one prefetch (PF).  Only the row stride is tested, and not the column offsets.
+            const bool pf = ((t.is(3, 3) || t.is(2, 2)) && (dc.sy == 1 || dc.sy == 2)) ||
+                            ((t.is(1, 1) || t.is(1, 2) || t.is(2, 1)) && dc.sy == 1);
+            if (!c16 && convS_ring_ok(dc, t))
+                plan_ring_fwd(P, CK_convS_fwd_ring, c, dc, 16, 5, t.NR, t.NC, dc.sy, 3, dc.Co == 16);
+            else if (!c16)
+                plan_step(P, CK_convS_fwd, c, false, ntask < 2048 ? ntask : 2048, 1, {(dc.nt * dc.Ci + 3) / 4, ntask, nseg, RW});
+            else if (dc.Ws >= 16 && (pf || (t.is(4, 4) && dc.sy == 2)))         // persistent form: <= 4 workgroups per CU
+                plan_step(P, CK_conv16_fwd_roll, c, true, ntask < 1024 ? ntask : 1024, 5,
+                          {t.NR, t.NC, dc.sy, pf, dc.Ws % 16 == 0 && dc.Co == 16, strips, RW, nseg, ntask});
+            else
+                plan_step(P, CK_conv16_fwd, c, false, ntask, 1, {dc.nt, strips, R, nseg});
+        }
+        return SVGP_OK;
+    }
     // union halo tile of all classes + the packed tap weights of every class
-    size_t lds = fwd_lds_all(d, ncls);
-    for (int c = 0; c < ncls; ++c) lds += (size_t)d[c].nt * ((d[0].Ci + 3) & ~3) * 16;
-    lds *= sizeof(T);
+    TapGrid u = P.tg[0];
+    for (int c = 1; c < ncls; ++c) {
+        const TapGrid& t = P.tg[c];
+        u.oy0 = t.oy0 < u.oy0 ? t.oy0 : u.oy0; u.oy1 = t.oy1 > u.oy1 ? t.oy1 : u.oy1;
+        u.ox0 = t.ox0 < u.ox0 ? t.ox0 : u.ox0; u.ox1 = t.ox1 > u.ox1 ? t.ox1 : u.ox1;
+    }
+    const int Ci4 = (d0.Ci + 3) & ~3;
+    size_t lds = halo_elems(d0, u);
+    for (int c = 0; c < ncls; ++c) lds += (size_t)d[c].nt * Ci4 * 16;
+    lds *= elem_size;
     SVGP_REQUIRE(lds <= 160 * 1024, SVGP_ERR_UNSUPPORTED, "conv tile needs %zu bytes of LDS", lds);
-    const int tiles = ((d[0].Ws + CT_TW - 1) / CT_TW) * ((d[0].Hs + CT_TH - 1) / CT_TH);
+    const int tiles = ((d0.Ws + CT_TW - 1) / CT_TW) * ((d0.Hs + CT_TH - 1) / CT_TH);
     // enough workgroups for ~8 per CU, each walking n / nchunk images of its tile position
     int nchunk = (2048 + tiles - 1) / tiles;
-    if (nchunk > d[0].n) nchunk = d[0].n;
+    if (nchunk > d0.n) nchunk = d0.n;
     if (nchunk < 1) nchunk = 1;
     // straight-line instances for the layer shapes of the SPRITES networks: 16 (or 4 = padded 3) input channels, 9 taps
     // (3 x 3) or 4 taps (the parity classes of the upsample-fused / transposed stride-2 layers), every class alike
-    const int Ci4 = (d[0].Ci + 3) & ~3;
-    int nt_all = d[0].nt;
+    int nt_all = d0.nt;
     for (int c = 1; c < ncls; ++c) if (d[c].nt != nt_all) nt_all = 0;
-#define CONV_FWD_LAUNCH(CI4_, NT_)                                                                                          \
-    do {                                                                                                                    \
-        SVGP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_conv_taps_fwd<T, CI4_, NT_>),                     \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                          \
-        hipLaunchKernelGGL((k_conv_taps_fwd<T, CI4_, NT_>), dim3(tiles, 1, nchunk), dim3(256), lds, (hipStream_t)stream, L,   \
-                           nchunk, in, w, bias, out);                                                                       \
-    } while (0)
-    if (Ci4 == 16 && nt_all == 9) CONV_FWD_LAUNCH(16, 9);
-    else if (Ci4 == 16 && nt_all == 4) CONV_FWD_LAUNCH(16, 4);
-    else if (Ci4 == 4 && nt_all == 9) CONV_FWD_LAUNCH(4, 9);
-    else CONV_FWD_LAUNCH(0, 0);
-#undef CONV_FWD_LAUNCH
-    SVGP_LAUNCH_CHECK();
+    const bool inst = (Ci4 == 16 && (nt_all == 9 || nt_all == 4)) || (Ci4 == 4 && nt_all == 9);
+    ConvStep& s = plan_step(P, CK_conv_taps_fwd, -1, false, tiles, 2, {inst ? Ci4 : 0, inst ? nt_all : 0, nchunk});
+    s.gz = nchunk; s.lds = lds;
     return SVGP_OK;
 }
 
-// part: (ncls * nwg, part_stride) scratch; dw (part_stride values, the layer's weight layout via woff) receives
-// the fixed-order sum over workgroups and classes (accumulate != 0 adds to dw).
-template <typename T>
-static int conv_taps_wgrad_impl(const svgp_conv_desc* d, int ncls, const T* in, const T* dout, T* part, int nwg,
-                                int part_stride, T* dw, int accumulate, void* stream) {
+// ---- the launches of svgp_conv_taps_wgrad_fused, in priority order.  One pass for the reverse of a layer's bias / activation /
+// weights: dpre = dout * elu'(out) in place (out == NULL: dpre = dout), db = column sums of dpre, dW_t = sum in * dpre.
+// part_b: (1024, 16) scratch, part: (nwg, part_stride) scratch.  plain_accumulate >= 0: the launches of svgp_conv_taps_wgrad, i.e.
+// the generic weight gradient alone: part (ncls * nwg, part_stride) scratch; dw (part_stride values, the layer's weight layout via
+// woff) receives the fixed-order sum over workgroups and classes (accumulate != 0 adds to dw).
+static int conv_wgrad_plan(const svgp_conv_desc* d, int ncls, int nwg, int part_stride, bool has_out, int elem_size, ConvPlan& P,
+                           int plain_accumulate = -1) {
     int rc = check_desc(d, ncls);
     if (rc) return rc;
-    SVGP_REQUIRE(in && dout && part && dw && nwg >= 1 && part_stride >= 1, SVGP_ERR_INVALID, "bad argument");
-    ConvLaunch L;
-    L.ncls = ncls;
-    size_t lds = 0;
-    for (int c = 0; c < ncls; ++c) {
-        L.d[c] = d[c];
-        const size_t e = fwd_lds(d[c]) + (size_t)CT_TH * CT_TW * 18 + 1024;
-        lds = e > lds ? e : lds;
+    SVGP_REQUIRE(nwg >= 1 && part_stride >= 1, SVGP_ERR_INVALID, "bad argument");
+    P.n = 0;
+    for (int c = 0; c < ncls; ++c) tap_grid(d[c], P.tg[c]);
+    const bool fused = plain_accumulate < 0;
+    const svgp_conv_desc& d0 = d[0];
+    const TapGrid& t0 = P.tg[0];
+    // thin layers: the taps in a GEMM index (k_convS_wgrad), MODE 0 thin input, MODE 1 thin output
+    const bool m0 = fused && all_classes(d, ncls, convS_ok);
+    const bool m1 = fused && ncls == 1 && d0.Ci == 16 && d0.nt * d0.Co <= 32 && plain_placement(d0) && d0.Hs == d0.Ho && d0.Ws == d0.Wo;
+    int nw = nwg > 1024 ? 1024 : nwg;
+    // 3 -> 16 channels, one class: k_convS_wgrad_ring
+    if (m0 && ncls == 1 && d0.Co == 16 && convS_ring_ok(d0, t0)) {
+        plan_step(P, CK_convS_wgrad_ring, 0, true, nw, 6, {t0.NR, t0.NC, d0.sy, 3, has_out, 0, nw, conv16_rows(d0.Hs)});
+        plan_sums(P, nw, part_stride, nw, 16);
+        return SVGP_OK;
     }
-    lds *= sizeof(T);
-    SVGP_REQUIRE(lds <= 160 * 1024, SVGP_ERR_UNSUPPORTED, "conv tile needs %zu bytes of LDS", lds);
-    SVGP_CHECK_HIP(hipMemsetAsync(part, 0, (size_t)nwg * part_stride * sizeof(T), (hipStream_t)stream));
-    SVGP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_conv_taps_wgrad<T>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(k_conv_taps_wgrad<T>, dim3(nwg, ncls), dim3(256), lds, (hipStream_t)stream, L, nwg, in, dout, part,
-                       part_stride);
-    SVGP_LAUNCH_CHECK();
-    return sum_partials<T>(nwg, part_stride, part_stride, (const T*)part, dw, accumulate, stream);
-}
-
-// One pass for the reverse of a layer's bias / activation / weights: dpre = dout * elu'(out) in place (out == NULL: dpre = dout),
-// db = column sums of dpre, dW_t = sum in * dpre.  16 input channels with 4 or 9 taps per class: the fused direct kernel;
-// otherwise the separate kernels in sequence.  part_b: (1024, 16) scratch, part: (nwg, part_stride) scratch.
-template <typename T> static int elu_bwd_bias_impl(long long, int, const T*, T*, T*, T*, void*);
-template <typename T>
-static int conv_wgrad_fused_impl(const svgp_conv_desc* d, int ncls, const T* in, const T* outv, T* dout, T* part, T* part_b,
-                                 int nwg, int part_stride, T* dw, T* db, void* stream) {
-    int rc = check_desc(d, ncls);
-    if (rc) return rc;
-    SVGP_REQUIRE(in && dout && part && part_b && dw && db && nwg >= 1 && part_stride >= 1, SVGP_ERR_INVALID, "bad argument");
-    // thin layers: the taps in a GEMM index (k_convS_wgrad)
-    {
-        bool m0 = true, m1 = ncls == 1;
+    if (m0 || m1) {
+        if (m1) {           // ELU' + bias sums by their own pass over the thin dout; the kernel then gathers dpre
+            SVGP_REQUIRE(plan_elu_bias(P, d0), SVGP_ERR_INVALID, "bad argument");
+            // 16 -> 3 channels, 3 x 3 grid of consecutive offsets, input width a multiple of 16: k_convS_wgrad_ring, MODE 1;
+            // rows per wave from the iteration space of this mode (input pixels)
+            if (d0.Co == 3 && d0.Wi % 16 == 0 && t0.is(3, 3) && t0.cols) {
+                plan_step(P, CK_convS_wgrad_ring, 0, true, nw, 6, {3, 3, 1, 3, false, 1, nw, conv16_rows(d0.Hi)});
+                plan_sums(P, nw, part_stride, 0, 0);
+                return SVGP_OK;
+            }
+        } else if (nw * ncls > 1024) {
+            nw = 1024 / ncls;
+        }
+        plan_step(P, CK_zero_part, -1, false, 0, 0, {nw});
         for (int c = 0; c < ncls; ++c) {
-            if (d[c].Ci >= 16 || d[c].nt * d[c].Ci > 32) m0 = false;
-            if (d[c].Ci != 16 || d[c].nt * d[c].Co > 32 || d[c].sy != 1 || d[c].sx != 1 || d[c].osy != 1 || d[c].osx != 1 ||
-                d[c].ooy || d[c].oox || d[c].Hs != d[c].Ho || d[c].Ws != d[c].Wo) m1 = false;
+            const int NB = ((m0 ? d[c].nt * d[c].Ci : d[c].nt * d[c].Co) + 15) / 16;
+            plan_step(P, CK_convS_wgrad, c, false, nw, 2, {NB == 1 ? 1 : 2, m0 ? 0 : 1, nw, conv16_rows(d[c].Hs)});
         }
-        // 3 -> 16 channels, one class, width a multiple of 16, full grid of consecutive offsets: k_convS_wgrad_ring
-        if (m0 && ncls == 1 && d[0].Ci == 3 && d[0].Co == 16 && d[0].Ws % 16 == 0 && d[0].sy == d[0].sx) {
-            svgp_conv_desc g;
-            int NR = 0, NC = 0;
-            bool ok = conv16_grid(d[0], &g, &NR, &NC);
-            for (int x = 1; ok && x < NC; ++x) ok = g.ox[x] == g.ox[0] + x;
-            const int S = d[0].sy;
-            ok = ok && ((NR == 3 && NC == 3 && S == 1) || (NR == 2 && NC == 2 && S == 2));
-            if (ok) {
-                const int nw = nwg > 1024 ? 1024 : nwg, RW = conv16_rows(d[0]);
-#define CSR(NR_, NC_, S_)                                                                                                   \
-                if (NR == NR_ && NC == NC_ && S == S_) {                                                                    \
-                    if (outv) hipLaunchKernelGGL((k_convS_wgrad_ring<T, NR_, NC_, S_, 3, true, 0>), dim3(nw), dim3(256), 0,    \
-                                                 (hipStream_t)stream, g, nw, RW, in, outv, dout, part, part_stride, part_b);\
-                    else hipLaunchKernelGGL((k_convS_wgrad_ring<T, NR_, NC_, S_, 3, false, 0>), dim3(nw), dim3(256), 0,        \
-                                            (hipStream_t)stream, g, nw, RW, in, outv, dout, part, part_stride, part_b);    \
-                }
-                CSR(3, 3, 1) CSR(2, 2, 2)
-#undef CSR
-                SVGP_LAUNCH_CHECK();
-                rc = sum_partials<T>(nw, part_stride, part_stride, (const T*)part, dw, 0, stream);
-                if (rc) return rc;
-                return sum_partials<T>(nw, 16, 16, (const T*)part_b, db, 0, stream);
-            }
-        }
-        if (m0 || m1) {
-            int nw = nwg > 1024 ? 1024 : nwg;
-            if (m1) {       // ELU' + bias sums by their own pass over the thin dout; the kernel then gathers dpre
-                rc = elu_bwd_bias_impl<T>((long long)d[0].n * d[0].Ho * d[0].Wo, d[0].Co, outv, dout, part_b, db, stream);
-                if (rc) return rc;
-                // 16 -> 3 channels, 3 x 3 grid of consecutive offsets, input width a multiple of 16: k_convS_wgrad_ring, MODE 1
-                svgp_conv_desc g;
-                int NR = 0, NC = 0;
-                bool ok = d[0].Co == 3 && d[0].Wi % 16 == 0 && conv16_grid(d[0], &g, &NR, &NC) && NR == 3 && NC == 3;
-                for (int x = 1; ok && x < NC; ++x) ok = g.ox[x] == g.ox[0] + x;
-                if (ok) {
-                    svgp_conv_desc gi = g;
-                    gi.Hs = g.Hi;                      // rows per wave from the iteration space of this mode (input pixels)
-                    hipLaunchKernelGGL((k_convS_wgrad_ring<T, 3, 3, 1, 3, false, 1>), dim3(nw), dim3(256), 0, (hipStream_t)stream, g,
-                                       nw, conv16_rows(gi), in, (const T*)nullptr, dout, part, part_stride, part_b);
-                    SVGP_LAUNCH_CHECK();
-                    return sum_partials<T>(nw, part_stride, part_stride, (const T*)part, dw, 0, stream);
-                }
-            } else if (nw * ncls > 1024) {
-                nw = 1024 / ncls;
-            }
-            SVGP_CHECK_HIP(hipMemsetAsync(part, 0, (size_t)nw * part_stride * sizeof(T), (hipStream_t)stream));
-            for (int c = 0; c < ncls; ++c) {
-                const svgp_conv_desc& dc = d[c];
-                const int RW = conv16_rows(dc), NB = ((m0 ? dc.nt * dc.Ci : dc.nt * dc.Co) + 15) / 16;
-                T* pb = part_b + (size_t)c * nw * 16;
-#define CSW(NB_, MODE_) hipLaunchKernelGGL((k_convS_wgrad<T, NB_, MODE_>), dim3(nw), dim3(256), 0, (hipStream_t)stream, dc, nw, RW, in,  \
-                                           m0 ? outv : (const T*)nullptr, dout, part, part_stride, pb)
-                if (m0) { if (NB == 1) CSW(1, 0); else CSW(2, 0); }
-                else { if (NB == 1) CSW(1, 1); else CSW(2, 1); }
-#undef CSW
-                SVGP_LAUNCH_CHECK();
-            }
-            rc = sum_partials<T>(nw, part_stride, part_stride, (const T*)part, dw, 0, stream);
-            if (rc) return rc;
-            if (m0) return sum_partials<T>(nw * ncls, d[0].Co, 16, (const T*)part_b, db, 0, stream);
-            return SVGP_OK;
-        }
+        plan_sums(P, nw, part_stride, m0 ? nw * ncls : 0, d0.Co);
+        return SVGP_OK;
     }
-    if (!conv16_direct_ok(d, ncls, true)) {
-        rc = elu_bwd_bias_impl<T>((long long)d[0].n * d[0].Ho * d[0].Wo, d[0].Co, outv, dout, part_b, db, stream);
-        if (rc) return rc;
-        return conv_taps_wgrad_impl<T>(d, ncls, in, dout, part, nwg, part_stride, dw, 0, stream);
+    // 16 input channels with 4 or 9 taps in every class: the fused direct kernels; otherwise the separate kernels in sequence
+    bool direct = fused && all_classes(d, ncls, conv16_ok) && (d0.nt == 4 || d0.nt == 9);
+    for (int c = 1; c < ncls; ++c) direct = direct && d[c].nt == d0.nt;
+    if (!direct) {
+        SVGP_REQUIRE(!fused || plan_elu_bias(P, d0), SVGP_ERR_INVALID, "bad argument");
+        size_t lds = 0;
+        for (int c = 0; c < ncls; ++c) {
+            const size_t e = halo_elems(d[c], P.tg[c]) + (size_t)CT_TH * CT_TW * 18 + 1024;
+            lds = e > lds ? e : lds;
+        }
+        lds *= elem_size;
+        SVGP_REQUIRE(lds <= 160 * 1024, SVGP_ERR_UNSUPPORTED, "conv tile needs %zu bytes of LDS", lds);
+        plan_step(P, CK_zero_part, -1, false, 0, 0, {nwg});
+        ConvStep& s = plan_step(P, CK_conv_taps_wgrad, -1, false, nwg, 0, {nwg});
+        s.gy = ncls; s.lds = lds;
+        plan_step(P, CK_sum_partials, -1, false, 0, 0, {nwg, part_stride, part_stride, fused ? 0 : plain_accumulate, 0});
+        return SVGP_OK;
     }
-    ConvLaunch L;
-    L.ncls = ncls;
     int nwg_c = nwg / ncls;
     if (nwg_c < 1) nwg_c = 1;
     if (nwg_c * ncls > 1024) nwg_c = 1024 / ncls;
+    const int RW = conv16_rows(d0.Hs), SY = d0.sy;
     // 16 -> 16 channels, width a multiple of 16, every class the same full grid of consecutive offsets: k_conv16_wgrad_grid
-    {
-        ConvLaunch G;
-        G.ncls = ncls;
-        int NR = 0, NC = 0;
-        bool ok = true;
-        for (int c = 0; c < ncls && ok; ++c) {
-            int nr = 0, nc = 0;
-            ok = d[c].Co == 16 && d[c].Ws % 16 == 0 && d[c].sy == d[0].sy && d[c].sx == d[0].sx && d[c].sy == d[c].sx &&
-                 d[c].Hs == d[0].Hs && d[c].Ws == d[0].Ws && conv16_grid(d[c], &G.d[c], &nr, &nc);
-            if (ok && c == 0) { NR = nr; NC = nc; }
-            ok = ok && nr == NR && nc == NC;
-            for (int x = 1; ok && x < nc; ++x) ok = G.d[c].ox[x] == G.d[c].ox[0] + x;
-        }
-        const int SY = d[0].sy;
-        ok = ok && ((NR == 3 && NC == 3 && (SY == 1 || SY == 2)) || (NR == 2 && NC == 2 && (SY == 1 || SY == 2)));
-        if (ok) {
-            const int RW = conv16_rows(d[0]), HW = 15 * SY + NC, PS = SY == 1 ? 16 : 24;
-            size_t lds = (size_t)4 * NR * HW * PS;
-            if (lds < 1024) lds = 1024;
-            lds *= sizeof(T);
-#define C16G(NR_, NC_, S_)                                                                                                  \
-            if (NR == NR_ && NC == NC_ && SY == S_) {                                                                       \
-                if (outv) {                                                                                                 \
-                    SVGP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_conv16_wgrad_grid<T, NR_, NC_, S_, S_, true>),  \
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));             \
-                    hipLaunchKernelGGL((k_conv16_wgrad_grid<T, NR_, NC_, S_, S_, true>), dim3(nwg_c, ncls), dim3(256), lds,  \
-                                       (hipStream_t)stream, G, nwg_c, RW, in, outv, dout, part, part_stride, part_b);      \
-                } else {                                                                                                    \
-                    SVGP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_conv16_wgrad_grid<T, NR_, NC_, S_, S_, false>), \
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));             \
-                    hipLaunchKernelGGL((k_conv16_wgrad_grid<T, NR_, NC_, S_, S_, false>), dim3(nwg_c, ncls), dim3(256), lds, \
-                                       (hipStream_t)stream, G, nwg_c, RW, in, outv, dout, part, part_stride, part_b);      \
-                }                                                                                                           \
-            }
-            C16G(3, 3, 1) C16G(3, 3, 2) C16G(2, 2, 1) C16G(2, 2, 2)
-#undef C16G
-            SVGP_LAUNCH_CHECK();
-            rc = sum_partials<T>(nwg_c, part_stride, part_stride, (const T*)part, dw, 0, stream);
-            if (rc) return rc;
-            return sum_partials<T>(nwg_c * ncls, 16, 16, (const T*)part_b, db, 0, stream);
-        }
+    bool grid = (t0.is(3, 3) || t0.is(2, 2)) && (SY == 1 || SY == 2);
+    for (int c = 0; c < ncls; ++c)
+        grid = grid && d[c].Co == 16 && d[c].Ws % 16 == 0 && d[c].sy == SY && d[c].sx == SY && d[c].Hs == d0.Hs &&
+               d[c].Ws == d0.Ws && P.tg[c].is(t0.NR, t0.NC) && P.tg[c].cols;
+    if (grid) {
+        const int HW = 15 * SY + t0.NC, PS = SY == 1 ? 16 : 24;
+        const size_t lds = (size_t)4 * t0.NR * HW * PS;
+        ConvStep& s = plan_step(P, CK_conv16_wgrad_grid, -1, true, nwg_c, 5, {t0.NR, t0.NC, SY, SY, has_out, nwg_c, RW});
+        s.gy = ncls; s.lds = (lds < 1024 ? 1024 : lds) * elem_size;
+        plan_sums(P, nwg_c, part_stride, nwg_c * ncls, 16);
+        return SVGP_OK;
     }
     size_t lpw = 0, lpw_roll = 0;
-    const int RW = conv16_rows(d[0]);
-    bool roll = d[0].Ws >= 16 && (d[0].sy == 1 || d[0].sy == 2);
+    bool roll = d0.Ws >= 16 && (SY == 1 || SY == 2);
     for (int c = 0; c < ncls; ++c) {
-        L.d[c] = d[c];
-        SVGP_REQUIRE(d[c].Co == d[0].Co && d[c].Hs == d[0].Hs && d[c].Ws == d[0].Ws && d[c].sy == d[0].sy, SVGP_ERR_INVALID,
+        const svgp_conv_desc& dc = d[c];
+        const TapGrid& t = P.tg[c];
+        SVGP_REQUIRE(dc.Co == d0.Co && dc.Hs == d0.Hs && dc.Ws == d0.Ws && dc.sy == SY, SVGP_ERR_INVALID,
                      "classes of one launch share Co, the row stride and the iteration space");
-        int oy0 = d[c].oy[0], oy1 = oy0, ox0 = d[c].ox[0], ox1 = ox0;
-        for (int t = 1; t < d[c].nt; ++t) {
-            oy0 = oy0 < d[c].oy[t] ? oy0 : d[c].oy[t]; oy1 = oy1 > d[c].oy[t] ? oy1 : d[c].oy[t];
-            ox0 = ox0 < d[c].ox[t] ? ox0 : d[c].ox[t]; ox1 = ox1 > d[c].ox[t] ? ox1 : d[c].ox[t];
-        }
-        const int segw = d[c].Ws < 16 ? d[c].Ws : 16, rpw = 16 / segw, PS = d[c].sx == 1 ? 16 : 24;
-        const size_t e = (size_t)((rpw - 1) * d[c].sy + (oy1 - oy0) + 1) * ((segw - 1) * d[c].sx + (ox1 - ox0) + 1) * PS;
+        const int segw = dc.Ws < 16 ? dc.Ws : 16, rpw = 16 / segw, PS = dc.sx == 1 ? 16 : 24;
+        const size_t e = (size_t)((rpw - 1) * dc.sy + (t.oy1 - t.oy0) + 1) * ((segw - 1) * dc.sx + (t.ox1 - t.ox0) + 1) * PS;
         lpw = e > lpw ? e : lpw;
-        const int HWr = 15 * d[c].sx + (ox1 - ox0) + 1;
+        const int HWr = 15 * dc.sx + (t.ox1 - t.ox0) + 1;
         if (HWr > 48) roll = false;
-        const size_t er = (size_t)(oy1 - oy0 + 1) * HWr * PS;
+        const size_t er = (size_t)(t.oy1 - t.oy0 + 1) * HWr * PS;
         lpw_roll = er > lpw_roll ? er : lpw_roll;
     }
     if (roll) lpw = lpw_roll;
     lpw = (lpw + 7) & ~(size_t)7;
-    size_t lds = 4 * lpw > 1024 ? 4 * lpw : 1024;
-    lds *= sizeof(T);
+    const size_t lds = (4 * lpw > 1024 ? 4 * lpw : 1024) * elem_size;
     SVGP_REQUIRE(lds <= 160 * 1024, SVGP_ERR_UNSUPPORTED, "conv halo needs %zu bytes of LDS", lds);
     // (no zero fill of `part`: every workgroup (x, class) stores all tap blocks of its class, and the classes' tap ranges tile a
     // partial row -- tests/test_gpu_conv.py runs on NaN-filled scratch)
-#define C16W(KERNEL_, ROWS_)                                                                                                \
-    do {                                                                                                                    \
-        SVGP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL_),                                          \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                          \
-        hipLaunchKernelGGL(KERNEL_, dim3(nwg_c, ncls), dim3(256), lds, (hipStream_t)stream, L, nwg_c, ROWS_, in,            \
-                           outv, dout, part, part_stride, part_b, (int)lpw);                                                \
-    } while (0)
-    if (roll) {
-        if (d[0].nt == 9 && d[0].sy == 1) C16W((k_conv16_wgrad_roll<T, 9, 1>), RW);
-        else if (d[0].nt == 9) C16W((k_conv16_wgrad_roll<T, 9, 2>), RW);
-        else if (d[0].sy == 1) C16W((k_conv16_wgrad_roll<T, 4, 1>), RW);
-        else C16W((k_conv16_wgrad_roll<T, 4, 2>), RW);
-    } else {
-        if (d[0].nt == 9) C16W((k_conv16_wgrad<T, 9>), 4 * RW); else C16W((k_conv16_wgrad<T, 4>), 4 * RW);
-    }
-#undef C16W
+    ConvStep& s = roll ? plan_step(P, CK_conv16_wgrad_roll, -1, false, nwg_c, 2, {d0.nt, SY, nwg_c, RW, (int)lpw})
+                       : plan_step(P, CK_conv16_wgrad, -1, false, nwg_c, 1, {d0.nt, nwg_c, 4 * RW, (int)lpw});
+    s.gy = ncls; s.lds = lds;
+    plan_sums(P, nwg_c, part_stride, nwg_c * ncls, d0.Co);
+    return SVGP_OK;
+}
+
+// ---- executors: one launch function per group of kernel families with the same parameter list; CONV_INST picks the instance whose
+// family and template values a step names (CONV_INST_TF: the last template flag both ways)
+template <typename T>
+struct ConvArgs {                // forward: in, w, bias, out; weight gradient: in, outv (may be NULL), dout, part, part_b, dw, db
+    hipStream_t st;
+    const T *in, *w, *bias;
+    T* out;
+    const T* outv;
+    T *dout, *part, *part_b, *dw, *db;
+    int part_stride;
+};
+template <typename... KA, typename... A>
+static int conv_launch(const ConvStep& s, hipStream_t st, void (*k)(KA...), const A&... args) {
+    SVGP_REQUIRE(k, SVGP_ERR_UNSUPPORTED, "no kernel instance for this plan step (%s)", CONV_TEXT[s.kernel]);
+    if (s.lds)
+        SVGP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.lds));
+    hipLaunchKernelGGL(k, dim3(s.gx, s.gy, s.gz), dim3(256), s.lds, st, args...);
     SVGP_LAUNCH_CHECK();
-    rc = sum_partials<T>(nwg_c, part_stride, part_stride, (const T*)part, dw, 0, stream);
+    return SVGP_OK;
+}
+#define CONV_INST(KERNEL_, ...) if (s.kernel == CK_##KERNEL_ && step_is(s, {__VA_ARGS__})) k = k_##KERNEL_<T, __VA_ARGS__>;
+#define CONV_INST_TF(KERNEL_, ...) CONV_INST(KERNEL_, __VA_ARGS__, true) CONV_INST(KERNEL_, __VA_ARGS__, false)
+template <typename T> static int run_fwd_rows(const ConvStep& s, const svgp_conv_desc& g, const ConvArgs<T>& a) {    // 4 scalars
+    decltype(&k_conv16_thin_fwd<T, 3, 3, 3>) k = nullptr;
+    CONV_INST(conv16_thin_fwd, 3, 3, 3) CONV_INST_TF(convS_fwd_ring, 3, 3, 1, 3) CONV_INST_TF(convS_fwd_ring, 2, 2, 2, 3)
+    CONV_INST_TF(conv16_fwd_roll, 3, 3, 1, true) CONV_INST_TF(conv16_fwd_roll, 3, 3, 2, true) CONV_INST_TF(conv16_fwd_roll, 2, 2, 1, true)
+    CONV_INST_TF(conv16_fwd_roll, 2, 2, 2, true) CONV_INST_TF(conv16_fwd_roll, 4, 4, 2, false) CONV_INST_TF(conv16_fwd_roll, 1, 1, 1, true)
+    CONV_INST_TF(conv16_fwd_roll, 1, 2, 1, true) CONV_INST_TF(conv16_fwd_roll, 2, 1, 1, true)
+    return conv_launch(s, a.st, k, g, s.a(0), s.a(1), s.a(2), s.a(3), a.in, a.w, a.bias, a.out);
+}
+template <typename T> static int run_fwd_strips(const ConvStep& s, const svgp_conv_desc& d, const ConvArgs<T>& a) {  // 3 scalars
+    decltype(&k_conv16_fwd<T, 1>) k = nullptr;
+    CONV_INST(conv16_fwd, 1) CONV_INST(conv16_fwd, 2) CONV_INST(conv16_fwd, 3) CONV_INST(conv16_fwd, 4) CONV_INST(conv16_fwd, 6)
+    CONV_INST(conv16_fwd, 9) CONV_INST(conv16_fwd, 16) CONV_INST(convS_fwd, 1) CONV_INST(convS_fwd, 2) CONV_INST(convS_fwd, 3)
+    CONV_INST(convS_fwd, 4) CONV_INST(convS_fwd, 5) CONV_INST(convS_fwd, 6) CONV_INST(convS_fwd, 7) CONV_INST(convS_fwd, 8)
+    return conv_launch(s, a.st, k, d, s.a(0), s.a(1), s.a(2), a.in, a.w, a.bias, a.out);
+}
+template <typename T> static int run_taps_fwd(const ConvStep& s, const ConvLaunch& L, const ConvArgs<T>& a) {
+    decltype(&k_conv_taps_fwd<T, 0, 0>) k = nullptr;
+    CONV_INST(conv_taps_fwd, 16, 9) CONV_INST(conv_taps_fwd, 16, 4) CONV_INST(conv_taps_fwd, 4, 9) CONV_INST(conv_taps_fwd, 0, 0)
+    return conv_launch(s, a.st, k, L, s.a(0), a.in, a.w, a.bias, a.out);
+}
+template <typename T> static int run_wgrad_thin(const ConvStep& s, const svgp_conv_desc& d, const ConvArgs<T>& a) {
+    decltype(&k_convS_wgrad<T, 1, 0>) k = nullptr;
+    CONV_INST(convS_wgrad, 1, 0) CONV_INST(convS_wgrad, 2, 0) CONV_INST(convS_wgrad, 1, 1) CONV_INST(convS_wgrad, 2, 1)
+    CONV_INST(convS_wgrad_ring, 3, 3, 1, 3, true, 0) CONV_INST(convS_wgrad_ring, 3, 3, 1, 3, false, 0)
+    CONV_INST(convS_wgrad_ring, 2, 2, 2, 3, true, 0) CONV_INST(convS_wgrad_ring, 2, 2, 2, 3, false, 0)
+    CONV_INST(convS_wgrad_ring, 3, 3, 1, 3, false, 1)
+    const bool mode1 = s.v[s.nt - 1];                          // MODE is the last template value of both families
+    return conv_launch(s, a.st, k, d, s.a(0), s.a(1), a.in, mode1 ? nullptr : a.outv, a.dout, a.part, a.part_stride,
+                       a.part_b + (size_t)s.cls * s.a(0) * 16);
+}
+template <typename T> static int run_wgrad_grid(const ConvStep& s, const ConvLaunch& G, const ConvArgs<T>& a) {
+    decltype(&k_conv16_wgrad_grid<T, 3, 3, 1, 1, true>) k = nullptr;
+    CONV_INST_TF(conv16_wgrad_grid, 3, 3, 1, 1) CONV_INST_TF(conv16_wgrad_grid, 3, 3, 2, 2)
+    CONV_INST_TF(conv16_wgrad_grid, 2, 2, 1, 1) CONV_INST_TF(conv16_wgrad_grid, 2, 2, 2, 2)
+    return conv_launch(s, a.st, k, G, s.a(0), s.a(1), a.in, a.outv, a.dout, a.part, a.part_stride, a.part_b);
+}
+template <typename T> static int run_wgrad_c16(const ConvStep& s, const ConvLaunch& L, const ConvArgs<T>& a) {       // rolling or not
+    decltype(&k_conv16_wgrad<T, 9>) k = nullptr;
+    CONV_INST(conv16_wgrad, 9) CONV_INST(conv16_wgrad, 4) CONV_INST(conv16_wgrad_roll, 9, 1) CONV_INST(conv16_wgrad_roll, 9, 2)
+    CONV_INST(conv16_wgrad_roll, 4, 1) CONV_INST(conv16_wgrad_roll, 4, 2)
+    return conv_launch(s, a.st, k, L, s.a(0), s.a(1), a.in, a.outv, a.dout, a.part, a.part_stride, a.part_b, s.a(2));
+}
+#undef CONV_INST_TF
+#undef CONV_INST
+
+template <typename T>
+static int conv_run(const ConvPlan& P, const svgp_conv_desc* d, int ncls, const ConvArgs<T>& a) {
+    for (int i = 0; i < P.n; ++i) {
+        const ConvStep& s = P.s[i];
+        ConvLaunch L;                                          // every class, as given or in grid order
+        L.ncls = ncls;
+        for (int c = 0; c < ncls && s.cls < 0 && s.kernel < CK_elu_bwd_colsum; ++c) L.d[c] = s.grid_order ? P.tg[c].g : d[c];
+        const svgp_conv_desc& dc = s.cls < 0 ? d[0] : s.grid_order ? P.tg[s.cls].g : d[s.cls];
+        const bool bias = s.a(4);                              // CK_sum_partials: part_b -> db
+        int rc = SVGP_OK;
+        switch (s.kernel) {
+        case CK_conv16_thin_fwd: case CK_conv16_fwd_roll: case CK_convS_fwd_ring: rc = run_fwd_rows<T>(s, dc, a); break;
+        case CK_conv16_fwd: case CK_convS_fwd: rc = run_fwd_strips<T>(s, dc, a); break;
+        case CK_conv_taps_fwd: rc = run_taps_fwd<T>(s, L, a); break;
+        case CK_convS_wgrad_ring: case CK_convS_wgrad: rc = run_wgrad_thin<T>(s, dc, a); break;
+        case CK_conv_taps_wgrad: rc = conv_launch(s, a.st, k_conv_taps_wgrad<T>, L, s.a(0), a.in, (const T*)a.dout, a.part, a.part_stride); break;
+        case CK_conv16_wgrad_grid: rc = run_wgrad_grid<T>(s, L, a); break;
+        case CK_conv16_wgrad_roll: case CK_conv16_wgrad: rc = run_wgrad_c16<T>(s, L, a); break;
+        case CK_elu_bwd_colsum: rc = conv_launch(s, a.st, k_elu_bwd_colsum<T>, (long long)dc.n * dc.Ho * dc.Wo, s.a(0), a.outv, a.dout, a.part_b); break;
+        case CK_zero_part: SVGP_CHECK_HIP(hipMemsetAsync(a.part, 0, (size_t)s.a(0) * a.part_stride * sizeof(T), a.st)); break;
+        default: rc = sum_partials<T>(s.a(0), s.a(1), s.a(2), (const T*)(bias ? a.part_b : a.part), bias ? a.db : a.dw, s.a(3), a.st);
+        }
+        if (rc) return rc;
+    }
+    return SVGP_OK;
+}
+
+// One convolution call: the plan, the pointer checks, the launches.  pass 0: forward; 1: fused weight gradient; 2: the generic
+// weight gradient alone (svgp_conv_taps_wgrad)
+template <typename T>
+static int conv_call(int pass, const svgp_conv_desc* d, int ncls, int nwg, int accumulate, bool pointers, const ConvArgs<T>& a) {
+    ConvPlan P;
+    const int rc = pass == 0 ? conv_fwd_plan(d, ncls, (int)sizeof(T), P)
+                             : conv_wgrad_plan(d, ncls, nwg, a.part_stride, a.outv != nullptr, (int)sizeof(T), P, pass == 2 ? accumulate != 0 : -1);
     if (rc) return rc;
-    return sum_partials<T>(nwg_c * ncls, d[0].Co, 16, (const T*)part_b, db, 0, stream);
+    SVGP_REQUIRE(pointers, SVGP_ERR_INVALID, pass == 0 ? "NULL device pointer" : "bad argument");
+    SVGP_REQUIRE(pass != 0 || !d[0].act || a.bias, SVGP_ERR_INVALID, "bias is NULL but act != 0");        // the classes share act
+    return conv_run<T>(P, d, ncls, a);
+}
+
+// The plan of a call as text, one line per launch / zero fill / partial-sum job: no GPU call, needs no device.
+extern "C" int svgp_conv_route(const svgp_conv_desc* d, int ncls, int pass, int has_out, int nwg, int part_stride, int elem_size,
+                               char* buf, int cap) {
+    SVGP_REQUIRE(buf && cap >= 1 && (pass == 0 || pass == 1) && (elem_size == 4 || elem_size == 8), SVGP_ERR_INVALID, "bad argument");
+    ConvPlan P;
+    const int rc = pass == 0 ? conv_fwd_plan(d, ncls, elem_size, P) : conv_wgrad_plan(d, ncls, nwg, part_stride, has_out != 0, elem_size, P);
+    if (rc) return rc;
+    int pos = 0;
+    buf[0] = 0;
+    for (int i = 0; i < P.n; ++i) {
+        const ConvStep& s = P.s[i];
+        const int* v = s.v;
+        pos += snprintf(buf + pos, cap - pos, CONV_TEXT[s.kernel], v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], v[8], v[9], v[10]);
+        if (pos < cap && s.gx)         // a launch of this call (sums may be deferred, the zero fill is a memset)
+            pos += snprintf(buf + pos, cap - pos, " grid=(%d,%d,%d) lds=%zu class=%d desc=%s", s.gx, s.gy, s.gz, s.lds, s.cls,
+                            s.grid_order ? "grid" : "given");
+        if (pos < cap) pos += snprintf(buf + pos, cap - pos, "\n");
+        SVGP_REQUIRE(pos < cap, SVGP_ERR_INVALID, "route text needs more than %d bytes", cap);
+    }
+    return SVGP_OK;
 }
 
 // dpre = dout * elu'(out) (in place on dout; out == NULL skips the activation) and db[c] = sum dpre[.., c].
@@ -2149,7 +2128,7 @@ static int conv_wgrad_fused_impl(const svgp_conv_desc* d, int ncls, const T* in,
 template <typename T>
 static int elu_bwd_bias_impl(long long npix, int C, const T* out, T* dout, T* part, T* db, void* stream) {
     SVGP_REQUIRE(npix >= 1 && C >= 1 && C <= 16 && dout && part && db, SVGP_ERR_INVALID, "bad argument");
-    const int nblk = 1024;     // 4 workgroups per CU keep the HBM queues full
+    const int nblk = ELU_NBLK;
     hipLaunchKernelGGL(k_elu_bwd_colsum<T>, dim3(nblk), dim3(256), 0, (hipStream_t)stream, npix, C, out, dout, part);
     SVGP_LAUNCH_CHECK();
     return sum_partials<T>(nblk, C, C, (const T*)part, db, 0, stream);
@@ -2174,50 +2153,48 @@ static int upconv_fold_impl(int Ci, int Co, const T* ge, T* g, void* stream) {
     return SVGP_OK;
 }
 
-extern "C" int svgp_conv_taps_fwd(const svgp_conv_desc* d, int ncls, const double* in, const double* w,
-                                  const double* bias, double* out, void* stream) {
-    return conv_taps_fwd_impl<double>(d, ncls, in, w, bias, out, stream);
-}
-extern "C" int svgp_conv_taps_wgrad(const svgp_conv_desc* d, int ncls, const double* in, const double* dout,
-                                    double* part, int nwg, int part_stride, double* dw, int accumulate, void* stream) {
-    return conv_taps_wgrad_impl<double>(d, ncls, in, dout, part, nwg, part_stride, dw, accumulate, stream);
-}
 extern "C" int svgp_elu_bwd_bias(long long npix, int C, const double* out, double* dout, double* part, double* db,
                                  void* stream) {
     return elu_bwd_bias_impl<double>(npix, C, out, dout, part, db, stream);
 }
-extern "C" int svgp_conv_taps_wgrad_fused(const svgp_conv_desc* d, int ncls, const double* in, const double* out, double* dout,
-                                          double* part, double* part_b, int nwg, int part_stride, double* dw, double* db,
-                                          void* stream) {
-    return conv_wgrad_fused_impl<double>(d, ncls, in, out, dout, part, part_b, nwg, part_stride, dw, db, stream);
-}
-extern "C" int svgp_conv_taps_wgrad_fused_f32(const svgp_conv_desc* d, int ncls, const float* in, const float* out, float* dout,
-                                              float* part, float* part_b, int nwg, int part_stride, float* dw, float* db,
-                                              void* stream) {
-    return conv_wgrad_fused_impl<float>(d, ncls, in, out, dout, part, part_b, nwg, part_stride, dw, db, stream);
-}
 // as svgp_conv_taps_wgrad_fused, but the closing reductions come back as job descriptors instead of being launched
 template <typename T>
-static int wgrad_fused_jobs(const svgp_conv_desc* d, int ncls, const T* in, const T* out, T* dout, T* part, T* part_b, int nwg,
-                            int part_stride, T* dw, T* db, svgp_sum_job* jobs, int cap, int* n_jobs, void* stream) {
+static int wgrad_fused_jobs(const svgp_conv_desc* d, int ncls, int nwg, bool pointers, const ConvArgs<T>& a, svgp_sum_job* jobs, int cap,
+                            int* n_jobs) {
     SVGP_REQUIRE(jobs && n_jobs && cap >= 1, SVGP_ERR_INVALID, "bad job array");
     SumCapture& c = sum_capture();
     c.jobs = jobs; c.cap = cap; c.n = 0;
-    const int rc = conv_wgrad_fused_impl<T>(d, ncls, in, out, dout, part, part_b, nwg, part_stride, dw, db, stream);
+    const int rc = conv_call<T>(1, d, ncls, nwg, 0, pointers, a);
     *n_jobs = c.n;
     c.jobs = nullptr; c.cap = 0; c.n = 0;
     return rc;
 }
-extern "C" int svgp_conv_taps_wgrad_fused_jobs(const svgp_conv_desc* d, int ncls, const double* in, const double* out,
-                                               double* dout, double* part, double* part_b, int nwg, int part_stride, double* dw,
-                                               double* db, svgp_sum_job* jobs, int cap, int* n_jobs, void* stream) {
-    return wgrad_fused_jobs<double>(d, ncls, in, out, dout, part, part_b, nwg, part_stride, dw, db, jobs, cap, n_jobs, stream);
-}
-extern "C" int svgp_conv_taps_wgrad_fused_jobs_f32(const svgp_conv_desc* d, int ncls, const float* in, const float* out,
-                                                   float* dout, float* part, float* part_b, int nwg, int part_stride, float* dw,
-                                                   float* db, svgp_sum_job* jobs, int cap, int* n_jobs, void* stream) {
-    return wgrad_fused_jobs<float>(d, ncls, in, out, dout, part, part_b, nwg, part_stride, dw, db, jobs, cap, n_jobs, stream);
-}
+// the convolution entry points, once per element type: float64, and float32 = the reference's dtype for the SPRITES networks
+#define CONV_ENTRY_POINTS(SFX_, T_)                                                                                         \
+    extern "C" int svgp_conv_taps_fwd##SFX_(const svgp_conv_desc* d, int ncls, const T_* in, const T_* w, const T_* bias,   \
+                                            T_* out, void* stream) {                                                        \
+        return conv_call<T_>(0, d, ncls, 0, 0, in && w && out, {(hipStream_t)stream, in, w, bias, out});                    \
+    }                                                                                                                       \
+    extern "C" int svgp_conv_taps_wgrad##SFX_(const svgp_conv_desc* d, int ncls, const T_* in, const T_* dout, T_* part,    \
+                                              int nwg, int part_stride, T_* dw, int accumulate, void* stream) {             \
+        return conv_call<T_>(2, d, ncls, nwg, accumulate, in && dout && part && dw,                                         \
+                             {(hipStream_t)stream, in, 0, 0, 0, 0, const_cast<T_*>(dout), part, 0, dw, 0, part_stride});    \
+    }                                                                                                                       \
+    extern "C" int svgp_conv_taps_wgrad_fused##SFX_(const svgp_conv_desc* d, int ncls, const T_* in, const T_* out,         \
+                                                    T_* dout, T_* part, T_* part_b, int nwg, int part_stride, T_* dw,       \
+                                                    T_* db, void* stream) {                                                 \
+        return conv_call<T_>(1, d, ncls, nwg, 0, in && dout && part && part_b && dw && db,                                  \
+                             {(hipStream_t)stream, in, 0, 0, 0, out, dout, part, part_b, dw, db, part_stride});             \
+    }                                                                                                                       \
+    extern "C" int svgp_conv_taps_wgrad_fused_jobs##SFX_(const svgp_conv_desc* d, int ncls, const T_* in, const T_* out,    \
+                                                         T_* dout, T_* part, T_* part_b, int nwg, int part_stride, T_* dw,  \
+                                                         T_* db, svgp_sum_job* jobs, int cap, int* n_jobs, void* stream) {  \
+        return wgrad_fused_jobs<T_>(d, ncls, nwg, in && dout && part && part_b && dw && db,                                 \
+                                    {(hipStream_t)stream, in, 0, 0, 0, out, dout, part, part_b, dw, db, part_stride}, jobs, cap, n_jobs); \
+    }
+CONV_ENTRY_POINTS(, double)
+CONV_ENTRY_POINTS(_f32, float)
+#undef CONV_ENTRY_POINTS
 extern "C" int svgp_sum_partials_multi(const svgp_sum_job* jobs, int n, void* stream) {
     return sum_partials_multi_impl<double>(jobs, n, stream);
 }
@@ -2269,14 +2246,6 @@ extern "C" int svgp_upconv_fold_wgrad(int Ci, int Co, const double* ge, double* 
 }
 // ---- float32 instantiations: the reference's dtype for the SPRITES networks (VAE_utils.py:277); same tap tables, the
 // gather-GEMM runs on v_mfma_f32_16x16x4_f32 (twice the matrix rate of the f64 form, half the LDS and HBM bytes)
-extern "C" int svgp_conv_taps_fwd_f32(const svgp_conv_desc* d, int ncls, const float* in, const float* w, const float* bias,
-                                      float* out, void* stream) {
-    return conv_taps_fwd_impl<float>(d, ncls, in, w, bias, out, stream);
-}
-extern "C" int svgp_conv_taps_wgrad_f32(const svgp_conv_desc* d, int ncls, const float* in, const float* dout, float* part,
-                                        int nwg, int part_stride, float* dw, int accumulate, void* stream) {
-    return conv_taps_wgrad_impl<float>(d, ncls, in, dout, part, nwg, part_stride, dw, accumulate, stream);
-}
 extern "C" int svgp_elu_bwd_bias_f32(long long npix, int C, const float* out, float* dout, float* part, float* db,
                                      void* stream) {
     return elu_bwd_bias_impl<float>(npix, C, out, dout, part, db, stream);
