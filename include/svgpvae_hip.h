@@ -894,6 +894,21 @@ int svgp_scale_f64(long long n, double f, double* x, void* stream);
 int svgp_mean_vectors_accumulate(int L, int m, const double* mu_hat, double* acc, void* stream);
 int svgp_mean_vectors_bias(int L, int m, const double* acc, const double* full, double* out, void* stream);
 
+/* ---- cubic-spline image rotation (rotate.hip): the rotated-MNIST data set generator, utils.py:507-657 --------------------
+ * svgp_rotate_cubic_f64: out[k][a] (H, W) = images[k] (H, W) rotated by the angle whose cosine and sine are cos_sin[a] =
+ *   (c, s), as scipy.ndimage.rotate(image, angle, reshape=False) does with its defaults (order 3, mode 'constant', cval 0,
+ *   prefilter on): the image is turned into cubic B-spline coefficients (pole sqrt(3) - 2, mirror boundary, axis 0 then
+ *   axis 1), output pixel (i, j) reads the input at (off0 + c i + s j, off1 - s i + c j), off = cen - [[c, s], [-s, c]] cen,
+ *   cen = ((H - 1) / 2, (W - 1) / 2), is 0 when a coordinate is below 0 or above H - 1 / W - 1, and otherwise the 4 x 4 sum
+ *   of coefficients (taps mirrored with period 2 (len - 1)) times the two cubic weights.  The coordinate products and sums
+ *   are rounded one by one (no fused multiply-add), so a pixel is inside here exactly when it is inside on the CPU; pass the
+ *   cosines and sines of scipy.special.cosdg / sindg to get the quarter turns exact, as scipy's rotate does.
+ *   images (n, H, W), cos_sin (A, 2), out (n, A, H, W), float64 device arrays.  One workgroup per image (the coefficients
+ *   live in LDS and are computed once for all A angles); no allocation, no synchronisation, capturable.
+ *   2 <= H, W <= 64 (else SVGP_ERR_UNSUPPORTED); n < 0, A < 1 or a NULL pointer -> SVGP_ERR_INVALID; all before any launch.
+ *   n = 0 returns SVGP_OK and launches nothing.                                                                            */
+int svgp_rotate_cubic_f64(int n, int H, int W, int A, const double* images, const double* cos_sin, double* out, void* stream);
+
 /* ---- runtime helpers: HIP graphs and events without going through torch ---------------------*/
 int svgp_stream_create(void** stream_out);
 /* HIP maps streams onto a small pool of hardware queues (GPU_MAX_HW_QUEUES) in creation order; two streams on one queue run

@@ -272,6 +272,7 @@ SIGNATURES = {
     "svgp_scale_f64": [C.c_longlong, C.c_double, _P, _P],
     "svgp_mean_vectors_accumulate": [C.c_int, C.c_int, _P, _P, _P],
     "svgp_mean_vectors_bias": [C.c_int, C.c_int, _P, _P, _P, _P],
+    "svgp_rotate_cubic_f64": [C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P],
     "svgp_stream_create": [C.POINTER(_P)],
     "svgp_stream_destroy": [_P],
     "svgp_stream_sync": [_P],

@@ -10,7 +10,10 @@
   compute_bias_variance_mean_estimators(arr_batch, arr_full)  utils.py:922-948 (host; the driver's --bias_analysis keeps the
                                                          sum on the device: engine.mean_vectors_*)
   latent_samples_SVGPVAE(train_images, train_aux_data, vae, svgp, clipping_qs)   utils.py:975-1008
+  generate_rotated_MNIST(save_path, N, nr_angles, ...)   utils.py:507-657 (the digits are an argument, not a download; the
+                                                         rotations run as `svgp_rotate_cubic_f64`: rotate_images)
 """
+import math
 import pickle
 import random
 
@@ -141,6 +144,156 @@ def latent_samples_SVGPVAE(train_images, train_aux_data, vae, svgp, clipping_qs=
     if epsilon is None:
         epsilon = torch.randn(N, vae.L, dtype=torch.float64, device=eng.device)
     return eng.latent_samples_full(train_images, train_aux_data, epsilon, clip_qs=clipping_qs)
+
+
+def rotate_images(images, angles_deg, device=None, chunk=4096):
+    """images (n, H, W) rotated by every angle of angles_deg (A, degrees), as `scipy.ndimage.rotate(image, angle, reshape=False)`
+    with its defaults (cubic spline, mode 'constant', cval 0, prefilter): an (n, A, H, W) float64 device tensor.  The work is
+    `svgp_rotate_cubic_f64` (csrc/rotate.hip; 2 <= H, W <= 64), launched on `chunk` images at a time on the current stream;
+    the cosines and sines come from scipy.special.cosdg / sindg like scipy's own, so the quarter turns are exact."""
+    import torch
+    from scipy.special import cosdg, sindg
+    from ._lib import SvgpError, call, load_library
+    load_library()
+    if not torch.cuda.is_available():
+        raise SvgpError("rotate_images needs a HIP device (torch.cuda.is_available() is False); there is no CPU execution path")
+    if device is None:
+        device = images.device if hasattr(images, "is_cuda") and images.is_cuda else "cuda"
+    dev = torch.device(device)
+    images = torch.as_tensor(images).to(device=dev, dtype=torch.float64).contiguous()
+    if images.dim() != 3:
+        raise ValueError(f"images must be (n, H, W), got {tuple(images.shape)}")
+    angles = np.atleast_1d(np.asarray(angles_deg, dtype=np.float64))
+    cos_sin = torch.as_tensor(np.stack([cosdg(angles), sindg(angles)], axis=1), dtype=torch.float64).to(dev).contiguous()
+    n, H, W = images.shape
+    A = len(angles)
+    out = torch.empty((n, A, H, W), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        s = torch.cuda.current_stream(dev).cuda_stream
+        for lo in range(0, n, chunk):
+            hi = min(lo + chunk, n)
+            call("svgp_rotate_cubic_f64", hi - lo, H, W, A, images[lo:hi].data_ptr(), cos_sin.data_ptr(), out[lo:hi].data_ptr(), s)
+    return out
+
+
+def _rotate_on_device(images, angles_deg, chunk=4096):
+    """The default `rotate` of generate_rotated_MNIST: rotate_images on `chunk` images at a time, every chunk copied to the host
+    before the next one runs, so a 60 000-digit run holds one chunk of rotations on the device, not all of them."""
+    images = np.asarray(images, dtype=np.float64)
+    out = np.empty((len(images), len(angles_deg)) + images.shape[1:], dtype=np.float64)
+    for lo in range(0, len(images), chunk):
+        out[lo:lo + chunk] = rotate_images(images[lo:lo + chunk], angles_deg).cpu().numpy()
+    return out
+
+
+def generate_rotated_MNIST(save_path, N=400, nr_angles=16, valid_set_size=0.1, drop_rate=0.25, digits=[3, 6],
+                           latent_dim_object_vector=8, shuffle_data=True, seed=0, *, mnist=None, driver_names=False, rotate=None):
+    """utils.py:507-657: the rotated-MNIST data sets of Casale's paper.  Writes the train, eval and test sets as pickles of
+    {'images': (rows, 28, 28, 1) float64, unclipped, 'aux_data': (rows, 2 + latent_dim_object_vector) rows [image id, angle in
+    radians, PCA embedding]} and the PCA embeddings of the N * len(digits) chosen digits (the object-vector init) as a fourth.
+
+    Positional arguments and behaviour are the reference's: `random.seed(seed)`, N images of every digit drawn with
+    random.sample, sklearn PCA over the chosen images, every image at the nr_angles angles of [0, 360) (rows image-major,
+    angle-minor), per digit the last valid_set_size of the rows to the eval set (shuffled with random.sample when
+    shuffle_data), one angle drawn with random.sample as the test angle, and drop_rate of the train and of the test rows dropped
+    (a random subset when shuffle_data; otherwise the tail, which is then written as `train_not_in_test_data...`).
+
+      mnist         (x_train uint8 (n, 28, 28), y_train (n)): the raw digits.  The reference downloads them through Keras
+                    (:534); nothing is fetched here, None raises a ValueError.
+      driver_names  False: the reference's file names `train_data<digits>_<M>.p`, `pca_ov_init<digits>_<M>.p`, ... with
+                    M = latent_dim_object_vector (:561, :644; `_not_shuffled_<M>.p` without shuffle_data) -- sic: the
+                    reference's own drivers never read these names.  True: the names the drivers do read,
+                    `train_data<digits>.p`, `eval_data<digits>.p`, `test_data<digits>.p`, `pca_ov_init<digits>.p`
+                    (MNIST_experiment.py --dataset <digits>; `<digits>_not_shuffled.p` without shuffle_data).
+      rotate        callable (images (n, H, W), angles_deg (A)) -> (n, A, H, W) array standing in for the device kernel, the
+                    seam for tests without a GPU.  Default: `svgp_rotate_cubic_f64` through rotate_images.  The package
+                    supplies no CPU implementation.
+
+    Returns {'train': path, 'eval': path, 'test': path, 'pca': path[, 'train_not_in_test': path]}."""
+    from sklearn.decomposition import PCA
+    if mnist is None:
+        raise ValueError("generate_rotated_MNIST: pass the raw digits as mnist=(x_train uint8 (n, 28, 28), y_train (n)); "
+                         "this build downloads nothing (the reference fetches them through tf.keras.datasets.mnist)")
+    M = latent_dim_object_vector
+    random.seed(seed)
+    angles = np.linspace(0, 360, nr_angles + 1)[:-1]
+    x_all, y_all = np.asarray(mnist[0]), np.asarray(mnist[1])
+    x_all = x_all / 255.0                                   # [0, 255] -> [0, 1]
+
+    chosen = []
+    for digit in digits:
+        x_digit = x_all[y_all == digit]
+        print('Number of images with digit {}: {}'.format(digit, len(x_digit)))
+        chosen.append(x_digit[random.sample(list(range(len(x_digit))), N)])      # (N, 28, 28)
+    x = np.concatenate(chosen)
+    n_obj = len(digits) * N
+    assert n_obj == x.shape[0]
+
+    pca = PCA(n_components=M)
+    pca_df = pca.fit_transform(x.copy().reshape((n_obj, -1)))
+    print("Explained variance ratio PCA: {}".format(pca.explained_variance_ratio_))
+    digit_ending = "".join(str(d) for d in digits)
+    paths = {"pca": save_path + ('pca_ov_init{}.p'.format(digit_ending) if driver_names
+                                 else 'pca_ov_init{}_{}.p'.format(digit_ending, M))}
+    with open(paths["pca"], 'wb') as f:
+        pickle.dump(pca_df, f)
+
+    # rows image-major, angle-minor: [id, radians(angle), pca...]
+    rotated = np.asarray((rotate or _rotate_on_device)(x, angles), dtype=np.float64)
+    if rotated.shape != (n_obj, nr_angles) + x.shape[1:]:
+        raise ValueError(f"rotate returned {rotated.shape}, expected {(n_obj, nr_angles) + x.shape[1:]}")
+    images = rotated.reshape((n_obj * nr_angles,) + x.shape[1:])[..., np.newaxis]
+    aux_data = np.concatenate([np.array([tuple([i, math.radians(angle)] + list(pca_df[i])) for angle in angles])
+                               for i in range(n_obj)])
+
+    # per digit: the head of its rows stays, the tail is the eval set
+    N_digit = int(len(images) / len(digits))
+    N_keep = int(N_digit * (1 - valid_set_size))
+    keep = np.concatenate([np.arange(d * N_digit, d * N_digit + N_keep) for d in range(len(digits))])
+    held = np.concatenate([np.arange(d * N_digit + N_keep, (d + 1) * N_digit) for d in range(len(digits))])
+    eval_images, eval_aux_data = images[held], aux_data[held]
+    images, aux_data = images[keep], aux_data[keep]
+    if shuffle_data:
+        eval_idx = random.sample(list(range(len(eval_images))), len(eval_images))
+        eval_images, eval_aux_data = eval_images[eval_idx], eval_aux_data[eval_idx]
+
+    # one angle is the test set
+    test_angle = random.sample(list(angles), 1)[0]
+    mask = aux_data[:, 1] == math.radians(test_angle)
+    train_images, train_aux_data, test_images, test_aux_data = images[~mask], aux_data[~mask], images[mask], aux_data[mask]
+    print("Test angle: {}".format(test_angle))
+
+    # drop some rows
+    n_train, n_test = int(len(train_images) * (1 - drop_rate)), int(len(test_images) * (1 - drop_rate))
+    if shuffle_data:
+        idx_train = random.sample(list(range(len(train_images))), n_train)
+        idx_test = random.sample(list(range(len(test_images))), n_test)
+    else:
+        idx_train, idx_test = list(range(n_train)), list(range(n_test))
+        rest_images, rest_aux_data = train_images[n_train:], train_aux_data[n_train:]
+    train_images, train_aux_data = train_images[idx_train], train_aux_data[idx_train]
+    test_images, test_aux_data = test_images[idx_test], test_aux_data[idx_test]
+
+    print('Size of training data: {}'.format(len(train_images)))
+    print('Size of validation data: {}'.format(len(eval_images)))
+    print('Size of test data: {}'.format(len(test_images)))
+    if not shuffle_data:
+        print('Size of training data without test ids: {}'.format(len(rest_images)))
+
+    if driver_names:
+        ending = digit_ending + ("" if shuffle_data else "_not_shuffled") + ".p"
+    else:
+        ending = digit_ending + ("_{}.p".format(M) if shuffle_data else "_not_shuffled_{}.p".format(M))
+    print(ending)
+    sets = [("train", 'train_data', train_images, train_aux_data), ("eval", 'eval_data', eval_images, eval_aux_data),
+            ("test", 'test_data', test_images, test_aux_data)]
+    if not shuffle_data:
+        sets.append(("train_not_in_test", 'train_not_in_test_data', rest_images, rest_aux_data))
+    for key, stem, im, aux in sets:
+        paths[key] = save_path + stem + ending
+        with open(paths[key], 'wb') as f:
+            pickle.dump({'images': im, 'aux_data': aux}, f)
+    return paths
 
 
 def __getattr__(name):
