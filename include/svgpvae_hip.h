@@ -770,6 +770,28 @@ int svgp_pearce_elbo_assemble(int B, int T, const double* lh, const double* ce, 
                               double* out, void* stream);
 int svgp_scale_rows(long long rows, int C, const double* w, double* x, void* stream);
 
+/* ---- the same exact per-video GP with every n x n matrix in global memory (pearce_long.hip): 1 <= n <= T <= 2048 -------
+ * Same svgp_pearce_bufs, same (T, B) frame-major per-frame buffers, same meaning of idx / tmask / seed_lh_scale /
+ * accumulate, same randomness (eps_x / eps_y, or both NULL: Philox on state[SVGP_ST_RNG_CTR], counter (t B + b) 2 + c) and
+ * the same results as svgp_pearce_gp_fwd/bwd up to rounding; svgp_pearce_elbo_assemble takes their lh / ce / row_ce.
+ * Forward: A = K + diag(s2) built into bufs->Ai, svgp_spd_inverse_batched in place, then one pass over Ai:
+ *   alpha = Ai y,  p_m = y - s2 alpha,  p_v = s2 - s2^2 diag(Ai),  lhood = -1/2 (n log 2pi + y.alpha + log det A).
+ * Reverse: one pass over Ai -> ybar, s2bar.  want_dls != 0 additionally forms Ai D Ai with one svgp_dgemm_batched and
+ *   d_ls_x / d_ls_y (+ bufs->dl_part (2,B)); want_dls == 0 leaves d_ls_x / d_ls_y / dl_part untouched (they may be NULL).
+ *   A context set (idx != NULL) needs no product: its d_ls is always formed, whatever want_dls says.
+ * work: svgp_pearce_long_workspace_elems(B, T, n, want_dls) doubles (0 for a shape the entry points refuse); scratch only,
+ *   nothing in it is carried from one call to the next, so the full set and the context sets of a step may share the one
+ *   sized for n = T -- provided the calls are ordered on one stream.  bufs->Ai, alpha, lh (and p_m, p_v, eps of the full
+ *   set) written by the forward call are what the reverse call of the same set reads.
+ * Refused with a message before any launch: NULL pointers, n < 1, n > T, T > 2048 (SVGP_ERR_UNSUPPORTED), B < 1, n != T
+ * without idx.  Explicit stream, no allocation, no host synchronisation, capturable; no float atomics (bitwise
+ * reproducible).                                                                                                          */
+size_t svgp_pearce_long_workspace_elems(int B, int T, int n, int want_dls);
+int svgp_pearce_long_fwd(const svgp_pearce_bufs*, const double* eps_x, const double* eps_y, const double* state,
+                         double* work, void* stream);
+int svgp_pearce_long_bwd(const svgp_pearce_bufs*, double seed_lh_scale, int accumulate, int want_dls, const double* state,
+                         double* d_ls_x, double* d_ls_y, double* work, void* stream);
+
 /* ---- deep SVIGP_Hensman baseline on rotated MNIST (svigp.hip): MNIST_experiment.py --elbo SVIGP_Hensman -------------
  * SVIGP_Hensman.variational_loss / approximate_posterior_params (SVIGP_Hensman_model.py:135-227) and the ELBO assembly
  * of forward_pass_deep_SVIGP_Hensman (:230-289) with free variational parameters loc (L,m), scale (L,m,m)

@@ -87,7 +87,7 @@ def build_engine(args, batch=35, px=32, py=32):
                   device=args.device, seed=seed)
     if args.elbo in ('GPVAE_Pearce', 'VAE', 'NP'):
         model_lt = 0.001 if args.elbo == 'VAE' else args.modellt
-        return ball.PearceStepEngine(args.elbo, model_lt, 0.5, args.GP_joint, args.GP_init, **common)
+        return ball.pearce_engine_class(tmax)(args.elbo, model_lt, 0.5, args.GP_joint, args.GP_init, **common)
     titsias = 'Titsias' in args.elbo
     mk = lambda name: ball.SVGP(titsias=titsias, num_inducing_points=args.m, fixed_inducing_points=not args.ip_joint,
                                 tmin=1, tmax=tmax, vidlt=args.vidlt, fixed_gp_params=not args.GP_joint, name=name,

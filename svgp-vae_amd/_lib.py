@@ -254,6 +254,8 @@ SIGNATURES = {
     "svgp_pearce_gp_bwd": [C.POINTER(PearceBufs), C.c_double, C.c_int, _P, _P, _P, _P],
     "svgp_pearce_elbo_assemble": [C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "svgp_scale_rows": [C.c_longlong, C.c_int, _P, _P, _P],
+    "svgp_pearce_long_fwd": [C.POINTER(PearceBufs), _P, _P, _P, _P, _P],
+    "svgp_pearce_long_bwd": [C.POINTER(PearceBufs), C.c_double, C.c_int, C.c_int, _P, _P, _P, _P, _P],
     "svgp_svigp_fwd": [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double] + [_P] * 9,
     "svgp_svigp_bwd": [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _P, _P, _P, _P, _P, _P, C.c_int] + [_P] * 8,
     "svgp_svigp_assemble": [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _P, _P, C.c_int, _P, _P, _P],
@@ -305,6 +307,7 @@ NON_STATUS = {"svgp_version": ([], C.c_int), "svgp_last_error": ([], C.c_char_p)
               "svgp_act_bwd_bias_scratch_elems": ([C.c_int], C.c_int),
               "svgp_dgemm_splitk_scratch_elems": ([C.c_int, C.c_int, C.c_int], C.c_longlong),
               "svgp_sprites_kernel_bwd_scratch_elems": ([C.POINTER(SpritesKcfg)], C.c_longlong),
+              "svgp_pearce_long_workspace_elems": ([C.c_int, C.c_int, C.c_int, C.c_int], C.c_size_t),
               "svgp_svigp_workspace_elems": ([C.c_int, C.c_int, C.c_int], C.c_longlong),
               "svgp_svigp_scale_offset": ([C.c_int, C.c_int, C.c_int], C.c_longlong)}
 

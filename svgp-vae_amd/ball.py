@@ -429,17 +429,17 @@ class BallStepEngine(_BallMlpEngine):
                 o["inside_elbo_kl"], p["ip_x"].clone(), p["ip_y"].clone(), cov[0], cov[1], self)
 
 
-class PearceStepEngine(_BallMlpEngine):
+class _PearceEngineBase(_BallMlpEngine):
     """BALL_experiment.py --elbo GPVAE_Pearce | VAE | NP: exact per-video GP regression on the recognition network's
-    outputs (build_pearce_elbo_graphs, GPVAE_Pearce_model.py:89-236)."""
+    outputs (build_pearce_elbo_graphs, GPVAE_Pearce_model.py:89-236).  The step is shared; a subclass says how long a
+    video it takes (_check_tmax), owns the GP matrices (_alloc_gp) and issues the GP-regression calls (_gp_fwd / _gp_bwd)."""
 
     def __init__(self, type_elbo="GPVAE_Pearce", lt=5.0, context_ratio=0.5, GP_joint=False, GP_init=2.0, *, batch=35,
                  tmax=30, px=32, py=32, hidden=500, beta=1.0, lr=1e-3, clip_grad=False, device="cuda:0", params=None,
                  seed=0):
         if type_elbo not in ("GPVAE_Pearce", "VAE", "NP"):
             raise ValueError(f"type_elbo {type_elbo!r}")
-        if tmax > 64:
-            raise _lib.SvgpError("the exact per-video GP keeps its tmax x tmax matrices in LDS (tmax <= 64)")
+        self._check_tmax(tmax)
         self.type_elbo, self.lt, self.context_ratio, self.GP_joint = type_elbo, float(lt), float(context_ratio), bool(GP_joint)
         l0 = float(GP_init) if GP_joint else float(lt)                  # GPVAE_Pearce_model.py:35-41
         init = dict(params or {})
@@ -452,10 +452,11 @@ class PearceStepEngine(_BallMlpEngine):
         self.times = torch.arange(0, tmax, **f64)                       # GPVAE_Pearce_model.py:119-120 (0-based)
         self.buf = {k: torch.zeros(2, T, B, **f64) for k in ("y", "var_raw", "s2", "p_m", "p_v", "eps", "z", "zbar", "ybar",
                                                             "s2bar", "row_ce")}
-        self.Ai, self.alpha = torch.zeros(2, B, T, T, **f64), torch.zeros(2, B, T, **f64)
+        self._alloc_gp()                                                # Ai, c_Ai (2,B,T,T) and what the GP calls need beyond
+        self.alpha = torch.zeros(2, B, T, **f64)
         self.lh, self.ce, self.dl_part = torch.zeros(2, B, **f64), torch.zeros(2, B, **f64), torch.zeros(2, B, **f64)
         # neural-process context sets
-        self.c_Ai, self.c_alpha = torch.zeros(2, B, T, T, **f64), torch.zeros(2, B, T, **f64)
+        self.c_alpha = torch.zeros(2, B, T, **f64)
         self.c_lh, self.c_dl, self.c_ls = torch.zeros(2, B, **f64), torch.zeros(2, **f64), torch.full((2,), float(lt), **f64)
         self.np_gen = np.random.RandomState(seed + 1)
         self.stream.wait_stream(torch.cuda.current_stream(self.dev))
@@ -517,12 +518,11 @@ class PearceStepEngine(_BallMlpEngine):
                 e = epsilon.to(self.dev, _F64)
                 ex, ey = e[:, :, 0].t().contiguous(), e[:, :, 1].t().contiguous()
             full = self._bufs(tmask=tmask)
-            call("svgp_pearce_gp_fwd", C.byref(full), None if ex is None else ex.data_ptr(),
-                 None if ey is None else ey.data_ptr(), st, s)
+            self._gp_fwd(full, ex, ey)
             ctx = None
             if is_np:
                 ctx = self._bufs(n=con_tf, idx=idx, context=True)
-                call("svgp_pearce_gp_fwd", C.byref(ctx), None, None, st, s)
+                self._gp_fwd(ctx, None, None)
             z = torch.empty(R, 2, **f64)
             call("svgp_ball_pack_z", B, T, b["z"][0].data_ptr(), b["z"][1].data_ptr(), z.data_ptr(), s)
             g1, pred, row_recon, dlog = self._decode_recon(z, X, backward, None if tmask is None else tmask.view(-1))
@@ -530,9 +530,9 @@ class PearceStepEngine(_BallMlpEngine):
             if backward:
                 dz = self._decoder_backward(z, g1, dlog)
                 call("svgp_ball_unpack_zbar", B, T, dz.data_ptr(), b["zbar"][0].data_ptr(), b["zbar"][1].data_ptr(), s)
-                call("svgp_pearce_gp_bwd", C.byref(full), 1.0, 0, st, g["l_x"].data_ptr(), g["l_y"].data_ptr(), s)
+                self._gp_bwd(full, 1.0, 0, g["l_x"], g["l_y"])
                 if is_np:
-                    call("svgp_pearce_gp_bwd", C.byref(ctx), -1.0, 1, st, self.c_dl[0:].data_ptr(), self.c_dl[1:].data_ptr(), s)
+                    self._gp_bwd(ctx, -1.0, 1, self.c_dl[0:], self.c_dl[1:])
                 if not self.GP_joint:
                     g["l_x"].zero_(); g["l_y"].zero_()
                 dh2 = torch.empty(R, 4, **f64)
@@ -560,6 +560,74 @@ class PearceStepEngine(_BallMlpEngine):
                 self.act["pred"], self.params["l_x"][0].clone(), self.params["l_y"][0].clone(), self)
 
 
+class PearceStepEngine(_PearceEngineBase):
+    """The exact per-video GP on the LDS kernels k_pearce_fwd / k_pearce_bwd (ball.hip): tmax <= 64."""
+
+    @staticmethod
+    def _check_tmax(tmax):
+        if tmax > 64:
+            raise _lib.SvgpError("the exact per-video GP keeps its tmax x tmax matrices in LDS (tmax <= 64)")
+
+    def _alloc_gp(self):
+        f64 = dict(dtype=_F64, device=self.dev)
+        self.Ai, self.c_Ai = torch.zeros(2, self.B, self.T, self.T, **f64), torch.zeros(2, self.B, self.T, self.T, **f64)
+
+    def _gp_fwd(self, q, ex, ey):
+        call("svgp_pearce_gp_fwd", C.byref(q), None if ex is None else ex.data_ptr(), None if ey is None else ey.data_ptr(),
+             self.state.data_ptr(), self.stream.cuda_stream)
+
+    def _gp_bwd(self, q, seed_lh_scale, accumulate, dl_x, dl_y):
+        call("svgp_pearce_gp_bwd", C.byref(q), seed_lh_scale, accumulate, self.state.data_ptr(), dl_x.data_ptr(),
+             dl_y.data_ptr(), self.stream.cuda_stream)
+
+
+LONG_TMAX = 2048
+
+
+class PearceLongStepEngine(_PearceEngineBase):
+    """The same step with every tmax x tmax matrix in global memory (pearce_long.hip): 1 <= tmax <= 2048.  The inverse is
+    svgp_spd_inverse_batched, the rest of the GP regression one pass over A^-1 forward and one reverse; only the length-scale
+    gradient (--GP_joint) costs a second tmax^3 term, one batched GEMM.  All buffers are sized here, once."""
+
+    @staticmethod
+    def _check_tmax(tmax):
+        if not 1 <= tmax <= LONG_TMAX:
+            raise _lib.SvgpError(f"tmax={tmax}: the global-memory exact per-video GP takes 1 <= tmax <= {LONG_TMAX}")
+
+    def _alloc_gp(self):
+        B, T, is_np = self.B, self.T, self.type_elbo == "NP"
+        self.want_dls = int(self.GP_joint)                             # the product Ai D Ai is formed for d l_x, d l_y only
+        n_work = int(self.lib.svgp_pearce_long_workspace_elems(B, T, T, self.want_dls))
+        if n_work == 0:
+            raise _lib.SvgpError(f"batch={B} tmax={T}: no workspace for the global-memory exact per-video GP")
+        mats = 2 * B * T * T * (2 if is_np else 1)
+        # what one step allocates on top (encoder / decoder activations and their gradients), so that a configuration that
+        # cannot run is refused here and not by an allocation in the middle of a step
+        step = B * T * (4 * self.P + 4 * self.H + 16)
+        need, (free, _) = 8 * (mats + n_work + step), torch.cuda.mem_get_info(self.dev)
+        if need > free:
+            raise _lib.SvgpError(f"batch={B} tmax={T}: the exact per-video GP needs {need / 2 ** 30:.1f} GiB "
+                                 f"({8 * mats / 2 ** 30:.1f} GiB of A^-1, {8 * n_work / 2 ** 30:.1f} GiB of workspace), "
+                                 f"{free / 2 ** 30:.1f} GiB are free on {self.dev}")
+        f64 = dict(dtype=_F64, device=self.dev)
+        self.Ai = torch.zeros(2, B, T, T, **f64)
+        self.c_Ai = torch.zeros(2, B, T, T, **f64) if is_np else self.Ai   # context sets exist under the NP ELBO only
+        self.work = torch.zeros(n_work, **f64)
+
+    def _gp_fwd(self, q, ex, ey):
+        call("svgp_pearce_long_fwd", C.byref(q), None if ex is None else ex.data_ptr(), None if ey is None else ey.data_ptr(),
+             self.state.data_ptr(), self.work.data_ptr(), self.stream.cuda_stream)
+
+    def _gp_bwd(self, q, seed_lh_scale, accumulate, dl_x, dl_y):
+        call("svgp_pearce_long_bwd", C.byref(q), seed_lh_scale, accumulate, self.want_dls, self.state.data_ptr(),
+             dl_x.data_ptr(), dl_y.data_ptr(), self.work.data_ptr(), self.stream.cuda_stream)
+
+
+def pearce_engine_class(tmax):
+    """The LDS engine while a video's matrices fit (tmax <= 64), the global-memory one above."""
+    return PearceStepEngine if tmax <= 64 else PearceLongStepEngine
+
+
 def build_pearce_elbo_graphs(vid_batch, beta, type_elbo="GPVAE_Pearce", lt=5, context_ratio=0.5, GP_joint=False,
                              GP_init=2.0, epsilon=None, params=None, engine=None, ran_ind=None, con_tf=None):
     """GPVAE_Pearce_model.py:89-236: one forward pass on the HIP library; returns the reference's 11-tuple (last slot =
@@ -568,8 +636,8 @@ def build_pearce_elbo_graphs(vid_batch, beta, type_elbo="GPVAE_Pearce", lt=5, co
     eng = engine
     if eng is None:
         hidden = 500 if params is None else int(np.asarray(params["encB1"]).size)
-        eng = PearceStepEngine(type_elbo, lt, context_ratio, GP_joint, GP_init, batch=B, tmax=T, px=px, py=py,
-                               hidden=hidden, beta=float(beta), params=params)
+        eng = pearce_engine_class(T)(type_elbo, lt, context_ratio, GP_joint, GP_init, batch=B, tmax=T, px=px, py=py,
+                                     hidden=hidden, beta=float(beta), params=params)
     eng.set_scalars(beta=float(beta))
     eng.step(vid_batch, epsilon, adam=False, backward=False, ran_ind=ran_ind, con_tf=con_tf)
     return eng.outputs()
