@@ -370,6 +370,18 @@ int svgp_mnist_encoder_bwd_km_regs(int* out);
 int svgp_mnist_decoder_bwd_data_pre_aji(const svgp_mnist_cfg*, const double* theta, const double* images, double* ws,
                                         const double* state, void* stream);
 int svgp_mnist_decoder_bwd_data_aji_regs(int* out);
+/* m <= 64, training step (SVGP_DEC_FUSE): svgp_mnist_decoder_fwd_pre followed by svgp_mnist_decoder_bwd_data_pre (_aji: by
+ * svgp_mnist_decoder_bwd_data_pre_aji, m <= 32) as ONE launch: workgroup n of the second launch consumed only what workgroup n of
+ * the first produced, so one image loop runs z -> h0, a1, a2, recon, squared error -> d2, d1, dh0 -> zbar with the activations and
+ * weights resident in LDS.  Same arithmetic in the same order: same bits in every output of the launches it replaces.
+ * _fused_regs: out[0..2] for the rider form, out[3..5] for the form without riders: registers per lane, scratch bytes per lane
+ * (hipFuncGetAttributes) and the dynamic LDS bytes of an image workgroup at latent size L.  A rider and an image workgroup share a CU
+ * only while registers <= 168, scratch == 0 and LDS <= 80 KB; the kernel carries no occupancy hint, tests check the numbers. */
+int svgp_mnist_decoder_fwd_bwd_data_pre(const svgp_mnist_cfg*, const double* theta, const double* images, double* ws,
+                                        const double* state, void* stream);
+int svgp_mnist_decoder_fwd_bwd_data_pre_aji(const svgp_mnist_cfg*, const double* theta, const double* images, double* ws,
+                                            const double* state, void* stream);
+int svgp_mnist_decoder_fused_regs(int L, int* out);
 /* m <= 64: svgp_gp_factor_bwd_nofinal + svgp_mnist_decoder_bwd_weights(threads = 256) in ONE launch: the L channel workgroups
  * first, then min(b, 256) rider workgroups with the decoder's weight-gradient partials (needs svgp_mnist_decoder_bwd_data before). */
 int svgp_gp_factor_bwd_nofinal_wgrad(const svgp_mnist_cfg*, const double* images, double* ws, const double* state,

@@ -142,6 +142,9 @@ SIGNATURES = {
     "svgp_mnist_encoder_bwd_km_regs": [C.POINTER(C.c_int)],
     "svgp_mnist_decoder_bwd_data_pre_aji": [_CFG, _P, _P, _P, _P, _P],
     "svgp_mnist_decoder_bwd_data_aji_regs": [C.POINTER(C.c_int)],
+    "svgp_mnist_decoder_fwd_bwd_data_pre": [_CFG, _P, _P, _P, _P, _P],
+    "svgp_mnist_decoder_fwd_bwd_data_pre_aji": [_CFG, _P, _P, _P, _P, _P],
+    "svgp_mnist_decoder_fused_regs": [C.c_int, C.POINTER(C.c_int)],
     "svgp_gp_posterior_bwd_rows": [_CFG, _P, _P, _P],
     "svgp_mnist_grad_reduce_part": [_CFG, _P, _P, C.c_int, _P],
     "svgp_gp_posterior_bwd_with_final": [_CFG, _P, _P, _P],
@@ -366,6 +369,7 @@ class Schedule:
         self.side_off = side.startswith("0")
         self.side_single = side.startswith("2")
         self.kbar_branch = on("SVGP_KBAR_BRANCH")
+        self.dec_fuse = on("SVGP_DEC_FUSE")                 # m <= 64: decoder forward + data reverse in one launch (csrc/api.hip)
         self.stream_probe = on("SVGP_STREAM_PROBE")
         pack = env.get("SVGP_DP_PACK")
         self.dp_pack = None if pack is None else not pack.startswith("0")      # None: the library's default for m

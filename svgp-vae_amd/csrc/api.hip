@@ -379,7 +379,11 @@ int step_phase_impl(const svgp_mnist_cfg* c, int phase, double* theta, const dou
         }
         if (c->titsias) RUN(svgp_gp_titsias_fwd(c, ws, state, stream));
         // m <= 64 with the split on: the `_pre` forms read the effective up-convolution weights phase 0 of this step left in ws.dec_weff
-        if (!large && sc.dec_split) {
+        if (!large && sc.dec_split && sc.dec_fuse) {
+            // SVGP_DEC_FUSE: the two launches of the branch below as one (same grid, workgroup n consumes only its own data; same bits)
+            if (aji_in_dec) RUN(svgp_mnist_decoder_fwd_bwd_data_pre_aji(c, theta, images, ws, state, stream));
+            else RUN(svgp_mnist_decoder_fwd_bwd_data_pre(c, theta, images, ws, state, stream));
+        } else if (!large && sc.dec_split) {
             RUN(svgp_mnist_decoder_fwd_pre(c, theta, images, ws, stream));
             if (aji_in_dec) RUN(svgp_mnist_decoder_bwd_data_pre_aji(c, theta, images, ws, state, stream));
             else RUN(svgp_mnist_decoder_bwd_data_pre(c, theta, images, ws, state, stream));

@@ -1537,6 +1537,35 @@ __global__ __launch_bounds__(VAE_NT) void k_decoder_bwd_data_aji(svgp_vae::DecBw
     svgp_vae::decoder_bwd_data_images<true>(d, l - a.L, (int)gridDim.x - a.L, smem);
 }
 
+// Training step, m <= 64 (SVGP_DEC_FUSE): the decoder's forward launch and the launch above as ONE launch -- same grid, back to back in
+// phase 1, workgroup n of the second consumed only what workgroup n of the first produced (decoder_fwd_bwd_data_images, vae_dev.hpp).
+// AJI: the L rider workgroups at the head, as above (m <= 32); otherwise image workgroups only.  No occupancy hint and nothing
+// outlined (both measured slower on the merged launches): the rolled-tap forward keeps the kernel at <= 168 VGPRs without scratch and the
+// reduced staging at <= 80 KB of LDS, which a rider and an image workgroup need to share a CU; tests check the three numbers.
+template <bool AJI>
+__global__ __launch_bounds__(VAE_NT) void k_decoder_fwd_bwd_data(svgp_vae::DecFwdBwdArgs d, AjiArgs a) {
+    extern __shared__ __align__(16) real smem[];
+    int l = blockIdx.x;
+    if (AJI) {
+        if (l < a.L) {
+            if (threadIdx.x >= SVGP_BLOCK) return;
+            const int m = a.m, ld = m + 1;
+            real* A = smem;
+            real* W = A + m * ld;
+            mat_load_nt(A, ld, a.Ahat + (size_t)l * m * m, m, SVGP_BLOCK);
+            __syncthreads();
+            if ((int)threadIdx.x < m) A[threadIdx.x * ld + threadIdx.x] += a.jitter;
+            const real ldA = chol_inv(A, W, ld, m);                 // m <= 32: wave 0 alone, any number of live waves
+            for (int o = threadIdx.x; o < m * m; o += SVGP_BLOCK) a.Aji[(size_t)l * m * m + o] = A[(o / m) * ld + (o % m)];
+            if (threadIdx.x == 0) a.KL[l] -= real(0.5) * ldA;
+            return;
+        }
+        l -= a.L;
+        __builtin_amdgcn_s_setprio(3);          // (the image waves before a rider's sweep wave on the same SIMD, as above)
+    }
+    svgp_vae::decoder_fwd_bwd_data_images(d, l, (int)gridDim.x - (AJI ? a.L : 0), smem);
+}
+
 template <typename F>
 int set_dyn_lds(F kernel, size_t bytes) {
     SVGP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
@@ -1696,6 +1725,53 @@ extern "C" int svgp_mnist_decoder_bwd_data_pre_aji(const svgp_mnist_cfg* c, cons
     if (rc) return rc;
     hipLaunchKernelGGL(k_decoder_bwd_data_aji, dim3(a.L + svgp_n_part(c)), dim3(VAE_NT), lds, (hipStream_t)stream, d, a);
     SVGP_LAUNCH_CHECK();
+    return SVGP_OK;
+}
+// svgp_mnist_decoder_fwd_pre + svgp_mnist_decoder_bwd_data_pre[_aji] in one launch; same bits (SVGP_DEC_FUSE, m <= 64 training step)
+static int decoder_fwd_bwd_data_impl(const svgp_mnist_cfg* c, const double* theta, const double* images, double* ws,
+                                     const double* state, bool aji, void* stream) {
+    GET_LAYOUTS();
+    SVGP_REQUIRE(theta && images && ws && state, SVGP_ERR_INVALID, "NULL device pointer");
+    SVGP_REQUIRE(!aji || c->m <= 32, SVGP_ERR_UNSUPPORTED, "the rider inverse is the single-wave sweep (m <= 32), m = %d", c->m);
+    svgp_vae::DecFwdBwdArgs d;
+    d.b = c->b; d.L = c->L; d.geco = c->geco; d.inv_bglobal = 1.0 / (double)c->b_global;
+    d.state = state; d.th_dec = theta + pl.n_enc; d.images = images; d.zg = ws + wl.z; d.weff = ws + wl.dec_weff;
+    d.h0g = ws + wl.dec_h0; d.a1g = ws + wl.dec_a1; d.a2g = ws + wl.dec_a2; d.recon = ws + wl.recon; d.part_sums = ws + wl.part_sums;
+    d.d2g = ws + wl.dec_d2; d.d1g = ws + wl.dec_d1; d.dh0g = ws + wl.dec_dh0; d.zbar = ws + wl.zbar;
+    AjiArgs a;
+    memset(&a, 0, sizeof(a));
+    size_t lds = (size_t)svgp_vae::dec_fwd_bwd_lds(c->L) * sizeof(real);
+    if (aji) {
+        a.m = c->m; a.L = c->L; a.jitter = c->jitter; a.Ahat = ws + wl.A; a.Aji = ws + wl.Aji; a.KL = ws + wl.KL;
+        const size_t lds_inv = mat_lds(c->m, 1) + (size_t)(5 * c->m + 80) * sizeof(real);
+        if (lds_inv > lds) lds = lds_inv;
+    }
+    SVGP_REQUIRE(lds <= SVGP_LDS_MAX_BYTES, SVGP_ERR_UNSUPPORTED, "L = %d: %zu bytes of LDS", c->L, lds);
+    int rc = aji ? set_dyn_lds(k_decoder_fwd_bwd_data<true>, lds) : set_dyn_lds(k_decoder_fwd_bwd_data<false>, lds);
+    if (rc) return rc;
+    if (aji) hipLaunchKernelGGL(k_decoder_fwd_bwd_data<true>, dim3(a.L + svgp_n_part(c)), dim3(VAE_NT), lds, (hipStream_t)stream, d, a);
+    else hipLaunchKernelGGL(k_decoder_fwd_bwd_data<false>, dim3(svgp_n_part(c)), dim3(VAE_NT), lds, (hipStream_t)stream, d, a);
+    SVGP_LAUNCH_CHECK();
+    return SVGP_OK;
+}
+extern "C" int svgp_mnist_decoder_fwd_bwd_data_pre(const svgp_mnist_cfg* c, const double* theta, const double* images, double* ws,
+                                                   const double* state, void* stream) {
+    return decoder_fwd_bwd_data_impl(c, theta, images, ws, state, false, stream);
+}
+extern "C" int svgp_mnist_decoder_fwd_bwd_data_pre_aji(const svgp_mnist_cfg* c, const double* theta, const double* images, double* ws,
+                                                       const double* state, void* stream) {
+    return decoder_fwd_bwd_data_impl(c, theta, images, ws, state, true, stream);
+}
+// out[0..2] (riders), out[3..5] (no riders): registers per lane, scratch bytes per lane, dynamic LDS bytes of the launch at latent size L
+extern "C" int svgp_mnist_decoder_fused_regs(int L, int* out) {
+    SVGP_REQUIRE(out, SVGP_ERR_INVALID, "out is NULL");
+    SVGP_REQUIRE(L >= 1 && L <= 64, SVGP_ERR_INVALID, "L = %d (1..64)", L);
+    hipFuncAttributes fa;
+    SVGP_CHECK_HIP(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(k_decoder_fwd_bwd_data<true>)));
+    out[0] = fa.numRegs; out[1] = (int)fa.localSizeBytes;
+    SVGP_CHECK_HIP(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(k_decoder_fwd_bwd_data<false>)));
+    out[3] = fa.numRegs; out[4] = (int)fa.localSizeBytes;
+    out[2] = out[5] = (int)(svgp_vae::dec_fwd_bwd_lds(L) * sizeof(real));
     return SVGP_OK;
 }
 extern "C" int svgp_mnist_decoder_bwd_data_aji_regs(int* out) {

@@ -275,7 +275,12 @@ struct UpConv3 {
     // ---- VALU variants (register-tiled LDS loops): faster than the MFMA forms where the tile would be mostly
     //      padding (single output channel) or the gather arithmetic dominates; chosen per layer from ablation timings
     // out = elu(conv(up(in)) + bias); item = (output pixel, group of COG channels)
+    // ROLL: the two tap loops stay loops (one tap of CIN x COG FMAs per trip) instead of hoisting the 32 activation and 64 weight
+    // LDS loads of an item: ~85 VGPRs fewer, same FMA order per output (bias, then ty, tx, ci), so the same bits.  For kernels that
+    // must stay within 168 VGPRs (decoder_fwd_bwd_data_images below).
+    template <bool ROLL = false>
     static __device__ void fwd_valu(const real* in, const real* We, const real* bias, real* out) {
+        constexpr int TAP_UNROLL = ROLL ? 1 : 2;     // 1: no unrolling; 2 = the trip count: full
         for (int it = threadIdx.x; it < NPIX * NCG; it += NT) {
             const int cg = it % NCG, p = it / NCG, x = p % HOUT, y = p / HOUT;
             const int by = y - PAD, bx = x - PAD, py = by & 1, px = bx & 1, Y = by >> 1, X = bx >> 1;
@@ -283,11 +288,11 @@ struct UpConv3 {
 #pragma unroll
             for (int g = 0; g < COG; ++g) acc[g] = bias[cg * COG + g];
             const real* wc = We + ((py * 2 + px) * 4) * CIN * COUT + cg * COG;
-#pragma unroll
+#pragma unroll TAP_UNROLL
             for (int ty = 0; ty < 2; ++ty) {
                 const int sy = Y + ty;
                 const bool vy = (unsigned)sy < (unsigned)HS;
-#pragma unroll
+#pragma unroll TAP_UNROLL
                 for (int tx = 0; tx < 2; ++tx) {
                     const int sx = X + tx;
                     const bool valid = vy && ((unsigned)sx < (unsigned)HS);
@@ -678,6 +683,133 @@ __device__ __forceinline__ void decoder_bwd_data_images(const DecBwdDataArgs& a,
             if (i < a.L && part8 == 0) a.zbar[(size_t)n * a.L + i] = acc;
         }
     }
+}
+
+// ------------------------------------------------------------------------------------------
+// decoder forward + reverse DATA half in one image loop (m <= 64 training step, SVGP_DEC_FUSE): what svgp_mnist_decoder_fwd_pre
+// followed by svgp_mnist_decoder_bwd_data_pre compute, same expressions in the same order, hence the same bits.  Workgroup n of the
+// second launch consumed only what workgroup n of the first produced: here a1, a2, recon and the weights stay in LDS between the
+// halves, the image pixels stay in registers (thread t owns pixels t and t + 512: squared error AND d3), d3 overwrites the
+// reconstruction in place.  Only the dense weights, the biases and ws.dec_weff are staged (the raw convolution weights are never
+// read in the `_pre` form): dec_fwd_bwd_lds(L) reals, 75.5 KB at L = 16, so two workgroups fit a CU (the rider form,
+// k_decoder_fwd_bwd_data in gp_kernels.hip, relies on that and on <= 168 VGPRs: the forward runs its rolled-tap form).
+// The z / pixel loads of an image are issued one image ahead (the first: before the weight staging), so no dependent round trip
+// sits behind the staging.  The squared-error partial of a workgroup goes to part_sums[4 * first + 2].
+// ------------------------------------------------------------------------------------------
+struct DecFwdBwdArgs {
+    int b, L, geco;
+    real inv_bglobal;
+    const real* state; const real* th_dec; const real* images; const real* zg; const real* weff;
+    real* h0g; real* a1g; real* a2g; real* recon; real* part_sums;
+    real* d2g; real* d1g; real* dh0g; real* zbar;
+};
+__host__ __device__ constexpr int dec_fwd_bwd_lds(int L) {
+    return L * 128 + 128 + 32 + DEC_NWE + 64 + 128 + 512 + 1568 + 784 + 1568 + 512 + 128 + 16;
+}
+__device__ __forceinline__ void decoder_fwd_bwd_data_images(const DecFwdBwdArgs& a, int first, int stride, real* smem) {
+    const DecOff od = dec_off(a.L);
+    real* w = smem;                  // dense weights L*128 | dense bias 128 (contiguous in theta)
+    real* db = w + a.L * 128;
+    real* cb = db + 128;             // c1b (8) | c2b (8) | c3b (1)
+    real* We1 = cb + 32;             // effective weights
+    real* We2 = We1 + UpC1::NWE;
+    real* We3 = We2 + UpC2::NWE;
+    real* z = We3 + UpC3::NWE;       // 64
+    real* h0 = z + 64;               // 128
+    real* a1 = h0 + 128;             // 512
+    real* a2 = a1 + 512;             // 1568
+    real* d3 = a2 + 1568;            // 784: the reconstruction, then d3 in place
+    real* d2 = d3 + 784;             // 1568
+    real* d1 = d2 + 1568;            // 512
+    real* dh0 = d1 + 512;            // 128
+    real* red = dh0 + 128;           // 16
+    const int t = threadIdx.x;
+    const real lag = a.geco ? a.state[SVGP_ST_LAGRANGE] : real(0);
+    // image `first` exists for every workgroup (the grid has min(b, 256) image workgroups)
+    real zr = t < a.L ? a.zg[(size_t)first * a.L + t] : real(0);
+    real px0 = a.images[(size_t)first * 784 + t];
+    real px1 = t + VAE_NT < 784 ? a.images[(size_t)first * 784 + t + VAE_NT] : real(0);
+    lds_copy_in(w, a.th_dec + od.dw, a.L * 128 + 128);
+    if (t < 8) { cb[t] = a.th_dec[od.c1b + t]; cb[8 + t] = a.th_dec[od.c2b + t]; }
+    if (t == 0) cb[16] = a.th_dec[od.c3b];
+    lds_copy_in(We1, a.weff, DEC_NWE);
+    const real gscale = (a.geco ? lag * a.inv_bglobal : real(1)) / real(784);
+    real sq = 0;
+    for (int n = first; n < a.b; n += stride) {
+        __syncthreads();
+        if (t < a.L) z[t] = zr;
+        __syncthreads();
+        if (t < 128) {
+            real acc = db[t];
+            for (int i = 0; i < a.L; ++i) acc += z[i] * w[i * 128 + t];
+            h0[t] = acc;
+        }
+        __syncthreads();
+        UpC1::fwd_valu<true>(h0, We1, cb, a1);
+        __syncthreads();
+        UpC2::fwd_valu<true>(a1, We2, cb + 8, a2);
+        __syncthreads();
+        UpC3::fwd_valu<true>(a2, We3, cb + 16, d3);
+        __syncthreads();
+        lds_copy_out(a.h0g + (size_t)n * 128, h0, 128);
+        lds_copy_out(a.a1g + (size_t)n * 512, a1, 512);
+        lds_copy_out(a.a2g + (size_t)n * 1568, a2, 1568);
+        {   // pixels t and t + 512: reconstruction out, squared error, d3 in place (each element read and written by its one owner)
+            const real o = d3[t];
+            a.recon[(size_t)n * 784 + t] = o;
+            const real df = px0 - o;
+            sq += df * df;
+            d3[t] = real(2) * gscale * (o - px0) * elu_grad_from_out(o);
+            if (t + VAE_NT < 784) {
+                const real o1 = d3[t + VAE_NT];
+                a.recon[(size_t)n * 784 + t + VAE_NT] = o1;
+                const real df1 = px1 - o1;
+                sq += df1 * df1;
+                d3[t + VAE_NT] = real(2) * gscale * (o1 - px1) * elu_grad_from_out(o1);
+            }
+        }
+        {   // the next image's z and pixels: in flight during the reverse half
+            const int nn = n + stride;
+            if (nn < a.b) {
+                zr = t < a.L ? a.zg[(size_t)nn * a.L + t] : real(0);
+                px0 = a.images[(size_t)nn * 784 + t];
+                px1 = t + VAE_NT < 784 ? a.images[(size_t)nn * 784 + t + VAE_NT] : real(0);
+            }
+        }
+        __syncthreads();
+        UpC3::bwd_data_valu(d3, We3, d2);
+        __syncthreads();
+        for (int i = t; i < 1568; i += VAE_NT) {
+            const real v = d2[i] * elu_grad_from_out(a2[i]);
+            d2[i] = v;
+            a.d2g[(size_t)n * 1568 + i] = v;
+        }
+        svgp_lds_barrier();             // (the stores to d2g / d1g / dh0g are for a later launch: no wave waits for them here)
+        UpC2::bwd_data_mfma(d2, We2, d1);
+        svgp_lds_barrier();
+        for (int i = t; i < 512; i += VAE_NT) {
+            const real v = d1[i] * elu_grad_from_out(a1[i]);
+            d1[i] = v;
+            a.d1g[(size_t)n * 512 + i] = v;
+        }
+        svgp_lds_barrier();
+        UpC1::bwd_data_mfma(d1, We1, dh0);
+        svgp_lds_barrier();
+        if (t < 128) a.dh0g[(size_t)n * 128 + t] = dh0[t];
+        // zbar[i] = sum_j dh0[j] w[i][j]: 8 lanes per latent channel, xor-shuffle combine
+        {
+            const int i = t >> 3, part8 = t & 7;
+            real acc = 0;
+            if (i < a.L)
+                for (int j = part8; j < 128; j += 8) acc += dh0[j] * w[i * 128 + j];
+            acc += __shfl_xor(acc, 1, 64);
+            acc += __shfl_xor(acc, 2, 64);
+            acc += __shfl_xor(acc, 4, 64);
+            if (i < a.L && part8 == 0) a.zbar[(size_t)n * a.L + i] = acc;
+        }
+    }
+    const real tot = block_sum(sq, red);
+    if (t == 0) a.part_sums[first * 4 + 2] = tot;
 }
 
 // ------------------------------------------------------------------------------------------

@@ -2,11 +2,22 @@
 # Round artefacts on the MI355X box: bench lines of every workload, rocprofv3 kernel stats, PMC traffic passes, GEMM / inverse probes.
 # usage (through gpurun, from the repo root): bash tools/collect_profiles.sh r02a <commit>     -> files under gpurun_out/r02a_*
 # (copy what is to be judged into profiles/ afterwards; see profiles/README.md)
+#        bash tools/collect_profiles.sh <tag> <commit> cfg2-kernels   -> only <tag>_cfg2_kernel_stats.csv + <tag>_commit.txt in the output directory:
+#        the per-kernel table of the config-2 step alone (no --full: the stage table would launch every entry point by name)
 tag=${1:-rXX}
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out
 mkdir -p $O
 cd $R
+if [ "${3:-all}" = cfg2-kernels ]; then
+  cd /tmp && export TMPDIR=/tmp
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/${tag}_prof_cfg2 -- python3 $R/bench.py --steps 200 --warmup 20 --repeats 2 > $O/${tag}_prof_cfg2.log 2>&1 || exit 1
+  f=$(find $O/${tag}_prof_cfg2 -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $O/${tag}_cfg2_kernel_stats.csv
+  rm -rf $O/${tag}_prof_cfg2
+  echo "${2:-unknown}" > $O/${tag}_commit.txt
+  ls -la $O | grep ${tag}_
+  exit 0
+fi
 python bench.py --full > $O/${tag}_bench.json 2> $O/${tag}_bench.err
 python bench.py --full --workload cfg3 > $O/${tag}_cfg3.json 2>> $O/${tag}_bench.err
 python bench.py --full --workload sprites800 > $O/${tag}_sprites800_f64.json 2>> $O/${tag}_bench.err

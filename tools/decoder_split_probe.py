@@ -1,6 +1,7 @@
 """Development probe (round 6): the decoder reverse pass as data half + weight half (riders of the reverse factor launch).
-Prints (1) equality of the two forms, (2) stand-alone times of every piece, (3) the eager config-2 step with SVGP_DEC_SPLIT=0/1
-(the env switch is read once per process, so the two steps are timed in child processes)."""
+Prints (1) equality of the two forms, (2) stand-alone times of every piece -- the fused forward + data-reverse launch
+(SVGP_DEC_FUSE) next to the two launches it replaces, with and without riders --, (3) the eager config-2 step with
+SVGP_DEC_SPLIT=0/1 and the later switches, SVGP_DEC_FUSE=0/1 last (child processes: one setting per process)."""
 import ctypes as C
 import json
 import os
@@ -33,7 +34,7 @@ def child():
             eng.run(adam=True)
         eng.synchronize()
         best = min(best, (time.perf_counter() - t0) / reps * 1e6)
-    print(json.dumps(dict(split=os.environ.get("SVGP_DEC_SPLIT", "1"), merge=os.environ.get("SVGP_ENC_KM_MERGE", ""), sum_merge=os.environ.get("SVGP_SUM_MERGE", ""), stat_merge=os.environ.get("SVGP_STAT_MERGE", ""), aji_dec=os.environ.get("SVGP_AJI_DEC", ""), step_us=best, elbo=eng.scalars()["elbo"])), flush=True)
+    print(json.dumps(dict(split=os.environ.get("SVGP_DEC_SPLIT", "1"), merge=os.environ.get("SVGP_ENC_KM_MERGE", ""), sum_merge=os.environ.get("SVGP_SUM_MERGE", ""), stat_merge=os.environ.get("SVGP_STAT_MERGE", ""), aji_dec=os.environ.get("SVGP_AJI_DEC", ""), dec_fuse=os.environ.get("SVGP_DEC_FUSE", ""), step_us=best, elbo=eng.scalars()["elbo"])), flush=True)
 
 
 def main():
@@ -99,6 +100,8 @@ def main():
             ("decoder_bwd_data_pre_aji", "svgp_mnist_decoder_bwd_data_pre_aji", (cfg, th, img, ws, st, s)),
             ("decoder_fwd", "svgp_mnist_decoder_fwd", (cfg, th, img, ws, s)),
             ("decoder_fwd_pre", "svgp_mnist_decoder_fwd_pre", (cfg, th, img, ws, s)),
+            ("decoder_fwd_bwd_data_pre", "svgp_mnist_decoder_fwd_bwd_data_pre", (cfg, th, img, ws, st, s)),
+            ("decoder_fwd_bwd_data_pre_aji", "svgp_mnist_decoder_fwd_bwd_data_pre_aji", (cfg, th, img, ws, st, s)),
             ("encoder_kernel_matrix_fwd", "svgp_mnist_encoder_kernel_matrix_fwd", (cfg, th, img, eng._bound[1].data_ptr(), ws, s)),
             ("decoder_bwd_weights 256 x 1", "svgp_mnist_decoder_bwd_weights", (cfg, img, ws, st, 256, 1, s)),
             ("decoder_bwd_weights 512 x 1", "svgp_mnist_decoder_bwd_weights", (cfg, img, ws, st, 512, 1, s)),
@@ -116,11 +119,20 @@ def main():
             ("gp_posterior_bwd_with_final", "svgp_gp_posterior_bwd_with_final", (cfg, ws, st, s)),
             ("gp_posterior_bwd_rows", "svgp_gp_posterior_bwd_rows", (cfg, ws, st, s)),
             ("grad_reduce_all", "svgp_mnist_grad_reduce_all", (cfg, eng._bound[1].data_ptr(), ws, s))]
+    us = {}
     for name, sym, args in rows:
-        print(f"{name:32s} {timeit(sym, args):7.2f} us", flush=True)
-    for flag, sm, st_, aj in (("0", "0", "0", "0"), ("1", "1", "0", "0"), ("1", "1", "1", "0"), ("1", "1", "1", "1"), ("1", "1", "1", "0"),
-                              ("1", "1", "1", "1"), ("1", "1", "1", "0"), ("1", "1", "1", "1")):
-        env = dict(os.environ, SVGP_DEC_SPLIT=flag, SVGP_ENC_KM_MERGE=flag, SVGP_SUM_MERGE=sm, SVGP_STAT_MERGE=st_, SVGP_AJI_DEC=aj)
+        us[name] = timeit(sym, args)
+        print(f"{name:32s} {us[name]:7.2f} us", flush=True)
+    for sfx in ("", "_aji"):
+        pair = us["decoder_fwd_pre"] + us["decoder_bwd_data_pre" + sfx]
+        print(f"fused{sfx:5s} {us['decoder_fwd_bwd_data_pre' + sfx]:6.2f} us against {us['decoder_fwd_pre']:.2f} + "
+              f"{us['decoder_bwd_data_pre' + sfx]:.2f} = {pair:.2f} us (stand-alone, no boundary between the two)", flush=True)
+    # (the KL terms the riders of the _aji rows decremented 200 times over are rebuilt by every step of the children below)
+    for flag, sm, st_, aj, fu in (("0", "0", "0", "0", "0"), ("1", "1", "0", "0", "0"), ("1", "1", "1", "0", "0"), ("1", "1", "1", "1", "0"),
+                                  ("1", "1", "1", "1", "1"), ("1", "1", "1", "1", "0"), ("1", "1", "1", "1", "1"), ("1", "1", "1", "1", "0"),
+                                  ("1", "1", "1", "1", "1"), ("1", "1", "1", "0", "0"), ("1", "1", "1", "0", "1")):
+        env = dict(os.environ, SVGP_DEC_SPLIT=flag, SVGP_ENC_KM_MERGE=flag, SVGP_SUM_MERGE=sm, SVGP_STAT_MERGE=st_, SVGP_AJI_DEC=aj,
+                   SVGP_DEC_FUSE=fu)
         r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child"], env=env, capture_output=True, text=True)
         print(r.stdout.strip().splitlines()[-1] if r.stdout.strip() else r.stderr[-2000:], flush=True)
 
