@@ -419,13 +419,31 @@ int svgp_elbo_finalize_noadam(const svgp_mnist_cfg*, double* ws, double* state, 
  * svgp_gp_factor_bwd_early on a side stream and records that for `ws`; phase 2 joins the branch and runs
  * svgp_gp_factor_bwd_late only when that record exists for the same (stream, ws) -- otherwise (phase-1 stages issued
  * through the individual entry points, switch changed in between, cfg.titsias) it runs the whole reverse factor
- * stage.  With cfg.titsias nothing is forked: svgp_gp_titsias_fwd uses the inverse scratch the tail would use.    */
+ * stage.  With cfg.titsias nothing is forked: svgp_gp_titsias_fwd uses the inverse scratch the tail would use.
+ * The lines above are the un-merged outline; what is issued for a configuration, in order, is printed by svgp_mnist_step_route. */
 int svgp_mnist_step_phase(const svgp_mnist_cfg*, int phase, double* theta, const double* images,
                           const double* aux, const double* eps, double* ws, double* state,
                           double* adam_m, double* adam_v, void* stream);
 int svgp_mnist_train_step(const svgp_mnist_cfg*, double* theta, const double* images,
                           const double* aux, const double* eps, double* ws, double* state,
                           double* adam_m, double* adam_v, void* stream);
+/* The launch schedule of a step as text, one op per line, in issue order: what svgp_mnist_step_phase (form 0, `phase` 0..5;
+ * early_issued: phase 1 recorded the early reverse half for the workspace), svgp_mnist_train_step (form 1) and
+ * svgp_mnist_train_step_dp on rank `rank` of `nranks` (form 2) enqueue for this configuration under the schedule switches of the
+ * environment (adam: adam_m != NULL).  It is the plan those entry points execute; no GPU call, needs no device.  Lines:
+ *   <lane> <entry point> [arg]      a stage on lane main (the caller's stream), side0 or side1 (the library's side branches); arg: the
+ *                                   piece set of svgp_gp_factor_fwd_pieces / svgp_big_factor_fwd / _bwd (K SIG KL TAIL HEAD ALL; EARLY
+ *                                   LATE_A CHANNELS KBAR FINAL LATE ALL) or the part of svgp_mnist_grad_reduce_part
+ *   fork <lane> / join <lane>       the side branch continues behind the caller's stream / the caller's stream behind the branch
+ *   <lane> allreduce <block>        statA statB gradC; gradC_hi = gradC[n_enc:], gradC_lo = gradC[:n_enc] (cfg.split_grad_exchange)
+ * and in points 1..4 of the channel-sharded form:
+ *   main point_begin <k> / main point_end <k>      (the timing bracket of svgp_comm_timing)
+ *   main pack <block> all|window  /  main unpack <block> all|window|others     tile-packing; window: the rank's channels
+ *   main group_begin / main group_end              one RCCL launch
+ *   main reduce_scatter <block> [packed]  /  main allgather <block> [packed]   block: S v Si t u A2 ud td Ssym vbar KL
+ * SVGP_ERR_INVALID when the text needs more than cap bytes. */
+int svgp_mnist_step_route(const svgp_mnist_cfg*, int form, int phase, int nranks, int rank, int adam, int early_issued,
+                          char* buf, int cap);
 
 /* ---- data-parallel exchange over RCCL on the compute stream -------------------------
  * The reference is single-process; these are the three sum-exchanges the row-sharded step needs

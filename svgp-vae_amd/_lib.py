@@ -162,6 +162,7 @@ SIGNATURES = {
     "svgp_elbo_finalize_noadam": [_CFG, _P, _P, _P],
     "svgp_mnist_step_phase": [_CFG, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "svgp_mnist_train_step": [_CFG, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "svgp_mnist_step_route": [_CFG, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_int],
     "svgp_stream_features_f32": [_P, C.c_int64, _P, C.c_int, C.c_int, _P, _P, _P],
     "svgp_stream_knm_f32": [_P, C.c_int64, C.c_int, _P, _P, _P, _P],
     "svgp_stream_stats_f32": [C.c_int64, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, C.c_int64, _P],

@@ -164,14 +164,14 @@ extern "C" int svgp_mnist_ws_layout_get(const svgp_mnist_cfg* c, svgp_mnist_ws_l
 namespace {
 // One Side per (device, caller stream): two engines that enqueue on different streams (or from different threads) never
 // share a fork event, a join decision or a side stream.  `open[k]` (branch k forked and not yet joined) and `early_ws`
-// (workspaces whose early reverse factor half was issued by phase 1 and not yet consumed by phase 2) are only touched under
-// the Side's own mutex, which fork / join hold for the whole record + wait pair.
+// (workspaces whose early reverse factor half was issued by a stand-alone phase 1 and not yet consumed by a stand-alone phase 2;
+// the whole-step forms do not touch it) are only touched under the Side's own mutex, which fork / join hold for the whole
+// record + wait pair.
 struct Side {
     hipStream_t s[2] = {nullptr, nullptr};
     hipEvent_t fork = nullptr, done[2] = {nullptr, nullptr};
     bool open[2] = {false, false};
     std::set<const void*> early_ws;
-    std::set<const void*> konly_ws;      // workspaces whose channel-independent factor block was issued by phase 0 on branch 1
     std::mutex mu;
 };
 std::mutex g_side_mu;
@@ -269,14 +269,12 @@ int side_join(Side* sd, int k, hipStream_t main) {
 }
 void side_mark_early(Side* sd, const void* ws) { std::lock_guard<std::mutex> lk(sd->mu); sd->early_ws.insert(ws); }
 bool side_take_early(Side* sd, const void* ws) { std::lock_guard<std::mutex> lk(sd->mu); return sd->early_ws.erase(ws) > 0; }
-void side_mark_konly(Side* sd, const void* ws) { std::lock_guard<std::mutex> lk(sd->mu); sd->konly_ws.insert(ws); }
-bool side_take_konly(Side* sd, const void* ws) { std::lock_guard<std::mutex> lk(sd->mu); return sd->konly_ws.erase(ws) > 0; }
 
 }  // namespace
 
-// comm.hip (channel-sharded step, branch 1) / cholesky.hip (look-ahead of the blocked factorisation, branch 0): side branch k
-// of the caller's stream.  _fork: the branch continues after everything issued on the caller's stream so far (re-forking an
-// open branch just adds that dependency); _join: the caller's stream continues after everything issued on the branch.
+// cholesky.hip (look-ahead of the blocked factorisation, branch 0): side branch k of the caller's stream.
+// _fork: the branch continues after everything issued on the caller's stream so far (re-forking an open branch just adds
+// that dependency); _join: the caller's stream continues after everything issued on the branch.
 int svgp_side_branch_fork(const SvgpSched& sc, void* main_stream, void** side_stream_out, int k) {
     Side* sd = nullptr;
     int rc = side_get((hipStream_t)main_stream, sc, &sd);
@@ -299,189 +297,133 @@ int svgp_side_branch_join(void* main_stream, int k) {
     return side_join(sd, k, (hipStream_t)main_stream);
 }
 
-namespace {
-// The schedule switches this function consults (sched.hpp) are read once per exported call and arrive in `sc`; a caller must not
-// change SVGP_DEC_SPLIT between phase 1 and phase 2 of a step.
-// `defer`: the caller issues all four phases back to back on one stream (svgp_mnist_train_step), so a
-// branch forked in one phase may be joined in a later one; otherwise every phase joins before returning
-// (each phase may be captured into its own graph, with a collective in between).  defer == 2: ... and NOTHING is exchanged
-// between the phases (the single-GPU step), so a stage may move across a phase boundary.
-int step_phase_impl(const svgp_mnist_cfg* c, int phase, double* theta, const double* images, const double* aux,
-                    const double* eps, double* ws, double* state, double* adam_m, double* adam_v, void* stream,
-                    int defer, const SvgpSched& sc) {
-    int rc = svgp_check_cfg(c);
-    if (rc) return rc;
-    SVGP_REQUIRE(theta && images && aux && ws && state, SVGP_ERR_INVALID, "NULL device pointer");
-    SVGP_REQUIRE(phase >= 0 && phase <= 5, SVGP_ERR_INVALID, "phase %d out of range 0..5", phase);
-    hipStream_t ms = (hipStream_t)stream;
-    // Measured on MI355X (tools/fork_probe.py): a fork + join costs ~10 us of cross-stream signalling.  The
-    // kernel-matrix reverse pass || encoder reverse pass branch hides ~20 us, which pays only in the
-    // per-phase-graph replay form (phase 2: 110 -> 100 us) and loses in the eager in-order form
-    // (261 -> 283 us per step), so it is opt-in: SVGP_SIDE_STREAMS=1.
-    const bool fork2 = sc.side_small_m;
-    // Large-m path: the tail of the forward factor stage ((A_hat + jI)^-1, its log det, KL: a whole batched inverse that only
-    // the reverse factor stage and the final ELBO need) runs on side stream 1, beside the row stage, the decoder and the
-    // reverse statistics.  That hides ~140 us at config 3 for ~10 us of signalling, so it is on unless SVGP_SIDE_STREAMS=0.
-    // Not with cfg.titsias: svgp_gp_titsias_fwd inverts its own batch through the SAME inverse scratch (ws.scr_inv) on the
-    // caller's stream, and the early reverse half would only multiply zero seeds.
-    const bool large = c->m > SVGP_M_MAX;
-    const bool fork1 = large && !c->titsias && !sc.side_off;
-    Side* sd = nullptr;
-    if (fork2 || large) {
-        rc = side_get(ms, sc, &sd);
-        if (rc) return rc;
-    }
-    hipStream_t s2 = fork2 ? sd->s[0] : ms;
-#define RUN(call) do { rc = (call); if (rc) return rc; } while (0)
-    const bool ksplit = phase == 0 && fork1 && defer && c->m < SVGP_CHOL_INVERSE_MIN_M && sc.konly_branch;
-    const bool sum_rides = phase == 2 && !large && !fork2 && !c->titsias && sc.enc_km_merge && sc.sum_merge;
-    const bool aji_in_dec = phase == 1 && c->m <= 32 && !c->titsias && sc.dec_split && sc.aji_dec;
-    const bool stat_rides = defer == 2 && !large && !c->titsias && c->L <= 56 && sc.dec_split && sc.stat_merge;
-    switch (phase) {
-    case 0:
-        RUN(svgp_mnist_encoder_kernel_matrix_fwd(c, theta, images, aux, ws, stream));   // one launch for the two
-        // 64 < m < 512, phases issued back to back (round 5): everything of the forward factor stage that is a function of the
-        // KERNEL MATRICES alone -- (K + jI)^-1 and its log det, Kn Ki, q, W = (Kn Ki) K, P^T = K Ki: one single-matrix blocked inverse
-        // (a chain of 8 block steps, as long as the channel batch's) and three products -- goes to side branch 1 now, beside the
-        // forward statistics and the channel inverses, instead of behind them on the caller's stream.  Joined in phase 1 where
-        // u = Ki mu needs it.  SVGP_KONLY_BRANCH=0: the in-line order.
-        // (The branch is FORKED here but its launches are ISSUED behind the statistics': the host -- and a replayed graph, which
-        // submits its nodes in capture order -- takes ~2.5 us per launch, and the branch's 15 launches in front of the statistics'
-        // first kernel left the caller's stream idle for 36 us in the kernel trace.)
-        if (ksplit) RUN(side_fork(sd, 1, ms));
-        RUN(svgp_gp_stats_fwd(c, ws, stream));
-        if (ksplit) {
-            RUN(svgp_gp_factor_fwd_pieces(c, ws, (void*)sd->s[1], SVGP_FWD_K));
-            side_mark_konly(sd, ws);
-        }
-        if (c->titsias) RUN(svgp_gp_titsias_stats(c, ws, stream));
-        break;
-    case 1:
-        if (large && side_take_konly(sd, ws)) {                // the channel block; then what needs the branch's (K + jI)^-1 too
-            RUN(svgp_gp_factor_fwd_pieces(c, ws, stream, SVGP_FWD_SIG));
-            RUN(side_join(sd, 1, ms));
-            RUN(svgp_gp_factor_fwd_pieces(c, ws, stream, SVGP_FWD_KL));
-        } else
-        RUN(svgp_gp_factor_fwd_defer_aji(c, ws, stream));      // m <= 64: (A_hat + jI)^-1 finishes inside the row-stage launch
-        // m > 64: the tail of the stage and the early half of the REVERSE factor stage (no reverse statistic needed; phase 2 then
-        // runs the late half only) go to the side stream.  The branch is FORKED here but ISSUED behind the row stage: its ~25
-        // launches take the host ~100 us to enqueue, during which the caller's stream had nothing to run (config 3, kernel trace of
-        // round 4: a 101 us hole in front of the row stage's product) -- the branch has that much slack, the caller's stream none.
-        if (c->m > SVGP_M_MAX && fork1) RUN(side_fork(sd, 1, ms));
-        if (aji_in_dec) RUN(svgp_gp_posterior_fwd(c, eps, ws, state, stream));
-        else RUN(svgp_gp_posterior_fwd_with_aji(c, eps, ws, state, stream));
-        if (c->m > SVGP_M_MAX) {
-            RUN(svgp_gp_factor_fwd_aji_tail(c, ws, fork1 ? (void*)sd->s[1] : stream));
-            if (fork1) {
-                RUN(svgp_gp_factor_bwd_early(c, ws, state, (void*)sd->s[1]));
-                side_mark_early(sd, ws);                       // phase 2 of THIS workspace may run the late half only
-            }
-        }
-        if (c->titsias) RUN(svgp_gp_titsias_fwd(c, ws, state, stream));
-        // m <= 64 with the split on: the `_pre` forms read the effective up-convolution weights phase 0 of this step left in ws.dec_weff
-        if (!large && sc.dec_split && sc.dec_fuse) {
-            // SVGP_DEC_FUSE: the two launches of the branch below as one (same grid, workgroup n consumes only its own data; same bits)
-            if (aji_in_dec) RUN(svgp_mnist_decoder_fwd_bwd_data_pre_aji(c, theta, images, ws, state, stream));
-            else RUN(svgp_mnist_decoder_fwd_bwd_data_pre(c, theta, images, ws, state, stream));
-        } else if (!large && sc.dec_split) {
-            RUN(svgp_mnist_decoder_fwd_pre(c, theta, images, ws, stream));
-            if (aji_in_dec) RUN(svgp_mnist_decoder_bwd_data_pre_aji(c, theta, images, ws, state, stream));
-            else RUN(svgp_mnist_decoder_bwd_data_pre(c, theta, images, ws, state, stream));
-        } else {
-            RUN(svgp_mnist_decoder_fwd(c, theta, images, ws, stream));
-            RUN(svgp_mnist_decoder_bwd(c, theta, images, ws, state, stream));
-        }
-        if (!stat_rides) RUN(svgp_gp_stats_bwd(c, ws, state, stream));      // (else: at the head of phase 2's first launch)
-        if (fork1 && !defer) RUN(side_join(sd, 1, ms));        // phase-at-a-time callers: joined before the phase returns
-        break;
-    case 2:
-    case 4:     // phase 2 up to and including the kernel-matrix reverse pass + gradient reduction part 1 (cfg.split_grad_exchange)
-    case 5:     // ... the encoder's reverse pass + gradient reduction part 2
-        if (phase == 5) {
-            RUN(svgp_mnist_encoder_bwd(c, theta, images, ws, stream));
-            RUN(svgp_mnist_grad_reduce_part(c, aux, ws, 2, stream));
-            break;
-        }
-        // The late half alone is valid only if phase 1 of this library issued the early half on this workspace (recorded per
-        // workspace, not inferred from the environment): a caller that ran the phase-1 stages through the individual entry
-        // points, or changed SVGP_SIDE_STREAMS in between, gets the full reverse factor stage.
-        if (large && side_take_early(sd, ws)) {
-            RUN(svgp_gp_factor_bwd_late_a(c, ws, state, stream));       // what does not read the branch's results: before the join
-            RUN(side_join(sd, 1, ms));                                  // (a no-op unless phase 1 left the branch open)
-            // round 6: the single-matrix chain of the gradient of Ki (five ~9 us launches) on the branch that has just been joined,
-            // beside the channel block on the caller's stream; SVGP_KBAR_BRANCH=0: one after the other
-            if (sc.kbar_branch) {
-                RUN(side_fork(sd, 1, ms));
-                RUN(svgp_gp_factor_bwd_late_b_kbar(c, ws, state, (void*)sd->s[1]));
-                RUN(svgp_gp_factor_bwd_late_b_channels(c, ws, state, stream));
-                RUN(side_join(sd, 1, ms));
-                RUN(svgp_gp_factor_bwd_late_b_final(c, ws, state, stream));
-            } else
-            RUN(svgp_gp_factor_bwd_late_b(c, ws, state, stream));
-        } else {
-            // channel sum Kbar: inside the next launch; m <= 64: + the decoder's weight gradients as riders (phase 1 ran the data half)
-            if (stat_rides) RUN(svgp_gp_stats_factor_bwd_wgrad_sched(c, images, ws, state, stream, sc));
-            else if (!large && sc.dec_split) RUN(svgp_gp_factor_bwd_nofinal_wgrad(c, images, ws, state, stream));
-            else RUN(svgp_gp_factor_bwd_nofinal(c, ws, state, stream));
-        }
-        // m <= 64 (round 6): pass 2 of the reverse row stage (the sums over channels, consumed by the kernel-matrix VJP only) rides in the
-        // encoder's reverse launch in front of the VJP workgroups.  Not with cfg.titsias (its reverse stage adds to Kbar / Knbar in
-        // between), the split gradient exchange (phase 4) or SVGP_ENC_KM_MERGE=0.
-        if (sum_rides) RUN(svgp_gp_posterior_bwd_rows(c, ws, state, stream));
-        else RUN(svgp_gp_posterior_bwd_with_final(c, ws, state, stream));
-        if (c->titsias) RUN(svgp_gp_titsias_bwd(c, ws, state, stream));
-        // (m > 64, measured round 5: the kernel-matrix reverse pass on side branch 0 beside the encoder's does NOT overlap -- 68 KB +
-        // 104 KB of LDS per workgroup do not fit one CU; the kernel-matrix launch stretched from 49 to 103 us and the step was unchanged)
-        if (phase == 4) {
-            RUN(svgp_kernel_matrix_bwd_partials(c, theta, aux, ws, stream));
-            RUN(svgp_mnist_grad_reduce_part(c, aux, ws, 1, stream));
-            break;
-        }
-        if (sum_rides) {
-            RUN(svgp_mnist_encoder_bwd_km_sum(c, theta, images, aux, ws, state, stream));
-        } else if (!large && !fork2 && sc.enc_km_merge) {
-            RUN(svgp_mnist_encoder_bwd_km(c, theta, images, aux, ws, stream));
-        } else {
-            if (fork2) RUN(side_fork(sd, 0, ms));
-            RUN(svgp_kernel_matrix_bwd_partials(c, theta, aux, ws, s2));
-            RUN(svgp_mnist_encoder_bwd(c, theta, images, ws, stream));
-            if (fork2) RUN(side_join(sd, 0, ms));
-        }
-        RUN(svgp_mnist_grad_reduce_all(c, aux, ws, stream));
-        break;
-    case 3: {
-        svgp_mnist_param_layout pl;
-        svgp_mnist_ws_layout wl;
-        RUN(svgp_mnist_param_layout_get(c, &pl));
-        RUN(svgp_mnist_ws_layout_get(c, &wl));
-        if (adam_m != nullptr) {
-            SVGP_REQUIRE(adam_v != nullptr, SVGP_ERR_INVALID, "adam_v is NULL");
-            RUN(svgp_adam_tf1_finalize(c, pl.n_total, theta, ws + wl.grad, adam_m, adam_v, ws, state, 0.9, 0.999,
-                                       1e-8, stream));
-        } else {
-            RUN(svgp_elbo_finalize_noadam(c, ws, state, stream));
-        }
-        break;
-    }
-    default:
-        SVGP_REQUIRE(false, SVGP_ERR_INVALID, "phase %d out of range 0..3", phase);
-    }
-#undef RUN
+// ---- the step: step_plan (step_plan.hpp) decides, svgp_step_run executes, svgp_mnist_step_route prints.  The schedule switches
+// (sched.hpp) are read once per exported call and arrive in `sc`; a caller must not change SVGP_DEC_SPLIT between phase 1 and
+// phase 2 of a step.
+int svgp_step_plan_checked(const svgp_mnist_cfg* c, int form, int phase, int nranks, int rank, bool adam, bool early_issued,
+                           const SvgpSched& sc, StepPlan& P) {
+    SVGP_REQUIRE(form != STEP_FORM_PHASE || (phase >= 0 && phase <= 5), SVGP_ERR_INVALID, "phase %d out of range 0..5", phase);
+    SVGP_REQUIRE(step_plan(c, form, phase, nranks, rank, adam, early_issued, sc, P) == SVGP_OK, SVGP_ERR_INVALID,
+                 "no step plan for form %d (0 phase, 1 step, 2 data parallel), rank %d of %d", form, rank, nranks);
     return SVGP_OK;
 }
+
+namespace {
+int step_stage(const StepOp& op, const StepArgs& a, void* st, const SvgpSched& sc) {
+    const svgp_mnist_cfg* c = a.c;
+    switch (op.stage) {
+    case STEP_ST_ENC_KM_FWD: return svgp_mnist_encoder_kernel_matrix_fwd(c, a.theta, a.images, a.aux, a.ws, st);
+    case STEP_ST_STATS_FWD: return svgp_gp_stats_fwd(c, a.ws, st);
+    case STEP_ST_TIT_STATS: return svgp_gp_titsias_stats(c, a.ws, st);
+    case STEP_ST_FACTOR_FWD_PIECES: return svgp_gp_factor_fwd_pieces(c, a.ws, st, op.arg);
+    case STEP_ST_FACTOR_FWD_DEFER_AJI: return svgp_gp_factor_fwd_defer_aji(c, a.ws, st);
+    case STEP_ST_FACTOR_FWD_AJI_TAIL: return svgp_gp_factor_fwd_aji_tail(c, a.ws, st);
+    case STEP_ST_BIG_FACTOR_FWD: return svgp_big_factor_fwd(c, *a.wl, a.ws, st, a.l0, a.nl, op.arg);
+    case STEP_ST_POST_FWD: return svgp_gp_posterior_fwd(c, a.eps, a.ws, a.state, st);
+    case STEP_ST_POST_FWD_AJI: return svgp_gp_posterior_fwd_with_aji(c, a.eps, a.ws, a.state, st);
+    case STEP_ST_TIT_FWD: return svgp_gp_titsias_fwd(c, a.ws, a.state, st);
+    case STEP_ST_DEC_FUSED_AJI: return svgp_mnist_decoder_fwd_bwd_data_pre_aji(c, a.theta, a.images, a.ws, a.state, st);
+    case STEP_ST_DEC_FUSED: return svgp_mnist_decoder_fwd_bwd_data_pre(c, a.theta, a.images, a.ws, a.state, st);
+    case STEP_ST_DEC_FWD_PRE: return svgp_mnist_decoder_fwd_pre(c, a.theta, a.images, a.ws, st);
+    case STEP_ST_DEC_BWD_DATA_PRE_AJI: return svgp_mnist_decoder_bwd_data_pre_aji(c, a.theta, a.images, a.ws, a.state, st);
+    case STEP_ST_DEC_BWD_DATA_PRE: return svgp_mnist_decoder_bwd_data_pre(c, a.theta, a.images, a.ws, a.state, st);
+    case STEP_ST_DEC_FWD: return svgp_mnist_decoder_fwd(c, a.theta, a.images, a.ws, st);
+    case STEP_ST_DEC_BWD: return svgp_mnist_decoder_bwd(c, a.theta, a.images, a.ws, a.state, st);
+    case STEP_ST_STATS_BWD: return svgp_gp_stats_bwd(c, a.ws, a.state, st);
+    case STEP_ST_FACTOR_BWD_EARLY: return svgp_gp_factor_bwd_early(c, a.ws, a.state, st);
+    case STEP_ST_FACTOR_BWD_LATE_A: return svgp_gp_factor_bwd_late_a(c, a.ws, a.state, st);
+    case STEP_ST_FACTOR_BWD_LATE_B: return svgp_gp_factor_bwd_late_b(c, a.ws, a.state, st);
+    case STEP_ST_FACTOR_BWD_LATE_B_KBAR: return svgp_gp_factor_bwd_late_b_kbar(c, a.ws, a.state, st);
+    case STEP_ST_FACTOR_BWD_LATE_B_CHANNELS: return svgp_gp_factor_bwd_late_b_channels(c, a.ws, a.state, st);
+    case STEP_ST_FACTOR_BWD_LATE_B_FINAL: return svgp_gp_factor_bwd_late_b_final(c, a.ws, a.state, st);
+    case STEP_ST_BIG_FACTOR_BWD: return svgp_big_factor_bwd(c, *a.wl, a.ws, a.state, st, a.l0, a.nl, op.arg);
+    case STEP_ST_STATS_FACTOR_BWD_WGRAD: return svgp_gp_stats_factor_bwd_wgrad_sched(c, a.images, a.ws, a.state, st, sc);
+    case STEP_ST_FACTOR_BWD_NOFINAL_WGRAD: return svgp_gp_factor_bwd_nofinal_wgrad(c, a.images, a.ws, a.state, st);
+    case STEP_ST_FACTOR_BWD_NOFINAL: return svgp_gp_factor_bwd_nofinal(c, a.ws, a.state, st);
+    case STEP_ST_POST_BWD_ROWS: return svgp_gp_posterior_bwd_rows(c, a.ws, a.state, st);
+    case STEP_ST_POST_BWD_FINAL: return svgp_gp_posterior_bwd_with_final(c, a.ws, a.state, st);
+    case STEP_ST_POST_BWD: return svgp_gp_posterior_bwd(c, a.ws, a.state, st);
+    case STEP_ST_TIT_BWD: return svgp_gp_titsias_bwd(c, a.ws, a.state, st);
+    case STEP_ST_KM_BWD_PARTIALS: return svgp_kernel_matrix_bwd_partials(c, a.theta, a.aux, a.ws, st);
+    case STEP_ST_ENC_BWD: return svgp_mnist_encoder_bwd(c, a.theta, a.images, a.ws, st);
+    case STEP_ST_ENC_BWD_KM: return svgp_mnist_encoder_bwd_km(c, a.theta, a.images, a.aux, a.ws, st);
+    case STEP_ST_ENC_BWD_KM_SUM: return svgp_mnist_encoder_bwd_km_sum(c, a.theta, a.images, a.aux, a.ws, a.state, st);
+    case STEP_ST_GRAD_REDUCE_ALL: return svgp_mnist_grad_reduce_all(c, a.aux, a.ws, st);
+    case STEP_ST_GRAD_REDUCE_PART: return svgp_mnist_grad_reduce_part(c, a.aux, a.ws, (int)op.arg, st);
+    case STEP_ST_ADAM_FINALIZE: {
+        svgp_mnist_param_layout pl;
+        svgp_mnist_ws_layout wl;
+        int rc = svgp_mnist_param_layout_get(c, &pl);
+        if (rc) return rc;
+        rc = svgp_mnist_ws_layout_get(c, &wl);
+        if (rc) return rc;
+        SVGP_REQUIRE(a.adam_v != nullptr, SVGP_ERR_INVALID, "adam_v is NULL");
+        return svgp_adam_tf1_finalize(c, pl.n_total, a.theta, a.ws + wl.grad, a.adam_m, a.adam_v, a.ws, a.state, 0.9, 0.999, 1e-8, st);
+    }
+    case STEP_ST_FINALIZE_NOADAM: return svgp_elbo_finalize_noadam(c, a.ws, a.state, st);
+    }
+    svgp_set_error("step plan: unknown stage %d", (int)op.stage);
+    return SVGP_ERR_INVALID;
+}
+
+// sd: the Side of `stream` if the caller has looked it up already
+int step_run(const StepPlan& P, const StepArgs& a, void* stream, const SvgpSched& sc, Side* sd) {
+    SVGP_REQUIRE(a.theta && a.images && a.aux && a.ws && a.state, SVGP_ERR_INVALID, "NULL device pointer");
+    hipStream_t lane[3] = {(hipStream_t)stream, (hipStream_t)stream, (hipStream_t)stream};
+    if (P.side) {
+        if (!sd) {
+            int rc = side_get(lane[STEP_MAIN], sc, &sd);
+            if (rc) return rc;
+        }
+        lane[STEP_SIDE0] = sd->s[0]; lane[STEP_SIDE1] = sd->s[1];
+    }
+    bool group = false, forked[2] = {false, false};
+    int rc = SVGP_OK, point = -1;
+    for (int i = 0; i < P.n && rc == SVGP_OK; ++i) {
+        const StepOp& op = P.op[i];
+        const int k = op.lane == STEP_SIDE1 ? 1 : 0;
+        switch (op.kind) {
+        case STEP_STAGE: rc = step_stage(op, a, (void*)lane[op.lane], sc); break;
+        case STEP_FORK: rc = side_fork(sd, k, lane[STEP_MAIN]); forked[k] = forked[k] || rc == SVGP_OK; break;
+        case STEP_JOIN: rc = side_join(sd, k, lane[STEP_MAIN]); forked[k] = false; break;
+        case STEP_GROUP_BEGIN: rc = svgp_comm_group_begin(a.comm); group = rc == SVGP_OK; break;
+        case STEP_GROUP_END: group = false; rc = svgp_comm_group_end(a.comm); break;
+        default: rc = svgp_step_exchange(op, a, (void*)lane[op.lane], &point); break;
+        }
+    }
+    if (rc != SVGP_OK) {            // (an open group defers every later RCCL call of the thread; an unjoined branch under capture is an unjoined capture)
+        if (group) (void)svgp_comm_group_end(a.comm);
+        for (int k = 0; k < 2; ++k)
+            if (forked[k]) (void)side_join(sd, k, lane[STEP_MAIN]);
+    }
+    return rc;
+}
 }  // namespace
+
+int svgp_step_run(const StepPlan& P, const StepArgs& a, void* stream, const SvgpSched& sc) { return step_run(P, a, stream, sc, nullptr); }
 
 extern "C" int svgp_mnist_step_phase(const svgp_mnist_cfg* c, int phase, double* theta, const double* images,
                                      const double* aux, const double* eps, double* ws, double* state,
                                      double* adam_m, double* adam_v, void* stream) {
-    return step_phase_impl(c, phase, theta, images, aux, eps, ws, state, adam_m, adam_v, stream, 0, sched_read());
-}
-
-// internal (comm.hip): one phase of a step whose phases are all issued back to back on one stream
-int svgp_mnist_step_phase_deferred(const svgp_mnist_cfg* c, int phase, double* theta, const double* images,
-                                   const double* aux, const double* eps, double* ws, double* state, double* adam_m,
-                                   double* adam_v, void* stream, const SvgpSched& sc) {
-    return step_phase_impl(c, phase, theta, images, aux, eps, ws, state, adam_m, adam_v, stream, 1, sc);
+    int rc = svgp_check_cfg(c);
+    if (rc) return rc;
+    SVGP_REQUIRE(theta && images && aux && ws && state, SVGP_ERR_INVALID, "NULL device pointer");
+    const SvgpSched sc = sched_read();
+    // The late reverse half alone is valid only if phase 1 of this library issued the early half on this workspace (recorded per
+    // workspace, not inferred from the environment).
+    Side* sd = nullptr;
+    bool early_issued = false;
+    if (c->m > SVGP_M_MAX && (phase == 1 || phase == 2 || phase == 4)) {
+        rc = side_get((hipStream_t)stream, sc, &sd);
+        if (rc) return rc;
+        if (phase != 1) early_issued = side_take_early(sd, ws);
+    }
+    StepPlan P;
+    rc = svgp_step_plan_checked(c, STEP_FORM_PHASE, phase, 1, 0, adam_m != nullptr, early_issued, sc, P);
+    if (rc) return rc;
+    rc = step_run(P, StepArgs{c, theta, images, aux, eps, ws, state, adam_m, adam_v}, stream, sc, sd);
+    if (rc == SVGP_OK && phase == 1 && P.early) side_mark_early(sd, ws);       // phase 2 of THIS workspace may run the late half only
+    return rc;
 }
 
 extern "C" int svgp_mnist_train_step(const svgp_mnist_cfg* c, double* theta, const double* images,
@@ -490,10 +432,72 @@ extern "C" int svgp_mnist_train_step(const svgp_mnist_cfg* c, double* theta, con
     SVGP_REQUIRE(c && c->b == c->b_global, SVGP_ERR_INVALID,
                  "svgp_mnist_train_step is the single-GPU form (b == b_global); use svgp_mnist_step_phase "
                  "with all-reduces between phases for data parallelism");
+    int rc = svgp_check_cfg(c);
+    if (rc) return rc;
     const SvgpSched sc = sched_read();
-    for (int ph = 0; ph < 4; ++ph) {
-        int rc = step_phase_impl(c, ph, theta, images, aux, eps, ws, state, adam_m, adam_v, stream, 2, sc);
-        if (rc) return rc;
+    StepPlan P;
+    rc = svgp_step_plan_checked(c, STEP_FORM_STEP, 0, 1, 0, adam_m != nullptr, false, sc, P);
+    if (rc) return rc;
+    return svgp_step_run(P, StepArgs{c, theta, images, aux, eps, ws, state, adam_m, adam_v}, stream, sc);
+}
+
+// The plan of a call as text, one op per line (the format: include/svgpvae_hip.h): no GPU call, needs no device.
+static const char* const STEP_STAGE_NAME[STEP_ST_COUNT] = {
+#define X(id, fn) #fn,
+    SVGP_STEP_STAGES(X)
+#undef X
+};
+static const char* const STEP_BLOCK_NAME[STEP_BLK_COUNT] = {
+#define X(id) #id,
+    SVGP_STEP_BLOCKS(X)
+#undef X
+};
+static const char* step_piece_name(bool fwd, unsigned p) {
+    static const struct { bool fwd; unsigned pieces; const char* name; } T[] = {
+        {true, SVGP_FWD_K, "K"}, {true, SVGP_FWD_SIG, "SIG"}, {true, SVGP_FWD_KL, "KL"}, {true, SVGP_FWD_TAIL, "TAIL"},
+        {true, SVGP_FWD_HEAD, "HEAD"}, {true, SVGP_FWD_ALL, "ALL"},
+        {false, SVGP_BWD_EARLY, "EARLY"}, {false, SVGP_BWD_LATE_A, "LATE_A"}, {false, SVGP_BWD_CHANNELS, "CHANNELS"},
+        {false, SVGP_BWD_KBAR, "KBAR"}, {false, SVGP_BWD_FINAL, "FINAL"}, {false, SVGP_BWD_LATE, "LATE"}, {false, SVGP_BWD_ALL, "ALL"}};
+    for (const auto& t : T)
+        if (t.fwd == fwd && t.pieces == p) return t.name;
+    return "?";
+}
+extern "C" int svgp_mnist_step_route(const svgp_mnist_cfg* c, int form, int phase, int nranks, int rank, int adam, int early_issued,
+                                     char* buf, int cap) {
+    SVGP_REQUIRE(buf && cap >= 1, SVGP_ERR_INVALID, "bad argument");
+    int rc = svgp_check_cfg(c);
+    if (rc) return rc;
+    StepPlan P;
+    rc = svgp_step_plan_checked(c, form, phase, nranks, rank, adam != 0, early_issued != 0, sched_read(), P);
+    if (rc) return rc;
+    static const char* const LANE[] = {"main", "side0", "side1"};
+    static const char* const PART[] = {"all", "window", "others", "packed"};
+    static const char* const KIND[] = {"", "fork", "join", "allreduce", "point_begin", "point_end", "pack", "unpack", "group_begin",
+                                       "group_end", "reduce_scatter", "allgather"};
+    int pos = 0;
+    buf[0] = 0;
+    for (int i = 0; i < P.n; ++i) {
+        const StepOp& op = P.op[i];
+        const char* ln = LANE[op.lane];
+        const char* kd = KIND[op.kind];
+        const char* blk = op.arg < STEP_BLK_COUNT ? STEP_BLOCK_NAME[op.arg] : "?";
+        switch (op.kind) {
+        case STEP_STAGE: {
+            const bool fwd = op.stage == STEP_ST_FACTOR_FWD_PIECES || op.stage == STEP_ST_BIG_FACTOR_FWD;
+            pos += snprintf(buf + pos, cap - pos, "%s %s", ln, STEP_STAGE_NAME[op.stage]);
+            if (pos < cap && (fwd || op.stage == STEP_ST_BIG_FACTOR_BWD)) pos += snprintf(buf + pos, cap - pos, " %s", step_piece_name(fwd, op.arg));
+            else if (pos < cap && op.stage == STEP_ST_GRAD_REDUCE_PART) pos += snprintf(buf + pos, cap - pos, " %u", op.arg);
+            break;
+        }
+        case STEP_FORK: case STEP_JOIN: pos += snprintf(buf + pos, cap - pos, "%s %s", kd, ln); break;
+        case STEP_GROUP_BEGIN: case STEP_GROUP_END: pos += snprintf(buf + pos, cap - pos, "%s %s", ln, kd); break;
+        case STEP_POINT_BEGIN: case STEP_POINT_END: pos += snprintf(buf + pos, cap - pos, "%s %s %u", ln, kd, op.arg); break;
+        case STEP_PACK: case STEP_UNPACK: pos += snprintf(buf + pos, cap - pos, "%s %s %s %s", ln, kd, blk, PART[op.part]); break;
+        default:        // the collectives
+            pos += snprintf(buf + pos, cap - pos, op.part == STEP_PART_PACKED ? "%s %s %s packed" : "%s %s %s", ln, kd, blk);
+        }
+        if (pos < cap) pos += snprintf(buf + pos, cap - pos, "\n");
+        SVGP_REQUIRE(pos < cap, SVGP_ERR_INVALID, "route text needs more than %d bytes", cap);
     }
     return SVGP_OK;
 }

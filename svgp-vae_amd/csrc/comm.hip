@@ -331,29 +331,63 @@ struct Point {
         return SVGP_OK;
     }
 };
-// (measured with a 1-rank communicator at m = 256, L = 16: the pack / unpack launches cost ~100 us per step, the 44 % of 8.4 MB
-// they take off each of the four points is worth ~15 us apiece on xGMI; at m = 800, L = 64 a point is 328 MB)
-bool dp_pack_default(int m) { return m >= 512; }
 }  // namespace
-extern "C" int svgp_dp_pack_default(int m) { return dp_pack_default(m) ? 1 : 0; }
-namespace {
-// Whatever way svgp_mnist_train_step_dp returns, an RCCL group it opened is closed and a side branch it forked is joined
-// (an error inside a group left ncclGroup depth above zero -- every later RCCL call of the thread deferred --, an
-// error behind the fork an unjoined branch, which under stream capture is an unjoined capture).
-struct DpGuard {
-    void* comm; void* stream; const SvgpSched& sc;
-    bool group = false, forked = false;
-    int begin_group() { int rc = svgp_comm_group_begin(comm); group = rc == SVGP_OK; return rc; }
-    int end_group() { group = false; return svgp_comm_group_end(comm); }
-    int fork(void** side) { int rc = svgp_side_branch_fork(sc, stream, side); forked = rc == SVGP_OK; return rc; }
-    int join() { forked = false; return svgp_side_branch_join(stream); }
-    ~DpGuard() {
-        if (group) (void)svgp_comm_group_end(comm);
-        if (forked) (void)svgp_side_branch_join(stream);
-    }
-};
-}  // namespace
+extern "C" int svgp_dp_pack_default(int m) { return svgp_dp_pack_rule(m) ? 1 : 0; }
 
+// One exchange op of a step plan (step_plan.hpp) on the communicator a.comm, enqueued on `stream`.  An all-reduce is an exchange
+// point of its own; points 1..4 of the channel-sharded form are bracketed by STEP_POINT_BEGIN / _END ops.
+int svgp_step_exchange(const StepOp& op, const StepArgs& a, void* stream, int* point) {
+    Comm* cm = (Comm*)a.comm;
+    SVGP_REQUIRE(cm && a.wl, SVGP_ERR_INVALID, "step plan: an exchange op without a communicator");
+    const svgp_mnist_ws_layout& wl = *a.wl;
+    Point pt{cm, (hipStream_t)stream, *point};
+    const int G = cm->nranks, L = a.c->L, m = a.c->m;
+    const int64_t mm = (int64_t)m * m, Lm = (int64_t)L * m;
+    int rc = SVGP_OK;
+    if (op.kind == STEP_POINT_BEGIN || op.kind == STEP_POINT_END) {
+        rc = op.kind == STEP_POINT_BEGIN ? pt.begin() : pt.end();
+        *point = op.kind == STEP_POINT_BEGIN ? pt.idx : -1;
+        return rc;
+    }
+    // the blocks in the order of SVGP_STEP_BLOCKS: offset, elements (the members of points 1..4: over all channels)
+    static_assert(STEP_BLK_gradC_lo == 4 && STEP_BLK_S == 5 && STEP_BLK_KL == 15 && STEP_BLK_COUNT == 16, "the two tables below");
+    const int64_t off[STEP_BLK_COUNT] = {wl.statA, wl.statB, wl.gradC, wl.gradC + a.n_enc, wl.gradC, wl.S, wl.v, wl.Si, wl.t, wl.u,
+                                         wl.A2, wl.ud, wl.td, wl.Ssym, wl.vbar, wl.KL};
+    const int64_t len[STEP_BLK_COUNT] = {wl.statA_len, wl.statB_len, wl.gradC_len, wl.gradC_len - a.n_enc, a.n_enc, L * mm, Lm, L * mm,
+                                         Lm, Lm, L * mm, Lm, Lm, L * mm, Lm, L};
+    SVGP_REQUIRE(op.arg < STEP_BLK_COUNT && (op.arg <= STEP_BLK_gradC_lo) == (op.kind == STEP_ALLREDUCE), SVGP_ERR_INVALID,
+                 "step plan: op kind %d on block %u", (int)op.kind, op.arg);
+    double* blk = a.ws + off[op.arg];
+    if (op.kind == STEP_ALLREDUCE) {
+        if ((rc = pt.begin())) return rc;
+        if ((rc = svgp_allreduce_sum_f64(cm, blk, len[op.arg], stream))) return rc;
+        return pt.end();
+    }
+    // a symmetric (L,m,m) block on the wire: the tile-packed buffer (all channels / the rank's window) or the block itself
+    const int64_t pe = svgp_sym_packed_elems(m);
+    double* xp0 = a.ws + wl.xpack;
+    const int l0 = a.l0, nl = a.nl, hi0 = l0 + nl;
+    switch (op.kind) {
+    case STEP_REDUCE_SCATTER:
+        return op.part == STEP_PART_PACKED ? rs(cm, xp0, L * pe, G, stream) : rs(cm, blk, len[op.arg], G, stream);
+    case STEP_ALLGATHER:
+        return op.part == STEP_PART_PACKED ? ag(cm, xp0, L * pe, G, stream) : ag(cm, blk, len[op.arg], G, stream);
+    case STEP_PACK:
+        return op.part == STEP_PART_WINDOW ? svgp_sym_pack(m, nl, 0, blk + (size_t)l0 * mm, xp0 + (size_t)l0 * pe, stream)
+                                           : svgp_sym_pack(m, L, 0, blk, xp0, stream);
+    case STEP_UNPACK:
+        if (op.part == STEP_PART_WINDOW) return svgp_sym_unpack(m, nl, xp0 + (size_t)l0 * pe, blk + (size_t)l0 * mm, stream);
+        if (op.part == STEP_PART_ALL) return svgp_sym_unpack(m, L, xp0, blk, stream);
+        // the other ranks' windows (the side branch reads the rank's own window only)
+        if ((rc = svgp_sym_unpack(m, l0, xp0, blk, stream))) return rc;
+        return svgp_sym_unpack(m, L - hi0, xp0 + (size_t)hi0 * pe, blk + (size_t)hi0 * mm, stream);
+    }
+    svgp_set_error("step plan: op kind %d is no exchange", (int)op.kind);
+    return SVGP_ERR_INVALID;
+}
+
+// The schedule of every form is step_plan's (step_plan.hpp); the stages of the channel-sharded form run on a copy of the
+// configuration with rep_weight 1 (Kbar = this rank's channel-window share: every share counts).
 extern "C" int svgp_mnist_train_step_dp(const svgp_mnist_cfg* c, void* comm, double* theta, const double* images,
                                         const double* aux, const double* eps, double* ws, double* state,
                                         double* adam_m, double* adam_v, void* stream) {
@@ -362,176 +396,22 @@ extern "C" int svgp_mnist_train_step_dp(const svgp_mnist_cfg* c, void* comm, dou
     int rc = svgp_mnist_ws_layout_get(c, &wl);
     if (rc) return rc;
     Comm* cm = (Comm*)comm;
-    const int G = cm->nranks, L = c->L, m = c->m;
-    const bool sharded = m > SVGP_M_MAX && L % G == 0 && !c->titsias && !c->kl_form;
-    Point pt{cm, (hipStream_t)stream, -1};
     const SvgpSched sc = sched_read();
-    DpGuard guard{comm, stream, sc};
-    if (cm->timing) cm->npoints = 0;
-#define RUN(call) do { rc = (call); if (rc) return rc; } while (0)
-    if (!sharded && c->split_grad_exchange) {
-        // The closing all-reduce in two parts (round 6; prepared for small-message all-reduce latencies above ~20 us on 8 ranks,
-        // where three of them per 165 us step would cap weak scaling below 6x): gradC[n_enc:] -- decoder + GP parameters + scalar
-        // sums -- is complete once the kernel-matrix reverse pass and reduction part 1 are done and travels on the side branch WHILE
-        // the encoder's reverse pass runs on the caller's stream; gradC[:n_enc] follows it.  Same sums, same order on every rank.
-        svgp_mnist_param_layout pl;
-        RUN(svgp_mnist_param_layout_get(c, &pl));
-        const int64_t off2[2] = {wl.statA, wl.statB}, len2[2] = {wl.statA_len, wl.statB_len};
-        for (int ph = 0; ph < 2; ++ph) {
-            RUN(svgp_mnist_step_phase_deferred(c, ph, theta, images, aux, eps, ws, state, adam_m, adam_v, stream, sc));
-            RUN(pt.begin());
-            RUN(svgp_allreduce_sum_f64(comm, ws + off2[ph], len2[ph], stream));
-            RUN(pt.end());
-        }
-        RUN(svgp_mnist_step_phase_deferred(c, 4, theta, images, aux, eps, ws, state, adam_m, adam_v, stream, sc));
-        void* side = stream;
-        RUN(guard.fork(&side));
-        Point pts{cm, (hipStream_t)side, -1};
-        RUN(pts.begin());
-        RUN(svgp_allreduce_sum_f64(comm, ws + wl.gradC + pl.n_enc, wl.gradC_len - pl.n_enc, side));
-        RUN(pts.end());
-        RUN(svgp_mnist_step_phase_deferred(c, 5, theta, images, aux, eps, ws, state, adam_m, adam_v, stream, sc));
-        RUN(pt.begin());
-        RUN(svgp_allreduce_sum_f64(comm, ws + wl.gradC, pl.n_enc, stream));
-        RUN(pt.end());
-        RUN(guard.join());
-        RUN(svgp_mnist_step_phase_deferred(c, 3, theta, images, aux, eps, ws, state, adam_m, adam_v, stream, sc));
-        return SVGP_OK;
-    }
-    if (!sharded) {
-        const int64_t off[3] = {wl.statA, wl.statB, wl.gradC}, len[3] = {wl.statA_len, wl.statB_len, wl.gradC_len};
-        for (int ph = 0; ph < 4; ++ph) {
-            RUN(svgp_mnist_step_phase_deferred(c, ph, theta, images, aux, eps, ws, state, adam_m, adam_v, stream, sc));
-            if (ph < 3) {
-                RUN(pt.begin());
-                RUN(svgp_allreduce_sum_f64(comm, ws + off[ph], len[ph], stream));
-                RUN(pt.end());
-            }
-        }
-        return SVGP_OK;
-    }
-    SVGP_REQUIRE(theta && images && aux && ws && state, SVGP_ERR_INVALID, "NULL device pointer");
+    StepPlan P;
+    rc = svgp_step_plan_checked(c, STEP_FORM_DP, 0, cm->nranks, cm->rank, adam_m != nullptr, false, sc, P);
+    if (rc) return rc;
     svgp_mnist_cfg cc = *c;
-    cc.rep_weight = 1.0;                         // Kbar = this rank's channel-window share: every share counts
-    const int nl = L / G, l0 = cm->rank * nl;
-    const int64_t mm = (int64_t)m * m, Lmm = (int64_t)L * mm, Lm = (int64_t)L * m;
-    const bool pack = sc.dp_pack < 0 ? dp_pack_default(m) : sc.dp_pack != 0;
-    const bool fork = !sc.side_off;
-    const int64_t pe = svgp_sym_packed_elems(m);
-    SVGP_REQUIRE(!pack || wl.xpack_len >= (int64_t)L * pe, SVGP_ERR_INVALID,
+    if (P.sharded) cc.rep_weight = 1.0;
+    StepArgs a{&cc, theta, images, aux, eps, ws, state, adam_m, adam_v, comm, &wl};
+    if (c->split_grad_exchange) {
+        svgp_mnist_param_layout pl;
+        rc = svgp_mnist_param_layout_get(c, &pl);
+        if (rc) return rc;
+        a.n_enc = pl.n_enc;
+    }
+    if (P.sharded) { a.nl = c->L / cm->nranks; a.l0 = cm->rank * a.nl; }
+    SVGP_REQUIRE(!P.pack || wl.xpack_len >= (int64_t)c->L * svgp_sym_packed_elems(c->m), SVGP_ERR_INVALID,
                  "the packed exchange needs the workspace's wire buffer: lay the workspace out with cfg.single_stat_block = 1");
-    double* xp0 = ws + wl.xpack;
-    // a symmetric (L,m,m) block on the wire: the tile-packed buffer (all channels / the rank's window) or the block itself
-    auto rs_sym = [&](double* blk, double* xp) -> int {        // (inside a group)
-        return pack ? rs(comm, xp, L * pe, G, stream) : rs(comm, blk, Lmm, G, stream);
-    };
-    auto ag_sym = [&](double* blk, double* xp) -> int {
-        return pack ? ag(comm, xp, L * pe, G, stream) : ag(comm, blk, Lmm, G, stream);
-    };
-    RUN(svgp_mnist_encoder_kernel_matrix_fwd(&cc, theta, images, aux, ws, stream));
-    // the channel-independent block of the forward factor stage ((K + jI)^-1, Kn Ki, q, W, P^T -- every rank computes it, and with
-    // L / G channels per rank it is most of the stage) on the side branch from here on, beside the statistics, exchange point 1
-    // and the window's channel inverses; joined where u = Ki mu needs it (as svgp_mnist_train_step does on one GPU, api.hip)
-    const bool ksplit = fork && m < SVGP_CHOL_INVERSE_MIN_M && sc.konly_branch;
-    void* side0 = stream;
-    if (ksplit) RUN(guard.fork(&side0));
-    RUN(svgp_gp_stats_fwd(&cc, ws, stream));         // (issued first: the branch's 15 launches would hold the caller's stream back)
-    if (ksplit) RUN(svgp_big_factor_fwd(&cc, wl, ws, side0, l0, nl, SVGP_FWD_K));
-    // ---- point 1: reduce-scatter [S | v] over the channels
-    RUN(pt.begin());
-    if (pack) RUN(svgp_sym_pack(m, L, 0, ws + wl.S, xp0, stream));
-    RUN(guard.begin_group());
-    RUN(rs_sym(ws + wl.S, xp0));
-    RUN(rs(comm, ws + wl.v, Lm, G, stream));
-    RUN(guard.end_group());
-    if (pack) RUN(svgp_sym_unpack(m, nl, xp0 + (size_t)l0 * pe, ws + wl.S + (size_t)l0 * mm, stream));
-    RUN(pt.end());
-    // window factor stage without its tail
-    if (ksplit) {
-        RUN(svgp_big_factor_fwd(&cc, wl, ws, stream, l0, nl, SVGP_FWD_SIG));
-        RUN(guard.join());
-        RUN(svgp_big_factor_fwd(&cc, wl, ws, stream, l0, nl, SVGP_FWD_KL));
-    } else {
-        RUN(svgp_big_factor_fwd(&cc, wl, ws, stream, l0, nl, SVGP_FWD_HEAD));
-    }
-    // ---- point 2: all-gather [Sigma^-1 | t | u]
-    RUN(pt.begin());
-    // the window goes to the wire format first, so that the side branch below never reads a block that is being rewritten
-    // (Sigma^-1 is exactly symmetric in memory: its lower tiles ARE the matrix and the owner keeps its own window as it is)
-    if (pack) RUN(svgp_sym_pack(m, nl, 0, ws + wl.Si + (size_t)l0 * mm, xp0 + (size_t)l0 * pe, stream));
-    // the tail ((A_hat + jI)^-1, log det, KL) and the early half of the reverse factor stage: on the side branch, beside the
-    // all-gather, the row stage, the networks and the reverse statistics.  The branch is forked here (it depends on the window
-    // stage only) but its launches are ISSUED behind the collective: enqueued first, the branch's GEMMs fill every CU and the
-    // collective's kernel waits for a slot -- with a 1-rank communicator the point measured 245 us at config 3 for a no-op
-    // gather (round 3: 260 us), and the row stage on the caller's stream waits behind it.
-    void* side = stream;
-    if (fork) RUN(guard.fork(&side));
-    RUN(guard.begin_group());
-    RUN(ag_sym(ws + wl.Si, xp0));
-    RUN(ag(comm, ws + wl.t, Lm, G, stream));
-    RUN(ag(comm, ws + wl.u, Lm, G, stream));
-    RUN(guard.end_group());
-    if (pack) {                                  // the other ranks' windows (the branch reads the rank's own window only)
-        const int hi0 = l0 + nl, nhi = L - hi0;
-        RUN(svgp_sym_unpack(m, l0, xp0, ws + wl.Si, stream));
-        RUN(svgp_sym_unpack(m, nhi, xp0 + (size_t)hi0 * pe, ws + wl.Si + (size_t)hi0 * mm, stream));
-    }
-    RUN(pt.end());
-    // (the row stage is issued first: the branch's ~25 launches take the host ~100 us to enqueue, during which the caller's stream
-    // would have nothing to run; the branch has that much slack)
-    RUN(svgp_gp_posterior_fwd(&cc, eps, ws, state, stream));
-    RUN(svgp_big_factor_fwd(&cc, wl, ws, side, l0, nl, SVGP_FWD_TAIL));
-    if (fork) RUN(svgp_big_factor_bwd(&cc, wl, ws, state, side, l0, nl, SVGP_BWD_EARLY));
-    RUN(svgp_mnist_decoder_fwd(&cc, theta, images, ws, stream));
-    RUN(svgp_mnist_decoder_bwd(&cc, theta, images, ws, state, stream));
-    RUN(svgp_gp_stats_bwd(&cc, ws, state, stream));
-    // ---- point 3: reduce-scatter [A2 | ud | td]
-    RUN(pt.begin());
-    if (pack) RUN(svgp_sym_pack(m, L, 0, ws + wl.A2, xp0, stream));
-    RUN(guard.begin_group());
-    RUN(rs_sym(ws + wl.A2, xp0));
-    RUN(rs(comm, ws + wl.ud, Lm, G, stream));
-    RUN(rs(comm, ws + wl.td, Lm, G, stream));
-    RUN(guard.end_group());
-    if (pack) RUN(svgp_sym_unpack(m, nl, xp0 + (size_t)l0 * pe, ws + wl.A2 + (size_t)l0 * mm, stream));
-    RUN(pt.end());
-    if (fork) {
-        RUN(guard.join());
-        // round 6 (as svgp_mnist_train_step does on one GPU, api.hip): the single-matrix chain of the gradient of Ki -- five small launches
-        // that every rank runs in full, while the channel block covers its L / G channels only -- on the branch that has just been
-        // joined, beside the channel block.  SVGP_KBAR_BRANCH=0: one launch after the other.
-        if (sc.kbar_branch) {
-            RUN(svgp_big_factor_bwd(&cc, wl, ws, state, stream, l0, nl, SVGP_BWD_LATE_A));
-            void* side2 = stream;
-            RUN(guard.fork(&side2));
-            RUN(svgp_big_factor_bwd(&cc, wl, ws, state, side2, l0, nl, SVGP_BWD_KBAR));
-            RUN(svgp_big_factor_bwd(&cc, wl, ws, state, stream, l0, nl, SVGP_BWD_CHANNELS));
-            RUN(guard.join());
-            RUN(svgp_big_factor_bwd(&cc, wl, ws, state, stream, l0, nl, SVGP_BWD_FINAL));
-        } else
-        RUN(svgp_big_factor_bwd(&cc, wl, ws, state, stream, l0, nl, SVGP_BWD_LATE));
-    } else {
-        RUN(svgp_big_factor_bwd(&cc, wl, ws, state, stream, l0, nl, SVGP_BWD_ALL));
-    }
-    // ---- point 4: all-gather [Ssym | vbar | KL]
-    RUN(pt.begin());
-    if (pack) RUN(svgp_sym_pack(m, nl, 0, ws + wl.Ssym + (size_t)l0 * mm, xp0 + (size_t)l0 * pe, stream));
-    RUN(guard.begin_group());
-    RUN(ag_sym(ws + wl.Ssym, xp0));
-    RUN(ag(comm, ws + wl.vbar, Lm, G, stream));
-    RUN(ag(comm, ws + wl.KL, L, G, stream));
-    RUN(guard.end_group());
-    if (pack) RUN(svgp_sym_unpack(m, L, xp0, ws + wl.Ssym, stream));
-    RUN(pt.end());
-    RUN(svgp_gp_posterior_bwd(&cc, ws, state, stream));
-    RUN(svgp_kernel_matrix_bwd_partials(&cc, theta, aux, ws, stream));
-    RUN(svgp_mnist_encoder_bwd(&cc, theta, images, ws, stream));
-    RUN(svgp_mnist_grad_reduce_all(&cc, aux, ws, stream));
-    // ---- point 5: gradients + scalar sums
-    RUN(pt.begin());
-    RUN(svgp_allreduce_sum_f64(comm, ws + wl.gradC, wl.gradC_len, stream));
-    RUN(pt.end());
-    RUN(svgp_mnist_step_phase_deferred(&cc, 3, theta, images, aux, eps, ws, state, adam_m, adam_v, stream, sc));
-#undef RUN
-    return SVGP_OK;
+    if (cm->timing) cm->npoints = 0;
+    return svgp_step_run(P, a, stream, sc);
 }

@@ -8,15 +8,15 @@
 
 #include "../../include/svgpvae_hip.h"
 #include "sched.hpp"
+#include "gp_pieces.hpp"      // SVGP_M_MAX, SVGP_CHOL_INVERSE_MIN_M, the piece sets SVGP_FWD_* / SVGP_BWD_*
+#include "step_plan.hpp"
 
 typedef double real;
 
 #define SVGP_BLOCK 256
 #define SVGP_MAX_PART 256      // max workgroups that write weight-gradient partials (= CUs)
-#define SVGP_M_MAX 64          // up to here the m x m stages stay LDS-resident (gp_kernels.hip)
 #define SVGP_M_LIMIT 2048      // beyond SVGP_M_MAX: global-memory matrices + batched MFMA GEMMs (gp_large.hip)
 #define SVGP_LDS_MAX_BYTES (160 * 1024)   // dynamic LDS one workgroup may declare on gfx950
-#define SVGP_CHOL_INVERSE_MIN_M 512   // spd inverse: fused 32-block Gauss-Jordan sweep below, potrf + potri from here on
 #define SVGP_LOG_2PI 1.8378770664093453
 
 void svgp_set_error(const char* fmt, ...);
@@ -51,9 +51,19 @@ int svgp_dgemm_splitk_rows2(int ta, int tb, int M, int N, int K, double alpha, d
                             void* stream);
 // gp_kernels.hip: a piece set (SVGP_FWD_*, below) of the large-m forward factor stage on all channels, with the entry points' checks
 int svgp_gp_factor_fwd_pieces(const svgp_mnist_cfg* c, double* ws, void* stream, unsigned pieces);
-int svgp_mnist_step_phase_deferred(const svgp_mnist_cfg* c, int phase, double* theta, const double* images,
-                                   const double* aux, const double* eps, double* ws, double* state, double* adam_m,
-                                   double* adam_v, void* stream, const SvgpSched& sc);
+// The step as a plan (step_plan.hpp) and its execution.  StepArgs: what the stages of one call run on; the second line is set by
+// svgp_mnist_train_step_dp only (wl: the layout of `c`; n_enc: with cfg.split_grad_exchange; [l0, l0 + nl): the rank's channels).
+struct StepArgs {
+    const svgp_mnist_cfg* c; double* theta; const double* images; const double* aux; const double* eps; double* ws; double* state;
+    double* adam_m; double* adam_v;
+    void* comm = nullptr; const svgp_mnist_ws_layout* wl = nullptr; int64_t n_enc = 0; int l0 = 0, nl = 0;
+};
+// api.hip: step_plan with the error text; the executor (on every return an RCCL group it opened is closed, a branch it forked joined)
+int svgp_step_plan_checked(const svgp_mnist_cfg* c, int form, int phase, int nranks, int rank, bool adam, bool early_issued,
+                           const SvgpSched& sc, StepPlan& P);
+int svgp_step_run(const StepPlan& P, const StepArgs& a, void* stream, const SvgpSched& sc);
+// comm.hip: one exchange op of a plan on a.comm; *point: the timing slot of the open exchange point (-1: none)
+int svgp_step_exchange(const StepOp& op, const StepArgs& a, void* stream, int* point);
 // gp_kernels.hip: svgp_gp_stats_factor_bwd_wgrad with the caller's reading of the schedule switches
 int svgp_gp_stats_factor_bwd_wgrad_sched(const svgp_mnist_cfg* c, const double* images, double* ws, const double* state,
                                          void* stream, const SvgpSched& sc);
@@ -169,29 +179,7 @@ int svgp_dgemm_epi_batched(int f32c, int ta, int tb, int M, int N, int K, double
 // large-m implementations (gp_large.hip)
 int svgp_big_stats(const svgp_mnist_cfg* c, const svgp_mnist_ws_layout& wl, double* ws, const double* state, int mode,
                    void* stream);
-// The pieces of the two factor stages: what a caller may issue on its own (on another stream, before or after a join).  A call runs
-// the pieces of its set in the order listed here; the data dependencies between pieces of different calls are the caller's business
-// (gp_large.hip has them at the two functions).
-enum : unsigned {
-    SVGP_FWD_K = 1,         // channel-independent block: (K + jI)^-1, log det, Kn Ki, q, W, P^T -- needs the kernel matrices only
-    SVGP_FWD_SIG = 2,       // channel block up to mu: Sigma^-1, t, G, A_hat (+ A_hat + jI), mu
-    SVGP_FWD_KL = 4,        // u = Ki mu and the trace partials: needs K and SIG
-    SVGP_FWD_TAIL = 8,      // (A_hat + jI)^-1, its log det, KL_l: only the reverse factor stage and the final ELBO need it
-    SVGP_FWD_HEAD = SVGP_FWD_K | SVGP_FWD_SIG | SVGP_FWD_KL,
-    SVGP_FWD_ALL = SVGP_FWD_HEAD | SVGP_FWD_TAIL,
-};
-enum : unsigned {
-    SVGP_BWD_SW = 1,        // T = S P, SW = P^T T (only when SW is not formed over the rows by the reverse statistics)
-    SVGP_BWD_EARLY_B = 2,   // H, HG, the three channel sums: needs (A_hat + jI)^-1
-    SVGP_BWD_LATE_A = 4,    // the vector chain; + the X block when it reads nothing EARLY_B writes (SW from the rows, or no SW)
-    SVGP_BWD_CHANNELS = 8,  // the X block otherwise; Ssym; the channel sum Sgs
-    SVGP_BWD_KBAR = 16,     // the single-matrix chain of the gradient of Ki (five launches that read nothing of CHANNELS)
-    SVGP_BWD_FINAL = 32,    // the closing assembly of Kbar
-    SVGP_BWD_EARLY = SVGP_BWD_SW | SVGP_BWD_EARLY_B,
-    SVGP_BWD_LATE_B = SVGP_BWD_CHANNELS | SVGP_BWD_KBAR | SVGP_BWD_FINAL,
-    SVGP_BWD_LATE = SVGP_BWD_LATE_A | SVGP_BWD_LATE_B,
-    SVGP_BWD_ALL = SVGP_BWD_EARLY | SVGP_BWD_LATE,
-};
+// (the piece sets SVGP_FWD_* / SVGP_BWD_*: gp_pieces.hpp)
 int svgp_big_factor_fwd(const svgp_mnist_cfg* c, const svgp_mnist_ws_layout& wl, double* ws, void* stream, int l0, int nl,
                         unsigned pieces = SVGP_FWD_ALL);
 int svgp_big_posterior_fwd(const svgp_mnist_cfg* c, const svgp_mnist_ws_layout& wl, const double* eps, double* ws,

@@ -22,7 +22,7 @@ struct SvgpSched {
     // means "unset" here; unset: the large-m branches on, the m <= 64 fork off.
     bool side_off;        //   '0'
     bool side_small_m;    //   '1'
-    int dp_pack;          // SVGP_DP_PACK       channel-sharded step: tile-packed symmetric exchange 1 / 0; -1 (unset): dp_pack_default(m)
+    int dp_pack;          // SVGP_DP_PACK       channel-sharded step: tile-packed symmetric exchange 1 / 0; -1 (unset): svgp_dp_pack_default(m)
 };
 
 inline SvgpSched sched_read() {

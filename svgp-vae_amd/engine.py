@@ -635,9 +635,11 @@ class MnistStepEngine:
 
     def sharded_stages(self, adam=True):
         """The channel-sharded data-parallel step (svgp_mnist_train_step_dp, m > 64) stage by stage: a generator that
-        enqueues the stages between two exchange points and yields the list of ExchangeOp of that point.  The C entry
-        point issues exactly this sequence with the RCCL collectives in between; this form exists so that the schedule
-        can be executed with virtual ranks on one GPU (tests/test_gpu_dp_virtual.py)."""
+        enqueues the stages between two exchange points and yields the list of ExchangeOp of that point.  This is the
+        virtual-rank form of the sharded route WITHOUT the K-only and Ki-gradient branches: the same stages on the same
+        data, so the same bits, but not the launch order of the C entry point (that one is csrc/step_plan.hpp, printed by
+        svgp_mnist_step_route and pinned in tests/test_step_route_cpu.py).  It exists so that the schedule can be executed
+        with virtual ranks on one GPU (tests/test_gpu_dp_virtual.py)."""
         assert self.base["m"] > 64 and self.base["L"] % self.world_size == 0
         images, aux, eps = self._bound
         cfg = self._make_cfg(self.cfg.b, self.cfg.b_global)
