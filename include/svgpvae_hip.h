@@ -189,7 +189,7 @@ const char* svgp_last_error(void);
 /* sizeof() of the ABI structs as compiled into the library, so a binding can verify its own mirror of a struct at load
  * time (a stale mirror shifts every later field silently): which = 0 svgp_mnist_cfg, 1 svgp_mnist_param_layout,
  * 2 svgp_mnist_ws_layout, 3 svgp_stream_kdesc, 4 svgp_conv_desc, 5 svgp_sprites_kcfg, 6 svgp_pearce_bufs,
- * 7 svgp_sum_job, 8 svgp_casale_cfg, 9 svgp_casale_layout; -1 otherwise. */
+ * 7 svgp_sum_job, 8 svgp_casale_cfg, 9 svgp_casale_layout, 10 svgp_ball_large_cfg; -1 otherwise. */
 int         svgp_struct_sizeof(int which);
 
 int svgp_mnist_param_layout_get(const svgp_mnist_cfg* cfg, svgp_mnist_param_layout* out);
@@ -821,6 +821,45 @@ int svgp_pearce_long_fwd(const svgp_pearce_bufs*, const double* eps_x, const dou
                          double* work, void* stream);
 int svgp_pearce_long_bwd(const svgp_pearce_bufs*, double seed_lh_scale, int accumulate, int want_dls, const double* state,
                          double* d_ls_x, double* d_ls_y, double* work, void* stream);
+
+/* ---- moving-ball SVGP-VAE with more than 64 inducing points or more than 64 videos (ball_large.hip, gp_large.hip) ----------
+ * BALL_experiment.py --elbo SVGPVAE_Hensman | SVGPVAE_Titsias beyond what the shared stage entry points accept with kl_form = 1
+ * (m <= 64, at most 64 channels: those refusals stand).  Same mapping as above -- rows = the T frames, channels = the B videos,
+ * N_train = T, one workspace per latent coordinate -- on the global-memory stages: (B, m, m) blocks, every m^3 contraction on
+ * the float64 MFMA GEMM, blocked inverses.  ALL B videos are channels of one workspace (no chunks), so the batch-wide scalar of
+ * the reference's KL (:135-137), the 1/B of the loss seed and the Philox counters (t B + b of coordinate c, state[SVGP_ST_RNG_CTR]
+ * advanced by one between the coordinates) are those of the whole batch, and the results equal those of the m <= 64 path up to
+ * rounding where both accept a shape.  The entry points take 1 <= m <= 2048 -- m <= 64 included, ON THE LARGE-M KERNELS: there is
+ * no hand-over to the LDS stages inside the library; ball.sparse_engine_class picks the engine --, 1 <= B <=
+ * SVGP_BALL_LARGE_MAX_VIDEOS, 1 <= T <= 16384, kl_form = 1, clip_pv = 2.  The struct carries no rank fields: the moving-ball KL
+ * couples all videos of the batch, which is never sharded over ranks.
+ *   svgp_ball_large_ws_layout_get: the workspace layout (svgp_mnist_ws_layout; the fields of the MNIST networks are empty, M2 /
+ *     Qm absent as in every large-m workspace).  The caller writes ws.qnet_mu / qnet_var_raw / qnet_var (svgp_ball_head_fwd) and
+ *     ws.zbar (svgp_ball_unpack_zbar) and reads ws.z, p_m, p_v, Si, ybar, s2bar.
+ *   svgp_ball_large_workspace_elems: doubles of one workspace; 0 for a configuration the entry points refuse.
+ *   svgp_ball_large_gp_fwd: one coordinate forward -- kernel matrices of (times, ip, *ls) -> statistics -> (Titsias statistics)
+ *     -> factor stage incl. KL_l = 1/2 (log det terms - m + tr(Ki A_l) + B tr(Ki A_l A_l)) and tr(Ki A_l A_l) behind it in ws.KL
+ *     -> row stage (eps (T, B), or NULL: Philox) -> (Titsias terms).
+ *   svgp_ball_large_gp_bwd: the reverse of that call on the same workspace, from ws.zbar and the loss seeds in `state` down to
+ *     ws.ybar, ws.s2bar, d_ip (m), d_ls (1).
+ *   svgp_ball_large_elbo_assemble: svgp_ball_elbo_assemble on two such workspaces, out (7, B).
+ * Explicit stream, no allocation, no host synchronisation, no float atomics (a repeated step is bitwise identical).  Refused with
+ * a message before any launch: NULL cfg / pointers, m > 2048, B > SVGP_BALL_LARGE_MAX_VIDEOS (SVGP_ERR_UNSUPPORTED), kl_form != 1,
+ * clip_pv != 2, non-positive sizes.                                                                                        */
+#define SVGP_BALL_LARGE_MAX_VIDEOS 256
+typedef struct {
+    int32_t T, B, m;                  /* frames per video, videos per batch, inducing points */
+    int32_t titsias, kl_form, clip_pv;
+    double jitter;
+} svgp_ball_large_cfg;
+int svgp_ball_large_ws_layout_get(const svgp_ball_large_cfg* cfg, svgp_mnist_ws_layout* out);
+long long svgp_ball_large_workspace_elems(const svgp_ball_large_cfg* cfg);
+int svgp_ball_large_gp_fwd(const svgp_ball_large_cfg* cfg, const double* times, const double* ip, const double* ls,
+                           const double* eps, double* ws, double* state, void* stream);
+int svgp_ball_large_gp_bwd(const svgp_ball_large_cfg* cfg, const double* times, const double* ip, const double* ls, double* ws,
+                           const double* state, double* d_ip, double* d_ls, void* stream);
+int svgp_ball_large_elbo_assemble(const svgp_ball_large_cfg* cfg, const double* ws_x, const double* ws_y,
+                                  const double* row_recon, const double* state, double* out, void* stream);
 
 /* ---- deep SVIGP_Hensman baseline on rotated MNIST (svigp.hip): MNIST_experiment.py --elbo SVIGP_Hensman -------------
  * SVIGP_Hensman.variational_loss / approximate_posterior_params (SVIGP_Hensman_model.py:135-227) and the ELBO assembly

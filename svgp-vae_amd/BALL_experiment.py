@@ -92,7 +92,7 @@ def build_engine(args, batch=35, px=32, py=32):
     mk = lambda name: ball.SVGP(titsias=titsias, num_inducing_points=args.m, fixed_inducing_points=not args.ip_joint,
                                 tmin=1, tmax=tmax, vidlt=args.vidlt, fixed_gp_params=not args.GP_joint, name=name,
                                 jitter=args.jitter, ip_min=args.ip_min, ip_max=args.ip_max, GP_init=args.GP_init)
-    return ball.BallStepEngine(mk('x'), mk('y'), clip_qs=args.clip_qs, **common)
+    return ball.sparse_engine_class(args.m, batch)(mk('x'), mk('y'), clip_qs=args.clip_qs, **common)
 
 
 def evaluate(eng, TT, TD, beta0):
@@ -102,7 +102,7 @@ def evaluate(eng, TT, TD, beta0):
     eng.step(vid, None, adam=False, backward=False)
     out = eng.outputs()
     sc = eng.scalars()
-    svgp = isinstance(eng, ball.BallStepEngine)
+    svgp = isinstance(eng, ball.SPARSE_ENGINES)
     p_m, p_v, q_m, q_v = (out[5], out[6], out[7], out[8]) if svgp else (out[3], out[4], out[5], out[6])
     p_m, p_v, q_m, q_v = [t.cpu().numpy() for t in (p_m, p_v, q_m, q_v)]
     _, _, MSE, _ = ball.MSE_rotation(p_m, np.asarray(TT), p_v)

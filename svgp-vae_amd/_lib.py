@@ -74,6 +74,14 @@ class PearceBufs(C.Structure):
                                           "dl_part")]
 
 
+class BallLargeCfg(C.Structure):
+    """svgp_ball_large_cfg (include/svgpvae_hip.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("T", "B", "m", "titsias", "kl_form", "clip_pv")] + [("jitter", C.c_double)]
+
+
+BALL_LARGE_MAX_VIDEOS = 256           # SVGP_BALL_LARGE_MAX_VIDEOS
+
+
 class CasaleCfg(C.Structure):
     """svgp_casale_cfg (include/svgpvae_hip.h)."""
     _fields_ = [(n, C.c_int32) for n in ("N", "n_obj", "Q", "M", "L", "b_cap", "normalize_obj", "train_gp", "train_ov")]
@@ -260,6 +268,10 @@ SIGNATURES = {
     "svgp_scale_rows": [C.c_longlong, C.c_int, _P, _P, _P],
     "svgp_pearce_long_fwd": [C.POINTER(PearceBufs), _P, _P, _P, _P, _P],
     "svgp_pearce_long_bwd": [C.POINTER(PearceBufs), C.c_double, C.c_int, C.c_int, _P, _P, _P, _P, _P],
+    "svgp_ball_large_ws_layout_get": [C.POINTER(BallLargeCfg), C.POINTER(WsLayout)],
+    "svgp_ball_large_gp_fwd": [C.POINTER(BallLargeCfg), _P, _P, _P, _P, _P, _P, _P],
+    "svgp_ball_large_gp_bwd": [C.POINTER(BallLargeCfg), _P, _P, _P, _P, _P, _P, _P, _P],
+    "svgp_ball_large_elbo_assemble": [C.POINTER(BallLargeCfg), _P, _P, _P, _P, _P, _P],
     "svgp_svigp_fwd": [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double] + [_P] * 9,
     "svgp_svigp_bwd": [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _P, _P, _P, _P, _P, _P, C.c_int] + [_P] * 8,
     "svgp_svigp_assemble": [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _P, _P, C.c_int, _P, _P, _P],
@@ -312,6 +324,7 @@ NON_STATUS = {"svgp_version": ([], C.c_int), "svgp_last_error": ([], C.c_char_p)
               "svgp_dgemm_splitk_scratch_elems": ([C.c_int, C.c_int, C.c_int], C.c_longlong),
               "svgp_sprites_kernel_bwd_scratch_elems": ([C.POINTER(SpritesKcfg)], C.c_longlong),
               "svgp_pearce_long_workspace_elems": ([C.c_int, C.c_int, C.c_int, C.c_int], C.c_size_t),
+              "svgp_ball_large_workspace_elems": ([C.POINTER(BallLargeCfg)], C.c_longlong),
               "svgp_svigp_workspace_elems": ([C.c_int, C.c_int, C.c_int], C.c_longlong),
               "svgp_svigp_scale_offset": ([C.c_int, C.c_int, C.c_int], C.c_longlong)}
 
@@ -342,7 +355,7 @@ def load_library(path=None):
         fn.restype = restype
     # the ctypes mirrors must have the layout the library was compiled with (svgp_struct_sizeof)
     for which, cls in enumerate((MnistCfg, ParamLayout, WsLayout, StreamKdesc, ConvDesc, SpritesKcfg, PearceBufs, SumJob,
-                                 CasaleCfg, CasaleLayout)):
+                                 CasaleCfg, CasaleLayout, BallLargeCfg)):
         if lib.svgp_struct_sizeof(which) != C.sizeof(cls):
             raise SvgpError(f"{p}: sizeof({cls.__name__}) is {lib.svgp_struct_sizeof(which)} in the library but "
                             f"{C.sizeof(cls)} in the binding; rebuild the library or update _lib.py")

@@ -8,7 +8,8 @@ Reference call surface mirrored here (eager float64 CUDA tensors instead of TF g
   Make_path_batch / Make_Video_batch / build_video_batch_graph / MSE_rotation     utils.py:29-121,138-192,195-245
 and `BallStepEngine.train_step` = the reference's `sess.run(optim_step)` (BALL_experiment.py:116-136, 213-217).
 
-The two SVGP objects of the SVGPVAE ELBOs run on the shared sparse-GP stage kernels: the tmax frames of a video
+Up to 64 inducing points and 64 videos per batch (BallStepEngine; beyond: BallLargeStepEngine, on the global-memory stages,
+picked by sparse_engine_class) the two SVGP objects of the SVGPVAE ELBOs run on the shared sparse-GP stage kernels: the tmax frames of a video
 are the rows, the videos of the batch are the channels (every video has the time stamps 1..tmax, so K_mm / K_nm
 are shared), N_train = tmax, cfg.kl_form = 1 (the reference's ball KL, SVGPVAE_model.py:135-137), cfg.clip_pv = 2
 (:693); one workspace per latent coordinate.  The MLPs are batched MFMA GEMMs + bias/tanh kernels, the Bernoulli
@@ -429,6 +430,119 @@ class BallStepEngine(_BallMlpEngine):
                 o["inside_elbo_kl"], p["ip_x"].clone(), p["ip_y"].clone(), cov[0], cov[1], self)
 
 
+class BallLargeStepEngine(_BallMlpEngine):
+    """The same step -- constructor arguments, step() and the outputs() tuple of BallStepEngine -- beyond the LDS-resident GP
+    stages: 1 <= m <= 2048 inducing points, up to _lib.BALL_LARGE_MAX_VIDEOS videos per batch (csrc/ball_large.hip: the large-m
+    stages of gp_large.hip with the moving-ball KL form, all videos channels of one workspace per latent coordinate).  One
+    library call per coordinate forward and one reverse instead of a chain of stage calls.  Everything is sized here, once; a
+    configuration whose (batch, m, m) blocks do not fit the device is refused here with the figures."""
+
+    def __init__(self, svgp_x, svgp_y, *, batch=35, tmax=30, px=32, py=32, hidden=500, clip_qs=False, beta=1.0,
+                 lr=1e-3, clip_grad=False, device="cuda:0", params=None, seed=0):
+        if svgp_x.titsias != svgp_y.titsias or svgp_x.num_inducing_points != svgp_y.num_inducing_points:
+            raise ValueError("svgp_x and svgp_y must agree on the ELBO branch and on the number of inducing points")
+        if svgp_x.jitter != svgp_y.jitter:
+            raise ValueError("svgp_x and svgp_y must use the same jitter")
+        self.m, self.titsias = svgp_x.num_inducing_points, svgp_x.titsias
+        self.svgp = (svgp_x, svgp_y)
+        self.clip_qs = bool(clip_qs)
+        self.cfg = _lib.BallLargeCfg(T=tmax, B=batch, m=self.m, titsias=int(self.titsias), kl_form=1, clip_pv=2,
+                                     jitter=svgp_x.jitter)
+        _lib.load_library()
+        self.wl = WsLayout()
+        call("svgp_ball_large_ws_layout_get", C.byref(self.cfg), C.byref(self.wl))     # validates before any allocation
+        if not torch.cuda.is_available():
+            raise _lib.SvgpError(f"{type(self).__name__} needs a HIP device; there is no CPU execution path")
+        # the two workspaces + what one step allocates on top (encoder / decoder activations and their gradients)
+        B, T, m, dev = batch, tmax, self.m, torch.device(device)
+        step = B * T * (4 * px * py + 4 * hidden + 16)
+        need, (free, _) = 8 * (2 * self.wl.total + step), torch.cuda.mem_get_info(dev)
+        if need > free:
+            raise _lib.SvgpError(f"batch={B} tmax={T} m={m}: the sparse GP step needs {need / 2 ** 30:.1f} GiB "
+                                 f"(2 workspaces of {8 * self.wl.total / 2 ** 30:.1f} GiB, about 16 (batch, m, m) blocks of "
+                                 f"{8 * B * m * m / 2 ** 30:.2f} GiB each), {free / 2 ** 30:.1f} GiB are free on {dev}")
+        init = dict(params or {})
+        for c, sv in zip("xy", self.svgp):
+            init.setdefault(f"ip_{c}", sv.inducing_index_points)
+            init.setdefault(f"l_{c}", sv.l_GP)
+        self._init_common(dict(ip_x=(m,), l_x=(1,), ip_y=(m,), l_y=(1,)), init, batch=batch, tmax=tmax, px=px,
+                          py=py, hidden=hidden, beta=beta, lr=lr, clip_grad=clip_grad, device=device, seed=seed)
+        for c, sv in zip("xy", self.svgp):
+            sv.inducing_index_points, sv.l_GP = self.params[f"ip_{c}"], self.params[f"l_{c}"]
+        f64 = dict(dtype=_F64, device=self.dev)
+        self.ws = [torch.zeros(self.wl.total, **f64) for _ in range(2)]
+        self.times = torch.arange(1, tmax + 1, **f64)                   # SVGPVAE_model.py:663
+        self.stream.wait_stream(torch.cuda.current_stream(self.dev))
+        self.stream.synchronize()
+
+    _v = BallStepEngine._v
+    outputs = BallStepEngine.outputs
+
+    def step(self, vid_batch, epsilon=None, adam=True, backward=True):
+        """As BallStepEngine.step."""
+        B, T, P = self.B, self.T, self.P
+        assert tuple(vid_batch.shape) == (B, T, self.px, self.py)
+        p, g, s = self.params, self.grads, self.stream.cuda_stream
+        cp, st = C.byref(self.cfg), self.state.data_ptr()
+        f64 = dict(dtype=_F64, device=self.dev)
+        R = B * T
+        self.stream.wait_stream(torch.cuda.current_stream(self.dev))
+        with torch.cuda.stream(self.stream):
+            X = vid_batch.to(self.dev, _F64).contiguous().view(R, P)
+            h1, h2 = self._encode(X)
+            fld = lambda n: [self._v(c, n, (T, B)) for c in range(2)]
+            mu, var_raw, var = fld("qnet_mu"), fld("qnet_var_raw"), fld("qnet_var")
+            call("svgp_ball_head_fwd", B, T, int(self.clip_qs), p["encB2"].data_ptr(), h2.data_ptr(), mu[0].data_ptr(),
+                 var_raw[0].data_ptr(), var[0].data_ptr(), mu[1].data_ptr(), var_raw[1].data_ptr(), var[1].data_ptr(), s)
+            eps_c = [None, None]
+            if epsilon is not None:
+                e = epsilon.to(self.dev, _F64)
+                eps_c = [e[:, :, c].t().contiguous() for c in range(2)]
+            for c, cn in enumerate("xy"):
+                call("svgp_ball_large_gp_fwd", cp, self.times.data_ptr(), p[f"ip_{cn}"].data_ptr(), p[f"l_{cn}"].data_ptr(),
+                     None if eps_c[c] is None else eps_c[c].data_ptr(), self.ws[c].data_ptr(), st, s)
+                if c == 0:
+                    call("svgp_state_add", st, STATE["RNG_CTR"], 1.0, s)      # fresh samples for the y coordinate
+            z = torch.empty(R, 2, **f64)
+            call("svgp_ball_pack_z", B, T, self._v(0, "z", (1,)).data_ptr(), self._v(1, "z", (1,)).data_ptr(),
+                 z.data_ptr(), s)
+            g1, pred, row_recon, dlog = self._decode_recon(z, X, backward)
+            self.act = dict(pred=pred.view(B, T, self.px, self.py), z=z.view(B, T, 2))
+            if backward:
+                dz = self._decoder_backward(z, g1, dlog)
+                call("svgp_ball_unpack_zbar", B, T, dz.data_ptr(), self._v(0, "zbar", (1,)).data_ptr(),
+                     self._v(1, "zbar", (1,)).data_ptr(), s)
+                for c, cn in enumerate("xy"):
+                    call("svgp_ball_large_gp_bwd", cp, self.times.data_ptr(), p[f"ip_{cn}"].data_ptr(),
+                         p[f"l_{cn}"].data_ptr(), self.ws[c].data_ptr(), st, g[f"ip_{cn}"].data_ptr(),
+                         g[f"l_{cn}"].data_ptr(), s)
+                    if self.svgp[c].fixed_inducing_points:
+                        g[f"ip_{cn}"].zero_()
+                    if self.svgp[c].fixed_gp_params:
+                        g[f"l_{cn}"].zero_()
+                dh2 = torch.empty(R, 4, **f64)
+                yb, sb = fld("ybar"), fld("s2bar")
+                call("svgp_ball_head_bwd", B, T, int(self.clip_qs), var_raw[0].data_ptr(), yb[0].data_ptr(),
+                     sb[0].data_ptr(), var_raw[1].data_ptr(), yb[1].data_ptr(), sb[1].data_ptr(), dh2.data_ptr(), s)
+                self._encoder_backward(X, h1, dh2)
+                self._clip_and_adam(adam)
+            call("svgp_ball_large_elbo_assemble", cp, self.ws[0].data_ptr(), self.ws[1].data_ptr(), row_recon.data_ptr(),
+                 st, self.out.data_ptr(), s)
+            call("svgp_ball_finalize", B, int(bool(adam and backward)), 1, self.out.data_ptr(), st, s)
+        return self
+
+    train_step = step
+
+
+def sparse_engine_class(m, batch):
+    """The LDS-resident engine while both the inducing points and the videos of a batch fit its stages (m <= 64, batch <= 64),
+    the global-memory one above."""
+    return BallStepEngine if m <= 64 and batch <= 64 else BallLargeStepEngine
+
+
+SPARSE_ENGINES = (BallStepEngine, BallLargeStepEngine)
+
+
 class _PearceEngineBase(_BallMlpEngine):
     """BALL_experiment.py --elbo GPVAE_Pearce | VAE | NP: exact per-video GP regression on the recognition network's
     outputs (build_pearce_elbo_graphs, GPVAE_Pearce_model.py:89-236).  The step is shared; a subclass says how long a
@@ -650,8 +764,8 @@ def build_SVGPVAE_elbo_graph(vid_batch, beta, svgp_x, svgp_y, clipping_qs=False,
     eng = engine or getattr(svgp_x, "_engine", None)
     if eng is None or (eng.B, eng.T, eng.px, eng.py) != (B, T, px, py) or eng.clip_qs != bool(clipping_qs):
         hidden = 500 if params is None else int(np.asarray(params["encB1"]).size)
-        eng = BallStepEngine(svgp_x, svgp_y, batch=B, tmax=T, px=px, py=py, hidden=hidden, clip_qs=clipping_qs,
-                             beta=float(beta), params=params)
+        eng = sparse_engine_class(svgp_x.num_inducing_points, B)(svgp_x, svgp_y, batch=B, tmax=T, px=px, py=py, hidden=hidden,
+                                                                 clip_qs=clipping_qs, beta=float(beta), params=params)
         svgp_x._engine = eng
     eng.set_scalars(beta=float(beta))
     eng.step(vid_batch, epsilon, adam=False, backward=False)

@@ -7,6 +7,7 @@
 #include <set>
 #include <utility>
 #include <cstdlib>
+#include <algorithm>
 
 static thread_local char g_err[512] = "";
 
@@ -31,6 +32,7 @@ extern "C" int svgp_struct_sizeof(int which) {
     case 7: return (int)sizeof(svgp_sum_job);
     case 8: return (int)sizeof(svgp_casale_cfg);
     case 9: return (int)sizeof(svgp_casale_layout);
+    case 10: return (int)sizeof(svgp_ball_large_cfg);
     default: return -1;
     }
 }
@@ -59,10 +61,10 @@ int svgp_check_cfg(const svgp_mnist_cfg* c) {
     return SVGP_OK;
 }
 
-extern "C" int svgp_mnist_param_layout_get(const svgp_mnist_cfg* c, svgp_mnist_param_layout* o) {
-    int rc = svgp_check_cfg(c);
-    if (rc) return rc;
-    SVGP_REQUIRE(o != nullptr, SVGP_ERR_INVALID, "out is NULL");
+// The two layouts as functions of a configuration that has ALREADY been validated by its entry point: svgp_check_cfg for the
+// svgp_mnist_* queries below, the checks of csrc/ball_large.hip for the moving-ball large engine (which lifts the 64-channel and
+// the kl_form = 1 / m <= 64 refusals of svgp_check_cfg for its own entry points only).
+static void param_layout_fill(const svgp_mnist_cfg* c, svgp_mnist_param_layout* o) {
     int64_t p = 0;
     auto take = [&](int64_t n) { int64_t r = p; p += n; return r; };
     o->enc_c1_w = take(3 * 3 * 1 * 8);  o->enc_c1_b = take(8);
@@ -80,26 +82,43 @@ extern "C" int svgp_mnist_param_layout_get(const svgp_mnist_cfg* c, svgp_mnist_p
     o->amplitude = take(1);
     o->ov = take((int64_t)c->n_obj * c->M);
     o->n_total = p;
+}
+
+extern "C" int svgp_mnist_param_layout_get(const svgp_mnist_cfg* c, svgp_mnist_param_layout* o) {
+    int rc = svgp_check_cfg(c);
+    if (rc) return rc;
+    SVGP_REQUIRE(o != nullptr, SVGP_ERR_INVALID, "out is NULL");
+    param_layout_fill(c, o);
     return SVGP_OK;
 }
 
 extern "C" int svgp_mnist_ws_layout_get(const svgp_mnist_cfg* c, svgp_mnist_ws_layout* o) {
-    svgp_mnist_param_layout pl;
-    int rc = svgp_mnist_param_layout_get(c, &pl);
+    int rc = svgp_check_cfg(c);
     if (rc) return rc;
     SVGP_REQUIRE(o != nullptr, SVGP_ERR_INVALID, "out is NULL");
     SVGP_REQUIRE(c->b_cap == 0 || c->b_cap >= c->b, SVGP_ERR_INVALID, "b_cap=%d < b=%d", c->b_cap, c->b);
+    return svgp_ws_layout_fill(c, o, false);
+}
+
+// ball_large: the workspace of one latent coordinate of the moving-ball large engine (csrc/ball_large.hip) -- the fields of the
+// large-m GP stages at EVERY m (also m <= SVGP_M_MAX, which that engine runs on the large-m kernels), none of the MNIST
+// networks' fields, and scratch floors for small m where the large-m stages otherwise rely on m > SVGP_M_MAX.
+int svgp_ws_layout_fill(const svgp_mnist_cfg* c, svgp_mnist_ws_layout* o, bool ball_large) {
+    svgp_mnist_param_layout pl;
+    param_layout_fill(c, &pl);
+    const bool big = ball_large || c->m > SVGP_M_MAX;
     svgp_mnist_cfg cc = *c;              // layout is a function of the capacity, not of the current rows
     cc.b = c->b_cap > 0 ? c->b_cap : c->b;
     const int64_t b = cc.b, m = c->m, L = c->L, M = c->M;
     int64_t p = 0;
     // every field starts on a 16-element (128-byte) boundary
     auto take = [&](int64_t n) { int64_t r = p; p += (n + 15) / 16 * 16; return r; };
-    o->enc_a1 = take(b * 13 * 13 * 8); o->enc_a2 = take(b * 6 * 6 * 8); o->enc_a3 = take(b * 32);
+    auto vae = [&](int64_t n) { return take(ball_large ? 0 : n); };      // fields of the MNIST networks
+    o->enc_a1 = vae(b * 13 * 13 * 8); o->enc_a2 = vae(b * 6 * 6 * 8); o->enc_a3 = vae(b * 32);
     o->qnet_mu = take(b * L); o->qnet_var_raw = take(b * L); o->qnet_var = take(b * L);
     // m > 64: the rows W = Kn Ki K (gp_large.hip, "W form") sit right behind the CURRENT b rows of K_nm, so that [Kn; W] is
     // one (2 b, m) operand of the row-stage product and of the reverse statistic
-    o->K = take(m * m); o->Kn = take(m > SVGP_M_MAX ? 2 * b * m : b * m); o->knn = take(b);
+    o->K = take(m * m); o->Kn = take(big ? 2 * b * m : b * m); o->knn = take(b);
     const int64_t P = svgp_stat_parts(c);      // capacity from b_cap
     o->stat_parts = P;
     o->statA = p; o->S = p; p += P * L * m * m; o->v = p; p += P * L * m;
@@ -113,39 +132,39 @@ extern "C" int svgp_mnist_ws_layout_get(const svgp_mnist_cfg* c, svgp_mnist_ws_l
     o->Ki = (L * m * m) % 16 == 0 ? o->Si + L * m * m : take(m * m);
     o->t = take(L * m); o->G = take(L * m * m); o->A = take(L * m * m);
     // (M2 = Ki A Ki and Qm exist on the LDS-resident path only: the large-m path evaluates k^T M2 k as w^T Si w)
-    o->Aji = take(L * m * m); o->mu_hat = take(L * m); o->u = take(L * m); o->M2 = take(m > SVGP_M_MAX ? 0 : L * m * m);
+    o->Aji = take(L * m * m); o->mu_hat = take(L * m); o->u = take(L * m); o->M2 = take(big ? 0 : L * m * m);
     o->KL = take(2 * L); o->q = take(b);   // [KL | kl_form 1: tr(Ki A_l A_l)]
     o->p_m = take(b * L); o->p_v = take(b * L); o->e = take(b * L); o->d = take(b * L);
     o->eps = take(b * L); o->z = take(b * L);
-    o->dec_h0 = take(b * 128); o->dec_a1 = take(b * 512); o->dec_a2 = take(b * 1568); o->recon = take(b * 784);
-    o->dec_d2 = take(b * 1568); o->dec_d1 = take(b * 512); o->dec_dh0 = take(b * 128); o->dec_weff = take(2176);
+    o->dec_h0 = vae(b * 128); o->dec_a1 = vae(b * 512); o->dec_a2 = vae(b * 1568); o->recon = vae(b * 784);
+    o->dec_d2 = vae(b * 1568); o->dec_d1 = vae(b * 512); o->dec_dh0 = vae(b * 128); o->dec_weff = vae(2176);
     o->flags = take(64);
     o->zbar = take(b * L); o->g_pv = take(b * L); o->g_pm = take(b * L); o->mvbar = take(b * L);
     o->statB = p; o->A2 = p; p += P * L * m * m; o->ud = p; p += P * L * m; o->td = p; p += P * L * m;
     o->statB_len = p - o->statB; take(0);
-    o->Kbar = take(m * m); o->fb_part = take(2 * L * m * m); o->Qm = take(m > SVGP_M_MAX ? 0 : L * m * m); o->vbar = take(L * m);
-    o->Ssym = take(L * m * m); o->Knbar_part = take(L * b * m);
+    o->Kbar = take(m * m); o->fb_part = take(ball_large ? svgp_ball_large_fb_part_elems(m, L) : 2 * L * m * m); o->Qm = take(big ? 0 : L * m * m); o->vbar = take(L * m);
+    o->Ssym = take(L * m * m); o->Knbar_part = take(ball_large ? std::max(L * b * m, b * m + 2 * b * L) : L * b * m);
     // scratch of the large-m path (gp_large.hip)
     // m > 64: (L,b,m) scratch + the forward products [Kn; W] Si_l (L,2b,m), Kn Ki (b,m) kept for the reverse pass + X (b,2m)
-    o->scr_bm = take(m > SVGP_M_MAX ? 3 * L * b * m + 3 * b * m : L * b * m); o->scr_mm = take(4 * L * m * m);
+    o->scr_bm = take(big ? 3 * L * b * m + 3 * b * m : L * b * m); o->scr_mm = take(4 * L * m * m);
     o->scr_vec = take(3 * L * m + 3 * L + 16 + b);
     o->scr_inv = take((int64_t)svgp_spd_inverse_workspace_elems((int)m, (int)L + 1)); o->scr_bl = take(2 * b * L);
     // m > 64: ten channel-independent m x m matrices + the split-K scratch of the (2 m, m, b) row contraction of the W form (K Ki, Kn^T Wbar, Kn^T diag(qbar) Kn, channel sums, temporaries)
-    o->scr_sm = take(m > SVGP_M_MAX ? 10 * m * m + svgp_dgemm_splitk_scratch_elems((int)(2 * m), (int)m, (int)b) : 0);
+    o->scr_sm = take(big ? 10 * m * m + svgp_dgemm_splitk_scratch_elems((int)(2 * m), (int)m, (int)b) : 0);
     o->Knbar = take(b * m); o->knnbar = take(b); o->ybar = take(b * L); o->s2bar = take(b * L);
     o->d_on = take(b * M);
     o->n_part = svgp_n_part(&cc);
-    o->part_dec = take(o->n_part * (pl.n_vae - pl.n_enc));
-    o->part_enc = take(o->n_part * pl.n_enc);
+    o->part_dec = vae(o->n_part * (pl.n_vae - pl.n_enc));
+    o->part_enc = vae(o->n_part * pl.n_enc);
     o->part_gp = take((m + svgp_n_postblk(&cc)) * 2);
     o->n_post = (int64_t)L * svgp_n_postblk(&cc);
     o->part_sums = take(o->n_part * 4 + o->n_post * 2);
-    o->gradC = p; o->grad = p; p += pl.n_total; o->sums = p; p += 8; o->gradC_len = p - o->gradC; take(0);
+    o->gradC = p; o->grad = p; p += ball_large ? 0 : pl.n_total; o->sums = p; p += 8; o->gradC_len = p - o->gradC; take(0);
     o->tit_Si = take(c->titsias ? L * m * m : 0); o->tit_t = take(c->titsias ? L * m : 0);
     o->tit_scal = take(c->titsias ? 2 * L + 1 : 0);
     // the wire buffer of the channel-sharded exchange: one tile-packed (L, m, m) block; only when the batch is sharded over
     // ranks (cfg.single_stat_block, set by the engines for world sizes > 1): a single-GPU workspace does not carry it
-    o->xpack_len = (m > SVGP_M_MAX && c->single_stat_block) ? L * svgp_sym_packed_elems((int)m) : 0;
+    o->xpack_len = (big && !ball_large && c->single_stat_block) ? L * svgp_sym_packed_elems((int)m) : 0;
     o->xpack = take(o->xpack_len);
     o->total = p;
     return SVGP_OK;

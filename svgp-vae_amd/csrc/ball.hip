@@ -2,7 +2,9 @@
 // shared sparse-GP stages.  The GP block of build_SVGPVAE_elbo_graph (SVGPVAE_model.py:638-715) runs on the
 // channel-batched stages of gp_kernels.hip with rows = the tmax frames and channels = the videos of the batch
 // (every video has the same time stamps 1..tmax, :663-664, so K_mm and K_nm are shared), cfg.kl_form = 1,
-// cfg.clip_pv = 2, N_train = tmax; one workspace per latent coordinate (svgp_x, svgp_y).
+// cfg.clip_pv = 2, N_train = tmax; one workspace per latent coordinate (svgp_x, svgp_y).  Those stages take m <= 64 inducing
+// points and at most 64 videos; beyond, the same block runs on the large-m stages through ball_large.hip, which shares the
+// kernel-matrix and assembly kernels of this file.
 //   SE kernel on scalar times + VJP                       SVGP.__init__ :60, kernel.matrix calls :80-86
 //   MLP bias / tanh layers + reverse                      VAE_utils.py:9-96 (the matmuls are svgp_dgemm_batched)
 //   encoder head exp / clip, (batch,tmax,4) <-> (tmax,batch) channel layout   VAE_utils.py:50-55, SVGPVAE_model.py:670-671
@@ -628,6 +630,10 @@ extern "C" int svgp_ball_elbo_assemble(const svgp_mnist_cfg* cx, const double* w
     svgp_mnist_ws_layout wl;
     int rc = svgp_mnist_ws_layout_get(cx, &wl);
     if (rc) return rc;
+    return svgp_ball_assemble_wl(cx, wl, ws_x, ws_y, row_recon, state, out, stream);
+}
+int svgp_ball_assemble_wl(const svgp_mnist_cfg* cx, const svgp_mnist_ws_layout& wl, const double* ws_x, const double* ws_y,
+                          const double* row_recon, const double* state, double* out, void* stream) {
     REQ_PTRS(ws_x, ws_y, row_recon, state, out);
     BallAsm a;
     a.B = cx->L; a.T = cx->b; a.titsias = cx->titsias; a.jitter = cx->jitter;

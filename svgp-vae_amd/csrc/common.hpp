@@ -124,6 +124,27 @@ inline int svgp_stat_parts(const svgp_mnist_cfg* c) {
 }
 
 int svgp_check_cfg(const svgp_mnist_cfg* c);
+// api.hip: the workspace layout of a configuration its caller has validated (svgp_mnist_ws_layout_get: svgp_check_cfg).
+// ball_large: the per-coordinate workspace of the moving-ball large engine (ball_large.hip): large-m fields at every m, no fields of
+// the MNIST networks, scratch floors for small m.
+int svgp_ws_layout_fill(const svgp_mnist_cfg* c, svgp_mnist_ws_layout* o, bool ball_large);
+// ws.fb_part of that layout: the first L m^2 elements as in every large-m workspace (trace partials of the forward tail, the D
+// matrices of the reverse pass), the rest the split-K scratch of the statistics stages, which takes up to 33 partial (2 L, m) blocks
+// whatever m is; and room for the (L, 32, 3) trace partials when m^2 < 96
+static inline int64_t svgp_ball_large_fb_part_elems(int64_t m, int64_t L) {
+    int64_t n = 2 * L * m * m;
+    if (n < L * m * m + 66 * L * m) n = L * m * m + 66 * L * m;
+    return n < 96 * L ? 96 * L : n;
+}
+// gp_titsias.hip: the three Titsias stages on a workspace whose layout the caller supplies (no configuration check of their own)
+int svgp_titsias_stats_wl(const svgp_mnist_cfg* c, const svgp_mnist_ws_layout& wl, double* ws, void* stream);
+int svgp_titsias_fwd_wl(const svgp_mnist_cfg* c, const svgp_mnist_ws_layout& wl, double* ws, const double* state, void* stream);
+// (knbar_part_elems: what ws.Knbar_part holds when that is more than L b m)
+int svgp_titsias_bwd_wl(const svgp_mnist_cfg* c, const svgp_mnist_ws_layout& wl, double* ws, const double* state, void* stream,
+                        long long knbar_part_elems);
+// ball.hip: svgp_ball_elbo_assemble on two workspaces of layout wl
+int svgp_ball_assemble_wl(const svgp_mnist_cfg* cx, const svgp_mnist_ws_layout& wl, const double* ws_x, const double* ws_y,
+                          const double* row_recon, const double* state, double* out, void* stream);
 
 static inline int svgp_n_part(const svgp_mnist_cfg* c) {
     return c->b < SVGP_MAX_PART ? c->b : SVGP_MAX_PART;

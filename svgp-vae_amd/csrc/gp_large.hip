@@ -14,6 +14,10 @@
 // Qs = Kn^T diag(qbar) Kn.  Row sums that enter the gradient of K_mm linearly
 // (Pbar, Qs) stay rank-local under data parallelism -- the ranks' shares of Kbar add up in the gradient all-reduce -- so
 // cfg.rep_weight is applied HERE to the replicated part of Kbar and the kernel-matrix reverse pass takes Kbar as it is.
+//
+// cfg.kl_form = 1 (the moving-ball KL, SVGPVAE_model.py:135-137) reaches this file through the svgp_ball_large_* entry points only
+// (ball_large.hip; svgp_check_cfg refuses it above m = 64 for every other one): the two factor stages then take the branches
+// marked ball_kl -- kernels k_ball_* below, DESIGN.md section 9e -- on all channels at once, at every m >= 1.
 #include "common.hpp"
 
 extern "C" int svgp_dgemm_batched(int ta, int tb, int M, int N, int K, double alpha, const double* A, int lda,
@@ -483,6 +487,72 @@ __global__ __launch_bounds__(256) void k_big_gemv_fb(FbArgs a, const real* __res
     }
 }
 
+// ---- moving-ball KL (cfg.kl_form = 1; SVGPVAE_model.py:135-137, oracle/staged_gp.py gp_factor_fwd / gp_factor_bwd) ------------------
+// The reference puts A_hat where mu_hat belongs and sums over the whole batch, so the last summand of KL_l is Btot tr(Ki A_l A_l)
+// (Btot = all videos of the batch = channels) instead of mu_l . u_l.  Forward: klq_l = tr(Ki A_l A_l) = sum_ij (Ki A_l)_ij (A_l)_ij
+// (A_l is a mirrored-store product, exactly symmetric) next to KL, as the LDS path stores it.  Reverse, in the W form of this file:
+//   Abar_l = gK/2 D_l  with  D_l = Ki - Aji_l + Btot (Ki A_l + A_l Ki)      (the trace term's derivative joins the log-det's)
+//   Kibar += gK/2 Btot sum_l A_l A_l                                        (carried inside the channel sum "Asum")
+//   ubar = ud, mubar = Ki ubar                                              (mu_hat enters through the mean vector only)
+// Every consumer of D (H = G D, HG = H G^T, their channel sums) and of Asum (k_big_fb_kib) is unchanged.
+//
+// klq partials: grid (KL_NCH, L) like k_big_kl_terms, part (L, KL_NCH); k_ball_kl adds them in index order.
+__global__ __launch_bounds__(256) void k_ball_klq_terms(int m, const real* __restrict__ KiA, const real* __restrict__ A,
+                                                        real* __restrict__ part) {
+    __shared__ real red[16];
+    const int l = blockIdx.y, ch = blockIdx.x;
+    const long long mm = (long long)m * m, per = (mm + KL_NCH - 1) / KL_NCH, lo = ch * per, hi = lo + per < mm ? lo + per : mm;
+    const real* Ml = KiA + (size_t)l * mm;
+    const real* Al = A + (size_t)l * mm;
+    real tr = 0;
+    for (long long o = lo + threadIdx.x; o < hi; o += blockDim.x) tr += Ml[o] * Al[o];
+    tr = block_sum(tr, red);
+    if (threadIdx.x == 0) part[(size_t)l * KL_NCH + ch] = tr;
+}
+// KL[l] = 1/2 (ldK - ldA_l - m + tr(Ki A_l) + Btot klq_l), KL[L + l] = klq_l   (tr(Ki A_l): the partials of k_big_kl_terms)
+__global__ void k_ball_kl(int m, int L, real Btot, const real* __restrict__ ldK, const real* __restrict__ ldA,
+                          const real* __restrict__ part, const real* __restrict__ qpart, real* __restrict__ KL) {
+    const int l = blockIdx.x * blockDim.x + threadIdx.x;
+    if (l >= L) return;
+    real tr = 0, qq = 0;
+    for (int ch = 0; ch < KL_NCH; ++ch) tr += part[((size_t)l * KL_NCH + ch) * 2];
+    for (int ch = 0; ch < KL_NCH; ++ch) qq += qpart[(size_t)l * KL_NCH + ch];
+    KL[L + l] = qq;
+    KL[l] = real(0.5) * (*ldK - ldA[l] - (real)m + tr + Btot * qq);
+}
+// D_l = Ki - Aji_l + Btot (M_l + M_l^T), M_l = Ki A_l.  Tile pairs as k_big_fb_ssym (both tiles of M through LDS, every global
+// access coalesced); the two mirrored elements add the same two numbers, so D is symmetric bit for bit like Ki - Aji.
+__global__ __launch_bounds__(256) void k_ball_dmat(int m, real Btot, const real* __restrict__ Ki, const real* __restrict__ Aji,
+                                                   const real* __restrict__ M, real* __restrict__ D) {
+    __shared__ real U[TP][TP + 1], V[TP][TP + 1];
+    TilePair t;
+    if (!t.init()) return;
+    const size_t mm = (size_t)m * m, lo = (size_t)t.l * mm;
+    tp_load(M + lo, m, t, U, V);
+#pragma unroll
+    for (int h = 0; h < 4; ++h) {
+        const int r = t.r0 + 8 * h;
+#pragma unroll
+        for (int side = 0; side < 2; ++side) {
+            if (side == 1 && t.ti == t.tj) break;
+            const int gi = (side ? t.tj : t.ti) * TP + r, gj = (side ? t.ti : t.tj) * TP + t.c;
+            if (gi < m && gj < m) {
+                const size_t o = (size_t)gi * m + gj;
+                const real mij = side ? V[r][t.c] : U[r][t.c], mji = side ? U[t.c][r] : V[t.c][r];
+                D[lo + o] = Ki[o] - Aji[lo + o] + Btot * (mij + mji);
+            }
+        }
+    }
+}
+// Asum = sum_l (A_l + Btot (A_l A_l)), channels in index order
+__global__ void k_ball_asum(int mm, int L, real Btot, const real* __restrict__ A, const real* __restrict__ AA, real* __restrict__ out) {
+    const int o = blockIdx.x * blockDim.x + threadIdx.x;
+    if (o >= mm) return;
+    real s = 0;
+    for (int l = 0; l < L; ++l) s += A[(size_t)l * mm + o] + Btot * AA[(size_t)l * mm + o];
+    out[o] = s;
+}
+
 inline unsigned nblk(long long n) { return (unsigned)((n + 255) / 256); }
 
 }  // namespace
@@ -565,13 +635,15 @@ int svgp_big_stats(const svgp_mnist_cfg* c, const svgp_mnist_ws_layout& wl, doub
                                    1));
     // v1 (L x m) = a^T Kn: L x m outputs and a contraction over the batch -> split-K (8 tiles of 32 otherwise walk all b rows)
     const long long sk = svgp_dgemm_splitk_scratch_elems(L, m, b);
-    SVGP_REQUIRE(sk >= 0 && sk <= (long long)c->L * m * m, SVGP_ERR_INVALID, "split-K scratch");
+    // (fb_part ends where Qm starts: 2 L m^2 elements, more in the moving-ball large engine's layout, whose m may be small)
+    const long long sks_room = c->kl_form ? (long long)(wl.Qm - wl.fb_part) - (long long)c->L * m * m : (long long)c->L * m * m;
+    SVGP_REQUIRE(sk >= 0 && sk <= sks_room, SVGP_ERR_INVALID, "split-K scratch");
     // scratch: the second half of fb_part (unused since round 4; scr_mm may be in use by the early reverse half on the side stream
     // while the reverse statistics run)
     real* sks = ws + wl.fb_part + (size_t)c->L * m * m;
     if (stacked) {
         const long long sk2 = svgp_dgemm_splitk_scratch_elems(2 * L, m, b);
-        SVGP_REQUIRE(sk2 >= 0 && sk2 <= (long long)c->L * m * m, SVGP_ERR_INVALID, "split-K scratch");
+        SVGP_REQUIRE(sk2 >= 0 && sk2 <= sks_room, SVGP_ERR_INVALID, "split-K scratch");
         RUNC(svgp_dgemm_splitk_rows2(1, 0, 2 * L, m, b, 1.0, cc, L, s.bl0, 2 * L, Kn, m, 0.0, v1, m, sks, sk2, stream));
     } else {
         RUNC(svgp_dgemm_splitk(1, 0, L, m, b, 1.0, abuf, L, Kn, m, 0.0, v1, m, sks, sk, stream));
@@ -637,6 +709,10 @@ int svgp_big_factor_fwd(const svgp_mnist_cfg* c, const svgp_mnist_ws_layout& wl,
     real *K = ws + wl.K, *Ki = ws + wl.Ki, *Si = ws + wl.Si + om, *G = ws + wl.G + om, *A = ws + wl.A + om, *Aji = ws + wl.Aji + om;
     real *t = ws + wl.t + ov, *mu = ws + wl.mu_hat + ov, *u = ws + wl.u + ov, *v = ws + wl.v + ov, *Kn = ws + wl.Kn;
     real* klp = ws + wl.fb_part;                 // (L, KL_NCH, 2) trace partials (fb_part is free until the reverse factor stage)
+    // cfg.kl_form = 1 (moving-ball large engine, ball_large.hip: all channels, never a window; the Titsias ELBO has no KL term)
+    const bool ball_kl = c->kl_form == 1 && !c->titsias;
+    real* klq = klp + (size_t)L * KL_NCH * 2;    // (L, KL_NCH) partials of tr(Ki A A)
+    SVGP_REQUIRE(!ball_kl || (l0 == 0 && nl == c->L), SVGP_ERR_UNSUPPORTED, "kl_form=1 couples all channels: no channel window");
     const bool alone = pieces == SVGP_FWD_K || pieces == SVGP_FWD_SIG || pieces == SVGP_FWD_KL;
     SVGP_REQUIRE(alone || pieces == SVGP_FWD_HEAD || pieces == SVGP_FWD_TAIL || pieces == SVGP_FWD_ALL, SVGP_ERR_INVALID,
                  "forward factor stage: piece set 0x%x is not one of K, SIG, KL, K|SIG|KL, TAIL, all", pieces);
@@ -687,6 +763,11 @@ int svgp_big_factor_fwd(const svgp_mnist_cfg* c, const svgp_mnist_ws_layout& wl,
         GEMV(1.0, Ki, 0, mu, u, L);                                                                  // u = Ki mu
         hipLaunchKernelGGL(k_big_kl_terms, dim3(KL_NCH, L), dim3(256), 0, st, m, Ki, A, mu, u, klp);
         SVGP_LAUNCH_CHECK();
+        if (ball_kl) {      // klq_l = tr(Ki A_l A_l): Ki A_l in mm0 (free during the forward factor stage), then one pass
+            GEMM(0, 0, m, m, m, 1.0, Ki, m, 0, A, m, mm, 0.0, s.mm0, m, mm, L);
+            hipLaunchKernelGGL(k_ball_klq_terms, dim3(KL_NCH, L), dim3(256), 0, st, m, (const real*)s.mm0, (const real*)A, klq);
+            SVGP_LAUNCH_CHECK();
+        }
     }
     if (do_k) {
         // q_n = k_n^T Ki k_n;  W = (Kn Ki) K behind the rows of Kn;  P^T = K Ki
@@ -700,7 +781,10 @@ int svgp_big_factor_fwd(const svgp_mnist_cfg* c, const svgp_mnist_ws_layout& wl,
     if (pieces & SVGP_FWD_TAIL) {
         // (Aji holds A_hat + jI: written by the product A = K G above; the tail inverts it in place)
         RUNC(svgp_spd_inverse_batched(m, L, Aji, s.ldtmp, s.inv, stream));
-        hipLaunchKernelGGL(k_big_kl, dim3(nblk(L)), dim3(256), 0, st, m, L, ws + wl.ldK, s.ldtmp, klp, ws + wl.KL + l0);
+        if (ball_kl)
+            hipLaunchKernelGGL(k_ball_kl, dim3(nblk(L)), dim3(256), 0, st, m, L, (real)c->L, ws + wl.ldK, s.ldtmp, klp, klq, ws + wl.KL);
+        else
+            hipLaunchKernelGGL(k_big_kl, dim3(nblk(L)), dim3(256), 0, st, m, L, ws + wl.ldK, s.ldtmp, klp, ws + wl.KL + l0);
         SVGP_LAUNCH_CHECK();
     }
     return SVGP_OK;
@@ -783,7 +867,27 @@ int svgp_big_factor_bwd(const svgp_mnist_cfg* c, const svgp_mnist_ws_layout& wl,
         GEMM(0, 1, m, m, m, 1.0, ws + wl.S + om, m, mm, s.PT, m, 0, 0.0, s.mm1, m, mm, L);        // T = S P   (P = (P^T)^T)
         GEMM_SYM(0, 0, m, m, 1.0, s.PT, m, 0, s.mm1, m, mm, 0.0, s.mm2, m, mm, L);                // SW = P^T T
     }
-    if (pieces & SVGP_BWD_EARLY_B) {
+    // cfg.kl_form = 1 (see k_ball_klq_terms): D and Asum gain the trace term's share, the vector chain loses its KL terms
+    const bool ball_kl = c->kl_form == 1 && !c->titsias;
+    SVGP_REQUIRE(!ball_kl || (l0 == 0 && nl == c->L), SVGP_ERR_UNSUPPORTED, "kl_form=1 couples all channels: no channel window");
+    if ((pieces & SVGP_BWD_EARLY_B) && ball_kl) {
+        real* G = ws + wl.G + om;
+        real* Db = ws + wl.fb_part;
+        const real Btot = (real)c->L;
+        GEMM(0, 0, m, m, m, 1.0, Ki, m, 0, A, m, mm, 0.0, s.mm0, m, mm, L);                        // M = Ki A          (mm0)
+        hipLaunchKernelGGL(k_ball_dmat, dim3(ntp, ntp, L), dim3(256), 0, st, m, Btot, (const real*)Ki, (const real*)Aji,
+                           (const real*)s.mm0, Db);
+        SVGP_LAUNCH_CHECK();
+        GEMM(0, 1, m, m, m, 1.0, A, m, mm, A, m, mm, 0.0, s.mm3, m, mm, L);                         // A A               (mm3)
+        hipLaunchKernelGGL(k_ball_asum, dim3(nblk(mm)), dim3(256), 0, st, (int)mm, L, Btot, (const real*)A, (const real*)s.mm3, s.Asum);
+        SVGP_LAUNCH_CHECK();
+        GEMM(0, 1, m, m, m, 1.0, G, m, mm, Db, m, mm, 0.0, s.mm0, m, mm, L);                        // H = G D           (mm0: M is consumed)
+        GEMM_SYM(0, 1, m, m, 1.0, s.mm0, m, mm, G, m, mm, 0.0, s.mm3, m, mm, L);                    // HG = H G^T        (mm3: A A is consumed)
+        hipLaunchKernelGGL(k_big_sum_channels, dim3(nblk(mm)), dim3(256), 0, st, (int)mm, L, real(1), s.mm0, s.Zs);
+        SVGP_LAUNCH_CHECK();
+        hipLaunchKernelGGL(k_big_sum_channels, dim3(nblk(mm)), dim3(256), 0, st, (int)mm, L, real(1), s.mm3, s.HGs);
+        SVGP_LAUNCH_CHECK();
+    } else if (pieces & SVGP_BWD_EARLY_B) {
         real* G = ws + wl.G + om;
         // H = G D = Si K (Ki - Aji) = Z', D = D^T read as [j][k].  Small m (launch-bound, config 3): D = Ki - Aji is formed while the
         // B operand is staged (one launch less: 1.307 -> 1.299 ms).  Large m: a pass materialises D first -- the second operand
@@ -824,8 +928,12 @@ int svgp_big_factor_bwd(const svgp_mnist_cfg* c, const svgp_mnist_ws_layout& wl,
     };
     if (pieces & SVGP_BWD_LATE_A) {
         // ubar = ud + gK/2 mu;  mubar = Ki ubar + gK/2 u;  tbar = td + c K mubar: two launches (k_big_gemv_fb)
-        hipLaunchKernelGGL(k_big_gemv_fb<1>, dim3((m + 15) / 16, L), dim3(256), (size_t)m * sizeof(real), st, a, (const real*)Ki);
-        SVGP_LAUNCH_CHECK();
+        if (ball_kl) {
+            GEMV(1.0, Ki, 0, a.ud, s.vec1, L);                                              // mubar = Ki ubar, ubar = ud
+        } else {
+            hipLaunchKernelGGL(k_big_gemv_fb<1>, dim3((m + 15) / 16, L), dim3(256), (size_t)m * sizeof(real), st, a, (const real*)Ki);
+            SVGP_LAUNCH_CHECK();
+        }
         hipLaunchKernelGGL(k_big_gemv_fb<2>, dim3((m + 15) / 16, L), dim3(256), (size_t)m * sizeof(real), st, a, (const real*)K);
         SVGP_LAUNCH_CHECK();
         if (x_early) RUNC(x_block());
@@ -842,7 +950,7 @@ int svgp_big_factor_bwd(const svgp_mnist_cfg* c, const svgp_mnist_ws_layout& wl,
     FinArgs f;
     f.m = m; f.L = L; f.Ltot = c->L; f.geco = SVGP_LOSS_FLAGS(c); f.b_global = c->b_global; f.c = cc; f.N_train = c->N_train;
     f.rep_weight = c->rep_weight; f.state = state;
-    f.Asum = s.Asum; f.ubar = s.vec0; f.mu = a.mu; f.Qs = s.Qs; f.PbarK = s.tA; f.Zs = s.Zs; f.mubar = s.vec1; f.t = ws + wl.t + ov;
+    f.Asum = s.Asum; f.ubar = ball_kl ? a.ud : s.vec0; f.mu = a.mu; f.Qs = s.Qs; f.PbarK = s.tA; f.Zs = s.Zs; f.mubar = s.vec1; f.t = ws + wl.t + ov;
     f.Sgs = s.Sgs; f.HGs = s.HGs; f.Ki = Ki; f.KiPbar = s.tB; f.KiKibKi = s.tA; f.Kib = s.tB; f.Kbar = ws + wl.Kbar;
     f.rank1_late = a.rank1_late; f.vbar = a.vbar;      // (KiPbar: KBAR's last product, read by FINAL only)
     if (pieces & SVGP_BWD_KBAR) {

@@ -21,6 +21,7 @@
 // The stages are compositions of svgp_dgemm_batched / svgp_spd_inverse_batched and element-wise kernels on the
 // workspace, valid for every m <= 2048; scratch comes from the large-m path's areas, free between stages.
 #include "common.hpp"
+#include <algorithm>
 
 namespace {
 
@@ -169,6 +170,9 @@ int layouts(const svgp_mnist_cfg* c, svgp_mnist_ws_layout* wl) {
 extern "C" int svgp_gp_titsias_stats(const svgp_mnist_cfg* c, double* ws, void* stream) {
     svgp_mnist_ws_layout wl;
     RUNC(layouts(c, &wl));
+    return svgp_titsias_stats_wl(c, wl, ws, stream);
+}
+int svgp_titsias_stats_wl(const svgp_mnist_cfg* c, const svgp_mnist_ws_layout& wl, double* ws, void* stream) {
     SVGP_REQUIRE(ws, SVGP_ERR_INVALID, "NULL device pointer");
     const int b = c->b, m = c->m, L = c->L;
     hipStream_t st = (hipStream_t)stream;
@@ -190,6 +194,9 @@ extern "C" int svgp_gp_titsias_stats(const svgp_mnist_cfg* c, double* ws, void* 
 extern "C" int svgp_gp_titsias_fwd(const svgp_mnist_cfg* c, double* ws, const double* state, void* stream) {
     svgp_mnist_ws_layout wl;
     RUNC(layouts(c, &wl));
+    return svgp_titsias_fwd_wl(c, wl, ws, state, stream);
+}
+int svgp_titsias_fwd_wl(const svgp_mnist_cfg* c, const svgp_mnist_ws_layout& wl, double* ws, const double* state, void* stream) {
     SVGP_REQUIRE(ws && state, SVGP_ERR_INVALID, "NULL device pointer");
     const int b = c->b, m = c->m, L = c->L;
     hipStream_t st = (hipStream_t)stream;
@@ -211,6 +218,10 @@ extern "C" int svgp_gp_titsias_fwd(const svgp_mnist_cfg* c, double* ws, const do
 extern "C" int svgp_gp_titsias_bwd(const svgp_mnist_cfg* c, double* ws, const double* state, void* stream) {
     svgp_mnist_ws_layout wl;
     RUNC(layouts(c, &wl));
+    return svgp_titsias_bwd_wl(c, wl, ws, state, stream, 0);
+}
+int svgp_titsias_bwd_wl(const svgp_mnist_cfg* c, const svgp_mnist_ws_layout& wl, double* ws, const double* state, void* stream,
+                        long long knbar_part_elems) {
     SVGP_REQUIRE(ws && state, SVGP_ERR_INVALID, "NULL device pointer");
     const int b = c->b, m = c->m, L = c->L, flags = SVGP_LOSS_FLAGS(c);
     const long long mm = (long long)m * m;
@@ -224,7 +235,9 @@ extern "C" int svgp_gp_titsias_bwd(const svgp_mnist_cfg* c, double* ws, const do
     real* W = ws + wl.Knbar_part;                    // (b, m)   Knbar_part is dead after svgp_gp_posterior_bwd
     real* cA = W + (size_t)b * m;                    // (b, L)   (Knbar_part holds L b m >= b m + 2 b L for m >= 2 ... )
     real* cB = cA + (size_t)b * L;
-    SVGP_REQUIRE((long long)L * b * m >= (long long)b * m + 2LL * b * L, SVGP_ERR_UNSUPPORTED,
+    // (ws.Knbar_part holds L b m elements; the moving-ball large engine's layout, api.hip, sizes it for this at every m)
+    const long long room = std::max<long long>((long long)L * b * m, knbar_part_elems);
+    SVGP_REQUIRE(room >= (long long)b * m + 2LL * b * L, SVGP_ERR_UNSUPPORTED,
                  "Titsias reverse pass needs (L - 1) m >= 2 L scratch elements per row (L=%d m=%d)", L, m);
     hipLaunchKernelGGL(k_tit_sb, dim3(nblk((long long)L * mm)), dim3(256), 0, st, m, L, flags, state, ws + wl.tit_Si,
                        ws + wl.tit_t, Sb);

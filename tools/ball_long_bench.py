@@ -3,7 +3,10 @@ moving-ball step at the reference's 35 videos, 32x32 frames, MLP 500, float64, f
 
   exact   PearceLongStepEngine (pearce_long.hip) per --elbo VAE | GPVAE_Pearce --GP_joint | NP --GP_joint at every tmax
   lds     PearceStepEngine (k_pearce_fwd / k_pearce_bwd) at tmax = 64 only, the last size it takes
-  sparse  BallStepEngine, SVGPVAE_Hensman, m = 15, at every tmax
+  sparse  the engine ball.sparse_engine_class picks (BallStepEngine up to m = 64, BallLargeStepEngine above), SVGPVAE_Hensman, at
+          every tmax twice: with the old m = 15 and with --m inducing points -- by default one per model length scale,
+          m = ceil(tmax / 2) capped at 2048 (`--m N`: N at every tmax), so that the sparse model can represent a length-scale-2
+          path as the exact one does
 
 Every configuration runs in a child process of its own under a time limit; the first child that fails ends the run (nothing
 more is started on the device after a fault).  A child warms up, then times `--blocks` blocks of `--steps` steps with device
@@ -12,7 +15,8 @@ minimum and maximum block.  `--stages TMAX` adds, for the exact engines at that 
 GP-regression calls of one step (forward / reverse, full set / context set); the rest of the step is MLP, reconstruction term,
 Adam.  There is no pass / fail number.
 
-    python tools/ball_long_bench.py [--tmax 64 128 256 512 1024] [--stages 256] > profiles/ball_long.json"""
+    python tools/ball_long_bench.py [--tmax 64 128 256 512 1024] [--m auto] [--kinds exact lds sparse] [--stages 256] \
+        > profiles/ball_long.json"""
 import argparse
 import json
 import os
@@ -26,10 +30,15 @@ sys.path.insert(0, ROOT)
 EXACT = {"VAE": [], "GPVAE_Pearce": ["--GP_joint"], "NP": ["--GP_joint"]}
 
 
-def _engine(kind, elbo, tmax):
+def sparse_m(rule, tmax):
+    """--m: `auto` = one inducing point per model length scale (2 frames), at most 2048; or a number."""
+    return min(-(-tmax // 2), 2048) if rule == "auto" else int(rule)
+
+
+def _engine(kind, elbo, tmax, m=15):
     from svgp_vae_amd import BALL_experiment as BE, ball
     if kind == "sparse":
-        flags = ["--elbo", "SVGPVAE_Hensman", "--m", "15", "--tmax", str(tmax), "--ip_max", str(tmax), "--clip_qs", "--jitter",
+        flags = ["--elbo", "SVGPVAE_Hensman", "--m", str(m), "--tmax", str(tmax), "--ip_max", str(tmax), "--clip_qs", "--jitter",
                  "1e-6", "--GP_joint", "--ip_joint"]
         return BE.build_engine(BE.build_parser().parse_args(flags))
     args = BE.build_parser().parse_args(["--elbo", elbo, "--tmax", str(tmax)] + EXACT[elbo])
@@ -41,7 +50,7 @@ def _engine(kind, elbo, tmax):
 def worker(a):
     import torch
     from svgp_vae_amd import ball
-    eng = _engine(a.kind, a.elbo, a.tmax)
+    eng = _engine(a.kind, a.elbo, a.tmax, int(a.m))
     vid = ball.VideoBatchSource(tmax=a.tmax, px=32, py=32, lt=2, batch=35, seed=1, r=3)()
     torch.cuda.synchronize()
     for _ in range(a.warmup):
@@ -56,7 +65,8 @@ def worker(a):
         e1.record(eng.stream)
         e1.synchronize()
         ms.append(e0.elapsed_time(e1) / a.steps)
-    res = dict(kind=a.kind, elbo=a.elbo, tmax=a.tmax, ms_per_step_median=statistics.median(ms), ms_per_step_min=min(ms),
+    res = dict(kind=a.kind, elbo=a.elbo, tmax=a.tmax, m=int(a.m) if a.kind == "sparse" else None, engine=type(eng).__name__,
+               ms_per_step_median=statistics.median(ms), ms_per_step_min=min(ms),
                ms_per_step_max=max(ms), blocks=a.blocks, steps_per_block=a.steps, elbo_after=eng.scalars()["elbo"])
     if a.stages and a.kind != "sparse":
         marks = []
@@ -89,6 +99,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--tmax", type=int, nargs="+", default=[64, 128, 256, 512, 1024])
     ap.add_argument("--elbo", nargs="+", default=list(EXACT))
+    ap.add_argument("--m", default="auto", help="inducing points of the second sparse column: auto = ceil(tmax / 2) <= 2048, or a number")
+    ap.add_argument("--kinds", nargs="+", default=["exact", "lds", "sparse"], choices=["exact", "lds", "sparse"])
     ap.add_argument("--stages", type=int, default=0, help="tmax at which the per-stage event times are taken too (0: none)")
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--blocks", type=int, default=5)
@@ -102,13 +114,15 @@ def main():
         return worker(a)
     jobs = []
     for T in a.tmax:
-        jobs += [("exact", e, T) for e in a.elbo]
-        if T == 64:
-            jobs += [("lds", e, T) for e in a.elbo]
-        jobs.append(("sparse", "SVGPVAE_Hensman", T))
+        if "exact" in a.kinds:
+            jobs += [("exact", e, T, 0) for e in a.elbo]
+        if T == 64 and "lds" in a.kinds:
+            jobs += [("lds", e, T, 0) for e in a.elbo]
+        if "sparse" in a.kinds:
+            jobs += [("sparse", "SVGPVAE_Hensman", T, m) for m in dict.fromkeys((15, sparse_m(a.m, T)))]
     rows = []
-    for kind, elbo, T in jobs:
-        cmd = [sys.executable, os.path.abspath(__file__), "--worker", "--kind", kind, "--elbo", elbo, "--tmax", str(T), "--steps",
+    for kind, elbo, T, m in jobs:
+        cmd = [sys.executable, os.path.abspath(__file__), "--worker", "--kind", kind, "--elbo", elbo, "--tmax", str(T), "--m", str(m), "--steps",
                str(a.steps), "--blocks", str(a.blocks), "--warmup", str(a.warmup), "--stages", str(int(a.stages == T))]
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=a.limit)
@@ -120,7 +134,7 @@ def main():
             print(f"{kind} {elbo} tmax {T}: exit status {r.returncode}; stopping\n{r.stderr[-2000:]}", file=sys.stderr)
             break
         rows.append(json.loads(line[0][7:]))
-        print(f"{kind:6s} {elbo:16s} tmax {T:5d}: {rows[-1]['ms_per_step_median']:9.3f} ms/step "
+        print(f"{kind:6s} {elbo:16s} tmax {T:5d} m {m:4d}: {rows[-1]['ms_per_step_median']:9.3f} ms/step "
               f"[{rows[-1]['ms_per_step_min']:.3f}, {rows[-1]['ms_per_step_max']:.3f}]", file=sys.stderr, flush=True)
     print(json.dumps(dict(workload="moving ball, batch 35, 32x32, MLP 500, float64; device-event time of the step alone, median "
                                    "[min, max] over blocks", rows=rows)))
