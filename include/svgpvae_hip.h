@@ -382,6 +382,25 @@ int svgp_mnist_decoder_fwd_bwd_data_pre(const svgp_mnist_cfg*, const double* the
 int svgp_mnist_decoder_fwd_bwd_data_pre_aji(const svgp_mnist_cfg*, const double* theta, const double* images, double* ws,
                                             const double* state, void* stream);
 int svgp_mnist_decoder_fused_regs(int L, int* out);
+/* m <= 32, no cfg.titsias: the forward block of the training step with ONLY what the decoder needs in front of it (schedule switch
+ * SVGP_FWD_SPLIT; svgp_mnist_train_step and the unsharded svgp_mnist_train_step_dp run these four in the slots of
+ * svgp_gp_factor_fwd_defer_aji, svgp_gp_posterior_fwd, svgp_mnist_decoder_fwd_bwd_data_pre_aji and svgp_gp_posterior_bwd_rows /
+ * _with_final).  Same arithmetic in the same order: every output has the bits of the full forms.
+ *   _factor_fwd_head: Si, t = Si v, mu_hat = c K t, u = Ki mu_hat and q; no G, A, M2, Aji, KL.
+ *   _posterior_fwd_z: p_m, p_v, e, eps, z and the CE partials from Si, t, u; no d, no L3 partial; M2 is not read.
+ *   _decoder_fwd_bwd_data_pre_tail: the fused decoder launch whose L riders run the rest of the factor stage from K, Ki, Si, mu_hat,
+ *     u: G, A, M2, the traces, (A_hat + jI)^-1, KL (both entries with cfg.kl_form).  _fused_tail_regs: out[0..2] registers per lane,
+ *     scratch bytes per lane, dynamic LDS bytes at latent size L (bounds as for svgp_mnist_decoder_fused_regs).
+ *   _posterior_bwd_rows_d: svgp_gp_posterior_bwd_rows that also forms d = (knn - q) + k^T M2 k + e^2 and the L3 partials.
+ * svgp_fwd_split_regs: out[0..11] registers and scratch bytes per lane of the head, z and d kernels (m = 32 instance, run-time-m
+ * instance).  SVGP_ERR_UNSUPPORTED for m > 32 or cfg.titsias, before anything is launched. */
+int svgp_gp_factor_fwd_head(const svgp_mnist_cfg*, double* ws, void* stream);
+int svgp_gp_posterior_fwd_z(const svgp_mnist_cfg*, const double* eps, double* ws, double* state, void* stream);
+int svgp_mnist_decoder_fwd_bwd_data_pre_tail(const svgp_mnist_cfg*, const double* theta, const double* images, double* ws,
+                                             const double* state, void* stream);
+int svgp_gp_posterior_bwd_rows_d(const svgp_mnist_cfg*, double* ws, const double* state, void* stream);
+int svgp_mnist_decoder_fused_tail_regs(int L, int* out);
+int svgp_fwd_split_regs(int* out);
 /* m <= 64: svgp_gp_factor_bwd_nofinal + svgp_mnist_decoder_bwd_weights(threads = 256) in ONE launch: the L channel workgroups
  * first, then min(b, 256) rider workgroups with the decoder's weight-gradient partials (needs svgp_mnist_decoder_bwd_data before). */
 int svgp_gp_factor_bwd_nofinal_wgrad(const svgp_mnist_cfg*, const double* images, double* ws, const double* state,
@@ -444,6 +463,11 @@ int svgp_mnist_train_step(const svgp_mnist_cfg*, double* theta, const double* im
  * SVGP_ERR_INVALID when the text needs more than cap bytes. */
 int svgp_mnist_step_route(const svgp_mnist_cfg*, int form, int phase, int nranks, int rank, int adam, int early_issued,
                           char* buf, int cap);
+/* The same text; where the plan runs the SVGP_FWD_SPLIT forms, the line of each of the four slots ends in " -> <entry that runs>"
+ * (svgp_gp_factor_fwd_head, svgp_gp_posterior_fwd_z, svgp_mnist_decoder_fwd_bwd_data_pre_tail, svgp_gp_posterior_bwd_rows_d or, where
+ * pass 2 stays in the stage, svgp_gp_posterior_bwd_with_final_d: _with_final with pass 1 in the d form). */
+int svgp_mnist_step_route_forms(const svgp_mnist_cfg*, int form, int phase, int nranks, int rank, int adam, int early_issued,
+                                char* buf, int cap);
 
 /* ---- data-parallel exchange over RCCL on the compute stream -------------------------
  * The reference is single-process; these are the three sum-exchanges the row-sharded step needs

@@ -154,6 +154,12 @@ SIGNATURES = {
     "svgp_mnist_decoder_fwd_bwd_data_pre_aji": [_CFG, _P, _P, _P, _P, _P],
     "svgp_mnist_decoder_fused_regs": [C.c_int, C.POINTER(C.c_int)],
     "svgp_gp_posterior_bwd_rows": [_CFG, _P, _P, _P],
+    "svgp_gp_factor_fwd_head": [_CFG, _P, _P],
+    "svgp_gp_posterior_fwd_z": [_CFG, _P, _P, _P, _P],
+    "svgp_mnist_decoder_fwd_bwd_data_pre_tail": [_CFG, _P, _P, _P, _P, _P],
+    "svgp_gp_posterior_bwd_rows_d": [_CFG, _P, _P, _P],
+    "svgp_mnist_decoder_fused_tail_regs": [C.c_int, C.POINTER(C.c_int)],
+    "svgp_fwd_split_regs": [C.POINTER(C.c_int)],
     "svgp_mnist_grad_reduce_part": [_CFG, _P, _P, C.c_int, _P],
     "svgp_gp_posterior_bwd_with_final": [_CFG, _P, _P, _P],
     "svgp_gp_titsias_stats": [_CFG, _P, _P],
@@ -171,6 +177,7 @@ SIGNATURES = {
     "svgp_mnist_step_phase": [_CFG, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "svgp_mnist_train_step": [_CFG, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "svgp_mnist_step_route": [_CFG, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_int],
+    "svgp_mnist_step_route_forms": [_CFG, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_int],
     "svgp_stream_features_f32": [_P, C.c_int64, _P, C.c_int, C.c_int, _P, _P, _P],
     "svgp_stream_knm_f32": [_P, C.c_int64, C.c_int, _P, _P, _P, _P],
     "svgp_stream_stats_f32": [C.c_int64, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, C.c_int64, _P],

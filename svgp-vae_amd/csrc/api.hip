@@ -328,8 +328,19 @@ int svgp_step_plan_checked(const svgp_mnist_cfg* c, int form, int phase, int nra
 }
 
 namespace {
-int step_stage(const StepOp& op, const StepArgs& a, void* st, const SvgpSched& sc) {
+// split: StepPlan::fwd_split -- the four slots below that have a second form run it
+int step_stage(const StepOp& op, const StepArgs& a, void* st, const SvgpSched& sc, bool split) {
     const svgp_mnist_cfg* c = a.c;
+    if (split) {
+        switch (op.stage) {
+        case STEP_ST_FACTOR_FWD_DEFER_AJI: return svgp_gp_factor_fwd_head(c, a.ws, st);
+        case STEP_ST_POST_FWD: return svgp_gp_posterior_fwd_z(c, a.eps, a.ws, a.state, st);
+        case STEP_ST_DEC_FUSED_AJI: return svgp_mnist_decoder_fwd_bwd_data_pre_tail(c, a.theta, a.images, a.ws, a.state, st);
+        case STEP_ST_POST_BWD_ROWS: return svgp_gp_posterior_bwd_rows_d(c, a.ws, a.state, st);
+        case STEP_ST_POST_BWD_FINAL: return svgp_gp_posterior_bwd_with_final_d(c, a.ws, a.state, st);
+        default: break;
+        }
+    }
     switch (op.stage) {
     case STEP_ST_ENC_KM_FWD: return svgp_mnist_encoder_kernel_matrix_fwd(c, a.theta, a.images, a.aux, a.ws, st);
     case STEP_ST_STATS_FWD: return svgp_gp_stats_fwd(c, a.ws, st);
@@ -402,7 +413,7 @@ int step_run(const StepPlan& P, const StepArgs& a, void* stream, const SvgpSched
         const StepOp& op = P.op[i];
         const int k = op.lane == STEP_SIDE1 ? 1 : 0;
         switch (op.kind) {
-        case STEP_STAGE: rc = step_stage(op, a, (void*)lane[op.lane], sc); break;
+        case STEP_STAGE: rc = step_stage(op, a, (void*)lane[op.lane], sc, P.fwd_split); break;
         case STEP_FORK: rc = side_fork(sd, k, lane[STEP_MAIN]); forked[k] = forked[k] || rc == SVGP_OK; break;
         case STEP_JOIN: rc = side_join(sd, k, lane[STEP_MAIN]); forked[k] = false; break;
         case STEP_GROUP_BEGIN: rc = svgp_comm_group_begin(a.comm); group = rc == SVGP_OK; break;
@@ -481,8 +492,20 @@ static const char* step_piece_name(bool fwd, unsigned p) {
         if (t.fwd == fwd && t.pieces == p) return t.name;
     return "?";
 }
-extern "C" int svgp_mnist_step_route(const svgp_mnist_cfg* c, int form, int phase, int nranks, int rank, int adam, int early_issued,
-                                     char* buf, int cap) {
+// The entry a slot runs when the plan has fwd_split (step_stage), or nullptr: the one table both the executor's switch and the forms
+// printer are checked against (tests/test_fwd_split_route_cpu.py compares the printed names with the stage-by-stage GPU test's calls).
+static const char* step_split_form(unsigned char stage) {
+    switch (stage) {
+    case STEP_ST_FACTOR_FWD_DEFER_AJI: return "svgp_gp_factor_fwd_head";
+    case STEP_ST_POST_FWD: return "svgp_gp_posterior_fwd_z";
+    case STEP_ST_DEC_FUSED_AJI: return "svgp_mnist_decoder_fwd_bwd_data_pre_tail";
+    case STEP_ST_POST_BWD_ROWS: return "svgp_gp_posterior_bwd_rows_d";
+    case STEP_ST_POST_BWD_FINAL: return "svgp_gp_posterior_bwd_with_final_d";
+    default: return nullptr;
+    }
+}
+static int step_route_text(const svgp_mnist_cfg* c, int form, int phase, int nranks, int rank, int adam, int early_issued,
+                           char* buf, int cap, bool forms) {
     SVGP_REQUIRE(buf && cap >= 1, SVGP_ERR_INVALID, "bad argument");
     int rc = svgp_check_cfg(c);
     if (rc) return rc;
@@ -506,6 +529,7 @@ extern "C" int svgp_mnist_step_route(const svgp_mnist_cfg* c, int form, int phas
             pos += snprintf(buf + pos, cap - pos, "%s %s", ln, STEP_STAGE_NAME[op.stage]);
             if (pos < cap && (fwd || op.stage == STEP_ST_BIG_FACTOR_BWD)) pos += snprintf(buf + pos, cap - pos, " %s", step_piece_name(fwd, op.arg));
             else if (pos < cap && op.stage == STEP_ST_GRAD_REDUCE_PART) pos += snprintf(buf + pos, cap - pos, " %u", op.arg);
+            if (pos < cap && forms && P.fwd_split && step_split_form(op.stage)) pos += snprintf(buf + pos, cap - pos, " -> %s", step_split_form(op.stage));
             break;
         }
         case STEP_FORK: case STEP_JOIN: pos += snprintf(buf + pos, cap - pos, "%s %s", kd, ln); break;
@@ -519,6 +543,15 @@ extern "C" int svgp_mnist_step_route(const svgp_mnist_cfg* c, int form, int phas
         SVGP_REQUIRE(pos < cap, SVGP_ERR_INVALID, "route text needs more than %d bytes", cap);
     }
     return SVGP_OK;
+}
+
+extern "C" int svgp_mnist_step_route(const svgp_mnist_cfg* c, int form, int phase, int nranks, int rank, int adam, int early_issued,
+                                     char* buf, int cap) {
+    return step_route_text(c, form, phase, nranks, rank, adam, early_issued, buf, cap, false);
+}
+extern "C" int svgp_mnist_step_route_forms(const svgp_mnist_cfg* c, int form, int phase, int nranks, int rank, int adam, int early_issued,
+                                           char* buf, int cap) {
+    return step_route_text(c, form, phase, nranks, rank, adam, early_issued, buf, cap, true);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -51,6 +51,8 @@ int svgp_dgemm_splitk_rows2(int ta, int tb, int M, int N, int K, double alpha, d
                             void* stream);
 // gp_kernels.hip: a piece set (SVGP_FWD_*, below) of the large-m forward factor stage on all channels, with the entry points' checks
 int svgp_gp_factor_fwd_pieces(const svgp_mnist_cfg* c, double* ws, void* stream, unsigned pieces);
+// gp_kernels.hip: svgp_gp_posterior_bwd_with_final whose pass 1 also forms d and the L3 partials (the d form of SVGP_FWD_SPLIT, m <= 32)
+int svgp_gp_posterior_bwd_with_final_d(const svgp_mnist_cfg* c, double* ws, const double* state, void* stream);
 // The step as a plan (step_plan.hpp) and its execution.  StepArgs: what the stages of one call run on; the second line is set by
 // svgp_mnist_train_step_dp only (wl: the layout of `c`; n_enc: with cfg.split_grad_exchange; [l0, l0 + nl): the rank's channels).
 struct StepArgs {

@@ -45,8 +45,10 @@ __device__ __forceinline__ void mat_load(real* R, int ld, const real* __restrict
         for (int u = 0; u < 4; ++u) { const int o = o0 + u * nt; if (o < mm) R[(o / m) * ld + (o % m)] = v[u]; }
     }
 }
-__device__ __forceinline__ void mat_store(real* __restrict__ g, const real* R, int ld, int m) {
-    for (int o = threadIdx.x; o < m * m; o += blockDim.x) g[o] = R[(o / m) * ld + (o % m)];
+// (nt: the live threads of a rider workgroup, a multiple of 64; 0: the whole workgroup -- also in mat_fetch4 / mat_put4 / mat_gemm)
+__device__ __forceinline__ void mat_store(real* __restrict__ g, const real* R, int ld, int m, int nt = 0) {
+    const int st = nt ? nt : (int)blockDim.x;
+    for (int o = threadIdx.x; o < m * m; o += st) g[o] = R[(o / m) * ld + (o % m)];
 }
 // Payload of an intra-launch hand-off between workgroups on different XCDs (svgp_mnist_encoder_bwd_km_sum): written THROUGH to memory
 // and read past the non-coherent per-XCD L2s (sc1 = relaxed agent-scope atomics), no cache-wide write-back / invalidate -- the
@@ -92,21 +94,23 @@ __device__ __forceinline__ d4_t mfma_tile(const real* A, const real* B, int ld, 
 // A matrix of <= 4 elements per thread (m * m <= 4 blockDim.x) fetched into registers now and put into LDS later: a global load in
 // the MIDDLE of a dependent chain of LDS products exposes a full L2 round trip; issued at the top of the workgroup it is free
 struct Mat4 { real v[4]; };
-__device__ __forceinline__ Mat4 mat_fetch4(const real* __restrict__ g, int m) {
+__device__ __forceinline__ Mat4 mat_fetch4(const real* __restrict__ g, int m, int nt = 0) {
+    const int st = nt ? nt : (int)blockDim.x;
     Mat4 r;
 #pragma unroll
-    for (int k = 0; k < 4; ++k) { const int o = threadIdx.x + k * blockDim.x; r.v[k] = o < m * m ? g[o] : real(0); }
+    for (int k = 0; k < 4; ++k) { const int o = threadIdx.x + k * st; r.v[k] = o < m * m ? g[o] : real(0); }
     return r;
 }
-__device__ __forceinline__ void mat_put4(real* R, int ld, const Mat4& r, int m) {
+__device__ __forceinline__ void mat_put4(real* R, int ld, const Mat4& r, int m, int nt = 0) {
+    const int st = nt ? nt : (int)blockDim.x;
 #pragma unroll
-    for (int k = 0; k < 4; ++k) { const int o = threadIdx.x + k * blockDim.x; if (o < m * m) R[(o / m) * ld + (o % m)] = r.v[k]; }
+    for (int k = 0; k < 4; ++k) { const int o = threadIdx.x + k * st; if (o < m * m) R[(o / m) * ld + (o % m)] = r.v[k]; }
 }
 // C = alpha * op(A) * op(B)   (all LDS padded, C must not alias A or B)
 template <bool TA, bool TB>
-__device__ __forceinline__ void mat_gemm(real* C, const real* A, const real* B, int ld, int m, real alpha) {
+__device__ __forceinline__ void mat_gemm(real* C, const real* A, const real* B, int ld, int m, real alpha, int nthr = 0) {
     const int mp = pad16(m), nt = mp >> 4, lane = threadIdx.x & 63, r = lane & 15, q = lane >> 4;
-    for (int t = threadIdx.x >> 6; t < nt * nt; t += (blockDim.x >> 6)) {
+    for (int t = threadIdx.x >> 6; t < nt * nt; t += ((nthr ? nthr : (int)blockDim.x) >> 6)) {
         const int ti = t / nt, tj = t % nt;
         const d4_t acc = mfma_tile<TA, TB>(A, B, ld, mp, ti, tj);
 #pragma unroll
@@ -769,9 +773,71 @@ struct FactArgs {
     real* Si; real* t; real* G; real* A; real* Aji; real* mu; real* u; real* M2; real* KL; real* q;
 };
 
+// Everything of a channel workgroup behind the first inverse, with `nt` live threads (a multiple of 64): the channel workgroup of
+// k_gp_factor_fwd (nt = blockDim.x) and, RIDER, a rider workgroup of the decoder launch (k_decoder_fwd_bwd_data<2>: the first
+// SVGP_BLOCK threads of a VAE_NT workgroup) behind the head form of the stage.  On entry R0 = K, R1 = Sigma_l^-1 (padded, pads zero),
+// pKi = Ki in registers when keep; !RIDER: vx = v_l, and t, mu_hat, u are computed and stored on the way; RIDER: vz = mu_hat_l,
+// vx = u_l (the head form stored them) and the stage ends with (A_hat + jI)^-1 and both roundings of KL_l.  Every loop strides by nt
+// and the sums go through block_sum_nt, so the two callers produce the same bits.
+template <int MC, bool RIDER>
+__device__ __forceinline__ void factor_fwd_tail(const FactArgs& a, int l, int nt, real* R0, real* R1, real* R2, real* R3,
+                                                real* vx, real* vy, real* vz, real* red, const Mat4& pKi, bool keep) {
+    const int m = MC ? MC : a.m, mp = pad16(m), ld = mp + 2;
+    const size_t om = (size_t)l * m * m, ov = (size_t)l * m;
+    if (!RIDER) mat_vec(vy, R1, ld, vx, m, real(1));       // t = Si v
+    mat_gemm<false, false>(R2, R1, R0, ld, m, real(1), nt);   // G = Si K
+    __syncthreads();
+    if (!RIDER && threadIdx.x < m) a.t[ov + threadIdx.x] = vy[threadIdx.x];
+    mat_store(a.G + om, R2, ld, m, nt);
+    mat_gemm<false, false>(R3, R0, R2, ld, m, real(1), nt);   // A = K G
+    if (!RIDER) mat_vec(vz, R0, ld, vy, m, a.c);           // mu_hat = c K t
+    __syncthreads();
+    mat_store(a.A + om, R3, ld, m, nt);
+    if (!RIDER && threadIdx.x < m) a.mu[ov + threadIdx.x] = vz[threadIdx.x];
+    if (keep) mat_put4(R1, ld, pKi, m, nt); else mat_load_nt(R1, ld, a.Ki, m, nt);      // R1 = Ki   (Si, G no longer needed in LDS)
+    __syncthreads();
+    if (!RIDER) mat_vec(vx, R1, ld, vz, m, real(1));       // u = Ki mu_hat
+    // tr(Ki A) = sum_ij Ki_ij A_ji
+    real tr = 0;
+    for (int o = threadIdx.x; o < m * m; o += nt) tr += R1[(o / m) * ld + (o % m)] * R3[(o % m) * ld + (o / m)];
+    mat_gemm<false, false>(R2, R3, R1, ld, m, real(1), nt);   // T = A Ki
+    __syncthreads();
+    tr = block_sum_nt(tr, red, nt);
+    real muu = 0;
+    if (threadIdx.x < m) {
+        if (!RIDER) a.u[ov + threadIdx.x] = vx[threadIdx.x];
+        muu = vz[threadIdx.x] * vx[threadIdx.x];
+    }
+    muu = block_sum_nt(muu, red, nt);
+    if (a.kl_form) {
+        // moving-ball KL (SVGPVAE_model.py:135-137): tr(Ki A A) = sum_ij (A Ki)_ij A_ji in the place of mu.u
+        real qq = 0;
+        for (int o = threadIdx.x; o < m * m; o += nt) qq += R2[(o / m) * ld + (o % m)] * R3[(o % m) * ld + (o / m)];
+        qq = block_sum_nt(qq, red, nt);
+        if (threadIdx.x == 0) a.KL[a.L + l] = qq;
+        muu = (real)a.L * qq;
+    }
+    mat_gemm<false, false>(R0, R1, R2, ld, m, real(1), nt);   // M2 = Ki A Ki   (K no longer needed)
+    __syncthreads();
+    mat_store(a.M2 + om, R0, ld, m, nt);
+    real kl0 = 0;
+    if (RIDER || a.defer_aji) {
+        if (threadIdx.x == 0) a.KL[l] = kl0 = real(0.5) * (*a.ldK - (real)m + tr + muu);     // - ldA / 2 follows
+        if (!RIDER) return;
+    }
+    if (threadIdx.x < m) R3[threadIdx.x * ld + threadIdx.x] += a.jitter;     // A + jitter I
+    const real ldA = chol_inv(R3, R2, ld, m);               // (m <= 32: wave 0 alone, any number of live waves)
+    mat_store(a.Aji + om, R3, ld, m, nt);
+    // RIDER: the two roundings of the deferred form (KL_l above, then - ldA / 2 by the launch that finishes the inverse)
+    if (threadIdx.x == 0) a.KL[l] = RIDER ? kl0 - real(0.5) * ldA : real(0.5) * (*a.ldK - ldA - (real)m + tr + muu);
+}
+
 // MC: compile-time m (0: a.m at run time).  With m = 32 known (config 2) the index arithmetic of every element loop (o / m,
 // o % m with a run-time divisor: ~35 instructions each) folds to shifts and the loops unroll.
-template <int MC>
+// HEAD (m <= 32, the step's SVGP_FWD_SPLIT form): the channel workgroup stops behind what the forward row stage and the reverse
+// statistics read -- Si, t = Si v, mu_hat = c K t, u = Ki mu_hat -- and runs no matrix product; factor_fwd_tail<.., true> does the
+// rest inside the decoder launch.
+template <int MC, bool HEAD>
 __global__ __launch_bounds__(SVGP_BLOCK) void k_gp_factor_fwd(FactArgs a) {
     extern __shared__ __align__(16) real smem[];
     const int m = MC ? MC : a.m, mp = pad16(m), ld = mp + 2, mm = mp * ld;
@@ -825,50 +891,18 @@ __global__ __launch_bounds__(SVGP_BLOCK) void k_gp_factor_fwd(FactArgs a) {
     if (threadIdx.x < m) vx[threadIdx.x] = part_sum(a.v + ov + threadIdx.x, (size_t)a.L * m, a.P);
     chol_inv(R1, R2, ld, m);                       // R1 = Sigma_l^{-1}
     mat_store(a.Si + om, R1, ld, m);
-    mat_vec(vy, R1, ld, vx, m, real(1));           // t = Si v
-    mat_gemm<false, false>(R2, R1, R0, ld, m, real(1));   // G = Si K
-    __syncthreads();
-    if (threadIdx.x < m) a.t[ov + threadIdx.x] = vy[threadIdx.x];
-    mat_store(a.G + om, R2, ld, m);
-    mat_gemm<false, false>(R3, R0, R2, ld, m, real(1));   // A = K G
-    mat_vec(vz, R0, ld, vy, m, a.c);               // mu_hat = c K t
-    __syncthreads();
-    mat_store(a.A + om, R3, ld, m);
-    if (threadIdx.x < m) a.mu[ov + threadIdx.x] = vz[threadIdx.x];
-    if (keep) mat_put4(R1, ld, pKi, m); else mat_load(R1, ld, a.Ki, m);      // R1 = Ki   (Si, G no longer needed in LDS)
-    __syncthreads();
-    mat_vec(vx, R1, ld, vz, m, real(1));           // u = Ki mu_hat
-    // tr(Ki A) = sum_ij Ki_ij A_ji
-    real tr = 0;
-    for (int o = threadIdx.x; o < m * m; o += blockDim.x) tr += R1[(o / m) * ld + (o % m)] * R3[(o % m) * ld + (o / m)];
-    mat_gemm<false, false>(R2, R3, R1, ld, m, real(1));   // T = A Ki
-    __syncthreads();
-    tr = block_sum(tr, red);
-    real muu = 0;
-    if (threadIdx.x < m) {
-        a.u[ov + threadIdx.x] = vx[threadIdx.x];
-        muu = vz[threadIdx.x] * vx[threadIdx.x];
-    }
-    muu = block_sum(muu, red);
-    if (a.kl_form) {
-        // moving-ball KL (SVGPVAE_model.py:135-137): tr(Ki A A) = sum_ij (A Ki)_ij A_ji in the place of mu.u
-        real qq = 0;
-        for (int o = threadIdx.x; o < m * m; o += blockDim.x) qq += R2[(o / m) * ld + (o % m)] * R3[(o % m) * ld + (o / m)];
-        qq = block_sum(qq, red);
-        if (threadIdx.x == 0) a.KL[a.L + l] = qq;
-        muu = (real)a.L * qq;
-    }
-    mat_gemm<false, false>(R0, R1, R2, ld, m, real(1));   // M2 = Ki A Ki   (K no longer needed)
-    __syncthreads();
-    mat_store(a.M2 + om, R0, ld, m);
-    if (a.defer_aji) {
-        if (threadIdx.x == 0) a.KL[l] = real(0.5) * (*a.ldK - (real)m + tr + muu);     // - ldA / 2 follows
+    if (HEAD) {
+        mat_vec(vy, R1, ld, vx, m, real(1));           // t = Si v
+        if (keep) mat_put4(R2, ld, pKi, m); else mat_load(R2, ld, a.Ki, m);      // R2 = Ki   (the inverse's scratch is free)
+        __syncthreads();
+        if (threadIdx.x < m) a.t[ov + threadIdx.x] = vy[threadIdx.x];
+        mat_vec(vz, R0, ld, vy, m, a.c);               // mu_hat = c K t
+        __syncthreads();
+        mat_vec(vx, R2, ld, vz, m, real(1));           // u = Ki mu_hat   (every thread reads back its own element below)
+        if (threadIdx.x < m) { a.mu[ov + threadIdx.x] = vz[threadIdx.x]; a.u[ov + threadIdx.x] = vx[threadIdx.x]; }
         return;
     }
-    if (threadIdx.x < m) R3[threadIdx.x * ld + threadIdx.x] += a.jitter;     // A + jitter I
-    const real ldA = chol_inv(R3, R2, ld, m);
-    mat_store(a.Aji + om, R3, ld, m);
-    if (threadIdx.x == 0) a.KL[l] = real(0.5) * (*a.ldK - ldA - (real)m + tr + muu);
+    factor_fwd_tail<MC, false>(a, l, (int)blockDim.x, R0, R1, R2, R3, vx, vy, vz, red, pKi, keep);
 }
 
 // =============================================================================================
@@ -890,7 +924,16 @@ struct PostArgs {
 
 __device__ __forceinline__ real philox_normal(unsigned long long ctr, unsigned long long idx) { return svgp_philox_normal(ctr, idx); }
 
-template <int MC>
+// The data term of a row, shared by the two kernels that may form it (k_gp_posterior_fwd, and k_gp_posterior_bwd_l in its d form):
+// one term of the quadratic form k^T M2 k in thread (row, i), d = (knn - q) + ss + e^2 and the row's L3 summand.  The contractions
+// are written out, so that the two kernels round alike.
+__device__ __forceinline__ real row_quad_term(real acc, real mji, real kj) { return fma(mji, kj, acc); }
+__device__ __forceinline__ real row_d(real kq, real ss, real ee) { return fma(ee, ee, kq + ss); }
+__device__ __forceinline__ real row_l3(real p, real dd, real ls2) { return real(-0.5) * fma(p, dd, ls2); }
+
+// ZF (the step's SVGP_FWD_SPLIT form): what the decoder and the reverse statistics read -- p_m, p_v, e, eps, z, the CE partial.  M2 is
+// not loaded; d and the L3 partial are left to the d form of k_gp_posterior_bwd_l.
+template <int MC, bool ZF>
 __global__ __launch_bounds__(SVGP_BLOCK) void k_gp_posterior_fwd(PostArgs a) {
     extern __shared__ __align__(16) real smem[];
     const int m = MC ? MC : a.m, ld = m + 1, mm = m * ld, l = blockIdx.y;
@@ -912,18 +955,18 @@ __global__ __launch_bounds__(SVGP_BLOCK) void k_gp_posterior_fwd(PostArgs a) {
         return;
     }
     real* R0 = smem;            // Si_l
-    real* R1 = R0 + mm;         // M2_l
-    real* tv = R1 + mm;         // t_l
+    real* R1 = R0 + mm;         // M2_l   (ZF: no such matrix, and three partial products)
+    real* tv = ZF ? R1 : R1 + mm;   // t_l
     real* uv = tv + m;          // u_l
     real* kr = uv + m;          // RB x m
-    real* sc = kr + SVGP_BLOCK; // 4 x 256 partial products
-    real* red = sc + 4 * SVGP_BLOCK;
+    real* sc = kr + SVGP_BLOCK; // 4 x 256 partial products: r, pm, mv, s
+    real* red = sc + (ZF ? 3 : 4) * SVGP_BLOCK;
     const int RB = blockDim.x / m;
     const int nl = threadIdx.x / m, i = threadIdx.x % m, n = bx * RB + nl;
     const bool act = nl < RB && n < a.b;
     const size_t om = (size_t)l * m * m;
     mat_load(R0, ld, a.Si + om, m);
-    mat_load(R1, ld, a.M2 + om, m);
+    if (!ZF) mat_load(R1, ld, a.M2 + om, m);
     if (threadIdx.x < m) { tv[threadIdx.x] = a.t[(size_t)l * m + threadIdx.x]; uv[threadIdx.x] = a.u[(size_t)l * m + threadIdx.x]; }
     if (act) kr[nl * m + i] = a.Kn[(size_t)n * m + i];
     __syncthreads();
@@ -934,43 +977,45 @@ __global__ __launch_bounds__(SVGP_BLOCK) void k_gp_posterior_fwd(PostArgs a) {
         for (int j = 0; j < m; ++j) {
             const real kj = kr[nl * m + j];
             r += R0[j * ld + i] * kj;       // symmetric matrices: column walk = row walk
-            s += R1[j * ld + i] * kj;
+            if (!ZF) s = row_quad_term(s, R1[j * ld + i], kj);
         }
         r *= ki; s *= ki; pm = tv[i] * ki; mv = uv[i] * ki;
     }
-    sc[threadIdx.x] = r; sc[SVGP_BLOCK + threadIdx.x] = s; sc[2 * SVGP_BLOCK + threadIdx.x] = pm;
-    sc[3 * SVGP_BLOCK + threadIdx.x] = mv;
+    sc[threadIdx.x] = r; sc[SVGP_BLOCK + threadIdx.x] = pm; sc[2 * SVGP_BLOCK + threadIdx.x] = mv;
+    if (!ZF) sc[3 * SVGP_BLOCK + threadIdx.x] = s;
     __syncthreads();
     real l3 = 0, ce = 0;
     if (act && i == 0) {
         real rs = 0, ss = 0, pms = 0, mvs = 0;
 #pragma unroll 8
         for (int k = 0; k < m; ++k) {
-            rs += sc[nl * m + k]; ss += sc[SVGP_BLOCK + nl * m + k];
-            pms += sc[2 * SVGP_BLOCK + nl * m + k]; mvs += sc[3 * SVGP_BLOCK + nl * m + k];
+            rs += sc[nl * m + k]; if (!ZF) ss += sc[3 * SVGP_BLOCK + nl * m + k];
+            pms += sc[SVGP_BLOCK + nl * m + k]; mvs += sc[2 * SVGP_BLOCK + nl * m + k];
         }
         const size_t e = (size_t)n * a.L + l;
         const real y = a.y[e], s2 = a.s2[e], p = recip_no_nan(s2);
         const real kq = a.knn[n] - a.q[n];
-        const real p_m = a.c * pms, ee = y - mvs, dd = kq + ss + ee * ee;
+        const real p_m = a.c * pms, ee = y - mvs, dd = row_d(kq, ss, ee);
         real p_v = kq + rs;
         if (a.clip_pv == 1) p_v = fmin(fmax(p_v, 1e-4), 100.0);
         real ep;
         if (a.use_rng) ep = philox_normal((unsigned long long)a.state[SVGP_ST_RNG_CTR], (unsigned long long)e);
         else ep = a.eps_in[e];
         a.eps[e] = ep;
-        a.p_m[e] = p_m; a.p_v[e] = p_v; a.e[e] = ee; a.d[e] = dd;
+        a.p_m[e] = p_m; a.p_v[e] = p_v; a.e[e] = ee;
+        if (!ZF) a.d[e] = dd;
         a.z[e] = p_m + ep * sqrt(a.clip_pv == 2 ? fmin(fmax(p_v, 1e-4), 1000.0) : p_v);
         const real ls2 = log(s2);
-        l3 = real(-0.5) * (p * dd + ls2);
+        if (!ZF) l3 = row_l3(p, dd, ls2);
         const real dm = p_m - y;
         ce = real(-0.5) * (real(SVGP_LOG_2PI) + ls2 + (p_v + dm * dm) * p);
     }
-    l3 = block_sum(l3, red);
+    if (!ZF) l3 = block_sum(l3, red);
     ce = block_sum(ce, red);
     if (threadIdx.x == 0) {
         const size_t pi = ((size_t)l * a.nb + bx) * 2;
-        a.part[pi] = l3; a.part[pi + 1] = ce;
+        if (!ZF) a.part[pi] = l3;
+        a.part[pi + 1] = ce;
     }
 }
 
@@ -1316,33 +1361,46 @@ struct PostBwdArgs {
     int nb_rows, n_final, b_global;
     real N_train;
     const real* Kbar_part; real* Kbar;
+    // d form of pass 1 (behind the z form of the forward row stage): d and the L3 partial are formed here
+    const real* M2; const real* knn; const real* q; real* d_out; real* part;
 };
 
-template <int MC>
+// DF (the step's SVGP_FWD_SPLIT form): the forward row stage ran in its z form, so this kernel -- same grid, same (row, i) thread
+// layout -- forms ss = k^T M2 k, d and the L3 partial of its row block the way that stage does (row_quad_term, row_d, row_l3, block_sum).
+template <int MC, bool DF>
 __global__ __launch_bounds__(SVGP_BLOCK) void k_gp_posterior_bwd_l(PostBwdArgs a) {
     extern __shared__ __align__(16) real smem[];
     const int m = MC ? MC : a.m, ld = m + 1, mm = m * ld, l = blockIdx.y;
     real* R0 = smem;            // Si_l
     real* R1 = R0 + mm;         // Q_l
     real* R2 = R1 + mm;         // Ssym_l
-    real* uv = R2 + mm;         // u_l
+    real* R3 = R2 + mm;         // DF: M2_l
+    real* uv = DF ? R3 + mm : R3;   // u_l
     real* tv = uv + m;          // t_l
     real* vb = tv + m;          // vbar_l
     real* kr = vb + m;          // RB x m
-    real* sc = kr + SVGP_BLOCK; // 2 x 256
+    real* sc = kr + SVGP_BLOCK; // 2 x 256 (DF: 3 x 256, + 16 for the block sum)
+    real* red = sc + 3 * SVGP_BLOCK;
     const int RB = blockDim.x / m;
     const int nl = threadIdx.x / m, i = threadIdx.x % m, n = blockIdx.x * RB + nl;
     const bool act = nl < RB && n < a.b;
     const size_t om = (size_t)l * m * m, ov = (size_t)l * m;
-    mat_load(R0, ld, a.Si + om, m);
-    mat_load(R1, ld, a.Qm + om, m);
-    mat_load(R2, ld, a.Ssym + om, m);
+    if (DF) {
+        // m <= 32: four elements of each matrix per thread, all sixteen loads in flight before the first LDS store (M2 and Q were
+        // written by workgroups of other XCDs one and two launches ago: four round trips one behind the other cost ~2 us)
+        const Mat4 p0 = mat_fetch4(a.Si + om, m), p1 = mat_fetch4(a.Qm + om, m), p2 = mat_fetch4(a.Ssym + om, m), p3 = mat_fetch4(a.M2 + om, m);
+        mat_put4(R0, ld, p0, m); mat_put4(R1, ld, p1, m); mat_put4(R2, ld, p2, m); mat_put4(R3, ld, p3, m);
+    } else {
+        mat_load(R0, ld, a.Si + om, m);
+        mat_load(R1, ld, a.Qm + om, m);
+        mat_load(R2, ld, a.Ssym + om, m);
+    }
     if (threadIdx.x < m) { uv[threadIdx.x] = a.u[ov + threadIdx.x]; tv[threadIdx.x] = a.t[ov + threadIdx.x]; vb[threadIdx.x] = a.vbar[ov + threadIdx.x]; }
     if (act) kr[nl * m + i] = a.Kn[(size_t)n * m + i];
     __syncthreads();
     const real gT = grad_KL_term(a.geco, a.L, a.state);
     const real g3 = svgp_seed_3(a.geco, gT);
-    real ksk = 0, kv = 0;
+    real ksk = 0, kv = 0, s = 0;
     if (act) {
         const size_t e = (size_t)n * a.L + l;
         const real p = recip_no_nan(a.s2[e]), gpv = a.g_pv[e];
@@ -1353,26 +1411,45 @@ __global__ __launch_bounds__(SVGP_BLOCK) void k_gp_posterior_bwd_l(PostBwdArgs a
             sik += R0[j * ld + i] * kj;
             qk += R1[j * ld + i] * kj;
             ssk += R2[j * ld + i] * kj;
+            if (DF) s = row_quad_term(s, R3[j * ld + i], kj);
         }
         const real ki = kr[nl * m + i];
+        s *= ki;
         a.Knbar_part[((size_t)l * a.b + n) * m + i] = real(2) * gpv * sik + p * qk + a.mvbar[e] * uv[i] +
                                                       a.c * a.g_pm[e] * tv[i] + p * a.y[e] * vb[i];
         ksk = real(0.5) * ssk * ki;
         kv = vb[i] * ki;
     }
     sc[threadIdx.x] = ksk; sc[SVGP_BLOCK + threadIdx.x] = kv;
+    if (DF) sc[2 * SVGP_BLOCK + threadIdx.x] = s;
     __syncthreads();
+    real l3 = 0;
     if (act && i == 0) {
         real kS = 0, kV = 0;
         for (int k = 0; k < m; ++k) { kS += sc[nl * m + k]; kV += sc[SVGP_BLOCK + nl * m + k]; }
         const size_t e = (size_t)n * a.L + l;
         const real y = a.y[e], s2 = a.s2[e], p = recip_no_nan(s2);
         const real dm = a.p_m[e] - y;
-        const real pbar = real(-0.5) * g3 * a.d[e] + kS + y * kV;
+        real dd;
+        if (DF) {
+            real ss = 0;
+#pragma unroll 8
+            for (int k = 0; k < m; ++k) ss += sc[2 * SVGP_BLOCK + nl * m + k];
+            dd = row_d(a.knn[n] - a.q[n], ss, a.e[e]);
+            a.d_out[e] = dd;
+            l3 = row_l3(p, dd, log(s2));
+        } else {
+            dd = a.d[e];
+        }
+        const real pbar = real(-0.5) * g3 * dd + kS + y * kV;
         const real ce_y = -gT * p * dm;
         const real ce_s2 = real(0.5) * gT * (p - (a.p_v[e] + dm * dm) * p * p);
         a.ybar[e] = ce_y - g3 * p * a.e[e] + p * kV;
         a.s2bar[e] = ce_s2 - real(0.5) * g3 * p - pbar * p * p;
+    }
+    if (DF) {
+        l3 = block_sum(l3, red);
+        if (threadIdx.x == 0) a.part[((size_t)l * a.nb_rows + blockIdx.x) * 2] = l3;
     }
 }
 
@@ -1537,18 +1614,51 @@ __global__ __launch_bounds__(VAE_NT) void k_decoder_bwd_data_aji(svgp_vae::DecBw
     svgp_vae::decoder_bwd_data_images<true>(d, l - a.L, (int)gridDim.x - a.L, smem);
 }
 
+// A rider workgroup of k_decoder_fwd_bwd_data<2>: channel l behind the head form of k_gp_factor_fwd, SVGP_BLOCK live threads.  Loads what
+// the head form left (K, Si, Ki, mu_hat, u) and runs factor_fwd_tail.
+template <int MC>
+__device__ __forceinline__ void factor_fwd_rider(const FactArgs& a, int l, real* smem) {
+    constexpr int nt = SVGP_BLOCK;
+    const int m = MC ? MC : a.m, mp = pad16(m), ld = mp + 2, mm = mp * ld;
+    real* R0 = smem;
+    real* R1 = R0 + mm;
+    real* R2 = R1 + mm;
+    real* R3 = R2 + mm;
+    for (int o = threadIdx.x; o < 4 * mm; o += nt) smem[o] = 0;   // zero pads (MFMA tiles read them)
+    __syncthreads();
+    real* vx = R3 + mm;       // m
+    real* vy = vx + m;        // m
+    real* vz = vy + m;        // m
+    real* red = vz + m;       // 16
+    const size_t om = (size_t)l * m * m, ov = (size_t)l * m;
+    const Mat4 pKi = mat_fetch4(a.Ki, m, nt);                  // m <= 32: m * m <= 4 nt
+    mat_load_nt(R0, ld, a.K, m, nt);
+    mat_load_nt(R1, ld, a.Si + om, m, nt);
+    if (threadIdx.x < m) { vz[threadIdx.x] = a.mu[ov + threadIdx.x]; vx[threadIdx.x] = a.u[ov + threadIdx.x]; }
+    __syncthreads();
+    factor_fwd_tail<MC, true>(a, l, nt, R0, R1, R2, R3, vx, vy, vz, red, pKi, true);
+}
+
 // Training step, m <= 64 (SVGP_DEC_FUSE): the decoder's forward launch and the launch above as ONE launch -- same grid, back to back in
 // phase 1, workgroup n of the second consumed only what workgroup n of the first produced (decoder_fwd_bwd_data_images, vae_dev.hpp).
 // AJI: the L rider workgroups at the head, as above (m <= 32); otherwise image workgroups only.  No occupancy hint and nothing
 // outlined (both measured slower on the merged launches): the rolled-tap forward keeps the kernel at <= 168 VGPRs without scratch and the
 // reduced staging at <= 80 KB of LDS, which a rider and an image workgroup need to share a CU; tests check the three numbers.
-template <bool AJI>
-__global__ __launch_bounds__(VAE_NT) void k_decoder_fwd_bwd_data(svgp_vae::DecFwdBwdArgs d, AjiArgs a) {
+// RIDE 0: no riders; 1: the riders finish (A_hat + jI)^-1; 2 (SVGP_FWD_SPLIT, behind the head form of the forward factor stage): the
+// riders run everything of the stage that the chain up to this launch does not read -- G, A, the traces, M2, then that inverse and
+// KL (factor_fwd_tail) -- with SVGP_BLOCK live threads; its consumers (the reverse factor stage, the d form of the reverse row stage,
+// the closing scalars) all sit behind this launch.
+template <int RIDE>
+__global__ __launch_bounds__(VAE_NT) void k_decoder_fwd_bwd_data(svgp_vae::DecFwdBwdArgs d, AjiArgs a, FactArgs f) {
     extern __shared__ __align__(16) real smem[];
     int l = blockIdx.x;
-    if (AJI) {
+    if (RIDE) {
         if (l < a.L) {
             if (threadIdx.x >= SVGP_BLOCK) return;
+            if (RIDE == 2) {
+                if (f.m == 32) factor_fwd_rider<32>(f, l, smem); else factor_fwd_rider<0>(f, l, smem);
+                return;
+            }
             const int m = a.m, ld = m + 1;
             real* A = smem;
             real* W = A + m * ld;
@@ -1563,7 +1673,7 @@ __global__ __launch_bounds__(VAE_NT) void k_decoder_fwd_bwd_data(svgp_vae::DecFw
         l -= a.L;
         __builtin_amdgcn_s_setprio(3);          // (the image waves before a rider's sweep wave on the same SIMD, as above)
     }
-    svgp_vae::decoder_fwd_bwd_data_images(d, l, (int)gridDim.x - (AJI ? a.L : 0), smem);
+    svgp_vae::decoder_fwd_bwd_data_images(d, l, (int)gridDim.x - (RIDE ? a.L : 0), smem);
 }
 
 template <typename F>
@@ -1579,6 +1689,22 @@ int set_dyn_lds(F kernel, size_t bytes) {
         if (rc_mc) return rc_mc;                                                                                      \
         if ((m_) == 32) hipLaunchKernelGGL(kern<32>, grid_, dim3(SVGP_BLOCK), lds_, (hipStream_t)(stream_), args_);    \
         else hipLaunchKernelGGL(kern<0>, grid_, dim3(SVGP_BLOCK), lds_, (hipStream_t)(stream_), args_);                \
+        SVGP_LAUNCH_CHECK();                                                                                          \
+    } while (0)
+// ... of a kernel template <int MC, bool FORM>, the form chosen at run time
+#define LAUNCH_MC_FORM(kern, m_, form_, grid_, lds_, stream_, args_)                                                  \
+    do {                                                                                                              \
+        if (form_) {                                                                                                  \
+            int rc_mc = (m_) == 32 ? set_dyn_lds(kern<32, true>, lds_) : set_dyn_lds(kern<0, true>, lds_);             \
+            if (rc_mc) return rc_mc;                                                                                  \
+            if ((m_) == 32) hipLaunchKernelGGL((kern<32, true>), grid_, dim3(SVGP_BLOCK), lds_, (hipStream_t)(stream_), args_); \
+            else hipLaunchKernelGGL((kern<0, true>), grid_, dim3(SVGP_BLOCK), lds_, (hipStream_t)(stream_), args_);    \
+        } else {                                                                                                      \
+            int rc_mc = (m_) == 32 ? set_dyn_lds(kern<32, false>, lds_) : set_dyn_lds(kern<0, false>, lds_);           \
+            if (rc_mc) return rc_mc;                                                                                  \
+            if ((m_) == 32) hipLaunchKernelGGL((kern<32, false>), grid_, dim3(SVGP_BLOCK), lds_, (hipStream_t)(stream_), args_); \
+            else hipLaunchKernelGGL((kern<0, false>), grid_, dim3(SVGP_BLOCK), lds_, (hipStream_t)(stream_), args_);   \
+        }                                                                                                             \
         SVGP_LAUNCH_CHECK();                                                                                          \
     } while (0)
 
@@ -1728,9 +1854,20 @@ extern "C" int svgp_mnist_decoder_bwd_data_pre_aji(const svgp_mnist_cfg* c, cons
     return SVGP_OK;
 }
 // svgp_mnist_decoder_fwd_pre + svgp_mnist_decoder_bwd_data_pre[_aji] in one launch; same bits (SVGP_DEC_FUSE, m <= 64 training step)
+static const char NEED_SPLIT_M[] = "the split forward block (SVGP_FWD_SPLIT) exists for m <= 32, m = %d";
+static const char NEED_SPLIT_TIT[] = "the split forward block (SVGP_FWD_SPLIT) does not exist with cfg.titsias";
+#define REQUIRE_FWD_SPLIT(c)                                                     \
+    do {                                                                         \
+        SVGP_REQUIRE((c) != nullptr, SVGP_ERR_INVALID, "cfg is NULL");           \
+        SVGP_REQUIRE((c)->m <= 32, SVGP_ERR_UNSUPPORTED, NEED_SPLIT_M, (c)->m);  \
+        SVGP_REQUIRE(!(c)->titsias, SVGP_ERR_UNSUPPORTED, NEED_SPLIT_TIT);       \
+    } while (0)
+static FactArgs make_fact_args(const svgp_mnist_cfg* c, const svgp_mnist_ws_layout& wl, double* ws, int defer_aji);
+// ride: 0 no riders, 1 the riders finish (A_hat + jI)^-1, 2 the riders run the whole tail of the forward factor stage
 static int decoder_fwd_bwd_data_impl(const svgp_mnist_cfg* c, const double* theta, const double* images, double* ws,
-                                     const double* state, bool aji, void* stream) {
+                                     const double* state, int ride, void* stream) {
     GET_LAYOUTS();
+    const bool aji = ride != 0;
     SVGP_REQUIRE(theta && images && ws && state, SVGP_ERR_INVALID, "NULL device pointer");
     SVGP_REQUIRE(!aji || c->m <= 32, SVGP_ERR_UNSUPPORTED, "the rider inverse is the single-wave sweep (m <= 32), m = %d", c->m);
     svgp_vae::DecFwdBwdArgs d;
@@ -1746,30 +1883,71 @@ static int decoder_fwd_bwd_data_impl(const svgp_mnist_cfg* c, const double* thet
         const size_t lds_inv = mat_lds(c->m, 1) + (size_t)(5 * c->m + 80) * sizeof(real);
         if (lds_inv > lds) lds = lds_inv;
     }
+    FactArgs f;
+    memset(&f, 0, sizeof(f));
+    if (ride == 2) {
+        f = make_fact_args(c, wl, ws, 1);
+        const size_t lds_tail = mat_lds_pad(c->m, 4) + (size_t)(3 * c->m + 16) * sizeof(real);
+        if (lds_tail > lds) lds = lds_tail;
+    }
     SVGP_REQUIRE(lds <= SVGP_LDS_MAX_BYTES, SVGP_ERR_UNSUPPORTED, "L = %d: %zu bytes of LDS", c->L, lds);
-    int rc = aji ? set_dyn_lds(k_decoder_fwd_bwd_data<true>, lds) : set_dyn_lds(k_decoder_fwd_bwd_data<false>, lds);
+    int rc = ride == 2 ? set_dyn_lds(k_decoder_fwd_bwd_data<2>, lds)
+             : aji     ? set_dyn_lds(k_decoder_fwd_bwd_data<1>, lds) : set_dyn_lds(k_decoder_fwd_bwd_data<0>, lds);
     if (rc) return rc;
-    if (aji) hipLaunchKernelGGL(k_decoder_fwd_bwd_data<true>, dim3(a.L + svgp_n_part(c)), dim3(VAE_NT), lds, (hipStream_t)stream, d, a);
-    else hipLaunchKernelGGL(k_decoder_fwd_bwd_data<false>, dim3(svgp_n_part(c)), dim3(VAE_NT), lds, (hipStream_t)stream, d, a);
+    const dim3 grid((aji ? a.L : 0) + svgp_n_part(c));
+    if (ride == 2) hipLaunchKernelGGL(k_decoder_fwd_bwd_data<2>, grid, dim3(VAE_NT), lds, (hipStream_t)stream, d, a, f);
+    else if (aji) hipLaunchKernelGGL(k_decoder_fwd_bwd_data<1>, grid, dim3(VAE_NT), lds, (hipStream_t)stream, d, a, f);
+    else hipLaunchKernelGGL(k_decoder_fwd_bwd_data<0>, grid, dim3(VAE_NT), lds, (hipStream_t)stream, d, a, f);
     SVGP_LAUNCH_CHECK();
     return SVGP_OK;
 }
 extern "C" int svgp_mnist_decoder_fwd_bwd_data_pre(const svgp_mnist_cfg* c, const double* theta, const double* images, double* ws,
                                                    const double* state, void* stream) {
-    return decoder_fwd_bwd_data_impl(c, theta, images, ws, state, false, stream);
+    return decoder_fwd_bwd_data_impl(c, theta, images, ws, state, 0, stream);
 }
 extern "C" int svgp_mnist_decoder_fwd_bwd_data_pre_aji(const svgp_mnist_cfg* c, const double* theta, const double* images, double* ws,
                                                        const double* state, void* stream) {
-    return decoder_fwd_bwd_data_impl(c, theta, images, ws, state, true, stream);
+    return decoder_fwd_bwd_data_impl(c, theta, images, ws, state, 1, stream);
+}
+// SVGP_FWD_SPLIT, behind svgp_gp_factor_fwd_head: the riders run the tail of the forward factor stage (G, A, M2, Aji, KL)
+extern "C" int svgp_mnist_decoder_fwd_bwd_data_pre_tail(const svgp_mnist_cfg* c, const double* theta, const double* images, double* ws,
+                                                        const double* state, void* stream) {
+    REQUIRE_FWD_SPLIT(c);
+    return decoder_fwd_bwd_data_impl(c, theta, images, ws, state, 2, stream);
+}
+// out[0..2]: registers per lane, scratch bytes per lane, dynamic LDS bytes of that launch at latent size L (m <= 32)
+extern "C" int svgp_mnist_decoder_fused_tail_regs(int L, int* out) {
+    SVGP_REQUIRE(out, SVGP_ERR_INVALID, "out is NULL");
+    SVGP_REQUIRE(L >= 1 && L <= 64, SVGP_ERR_INVALID, "L = %d (1..64)", L);
+    hipFuncAttributes fa;
+    SVGP_CHECK_HIP(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(k_decoder_fwd_bwd_data<2>)));
+    out[0] = fa.numRegs; out[1] = (int)fa.localSizeBytes;
+    size_t lds = svgp_vae::dec_fwd_bwd_lds(L) * sizeof(real);
+    const size_t lds_tail = mat_lds_pad(32, 4) + (size_t)(3 * 32 + 16) * sizeof(real);
+    out[2] = (int)(lds_tail > lds ? lds_tail : lds);
+    return SVGP_OK;
+}
+// out[0..11]: registers per lane and scratch bytes per lane of the head, z and d kernels, the m = 32 instance then the run-time-m one
+extern "C" int svgp_fwd_split_regs(int* out) {
+    SVGP_REQUIRE(out, SVGP_ERR_INVALID, "out is NULL");
+    const void* k[6] = {reinterpret_cast<const void*>(k_gp_factor_fwd<32, true>), reinterpret_cast<const void*>(k_gp_factor_fwd<0, true>),
+                        reinterpret_cast<const void*>(k_gp_posterior_fwd<32, true>), reinterpret_cast<const void*>(k_gp_posterior_fwd<0, true>),
+                        reinterpret_cast<const void*>(k_gp_posterior_bwd_l<32, true>), reinterpret_cast<const void*>(k_gp_posterior_bwd_l<0, true>)};
+    for (int i = 0; i < 6; ++i) {
+        hipFuncAttributes fa;
+        SVGP_CHECK_HIP(hipFuncGetAttributes(&fa, k[i]));
+        out[2 * i] = fa.numRegs; out[2 * i + 1] = (int)fa.localSizeBytes;
+    }
+    return SVGP_OK;
 }
 // out[0..2] (riders), out[3..5] (no riders): registers per lane, scratch bytes per lane, dynamic LDS bytes of the launch at latent size L
 extern "C" int svgp_mnist_decoder_fused_regs(int L, int* out) {
     SVGP_REQUIRE(out, SVGP_ERR_INVALID, "out is NULL");
     SVGP_REQUIRE(L >= 1 && L <= 64, SVGP_ERR_INVALID, "L = %d (1..64)", L);
     hipFuncAttributes fa;
-    SVGP_CHECK_HIP(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(k_decoder_fwd_bwd_data<true>)));
+    SVGP_CHECK_HIP(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(k_decoder_fwd_bwd_data<1>)));
     out[0] = fa.numRegs; out[1] = (int)fa.localSizeBytes;
-    SVGP_CHECK_HIP(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(k_decoder_fwd_bwd_data<false>)));
+    SVGP_CHECK_HIP(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(k_decoder_fwd_bwd_data<0>)));
     out[3] = fa.numRegs; out[4] = (int)fa.localSizeBytes;
     out[2] = out[5] = (int)(svgp_vae::dec_fwd_bwd_lds(L) * sizeof(real));
     return SVGP_OK;
@@ -1869,7 +2047,12 @@ extern "C" int svgp_gp_stats_bwd_with_aji(const svgp_mnist_cfg* c, double* ws, c
 
 static inline int rows_per_block(int m) { return SVGP_BLOCK / m; }
 
-static int factor_fwd_impl(const svgp_mnist_cfg* c, double* ws, int defer_aji, void* stream);
+static int factor_fwd_impl(const svgp_mnist_cfg* c, double* ws, int defer_aji, void* stream, bool head = false);
+// SVGP_FWD_SPLIT (m <= 32): Si, t, mu_hat, u and q only; svgp_mnist_decoder_fwd_bwd_data_pre_tail finishes the stage
+extern "C" int svgp_gp_factor_fwd_head(const svgp_mnist_cfg* c, double* ws, void* stream) {
+    REQUIRE_FWD_SPLIT(c);
+    return factor_fwd_impl(c, ws, 1, stream, true);
+}
 extern "C" int svgp_gp_factor_fwd(const svgp_mnist_cfg* c, double* ws, void* stream) {
     return factor_fwd_impl(c, ws, 0, stream);
 }
@@ -1927,29 +2110,34 @@ extern "C" int svgp_gp_factor_bwd_channels_part(const svgp_mnist_cfg* c, int l0,
     return big_factor(c, ws, state, false, stream, BWD_PART[part], NEED_BIG_WIN_PART, true, l0, nl);
 }
 
-static int factor_fwd_impl(const svgp_mnist_cfg* c, double* ws, int defer_aji, void* stream) {
-    GET_LAYOUTS();
-    SVGP_REQUIRE(ws, SVGP_ERR_INVALID, "NULL device pointer");
-    if (c->m > SVGP_M_MAX) return svgp_big_factor_fwd(c, wl, ws, stream, 0, c->L, defer_aji ? SVGP_FWD_HEAD : SVGP_FWD_ALL);
+static FactArgs make_fact_args(const svgp_mnist_cfg* c, const svgp_mnist_ws_layout& wl, double* ws, int defer_aji) {
     FactArgs a;
     a.defer_aji = defer_aji; a.kl_form = c->kl_form; a.P = svgp_stat_parts(c);
     a.b = c->b; a.m = c->m; a.L = c->L; a.c = c->N_train / (double)c->b_global; a.jitter = c->jitter;
     a.K = ws + wl.K; a.Ki = ws + wl.Ki; a.ldK = ws + wl.ldK; a.S = ws + wl.S; a.v = ws + wl.v; a.Kn = ws + wl.Kn;
     a.Si = ws + wl.Si; a.t = ws + wl.t; a.G = ws + wl.G; a.A = ws + wl.A; a.Aji = ws + wl.Aji; a.mu = ws + wl.mu_hat;
     a.u = ws + wl.u; a.M2 = ws + wl.M2; a.KL = ws + wl.KL; a.q = ws + wl.q;
+    return a;
+}
+static int factor_fwd_impl(const svgp_mnist_cfg* c, double* ws, int defer_aji, void* stream, bool head) {
+    GET_LAYOUTS();
+    SVGP_REQUIRE(ws, SVGP_ERR_INVALID, "NULL device pointer");
+    if (c->m > SVGP_M_MAX) return svgp_big_factor_fwd(c, wl, ws, stream, 0, c->L, defer_aji ? SVGP_FWD_HEAD : SVGP_FWD_ALL);
+    const FactArgs a = make_fact_args(c, wl, ws, defer_aji);
     const int m = c->m, RB = rows_per_block(m);
     const size_t lds = mat_lds_pad(m, 4) + (size_t)(3 * m + 16 + SVGP_BLOCK) * sizeof(real);
-    int rc = m == 32 ? set_dyn_lds(k_gp_factor_fwd<32>, lds) : set_dyn_lds(k_gp_factor_fwd<0>, lds);
-    if (rc) return rc;
     const dim3 grid(c->L + (c->b + RB - 1) / RB);
-    if (m == 32) hipLaunchKernelGGL(k_gp_factor_fwd<32>, grid, dim3(SVGP_BLOCK), lds, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(k_gp_factor_fwd<0>, grid, dim3(SVGP_BLOCK), lds, (hipStream_t)stream, a);
-    SVGP_LAUNCH_CHECK();
+    LAUNCH_MC_FORM(k_gp_factor_fwd, m, head, grid, lds, stream, a);
     return SVGP_OK;
 }
 
 static int posterior_fwd_impl(const svgp_mnist_cfg* c, const double* eps, double* ws, double* state, bool with_aji,
-                              void* stream);
+                              void* stream, bool zform = false);
+// SVGP_FWD_SPLIT (m <= 32): p_m, p_v, e, eps, z and the CE partial from Si, t, u; d and the L3 partial: svgp_gp_posterior_bwd_rows_d
+extern "C" int svgp_gp_posterior_fwd_z(const svgp_mnist_cfg* c, const double* eps, double* ws, double* state, void* stream) {
+    REQUIRE_FWD_SPLIT(c);
+    return posterior_fwd_impl(c, eps, ws, state, false, stream, true);
+}
 extern "C" int svgp_gp_posterior_fwd(const svgp_mnist_cfg* c, const double* eps, double* ws, double* state,
                                      void* stream) {
     return posterior_fwd_impl(c, eps, ws, state, false, stream);
@@ -1961,7 +2149,7 @@ extern "C" int svgp_gp_posterior_fwd_with_aji(const svgp_mnist_cfg* c, const dou
     return posterior_fwd_impl(c, eps, ws, state, true, stream);
 }
 static int posterior_fwd_impl(const svgp_mnist_cfg* c, const double* eps, double* ws, double* state, bool with_aji,
-                              void* stream) {
+                              void* stream, bool zform) {
     GET_LAYOUTS();
     SVGP_REQUIRE(ws && state, SVGP_ERR_INVALID, "NULL device pointer");
     if (c->m > SVGP_M_MAX) return svgp_big_posterior_fwd(c, wl, eps, ws, state, stream);
@@ -1974,11 +2162,11 @@ static int posterior_fwd_impl(const svgp_mnist_cfg* c, const double* eps, double
     a.part = ws + wl.part_sums + (size_t)svgp_n_part(c) * 4;
     const int m = c->m, RB = rows_per_block(m), nb = (c->b + RB - 1) / RB;
     SVGP_REQUIRE((int64_t)c->L * nb <= wl.n_post, SVGP_ERR_INVALID, "partial-sum layout mismatch");
-    size_t lds = mat_lds(m, 2) + (size_t)(2 * m + SVGP_BLOCK + 4 * SVGP_BLOCK + 16) * sizeof(real);
+    size_t lds = mat_lds(m, zform ? 1 : 2) + (size_t)(2 * m + SVGP_BLOCK + (zform ? 3 : 4) * SVGP_BLOCK + 16) * sizeof(real);
     const size_t lds_inv = mat_lds(m, 1) + (size_t)(5 * m + 80) * sizeof(real);
     if (with_aji && lds_inv > lds) lds = lds_inv;
     a.nb = nb; a.with_aji = with_aji; a.jitter = c->jitter; a.Ahat = ws + wl.A; a.Aji = ws + wl.Aji; a.KL = ws + wl.KL;
-    LAUNCH_MC(k_gp_posterior_fwd, m, dim3(nb + (with_aji ? 1 : 0), c->L), lds, stream, a);
+    LAUNCH_MC_FORM(k_gp_posterior_fwd, m, zform, dim3(nb + (with_aji ? 1 : 0), c->L), lds, stream, a);
     return SVGP_OK;
 }
 
@@ -2116,7 +2304,8 @@ static int factor_bwd_impl(const svgp_mnist_cfg* c, double* ws, const double* st
     return SVGP_OK;
 }
 
-static int posterior_bwd_impl(const svgp_mnist_cfg* c, double* ws, const double* state, bool with_final, void* stream, int pass = 0);
+static int posterior_bwd_impl(const svgp_mnist_cfg* c, double* ws, const double* state, bool with_final, void* stream, int pass = 0,
+                              bool dform = false);
 extern "C" int svgp_gp_posterior_bwd(const svgp_mnist_cfg* c, double* ws, const double* state, void* stream) {
     return posterior_bwd_impl(c, ws, state, false, stream);
 }
@@ -2136,17 +2325,21 @@ static PostBwdArgs make_pb(const svgp_mnist_cfg* c, const svgp_mnist_ws_layout& 
     a.nb_rows = nb; a.n_final = with_final ? (m * m + SVGP_BLOCK - 1) / SVGP_BLOCK : 0;
     a.b_global = c->b_global; a.N_train = c->N_train;
     a.Kbar_part = ws + wl.fb_part; a.Kbar = ws + wl.Kbar;
+    a.M2 = ws + wl.M2; a.knn = ws + wl.knn; a.q = ws + wl.q; a.d_out = ws + wl.d;
+    a.part = ws + wl.part_sums + (size_t)svgp_n_part(c) * 4;
     return a;
 }
 // pass: 0 = both passes, 1 = the per-channel row terms only (ybar, s2bar, the (L, b, m) partials of Knbar)
-static int posterior_bwd_impl(const svgp_mnist_cfg* c, double* ws, const double* state, bool with_final, void* stream, int pass) {
+static int posterior_bwd_impl(const svgp_mnist_cfg* c, double* ws, const double* state, bool with_final, void* stream, int pass,
+                              bool dform) {
     GET_LAYOUTS();
     SVGP_REQUIRE(ws && state, SVGP_ERR_INVALID, "NULL device pointer");
     if (c->m > SVGP_M_MAX) return svgp_big_posterior_bwd(c, wl, ws, state, stream);
     PostBwdArgs a = make_pb(c, wl, ws, state, with_final);
     const int m = c->m, nb = a.nb_rows;
-    const size_t lds = mat_lds(m, 3) + (size_t)(3 * m + SVGP_BLOCK + 2 * SVGP_BLOCK) * sizeof(real);
-    LAUNCH_MC(k_gp_posterior_bwd_l, m, dim3(nb, c->L), lds, stream, a);
+    SVGP_REQUIRE(!dform || (int64_t)c->L * nb <= wl.n_post, SVGP_ERR_INVALID, "partial-sum layout mismatch");
+    const size_t lds = mat_lds(m, dform ? 4 : 3) + (size_t)(3 * m + SVGP_BLOCK + (dform ? 3 * SVGP_BLOCK + 16 : 2 * SVGP_BLOCK)) * sizeof(real);
+    LAUNCH_MC_FORM(k_gp_posterior_bwd_l, m, dform, dim3(nb, c->L), lds, stream, a);
     if (pass == 1) return SVGP_OK;
     const size_t lds2 = mat_lds(m, 1) + (size_t)(SVGP_BLOCK + (SVGP_BLOCK / m) * (1 + c->L)) * sizeof(real);
     LAUNCH_MC(k_gp_posterior_bwd_sum, m, dim3(nb + a.n_final), lds2, stream, a);
@@ -2157,4 +2350,15 @@ static int posterior_bwd_impl(const svgp_mnist_cfg* c, double* ws, const double*
 extern "C" int svgp_gp_posterior_bwd_rows(const svgp_mnist_cfg* c, double* ws, const double* state, void* stream) {
     SVGP_REQUIRE(c && c->m <= SVGP_M_MAX, SVGP_ERR_UNSUPPORTED, "the two-pass reverse row stage exists for m <= %d", SVGP_M_MAX);
     return posterior_bwd_impl(c, ws, state, true, stream, 1);
+}
+// SVGP_FWD_SPLIT (m <= 32), behind svgp_gp_posterior_fwd_z and svgp_mnist_decoder_fwd_bwd_data_pre_tail: pass 1 also forms d and the
+// L3 partials, which that row stage left out (same bits as svgp_gp_posterior_fwd's)
+extern "C" int svgp_gp_posterior_bwd_rows_d(const svgp_mnist_cfg* c, double* ws, const double* state, void* stream) {
+    REQUIRE_FWD_SPLIT(c);
+    return posterior_bwd_impl(c, ws, state, true, stream, 1, true);
+}
+// internal (api.hip): svgp_gp_posterior_bwd_with_final with pass 1 in that form (the step's routes that keep pass 2 in this stage)
+int svgp_gp_posterior_bwd_with_final_d(const svgp_mnist_cfg* c, double* ws, const double* state, void* stream) {
+    REQUIRE_FWD_SPLIT(c);
+    return posterior_bwd_impl(c, ws, state, true, stream, 0, true);
 }

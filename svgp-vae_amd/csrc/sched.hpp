@@ -13,6 +13,7 @@ struct SvgpSched {
     bool stat_merge;      // SVGP_STAT_MERGE    m <= 64, single GPU: reverse statistics ride in the reverse factor launch; 0: their own
     bool aji_dec;         // SVGP_AJI_DEC       m <= 32: deferred (A_hat + jI)^-1 rides in the decoder's data-reverse launch; 0: row stage
     bool dec_fuse;        // SVGP_DEC_FUSE      m <= 64, split on: decoder forward + data-reverse launches as ONE launch; 0: two launches
+    bool fwd_split;       // SVGP_FWD_SPLIT     m <= 32, decoder riders + fused decoder on: only Si, t, u ahead of the decoder (step_plan.hpp); 0: full forms
     bool stat_four;       // SVGP_STAT_FOUR     set (any value): the four-matrix form of the merged statistics launch also where five fit
     bool konly_branch;    // SVGP_KONLY_BRANCH  64 < m < 512: the kernel-matrix-only block of the forward factor stage on side branch 1; 0: in line
     bool kbar_branch;     // SVGP_KBAR_BRANCH   m > 64: the single-matrix chain of the gradient of Ki beside the channel block; 0: in line
@@ -34,6 +35,7 @@ inline SvgpSched sched_read() {
     s.stat_merge = on("SVGP_STAT_MERGE");
     s.aji_dec = on("SVGP_AJI_DEC");
     s.dec_fuse = on("SVGP_DEC_FUSE");
+    s.fwd_split = on("SVGP_FWD_SPLIT");
     s.stat_four = getenv("SVGP_STAT_FOUR") != nullptr;
     s.konly_branch = on("SVGP_KONLY_BRANCH");
     s.kbar_branch = on("SVGP_KBAR_BRANCH");

@@ -98,6 +98,11 @@ struct StepOp { unsigned char kind, lane, stage, part; unsigned arg; };
 struct StepPlan {
     int n = 0;
     bool side = false;      // the call looks up (the first time: creates) the side branches of the caller's stream
+    // m <= 32 (SVGP_FWD_SPLIT): four launch slots run another form of their entry -- the forward factor stage its head form (Si, t,
+    // mu_hat, u, q), the forward row stage its z form (no d, no L3 partial), the fused decoder launch the riders that finish the
+    // factor stage (G, A, M2, Aji, KL), pass 1 of the reverse row stage its d form (d, L3 partial).  The slots and their names in the
+    // route text stay; svgp_mnist_step_route_forms prints the forms.
+    bool fwd_split = false;
     bool early = false;     // the plan issues the early reverse factor half on branch 1: the late half alone may follow
     bool sharded = false;   // the channel-sharded form: stages run on a copy of cfg with rep_weight 1
     bool pack = false;      // ... whose symmetric blocks travel tile-packed: the workspace must carry the wire buffer
@@ -147,6 +152,10 @@ inline int step_plan(const svgp_mnist_cfg* c, int form, int phase, int nranks, i
     // between), the split gradient exchange (phase 4) or SVGP_ENC_KM_MERGE=0.
     const bool sum_rides = !large && !fork2 && !c->titsias && sc.enc_km_merge && sc.sum_merge;
     const bool aji_in_dec = c->m <= 32 && !c->titsias && sc.dec_split && sc.aji_dec;
+    // Everything of the forward factor stage behind Si, t, u, and the d / L3 half of the forward row stage, is first read BEHIND the
+    // decoder launch: it rides there (the riders that already finish (A_hat + jI)^-1) and in pass 1 of the reverse row stage.  Only
+    // where the step is issued whole (a stand-alone phase 1 must leave d, M2 and KL behind) and the fused decoder launch has riders.
+    P.fwd_split = (form == STEP_FORM_STEP || form == STEP_FORM_DP) && aji_in_dec && sc.dec_fuse && sc.fwd_split;
     // the reverse statistics at the head of the reverse factor launch: only where nothing is exchanged between the two
     const bool stat_rides = defer == 2 && !large && !c->titsias && c->L <= 56 && sc.dec_split && sc.stat_merge;
     // The late reverse half alone is valid only if the early half was issued on this workspace: a whole-step form knows, the

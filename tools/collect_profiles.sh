@@ -4,6 +4,11 @@
 # (copy what is to be judged into profiles/ afterwards; see profiles/README.md)
 #        bash tools/collect_profiles.sh <tag> <commit> cfg2-kernels   -> only <tag>_cfg2_kernel_stats.csv + <tag>_commit.txt in the output directory:
 #        the per-kernel table of the config-2 step alone (no --full: the stage table would launch every entry point by name)
+#        A before / after pair is two such calls, each from the root of its own built checkout (the tree the script is started in is
+#        the one whose bench.py and library run): decfuse_parent / decfuse_head, and for SVGP_FWD_SPLIT
+#        bash tools/collect_profiles.sh fwdsplit_parent <parent commit> cfg2-kernels   (in the parent's tree)
+#        bash tools/collect_profiles.sh fwdsplit_head <head commit> cfg2-kernels       (in this tree)
+#        -> profiles/fwdsplit_{parent,head}_cfg2_kernel_stats.csv + _commit.txt
 tag=${1:-rXX}
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out

@@ -1,7 +1,9 @@
 """Development probe (round 6): the decoder reverse pass as data half + weight half (riders of the reverse factor launch).
 Prints (1) equality of the two forms, (2) stand-alone times of every piece -- the fused forward + data-reverse launch
 (SVGP_DEC_FUSE) next to the two launches it replaces, with and without riders --, (3) the eager config-2 step with
-SVGP_DEC_SPLIT=0/1 and the later switches, SVGP_DEC_FUSE=0/1 last (child processes: one setting per process)."""
+SVGP_DEC_SPLIT=0/1 and the later switches, SVGP_DEC_FUSE=0/1 and then SVGP_FWD_SPLIT=0/1 last (child processes: one setting per
+process).  The stand-alone table carries the four SVGP_FWD_SPLIT forms (forward factor head, forward row z form, decoder launch with
+the tail riders, reverse row pass 1 in its d form) next to the full forms they replace in the step."""
 import ctypes as C
 import json
 import os
@@ -34,7 +36,7 @@ def child():
             eng.run(adam=True)
         eng.synchronize()
         best = min(best, (time.perf_counter() - t0) / reps * 1e6)
-    print(json.dumps(dict(split=os.environ.get("SVGP_DEC_SPLIT", "1"), merge=os.environ.get("SVGP_ENC_KM_MERGE", ""), sum_merge=os.environ.get("SVGP_SUM_MERGE", ""), stat_merge=os.environ.get("SVGP_STAT_MERGE", ""), aji_dec=os.environ.get("SVGP_AJI_DEC", ""), dec_fuse=os.environ.get("SVGP_DEC_FUSE", ""), step_us=best, elbo=eng.scalars()["elbo"])), flush=True)
+    print(json.dumps(dict(split=os.environ.get("SVGP_DEC_SPLIT", "1"), merge=os.environ.get("SVGP_ENC_KM_MERGE", ""), sum_merge=os.environ.get("SVGP_SUM_MERGE", ""), stat_merge=os.environ.get("SVGP_STAT_MERGE", ""), aji_dec=os.environ.get("SVGP_AJI_DEC", ""), dec_fuse=os.environ.get("SVGP_DEC_FUSE", ""), fwd_split=os.environ.get("SVGP_FWD_SPLIT", ""), step_us=best, elbo=eng.scalars()["elbo"])), flush=True)
 
 
 def main():
@@ -52,7 +54,7 @@ def main():
     eng.run(adam=False)
     eng.synchronize()
     cfg, th, ws, st = C.byref(eng.cfg), eng.theta.data_ptr(), eng.ws.data_ptr(), eng.state.data_ptr()
-    img = eng._bound[0].data_ptr()
+    img, ep = eng._bound[0].data_ptr(), eng._bound[2].data_ptr()
     s = eng.stream.cuda_stream
     n_dec = eng.pl.n_vae - eng.pl.n_enc
 
@@ -118,21 +120,36 @@ def main():
             ("encoder_bwd_km_sum", "svgp_mnist_encoder_bwd_km_sum", (cfg, th, img, eng._bound[1].data_ptr(), ws, st, s)),
             ("gp_posterior_bwd_with_final", "svgp_gp_posterior_bwd_with_final", (cfg, ws, st, s)),
             ("gp_posterior_bwd_rows", "svgp_gp_posterior_bwd_rows", (cfg, ws, st, s)),
-            ("grad_reduce_all", "svgp_mnist_grad_reduce_all", (cfg, eng._bound[1].data_ptr(), ws, s))]
+            ("grad_reduce_all", "svgp_mnist_grad_reduce_all", (cfg, eng._bound[1].data_ptr(), ws, s)),
+            # SVGP_FWD_SPLIT: the full form of each of the four slots, then the form the step runs there
+            ("gp_factor_fwd_defer_aji", "svgp_gp_factor_fwd_defer_aji", (cfg, ws, s)),
+            ("gp_factor_fwd_head", "svgp_gp_factor_fwd_head", (cfg, ws, s)),
+            ("gp_posterior_fwd", "svgp_gp_posterior_fwd", (cfg, ep, ws, st, s)),
+            ("gp_posterior_fwd_z", "svgp_gp_posterior_fwd_z", (cfg, ep, ws, st, s)),
+            ("decoder_fwd_bwd_data_pre_aji (again)", "svgp_mnist_decoder_fwd_bwd_data_pre_aji", (cfg, th, img, ws, st, s)),
+            ("decoder_fwd_bwd_data_pre_tail", "svgp_mnist_decoder_fwd_bwd_data_pre_tail", (cfg, th, img, ws, st, s)),
+            ("gp_posterior_bwd_rows (again)", "svgp_gp_posterior_bwd_rows", (cfg, ws, st, s)),
+            ("gp_posterior_bwd_rows_d", "svgp_gp_posterior_bwd_rows_d", (cfg, ws, st, s))]
     us = {}
     for name, sym, args in rows:
         us[name] = timeit(sym, args)
-        print(f"{name:32s} {us[name]:7.2f} us", flush=True)
+        print(f"{name:40s} {us[name]:7.2f} us", flush=True)
     for sfx in ("", "_aji"):
         pair = us["decoder_fwd_pre"] + us["decoder_bwd_data_pre" + sfx]
         print(f"fused{sfx:5s} {us['decoder_fwd_bwd_data_pre' + sfx]:6.2f} us against {us['decoder_fwd_pre']:.2f} + "
               f"{us['decoder_bwd_data_pre' + sfx]:.2f} = {pair:.2f} us (stand-alone, no boundary between the two)", flush=True)
     # (the KL terms the riders of the _aji rows decremented 200 times over are rebuilt by every step of the children below)
-    for flag, sm, st_, aj, fu in (("0", "0", "0", "0", "0"), ("1", "1", "0", "0", "0"), ("1", "1", "1", "0", "0"), ("1", "1", "1", "1", "0"),
-                                  ("1", "1", "1", "1", "1"), ("1", "1", "1", "1", "0"), ("1", "1", "1", "1", "1"), ("1", "1", "1", "1", "0"),
-                                  ("1", "1", "1", "1", "1"), ("1", "1", "1", "0", "0"), ("1", "1", "1", "0", "1")):
+    old = sum(us[k] for k in ("gp_factor_fwd_defer_aji", "gp_posterior_fwd", "decoder_fwd_bwd_data_pre_aji (again)", "gp_posterior_bwd_rows (again)"))
+    new = sum(us[k] for k in ("gp_factor_fwd_head", "gp_posterior_fwd_z", "decoder_fwd_bwd_data_pre_tail", "gp_posterior_bwd_rows_d"))
+    print(f"SVGP_FWD_SPLIT, the four slots stand-alone: {new:.2f} us against {old:.2f} us", flush=True)
+    for flag, sm, st_, aj, fu, fs in (("0", "0", "0", "0", "0", "0"), ("1", "1", "0", "0", "0", "0"), ("1", "1", "1", "0", "0", "0"),
+                                      ("1", "1", "1", "1", "0", "0"), ("1", "1", "1", "1", "1", "0"), ("1", "1", "1", "1", "0", "0"),
+                                      ("1", "1", "1", "1", "1", "0"), ("1", "1", "1", "1", "0", "0"), ("1", "1", "1", "1", "1", "0"),
+                                      ("1", "1", "1", "0", "0", "0"), ("1", "1", "1", "0", "1", "0"), ("1", "1", "1", "1", "1", "1"),
+                                      ("1", "1", "1", "1", "1", "0"), ("1", "1", "1", "1", "1", "1"), ("1", "1", "1", "1", "1", "0"),
+                                      ("1", "1", "1", "1", "1", "1")):
         env = dict(os.environ, SVGP_DEC_SPLIT=flag, SVGP_ENC_KM_MERGE=flag, SVGP_SUM_MERGE=sm, SVGP_STAT_MERGE=st_, SVGP_AJI_DEC=aj,
-                   SVGP_DEC_FUSE=fu)
+                   SVGP_DEC_FUSE=fu, SVGP_FWD_SPLIT=fs)
         r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child"], env=env, capture_output=True, text=True)
         print(r.stdout.strip().splitlines()[-1] if r.stdout.strip() else r.stderr[-2000:], flush=True)
 
