@@ -189,7 +189,7 @@ const char* svgp_last_error(void);
 /* sizeof() of the ABI structs as compiled into the library, so a binding can verify its own mirror of a struct at load
  * time (a stale mirror shifts every later field silently): which = 0 svgp_mnist_cfg, 1 svgp_mnist_param_layout,
  * 2 svgp_mnist_ws_layout, 3 svgp_stream_kdesc, 4 svgp_conv_desc, 5 svgp_sprites_kcfg, 6 svgp_pearce_bufs,
- * 7 svgp_sum_job, 8 svgp_casale_cfg, 9 svgp_casale_layout, 10 svgp_ball_large_cfg; -1 otherwise. */
+ * 7 svgp_sum_job, 8 svgp_casale_cfg, 9 svgp_casale_layout, 10 svgp_ball_large_cfg, 11 svgp_mnist_cache_layout; -1 otherwise. */
 int         svgp_struct_sizeof(int which);
 
 int svgp_mnist_param_layout_get(const svgp_mnist_cfg* cfg, svgp_mnist_param_layout* out);
@@ -1023,6 +1023,50 @@ int svgp_mean_vectors_bias(int L, int m, const double* acc, const double* full, 
  *   2 <= H, W <= 64 (else SVGP_ERR_UNSUPPORTED); n < 0, A < 1 or a NULL pointer -> SVGP_ERR_INVALID; all before any launch.
  *   n = 0 returns SVGP_OK and launches nothing.                                                                            */
 int svgp_rotate_cubic_f64(int n, int H, int W, int A, const double* images, const double* cos_sin, double* out, void* stream);
+
+/* ---- posterior cache and conditional generation (generate.hip) --------------------------------------
+ * The GP posterior of mainSVGP.approximate_posterior_params (SVGPVAE_model.py:303-343) depends on the train set only through
+ *   Sigma_l = K_mm + c S_l,  S_l = K_mn diag(1/var_l) K_nm,  v_l = K_mn (mu_l / var_l),  c = N_train / rows
+ *   w_l = c (Sigma_l + jI)^-1 v_l   (L, m)          X_l = (Sigma_l + jI)^-1 - (K_mm + jI)^-1   (L, m, m)
+ *   p_m[x,l] = k_x . w_l            p_v[x,l] = k_xx + k_x^T X_l k_x            k_x = K(x, inducing points)
+ * so [w | X] is accumulated once over the train set in row chunks (no N-row workspace) and a query needs no train row.
+ * The cache is ONE float64 array; svgp_mnist_cache_layout_get gives its offsets in elements (each field on a 16-element
+ * boundary, as the workspace's): acc_S (L,m,m) and acc_v (L,m) the raw sums over the accumulated rows (the factor c is NOT in
+ * them), acc_rows (1) their row count, then w and X.  m, L, M, n_obj, normalize_obj, jitter and N_train come from the cfg.
+ *
+ * svgp_gp_stats_accumulate: behind svgp_gp_stats_fwd on the same workspace and cfg (cfg->b rows): acc_S / acc_v += the
+ *   statistics in ws.statA (m <= 64: the P row partials of a channel are added in index order first, as the consumers do on
+ *   load), acc_rows += b; first != 0 overwrites instead.  One thread per element, no atomics: after k calls the value is the
+ *   left-to-right float64 sum over the chunks.
+ * svgp_mnist_cache_build: K_mm from theta, c = cfg->N_train / acc_rows read ON THE DEVICE, the two jittered inverses (m <= 64:
+ *   one launch, the LDS sweep of the factor stage; beyond: svgp_spd_inverse_batched on the (L + 1) matrices), then w and X;
+ *   X is written exactly symmetric ((D + D^T) / 2 of D = Sigma^-1 - K^-1).  work: svgp_mnist_cache_workspace_elems(cfg)
+ *   doubles (0 for m <= 64: work may then be NULL).
+ * svgp_mnist_generate: cfg->b query rows aux (b, 2+M) = [id, angle, o_1..o_M] -> images_out (b,28,28,1) = decode(z),
+ *   z = p_m + eps sqrt(p_v); eps (b, L) may be NULL: z = p_m (no device generator, `state` is not an argument).  gather != 0:
+ *   the object vector of a row is table[(int)row[0]] (needs n_obj > 0; a row whose id is outside [0, n_obj) gets NaN images
+ *   and moments instead of an out-of-range read), gather == 0: the row's own columns 2:.  p_m_out / p_v_out (b, L) may each be
+ *   NULL.  No image input, no loss.  m <= 64: exactly ONE launch for any b (kernel row, moments, sample and decoder per image in a
+ *   workgroup that strides over the images; X is read through L2); 64 < m <= 2048: k_x by a bounds-checked kernel with the
+ *   arithmetic of svgp_kernel_matrix_xy, K_x X_l and K_x w^T by svgp_dgemm_batched into `work`, a row-sum kernel, then the same
+ *   generation kernel with z given.  The out-of-table rule above holds on both routes.  work:
+ *   svgp_mnist_generate_workspace_elems(cfg) doubles, sized for max(cfg->b, cfg->b_cap) rows; 0 for m <= 64 (work may be NULL).
+ * svgp_mnist_generate_route: the kernels of one svgp_mnist_generate call as text, one name per line in launch order, from the
+ *   plan the call itself executes; needs no device.
+ * All: svgp_check_cfg's refusals (m > 2048, L > 64, M > 128 -> SVGP_ERR_UNSUPPORTED), then NULL pointers, b < 1, gather with
+ *   n_obj = 0, NULL work where the size is non-zero -> SVGP_ERR_INVALID; every refusal before any pointer is looked at and
+ *   before any launch.  Explicit stream, no allocation, no synchronisation, capturable.                                     */
+typedef struct {
+    int64_t acc_S, acc_v, acc_rows, w, X, total;
+} svgp_mnist_cache_layout;
+int svgp_mnist_cache_layout_get(const svgp_mnist_cfg* cfg, svgp_mnist_cache_layout* out);
+int svgp_gp_stats_accumulate(const svgp_mnist_cfg* cfg, const double* ws, double* cache, int first, void* stream);
+long long svgp_mnist_cache_workspace_elems(const svgp_mnist_cfg* cfg);
+int svgp_mnist_cache_build(const svgp_mnist_cfg* cfg, const double* theta, double* cache, double* work, void* stream);
+long long svgp_mnist_generate_workspace_elems(const svgp_mnist_cfg* cfg);
+int svgp_mnist_generate(const svgp_mnist_cfg* cfg, const double* theta, const double* cache, const double* aux, int gather,
+                        const double* eps, double* images_out, double* p_m_out, double* p_v_out, double* work, void* stream);
+int svgp_mnist_generate_route(const svgp_mnist_cfg* cfg, char* buf, int cap);
 
 /* ---- runtime helpers: HIP graphs and events without going through torch ---------------------*/
 int svgp_stream_create(void** stream_out);

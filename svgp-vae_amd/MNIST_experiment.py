@@ -13,6 +13,9 @@ generation MSE on the test set (:457-486) and `pics/test_metrics.txt` lines `epo
 between the epoch's average of the per-step inducing mean vectors and the ones of the whole train set; `--save_latents`
 (:181-187, 531-541; needs `--save`) pickles the latent samples of the whole train set after the last epoch to
 `latents_train_full.p`.  Both are wired for the two SVGPVAE objectives only.
+`--restore RUN/model_<k>.pt [--first_epoch K]` (the two SVGPVAE objectives) resumes a run from a checkpoint that `--save
+--save_model_weights` wrote: the epochs K .. nr_epochs - 1 (default K = k + 1) run with their own indices, so with
+`--epsilon_seed` the resumed run is the tail of the uninterrupted one (svgp_vae_amd/checkpoint.py).
 Accepted without effect: `--test_set_metrics` (it selects the split of the reference's pandas rows, which this build does not
 write), `--show_pics` (no plots) and `--ram` (the reference's TensorFlow memory fraction).
 `--elbo SVIGP_Hensman` mirrors run_experiment_rotated_mnist_SVIGP_Hensman (:544-760): deep SVIGP with free variational
@@ -82,6 +85,11 @@ def build_parser():
     p.add_argument('--split_grad_exchange', action='store_true',
                    help="data parallel: the gradient all-reduce in two parts, the first (decoder + GP parameters) beside the encoder's "
                         "reverse pass (cfg.split_grad_exchange; a fallback for slow small-message all-reduces)")
+    p.add_argument('--restore', type=str, default=None,
+                   help="SVGPVAE_Hensman / SVGPVAE_Titsias: a model_<epoch>.pt written by --save --save_model_weights; parameters, Adam "
+                        "moments and the device state vector are loaded into the engine before the first step")
+    p.add_argument('--first_epoch', type=int, default=None,
+                   help="index of the first epoch to run; default: k + 1 when --restore names a model_<k>.pt, else 0")
     p.add_argument('--log_json', type=str, default=None,
                    help="rank 0 writes the per-step log (elbo, recon_loss, C_ma, lagrange_mult), the evaluation series and the "
                         "final flat parameter vector to this file")
@@ -159,8 +167,18 @@ def run_experiment_rotated_mnist_SVGPVAE(args, args_dict=None, ctx=None):
     eng = rt.eng
     dev = eng.device
     comm_fallback = attach_library_comm(eng, ctx)
+    first_epoch = 0
+    if getattr(args, "restore", None):           # every rank loads the same file: the parameters stay replicated
+        from . import checkpoint
+        checkpoint.restore(eng, args.restore)
+        given = getattr(args, "first_epoch", None)
+        first_epoch = checkpoint.first_epoch_of(args.restore) if given is None else given
+    elif getattr(args, "first_epoch", None):
+        first_epoch = args.first_epoch
     if root:
         print(f"Number of train params: {eng.pl.n_total}")
+        if getattr(args, "restore", None):
+            print(f"Restored {args.restore}; first epoch {first_epoch}", flush=True)
         if ctx.multi:
             print(f"Data parallel over {ctx.world} ranks: " + ("RCCL communicator of the library, collectives on the compute stream"
                   if eng.comm is not None else f"torch.distributed all-reduces between the phases ({comm_fallback})"), flush=True)
@@ -264,7 +282,7 @@ def run_experiment_rotated_mnist_SVGPVAE(args, args_dict=None, ctx=None):
     start = time.time()
 
     log = run_sharded_epochs(ctx, train_batches, nr_epochs, local_step, N_train=N_train, on_epoch_end=on_epoch_end,
-                             on_epoch_start=on_epoch_start)
+                             on_epoch_start=on_epoch_start, first_epoch=first_epoch)
     log.setdefault("eval_mse", []); log.setdefault("cgen_mse", [])
     if args.bias_analysis:
         log.setdefault("bias", [])
@@ -287,13 +305,23 @@ def run_experiment_rotated_mnist_SVGPVAE(args, args_dict=None, ctx=None):
         json.dump(dict({k: v for k, v in log.items()}, theta=eng.theta.cpu().tolist(), adam_t=eng.scalars()["adam_t"],
                        param_order=list(eng.shapes)), open(args.log_json, "wt"))
     log["_engine"] = eng                     # (the final parameters / optimiser state for callers; not serialised)
+    log["chkpnt_dir"] = chkpnt_dir           # (where --save wrote args.json and the model_<epoch>.pt files; None without it)
     if latents is not None:
         log["_latents"] = latents            # (N, L) device tensor of --save_latents; not serialised
     return log
 
 
+def _refuse_restore(args):
+    """--restore / --first_epoch exist for the two SVGPVAE objectives only; the other drivers refuse them instead of training
+    from scratch."""
+    if getattr(args, "restore", None) or getattr(args, "first_epoch", None):
+        raise NotImplementedError(f"--restore / --first_epoch are implemented for --elbo SVGPVAE_Hensman | SVGPVAE_Titsias, "
+                                  f"not for --elbo {args.elbo}")
+
+
 def run_experiment_rotated_mnist_SVIGP_Hensman(args, args_dict=None):
     """MNIST_experiment.py:544-760.  Returns a dict of the logged series."""
+    _refuse_restore(args)
     from .SVIGP_Hensman_model import SVIGP_Hensman, SVIGP_Hensman_decoder, SvigpStepEngine
     np.random.seed(args.seed)
     n = len(args.dataset)
@@ -361,6 +389,7 @@ def run_experiment_rotated_mnist_SVIGP_Hensman(args, args_dict=None):
 
 def run_experiment_rotated_mnist_Casale(args, args_dict=None):
     """MNIST_experiment.py:786-1110.  Returns a dict of the logged series (per-step ELBO included)."""
+    _refuse_restore(args)
     from .GPVAE_Casale_model import CasaleStepEngine, _angles_mask, casaleGP, sort_train_data
     np.random.seed(args.seed)
     n = len(args.dataset)

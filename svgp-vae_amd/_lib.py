@@ -99,6 +99,11 @@ class CasaleLayout(C.Structure):
     _fields_ = [(n, C.c_int64) for n in CASALE_FIELDS]
 
 
+class CacheLayout(C.Structure):
+    """svgp_mnist_cache_layout (include/svgpvae_hip.h): offsets into the posterior cache, in float64 elements."""
+    _fields_ = [(n, C.c_int64) for n in ("acc_S", "acc_v", "acc_rows", "w", "X", "total")]
+
+
 STATE = dict(C_MA=0, LAGRANGE=1, ALPHA=2, ADAM_T=3, LR=4, BETA=5, ELBO=6, RECON_LOSS=7, KL_TERM=8,
              INSIDE_ELBO=9, CE_TERM=10, INSIDE_RECON=11, INSIDE_KL=12, RNG_CTR=13)
 STATE_LEN = 16
@@ -298,6 +303,11 @@ SIGNATURES = {
     "svgp_mean_vectors_accumulate": [C.c_int, C.c_int, _P, _P, _P],
     "svgp_mean_vectors_bias": [C.c_int, C.c_int, _P, _P, _P, _P],
     "svgp_rotate_cubic_f64": [C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P],
+    "svgp_mnist_cache_layout_get": [_CFG, C.POINTER(CacheLayout)],
+    "svgp_gp_stats_accumulate": [_CFG, _P, _P, C.c_int, _P],
+    "svgp_mnist_cache_build": [_CFG, _P, _P, _P, _P],
+    "svgp_mnist_generate": [_CFG, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P],
+    "svgp_mnist_generate_route": [_CFG, C.c_char_p, C.c_int],
     "svgp_stream_create": [C.POINTER(_P)],
     "svgp_stream_destroy": [_P],
     "svgp_stream_sync": [_P],
@@ -333,6 +343,8 @@ NON_STATUS = {"svgp_version": ([], C.c_int), "svgp_last_error": ([], C.c_char_p)
               "svgp_pearce_long_workspace_elems": ([C.c_int, C.c_int, C.c_int, C.c_int], C.c_size_t),
               "svgp_ball_large_workspace_elems": ([C.POINTER(BallLargeCfg)], C.c_longlong),
               "svgp_svigp_workspace_elems": ([C.c_int, C.c_int, C.c_int], C.c_longlong),
+              "svgp_mnist_cache_workspace_elems": ([_CFG], C.c_longlong),
+              "svgp_mnist_generate_workspace_elems": ([_CFG], C.c_longlong),
               "svgp_svigp_scale_offset": ([C.c_int, C.c_int, C.c_int], C.c_longlong)}
 
 _lib = None
@@ -362,7 +374,7 @@ def load_library(path=None):
         fn.restype = restype
     # the ctypes mirrors must have the layout the library was compiled with (svgp_struct_sizeof)
     for which, cls in enumerate((MnistCfg, ParamLayout, WsLayout, StreamKdesc, ConvDesc, SpritesKcfg, PearceBufs, SumJob,
-                                 CasaleCfg, CasaleLayout, BallLargeCfg)):
+                                 CasaleCfg, CasaleLayout, BallLargeCfg, CacheLayout)):
         if lib.svgp_struct_sizeof(which) != C.sizeof(cls):
             raise SvgpError(f"{p}: sizeof({cls.__name__}) is {lib.svgp_struct_sizeof(which)} in the library but "
                             f"{C.sizeof(cls)} in the binding; rebuild the library or update _lib.py")

@@ -33,6 +33,7 @@ extern "C" int svgp_struct_sizeof(int which) {
     case 8: return (int)sizeof(svgp_casale_cfg);
     case 9: return (int)sizeof(svgp_casale_layout);
     case 10: return (int)sizeof(svgp_ball_large_cfg);
+    case 11: return (int)sizeof(svgp_mnist_cache_layout);
     default: return -1;
     }
 }

@@ -1676,6 +1676,49 @@ __global__ __launch_bounds__(VAE_NT) void k_decoder_fwd_bwd_data(svgp_vae::DecFw
     svgp_vae::decoder_fwd_bwd_data_images(d, l, (int)gridDim.x - (RIDE ? a.L : 0), smem);
 }
 
+// =============================================================================================
+// posterior cache, m <= 64 (svgp_mnist_cache_build, generate.hip): one workgroup per channel.  K_mm from the inducing points
+// (the arithmetic of svgp_km_fwd_element), c = N_train / accumulated rows read on the device, (K + c S_l + jI)^-1 and (K + jI)^-1
+// by the LDS sweep of the factor stage, w_l = c Sigma_l^-1 v_l, X_l = Sigma_l^-1 - K^-1 stored as (D + D^T) / 2: the sum of two
+// numbers does not depend on their order, so X is symmetric bit for bit.
+// =============================================================================================
+struct CacheArgs {
+    int m, L;
+    real N_train, jitter;
+    KernArgs ka;             // b = 0: only the K_mm elements exist
+    const real* accS; const real* accv; const real* rows;
+    real* w; real* X;
+};
+__global__ __launch_bounds__(SVGP_BLOCK) void k_cache_build(CacheArgs a) {
+    extern __shared__ __align__(16) real smem[];
+    const int m = a.m, ld = m + 1, l = blockIdx.x;
+    real* Kd = smem;                  // m x m, dense
+    real* A = Kd + m * m;             // m x ld: Sigma_l, then its inverse
+    real* B = A + m * ld;             // m x ld: K + jI, then its inverse
+    real* W = B + m * ld;             // 5 m + 80: scratch of the sweep
+    real* vv = W + 5 * m + 80;        // m
+    real* wv = vv + m;                // m
+    const real c = a.N_train / a.rows[0];
+    for (int o = threadIdx.x; o < m * m; o += blockDim.x) svgp_km_fwd_element(a.ka, o, Kd, nullptr, nullptr);
+    __syncthreads();
+    const size_t om = (size_t)l * m * m;
+    for (int o = threadIdx.x; o < m * m; o += blockDim.x) {
+        const int i = o / m, j = o % m;
+        const real jit = i == j ? a.jitter : real(0);
+        A[i * ld + j] = Kd[o] + c * a.accS[om + o] + jit;
+        B[i * ld + j] = Kd[o] + jit;
+    }
+    if ((int)threadIdx.x < m) vv[threadIdx.x] = a.accv[(size_t)l * m + threadIdx.x];
+    chol_inv(A, W, ld, m);
+    chol_inv(B, W, ld, m);
+    mat_vec(wv, A, ld, vv, m, c);
+    if ((int)threadIdx.x < m) a.w[(size_t)l * m + threadIdx.x] = wv[threadIdx.x];
+    for (int o = threadIdx.x; o < m * m; o += blockDim.x) {
+        const int i = o / m, j = o % m;
+        a.X[om + o] = real(0.5) * ((A[i * ld + j] - B[i * ld + j]) + (A[j * ld + i] - B[j * ld + i]));
+    }
+}
+
 template <typename F>
 int set_dyn_lds(F kernel, size_t bytes) {
     SVGP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
@@ -1986,6 +2029,23 @@ extern "C" int svgp_kernel_matrix_bwd(const svgp_mnist_cfg* c, const double* the
 extern "C" int svgp_kernel_matrix_bwd_partials(const svgp_mnist_cfg* c, const double* theta, const double* aux,
                                                double* ws, void* stream) {
     return kernel_matrix_bwd_impl(c, theta, aux, ws, false, stream);
+}
+
+// generate.hip: the m <= 64 form of svgp_mnist_cache_build on a validated configuration and checked pointers
+int svgp_cache_build_small(const svgp_mnist_cfg* c, const svgp_mnist_param_layout& pl, const double* theta, const double* accS,
+                           const double* accv, const double* rows, double* w, double* X, void* stream) {
+    CacheArgs a;
+    a.m = c->m; a.L = c->L; a.N_train = c->N_train; a.jitter = c->jitter;
+    a.ka = make_kern_args(c, pl, theta, nullptr);
+    a.ka.b = 0;
+    a.accS = accS; a.accv = accv; a.rows = rows; a.w = w; a.X = X;
+    const int m = c->m;
+    const size_t lds = (size_t)(m * m + 2 * m * (m + 1) + 5 * m + 80 + 2 * m) * sizeof(real);
+    int rc = set_dyn_lds(k_cache_build, lds);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_cache_build, dim3(c->L), dim3(SVGP_BLOCK), lds, (hipStream_t)stream, a);
+    SVGP_LAUNCH_CHECK();
+    return SVGP_OK;
 }
 
 static StatArgs make_stat_args(const svgp_mnist_cfg* c, const svgp_mnist_ws_layout& wl, double* ws, const double* state,

@@ -84,20 +84,21 @@ def shard_batch(lo, hi, world, rank, group_rows=1):
 
 
 def run_sharded_epochs(ctx, train_batches, nr_epochs, local_step, *, N_train, group_rows=1, on_epoch_end=None, say=print,
-                       elbo_reduce="sum", on_epoch_start=None):
+                       elbo_reduce="sum", on_epoch_start=None, first_epoch=0):
     """The reference's epoch loop (MNIST_experiment.py:313-355: un-shuffled batches, ragged last batch, elbo / recon_loss /
     C_ma / lagrange_mult fetched every step) with every batch cut over the ranks of `ctx`.
 
     local_step(llo, lhi, lo, hi, epoch, i) runs ONE optimiser step on this rank's rows [llo, lhi) of the global batch
     [lo, hi) (c = N_train / (hi - lo); the exchanges are the engine's) and returns the step's scalars -- global values,
     identical on every rank: dict(elbo=, recon_loss=, c_ma=, lagrange=).  on_epoch_start(epoch) and on_epoch_end(epoch, log)
-    are called on EVERY rank (evaluation on rank 0 + barrier is the caller's choice).  Only rank 0 prints.  Returns the log of
-    the series."""
+    are called on EVERY rank (evaluation on rank 0 + barrier is the caller's choice).  Only rank 0 prints.  first_epoch: the
+    loop runs epochs first_epoch .. nr_epochs - 1 with their own indices (a run resumed from a checkpoint: the epoch index that
+    reaches local_step and the two hooks is the one of the uninterrupted run).  Returns the log of the series."""
     import time
 
     import numpy as np
     log = dict(epoch=[], elbo=[], recon_loss=[], epoch_time=[], steps=[])
-    for epoch in range(nr_epochs):
+    for epoch in range(first_epoch, nr_epochs):
         t0 = time.time()
         elbos, losses, sc = [], [], None
         if on_epoch_start is not None:
