@@ -31,8 +31,88 @@ CASES = dict(
 )
 
 
+# The shapes at which casale.hip and the library routines under it change form (check_cfg: 1 <= Q <= 32, 1 <= M <= 128,
+# H = M Q <= 2048, 1 <= L <= 64, any N).  keep: kept share of the (object, angle) pairs (1.0: all pairs, no single-row object);
+# edges: whether table rows 0 and n_obj - 1 occur in the data; norm: also run with the normalised object kernel.
+ENVELOPE_CASES = dict(
+    # H = Q = M = 1: every GEMM degenerate, a 1 x 1 Cholesky.  Raw only: ov / |ov| is +-1, its gradient identically 0
+    H1=dict(P=7, Q=1, M=1, L=2, l_GP=0.8, seed=31, edges=False),
+    # Q = 1: the trailing updates of k_kw_chol and both triangular solves of k_chol_bwd are empty
+    Q1=dict(P=9, Q=1, M=4, L=3, l_GP=0.8, seed=32, edges=True),
+    # Q = 32: the [32][33] LDS tiles are full, solves on 32 threads; H = 64 is one GEMM tile
+    Q32=dict(P=4, Q=32, M=2, L=2, l_GP=0.3, seed=33, edges=False, norm=True),
+    # M = 128: every thread of k_ov_bwd, both waves of its normalised reduction; N < H = 384
+    M128=dict(P=5, Q=3, M=128, L=2, l_GP=0.8, seed=34, edges=True, norm=True),
+    # H = 511 / 512 / 513: last size of the inverse's 32-block sweep, first two of potrf + potri; N < 256: no split-K
+    H511=dict(P=30, Q=7, M=73, L=3, l_GP=0.8, seed=35, edges=False),
+    H512=dict(P=30, Q=8, M=64, L=3, l_GP=0.8, seed=36, edges=True),
+    H513=dict(P=12, Q=19, M=27, L=3, l_GP=0.5, seed=37, edges=False, norm=True),
+    # N >= 256 with 64 output tiles: V^T V and V^T Z both take the split-K path with scratch
+    H512_N=dict(P=120, Q=8, M=64, L=3, l_GP=0.8, seed=38, edges=True),
+    # H = 1024, N >= 256: 256 tiles, V^T V no longer splits, V^T Z (H x L) still does; the scratch is the larger of the two
+    H1024=dict(P=12, Q=32, M=32, L=3, l_GP=0.3, seed=39, edges=False, keep=0.85),
+    # both limits at once: H = 2048, L = 64, N < H
+    H2048_L64=dict(P=3, Q=32, M=64, L=64, l_GP=0.3, seed=40, edges=True, keep=0.9),
+    # L = 64 / L = 1: every lane / one lane of the row kernels' waves, the whole / one entry of a cms row
+    L64=dict(P=6, Q=5, M=3, L=64, l_GP=0.8, seed=41, edges=False),
+    L1=dict(P=6, Q=5, M=3, L=1, l_GP=0.8, seed=42, edges=True),
+    # N = 64 / 65: one full chunk of k_lw_part / one row in a second chunk; N % 4 = 0 / 1 (three dead waves that still pass
+    # the __syncthreads() of k_rows_bwd); L = 17 is no divisor of 64
+    N64=dict(P=16, Q=4, M=3, L=17, l_GP=0.8, seed=43, edges=False, keep=1.0),
+    N65=dict(P=13, Q=5, M=3, L=17, l_GP=0.8, seed=44, edges=True, keep=1.0, norm=True),
+)
+
+
 def t64(x):
     return torch.as_tensor(np.asarray(x), dtype=DT)
+
+
+def envelope_variants():
+    """(name, normalize) of every run of the envelope table: raw everywhere, normalised where the entry asks for it."""
+    return [(n, nz) for n, c in ENVELOPE_CASES.items() for nz in ((False, True) if c.get("norm") else (False,))]
+
+
+def make_envelope_case(name, normalize=False):
+    """Seeded GP-stage problem of ENVELOPE_CASES, same fields as make_case.
+    Angles: k 2 pi / Q moved by at most +-20 % of the spacing (uniformly random angles at Q = 32 give cond(K_W) ~ 4e9).
+    Mask: ~keep of the pairs, at least one row per object and per angle (Q and P do not shrink); unless keep is 1, one object
+    (first, last or a middle one) has a single row.  Object table of P + 3 rows, three of them unused: with edges False rows 0
+    and n_obj - 1 are among the unused ones, with edges True both occur.  Object vectors randn 1.5 / sqrt(M): cond(alpha I + G)
+    stays ~1e2 at M >= 64.  Batches on one workspace (b_cap = N), in this order: the whole set, the last row alone, a ragged
+    middle range."""
+    c = dict(ENVELOPE_CASES[name])
+    rng = np.random.RandomState(c["seed"])
+    P, Q, M, L, keep = c["P"], c["Q"], c["M"], c["L"], c.get("keep", 0.75)
+    angles = (np.arange(Q) + rng.uniform(-0.2, 0.2, Q)) * (2 * math.pi / Q)
+    assert np.all(np.diff(angles) > 0)
+    mask = rng.rand(P, Q) < keep
+    single = None
+    if keep < 1.0:
+        single = (0, P - 1, P // 2)[c["seed"] % 3]
+        mask[single] = False
+        mask[single, rng.randint(Q)] = True
+    for p in range(P):
+        if not mask[p].any():
+            mask[p, rng.randint(Q)] = True
+    for q in range(Q):
+        if not mask[:, q].any():
+            mask[rng.choice([p for p in range(P) if p != single] or [0]), q] = True
+    n_obj = P + 3
+    if c["edges"]:
+        ids = np.concatenate([[0], np.sort(rng.choice(np.arange(1, n_obj - 1), P - 2, replace=False)), [n_obj - 1]])
+    else:
+        ids = np.sort(rng.choice(np.arange(1, n_obj - 1), P, replace=False))
+    jj, rr = np.nonzero(mask)
+    N = len(jj)
+    aux = np.stack([np.arange(N, dtype=np.float64), ids[jj].astype(np.float64), angles[rr]], 1)
+    lo = max(1, N // 3)
+    mid = (lo, min(N - 1, lo + max(1, (2 * N) // 5) + 1))
+    c.update(name=name, N=N, H=M * Q, n_obj=n_obj, angles=angles, mask=mask.reshape(-1), aux=aux, normalize=bool(normalize),
+             ids=ids, unused=np.setdiff1d(np.arange(n_obj), ids), single=None if single is None else int(ids[single]),
+             object_vectors=rng.randn(n_obj, M) * 1.5 / math.sqrt(M), amplitude=0.9, alpha=0.15, Z=rng.randn(N, L),
+             batches=((0, N), (N - 1, N), mid))
+    c["zb"] = {b: rng.randn(b[1] - b[0], L) for b in c["batches"]}
+    return c
 
 
 def make_case(name, normalize=None):

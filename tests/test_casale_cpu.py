@@ -18,12 +18,26 @@ from tests.helpers import relerr
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-@pytest.mark.parametrize("name", ["A", "B", "C"])
+_ENV = {}
+
+
+def _env_case(name, normalize=False):
+    """Envelope cases are built once per module."""
+    if (name, normalize) not in _ENV:
+        _ENV[name, normalize] = CC.make_envelope_case(name, normalize)
+    return _ENV[name, normalize]
+
+
+# envelope cases whose literal (L, N, H) tensor B stays under ~50 MB, from the table alone (N <= P Q): no case is built at import
+LITERAL_ENVELOPE = [n for n, c in CC.ENVELOPE_CASES.items() if 8 * c["L"] * (c["P"] * c["Q"]) * (c["M"] * c["Q"]) < 50e6]
+
+
+@pytest.mark.parametrize("name", ["A", "B", "C"] + LITERAL_ENVELOPE)
 def test_literal_equals_efficient(name):
     """The N x N form of the reference and the H x H form agree at least 100 times below the bar the GPU tests use for the
-    same quantity; the disagreement is printed (NOTEBOOK.md has the values)."""
-    case = CC.make_case(name)
-    batch = case["batches"][0]
+    same quantity; the disagreement is printed (NOTEBOOK.md has the values).  Envelope cases: the ragged middle batch."""
+    case = CC.make_case(name) if name in CC.CASES else _env_case(name)
+    batch = case["batches"][0 if name in CC.CASES else 2]
     lit = CC.gp_stage_reference(case, batch, formulation="literal")
     eff = CC.gp_stage_reference(case, batch, formulation="efficient")
     worst = {}
@@ -33,6 +47,72 @@ def test_literal_equals_efficient(name):
     print(f"case {name} N={case['N']} H={case['H']}: " + ", ".join(f"{k} {e:.1e}" for k, (e, _) in worst.items()))
     for k, (e, bar) in worst.items():
         assert e <= bar / 100, (k, e, bar)
+
+
+def test_envelope_case_builder_keeps_its_promises():
+    """Every object and every angle keeps a row, table rows are unused (0 and the last one in some cases, both used in
+    others), one object has a single row unless all pairs are kept, the three batches are the whole set, the last row and a
+    ragged middle range, and the sizes the cases are named for hold."""
+    assert LITERAL_ENVELOPE == [n for n in CC.ENVELOPE_CASES if n != "H2048_L64"]
+    edges = set()
+    for name, spec in CC.ENVELOPE_CASES.items():
+        c = _env_case(name)
+        N, P, Q = c["N"], spec["P"], spec["Q"]
+        mask = c["mask"].reshape(P, Q)
+        assert mask.any(1).all() and mask.any(0).all() and N == mask.sum()
+        assert len(np.unique(c["aux"][:, 2])) == Q and len(np.unique(c["aux"][:, 1])) == P
+        assert np.all(np.diff(c["aux"][:, 1]) >= 0) and c["H"] == spec["M"] * Q
+        spacing = 2 * np.pi / Q
+        assert np.all(np.abs(c["angles"] - np.arange(Q) * spacing) <= 0.2 * spacing + 1e-15)
+        used = np.unique(c["aux"][:, 1]).astype(int)
+        assert len(c["unused"]) == 3 and not set(c["unused"]) & set(used) and c["n_obj"] == P + 3
+        edges.add((0 in used, c["n_obj"] - 1 in used))
+        rows = np.bincount(c["aux"][:, 1].astype(int), minlength=c["n_obj"])
+        if spec.get("keep", 0.75) < 1.0:
+            assert rows[c["single"]] == 1
+        else:
+            assert N == P * Q
+        (a0, a1), (b0, b1), (m0, m1) = c["batches"]
+        assert (a0, a1) == (0, N) and (b0, b1) == (N - 1, N) and 0 < m0 < m1 < N
+        assert set(c["zb"]) == set(c["batches"])
+    assert edges == {(False, False), (True, True)}
+    N = {n: _env_case(n)["N"] for n in CC.ENVELOPE_CASES}
+    H = {n: _env_case(n)["H"] for n in CC.ENVELOPE_CASES}
+    assert (H["H1"], H["Q32"], H["M128"], H["H511"], H["H512"], H["H513"], H["H512_N"], H["H1024"], H["H2048_L64"]) == \
+        (1, 64, 384, 511, 512, 513, 512, 1024, 2048)
+    assert (N["N64"], N["N65"]) == (64, 65) and N["M128"] < H["M128"] and N["H2048_L64"] < 2048
+    assert max(N["H511"], N["H512"], N["H513"]) < 256 <= min(N["H512_N"], N["H1024"])
+    assert N["L64"] % 4 != 0 or N["L1"] % 4 != 0
+
+
+@pytest.mark.parametrize("name,normalize", CC.envelope_variants(), ids=lambda v: {False: "raw", True: "norm"}.get(v, v))
+def test_envelope_oracle_response_is_far_below_the_tolerances(name, normalize):
+    """The guard of tests/test_gpu_casale_envelope.py: every real input of gp_stage_reference (Z, zb, object vectors, l_GP,
+    amplitude, alpha) moved by one ulp moves no compared quantity by more than a hundredth of its bar, for every case and
+    batch.  A case that fails here gets other inputs, never a wider bar."""
+    case = _env_case(name, normalize)
+    gen = torch.Generator().manual_seed(17)
+    ulp = lambda x: (CC.t64(x) * (1.0 + 2.0 ** -52 * (torch.randint(0, 2, np.shape(x), generator=gen).to(CC.DT) * 2 - 1))).numpy()
+    moved = dict(case, Z=ulp(case["Z"]), object_vectors=ulp(case["object_vectors"]), l_GP=float(ulp(case["l_GP"])),
+                 amplitude=float(ulp(case["amplitude"])), alpha=float(ulp(case["alpha"])),
+                 zb={b: ulp(v) for b, v in case["zb"].items()})
+    assert moved["l_GP"] != case["l_GP"] and not np.array_equal(moved["Z"], case["Z"])
+    worst = {}
+    for batch in case["batches"]:
+        ref, ref2 = CC.gp_stage_reference(case, batch), CC.gp_stage_reference(moved, batch)
+        for k, v in ref.items():
+            assert torch.isfinite(v).all(), (k, batch)
+        resp = {k: (relerr(ref2[k], ref[k]), CC.FWD_TOL) for k in ("K_W", "L_W", "V", "G", "P", "U", "A")}
+        resp["terms"] = (relerr(ref2["terms"], ref["terms"]), CC.SCALAR_TOL)
+        resp["GP_prior_term"] = (abs(float(ref2["GP_prior_term"]) - float(ref["GP_prior_term"]))
+                                 / abs(float(ref["GP_prior_term"])), CC.SCALAR_TOL)
+        for k in ("Zbar", "zbbar") + CC.GP_NAMES:
+            resp[k] = (relerr(ref2[k], ref[k]), CC.GRAD_TOL)
+        for k, (e, bar) in resp.items():
+            assert e <= bar / 100, (name, batch, k, e, bar)
+            worst[bar] = max(worst.get(bar, 0.0), e)
+    print(f"envelope {name}{' norm' if normalize else ''} N={case['N']} H={case['H']} L={case['L']}: worst oracle response "
+          + ", ".join(f"{e:.1e} (bar {bar:.0e})" for bar, e in sorted(worst.items())))
 
 
 def test_v_rowwise_is_the_masked_kronecker_product():
@@ -160,6 +240,23 @@ def test_layout_and_refusals_without_a_launch():
             _lib.call("svgp_casale_gp_fwd", C.byref(cfg), fake, fake, fake, fake, fake, fake, lo, hi, fake, None)
     with pytest.raises(svgp_vae_amd.SvgpError, match="NULL"):
         _lib.call("svgp_casale_gp_bwd", C.byref(cfg), fake, fake, fake, fake, None, fake, 0, 10, 1.0, fake, None)
+    # the envelope cases: the split-K scratch is the larger of the two tall products', n_lv and n_chunk follow their formulas
+    lib = svgp_vae_amd.load_library()
+    scratch = {}
+    for name in CC.ENVELOPE_CASES:
+        c = _env_case(name)
+        N, H, L = c["N"], c["H"], c["L"]
+        _lib.call("svgp_casale_layout_get", C.byref(_lib.CasaleCfg(N=N, n_obj=c["n_obj"], Q=c["Q"], M=c["M"], L=L, b_cap=N)),
+                  C.byref(wl))
+        s1, s2 = (int(lib.svgp_dgemm_splitk_scratch_elems(H, n, N)) for n in (H, L))
+        scratch[name] = (s1, s2)
+        assert wl.scr_splitk_len == max(s1, s2), name
+        assert (wl.n_lv, wl.n_chunk) == (-(-N * L // 256), -(-N // 64)), name
+        assert wl.n_total == wl.th_ov + c["n_obj"] * c["M"] and wl.scr_splitk + wl.scr_splitk_len <= wl.total
+    # what the cases are there for: both products split at H512_N, only the H x L one at H1024, none below 256 rows
+    assert min(scratch["H512_N"]) > 0 and scratch["H1024"][0] == 0 and scratch["H1024"][1] > 0
+    assert all(scratch[n] == (0, 0) for n in CC.ENVELOPE_CASES if _env_case(n)["N"] < 256)
+    assert (_env_case("N64")["N"] * 17, _env_case("N65")["N"]) == (64 * 17, 65)
 
 
 def test_engine_refuses_to_run_without_a_gpu():
