@@ -476,6 +476,63 @@ __device__ __forceinline__ void lds_zero(real* dst, int n) {
     for (int i = threadIdx.x; i < n; i += blockDim.x) dst[i] = 0;
 }
 
+// Staging in two halves (the chain kernels of the m <= 64 step).  lds_copy_in above compiles to one global load, a full wait and
+// the LDS store per pass -- ceil(n / NT) dependent round trips per array, the arrays one after another.  Here the loads of a GROUP of
+// arrays are issued first and stored afterwards, so a group costs one round trip.  The rule: the loads of a group sit in one basic
+// block (an unconditional load from an index kept inside the array and a predicated store; no branch per element),
+// and the thread count is the template parameter (the callers run with exactly NT threads), never blockDim.x, which is itself a
+// load from the dispatch packet.
+// A lane past the end loads the element its first pass loads (a line that pass fetches anyway), not the array's last one: of a weight
+// array every workgroup of the launch reads the same addresses, and whole passes of lanes on ONE of them queue up at a single L2
+// channel (NOTEBOOK 14.5c).
+template <int N, int NT>
+__device__ __forceinline__ int stage_spare() { return N >= NT ? (int)threadIdx.x : min((int)threadIdx.x, N - 1); }
+// Compile-time count N: stage_issue returns the ceil(N / NT) values of this thread, stage_commit stores them.
+template <int N, int NT>
+struct StageRegs {
+    static constexpr int C = (N + NT - 1) / NT;
+    real v[C];
+};
+template <int N, int NT>
+__device__ __forceinline__ StageRegs<N, NT> stage_issue(const real* __restrict__ src) {
+    StageRegs<N, NT> r;
+#pragma unroll
+    for (int k = 0; k < StageRegs<N, NT>::C; ++k) {
+        const int i = (int)threadIdx.x + k * NT;
+        r.v[k] = src[(k + 1) * NT <= N || i < N ? i : stage_spare<N, NT>()];
+    }
+    return r;
+}
+template <int N, int NT>
+__device__ __forceinline__ void stage_commit(real* dst, const StageRegs<N, NT>& r) {
+#pragma unroll
+    for (int k = 0; k < StageRegs<N, NT>::C; ++k) {
+        const int i = (int)threadIdx.x + k * NT;
+        if ((k + 1) * NT <= N || i < N) dst[i] = r.v[k];
+    }
+}
+// Run-time count n >= 1 (the weights: their size depends on L): straight-line chunks of CH loads in flight per thread, then the CH
+// stores.  Loads issued by the caller before this call stay in flight through the first chunk and are complete after it.
+template <int NT, int CH>
+__device__ __forceinline__ void stage_chunk(real* dst, const real* __restrict__ src, int n, int c0) {
+    const int base = c0 + (int)threadIdx.x, spare = min(base, n - 1);
+    real r[CH];
+#pragma unroll
+    for (int k = 0; k < CH; ++k) r[k] = src[base + k * NT < n ? base + k * NT : spare];
+    // (compiler only: behind its store's test a load needs no clamp, and the optimizer would sink it there -- a round trip of its own)
+    __atomic_signal_fence(__ATOMIC_SEQ_CST);
+#pragma unroll
+    for (int k = 0; k < CH; ++k)
+        if (base + k * NT < n) dst[base + k * NT] = r[k];
+}
+template <int NT, int CH = 8>
+__device__ __forceinline__ void stage_copy(real* dst, const real* __restrict__ src, int n) {
+    // The first chunk stands outside the loop: inside it, the wait for the registers that the previous trip loaded lands in front
+    // of the chunk's loads, and on the first trip that wait would be for the caller's group.
+    stage_chunk<NT, CH>(dst, src, n, 0);
+    for (int c0 = CH * NT; c0 < n; c0 += CH * NT) stage_chunk<NT, CH>(dst, src, n, c0);      // (uniform trip count: a scalar branch)
+}
+
 struct EncOff { int c1w, c1b, c2w, c2b, c3w, c3b, dw, db, n; };
 struct DecOff { int dw, db, c1w, c1b, c2w, c2b, c3w, c3b, n; };
 
@@ -632,11 +689,22 @@ __device__ __forceinline__ void decoder_bwd_data_images(const DecBwdDataArgs& a,
     real* d1 = d2 + 1568;            // 512
     real* dh0 = d1 + 512;            // 128
     real* raw = dh0 + 128;           // raw conv weights (+ biases), staged once: od.n - od.c1w
-    lds_copy_in(w, a.th_dec + od.dw, a.L * 128);
+    // one group of loads: the first image's a1, a2, reconstruction and pixels, the effective (or raw) weights, the dense weights
+    // (image `first` exists for every workgroup -- the grids have min(b, 256) image workgroups; nf keeps a larger grid inside the arrays)
+    const int nf = first < a.b ? first : a.b - 1;
+    auto ra1 = stage_issue<512, VAE_NT>(a.a1g + (size_t)nf * 512);
+    auto ra2 = stage_issue<1568, VAE_NT>(a.a2g + (size_t)nf * 1568);
+    auto rrec = stage_issue<784, VAE_NT>(a.recon + (size_t)nf * 784);
+    auto rpx = stage_issue<784, VAE_NT>(a.images + (size_t)nf * 784);
     if (PRE) {
-        lds_copy_in(We1, a.weff, DEC_NWE);
+        const auto rwe = stage_issue<DEC_NWE, VAE_NT>(a.weff);
+        stage_copy<VAE_NT>(w, a.th_dec + od.dw, a.L * 128);
+        stage_commit<DEC_NWE, VAE_NT>(We1, rwe);
     } else {
-        lds_copy_in(raw, a.th_dec + od.c1w, od.n - od.c1w);
+        constexpr int NRAW = 576 + 8 + 576 + 8 + 72 + 1;     // od.n - od.c1w
+        const auto rraw = stage_issue<NRAW, VAE_NT>(a.th_dec + od.c1w);
+        stage_copy<VAE_NT>(w, a.th_dec + od.dw, a.L * 128);
+        stage_commit<NRAW, VAE_NT>(raw, rraw);
         __syncthreads();
         UpC1::build_weff(raw, We1);
         UpC2::build_weff(raw + (od.c2w - od.c1w), We2);
@@ -645,11 +713,19 @@ __device__ __forceinline__ void decoder_bwd_data_images(const DecBwdDataArgs& a,
     const real gscale = (a.geco ? a.state[SVGP_ST_LAGRANGE] * a.inv_bglobal : real(1)) / real(784);
     for (int n = first; n < a.b; n += stride) {
         __syncthreads();
-        lds_copy_in(a1, a.a1g + (size_t)n * 512, 512);
-        lds_copy_in(a2, a.a2g + (size_t)n * 1568, 1568);
-        for (int i = threadIdx.x; i < 784; i += blockDim.x) {
-            const real o = a.recon[(size_t)n * 784 + i];
-            d3[i] = real(2) * gscale * (o - a.images[(size_t)n * 784 + i]) * elu_grad_from_out(o);
+        if (n != first) {                // later images: one group per image
+            ra1 = stage_issue<512, VAE_NT>(a.a1g + (size_t)n * 512);
+            ra2 = stage_issue<1568, VAE_NT>(a.a2g + (size_t)n * 1568);
+            rrec = stage_issue<784, VAE_NT>(a.recon + (size_t)n * 784);
+            rpx = stage_issue<784, VAE_NT>(a.images + (size_t)n * 784);
+        }
+        stage_commit<512, VAE_NT>(a1, ra1);
+        stage_commit<1568, VAE_NT>(a2, ra2);
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const int i = (int)threadIdx.x + k * VAE_NT;
+            const real o = rrec.v[k];
+            if (i < 784) d3[i] = real(2) * gscale * (o - rpx.v[k]) * elu_grad_from_out(o);
         }
         __syncthreads();
         UpC3::bwd_data_valu(d3, We3, d2);
@@ -693,8 +769,10 @@ __device__ __forceinline__ void decoder_bwd_data_images(const DecBwdDataArgs& a,
 // reconstruction in place.  Only the dense weights, the biases and ws.dec_weff are staged (the raw convolution weights are never
 // read in the `_pre` form): dec_fwd_bwd_lds(L) reals, 75.5 KB at L = 16, so two workgroups fit a CU (the rider form,
 // k_decoder_fwd_bwd_data in gp_kernels.hip, relies on that and on <= 168 VGPRs: the forward runs its rolled-tap form).
-// The z / pixel loads of an image are issued one image ahead (the first: before the weight staging), so no dependent round trip
-// sits behind the staging.  The squared-error partial of a workgroup goes to part_sums[4 * first + 2].
+// The z / pixel loads of an image are issued one image ahead (the first: before the weight staging).  The staging behind them is
+// still lds_copy_in: twelve dependent round trips.  Staged in groups (stage_issue / stage_copy above) the launch with its riders was
+// no faster stand-alone and the straight-line form cost six registers (170 > 168), so this kernel keeps the loops (NOTEBOOK 14.5c).
+// The squared-error partial of a workgroup goes to part_sums[4 * first + 2].
 // ------------------------------------------------------------------------------------------
 struct DecFwdBwdArgs {
     int b, L, geco;
@@ -848,26 +926,35 @@ __device__ __forceinline__ void encoder_bwd_images(const EncBwdArgs& a, int firs
     using C2 = Conv3<13, 1, 0, 2, 8, 8, 6, NT>;
     using C3 = Conv3<6, 1, 0, 2, 8, 8, 2, NT>;
     static_assert(72 * (NT / 72) <= ENC_BWD_SCRATCH, "first-layer chunk scratch");
-    lds_copy_in(w, a.th_enc, eo.n);
-    lds_zero(g, eo.n);
-    const int twoL = 2 * L;
+    static_assert(NT >= 128, "thread j stages dout[j], j < 2L <= 128");
+    const int twoL = 2 * L, t = threadIdx.x;
+    // One group of loads per image: pixels, a1, a2, a3 and the three inputs of dout[t] (10 values per thread; all three of the last
+    // unconditional, from clamped rows).  The first image's group is issued ahead of the weight staging and flies with its first chunk.
+    const int jy = t < L ? t : L - 1, jv = t < L ? 0 : t < twoL ? t - L : L - 1;
+    StageRegs<784, NT> rimg; StageRegs<1352, NT> ra1; StageRegs<288, NT> ra2; StageRegs<32, NT> ra3;
+    real ryb, rvr, rsb;
+    auto issue = [&](int n) {
+        rimg = stage_issue<784, NT>(a.images + (size_t)n * 784);
+        ra1 = stage_issue<1352, NT>(a.a1g + (size_t)n * 1352);
+        ra2 = stage_issue<288, NT>(a.a2g + (size_t)n * 288);
+        ra3 = stage_issue<32, NT>(a.a3g + (size_t)n * 32);
+        ryb = a.ybar[(size_t)n * L + jy];
+        rvr = a.var_raw[(size_t)n * L + jv];
+        rsb = a.s2bar[(size_t)n * L + jv];
+    };
+    issue(first < a.b ? first : a.b - 1);
+    stage_copy<NT>(w, a.th_enc, eo.n);
+    for (int i = t; i < eo.n; i += NT) g[i] = 0;
     for (int n = first; n < a.b; n += stride) {
         __syncthreads();
-        lds_copy_in(img, a.images + (size_t)n * 784, 784);
-        lds_copy_in(a1, a.a1g + (size_t)n * 1352, 1352);
-        lds_copy_in(a2, a.a2g + (size_t)n * 288, 288);
-        lds_copy_in(a3, a.a3g + (size_t)n * 32, 32);
-        for (int j = threadIdx.x; j < twoL; j += NT) {
-            real dj;
-            if (j < L) {
-                dj = a.ybar[(size_t)n * L + j];
-            } else {
-                const real vr = a.var_raw[(size_t)n * L + j - L];
-                const real sb = a.s2bar[(size_t)n * L + j - L];      // (unconditional: behind the test it was a second, dependent round trip)
-                const bool pass = !a.clip || (vr >= 1e-3 && vr <= 10.0);
-                dj = pass ? sb * vr : real(0);
-            }
-            dout[j] = dj;
+        if (n != first) issue(n);
+        stage_commit<784, NT>(img, rimg);
+        stage_commit<1352, NT>(a1, ra1);
+        stage_commit<288, NT>(a2, ra2);
+        stage_commit<32, NT>(a3, ra3);
+        if (t < twoL) {
+            const bool pass = !a.clip || (rvr >= 1e-3 && rvr <= 10.0);
+            dout[t] = t < L ? ryb : pass ? rsb * rvr : real(0);
         }
         __syncthreads();
         // dense: weight / bias gradients and da3

@@ -52,6 +52,7 @@ __global__ __launch_bounds__(VAE_NT) void k_encoder_fwd(int b, int L, int clip, 
     real* a1 = img + 784;           // 1352
     real* a2 = a1 + 1352;           // 288
     real* a3 = a2 + 288;            // 32
+    // (lds_copy_in, not the batched staging of vae_dev.hpp: with it this launch was slower stand-alone, NOTEBOOK 14.5c)
     lds_copy_in(w, th_enc, eo.n);
     for (int n = blockIdx.x; n < b; n += n_img_blocks) {
         __syncthreads();
@@ -113,10 +114,15 @@ __global__ __launch_bounds__(VAE_NT) void k_decoder_fwd(int b, int L, const real
     real* We1 = red + 16;            // effective weights of the three up-convolutions
     real* We2 = We1 + UpC1::NWE;
     real* We3 = We2 + UpC2::NWE;
-    lds_copy_in(w, th_dec, od.n);
+    // one group of loads (stage_issue, vae_dev.hpp): the first image's z, the effective weights, then theta in chunks
+    const int t = threadIdx.x, lz = t < L ? t : L - 1;
+    real zr = zg[(size_t)min((int)blockIdx.x, b - 1) * L + lz];
     if (PRE) {
-        lds_copy_in(We1, weff, DEC_NWE);
+        const auto rwe = stage_issue<DEC_NWE, VAE_NT>(weff);
+        stage_copy<VAE_NT>(w, th_dec, od.n);
+        stage_commit<DEC_NWE, VAE_NT>(We1, rwe);
     } else {
+        stage_copy<VAE_NT>(w, th_dec, od.n);
         __syncthreads();
         UpC1::build_weff(w + od.c1w, We1);       // from the LDS copy (one coalesced read of the raw weights)
         UpC2::build_weff(w + od.c2w, We2);
@@ -125,7 +131,10 @@ __global__ __launch_bounds__(VAE_NT) void k_decoder_fwd(int b, int L, const real
     real sq = 0;
     for (int n = blockIdx.x; n < b; n += gridDim.x) {
         __syncthreads();
-        lds_copy_in(z, zg + (size_t)n * L, L);
+        if (t < L) z[t] = zr;
+        // this image's pixels (read at the end of the iteration) and the next image's z: in flight during the layers
+        const auto px = stage_issue<784, VAE_NT>(images + (size_t)n * 784);
+        if (n + (int)gridDim.x < b) zr = zg[(size_t)(n + gridDim.x) * L + lz];
         __syncthreads();
         if (threadIdx.x < 128) {
             real acc = w[od.db + threadIdx.x];
@@ -142,11 +151,15 @@ __global__ __launch_bounds__(VAE_NT) void k_decoder_fwd(int b, int L, const real
         lds_copy_out(h0g + (size_t)n * 128, h0, 128);
         lds_copy_out(a1g + (size_t)n * 512, a1, 512);
         lds_copy_out(a2g + (size_t)n * 1568, a2, 1568);
-        for (int i = threadIdx.x; i < 784; i += blockDim.x) {
-            const real o = out[i];
-            recon[(size_t)n * 784 + i] = o;
-            const real df = images[(size_t)n * 784 + i] - o;
-            sq += df * df;
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const int i = t + k * VAE_NT;
+            if (i < 784) {
+                const real o = out[i];
+                recon[(size_t)n * 784 + i] = o;
+                const real df = px.v[k] - o;
+                sq += df * df;
+            }
         }
     }
     const real tot = block_sum(sq, red);

@@ -3,7 +3,8 @@ Prints (1) equality of the two forms, (2) stand-alone times of every piece -- th
 (SVGP_DEC_FUSE) next to the two launches it replaces, with and without riders --, (3) the eager config-2 step with
 SVGP_DEC_SPLIT=0/1 and the later switches, SVGP_DEC_FUSE=0/1 and then SVGP_FWD_SPLIT=0/1 last (child processes: one setting per
 process).  The stand-alone table carries the four SVGP_FWD_SPLIT forms (forward factor head, forward row z form, decoder launch with
-the tail riders, reverse row pass 1 in its d form) next to the full forms they replace in the step."""
+the tail riders, reverse row pass 1 in its d form) next to the full forms they replace in the step.
+--stage: only the stand-alone times of the launches with batched staging (NOTEBOOK 14.5c), one JSON line."""
 import ctypes as C
 import json
 import os
@@ -96,6 +97,21 @@ def main():
             best = min(best, ms.value * 1e3 / reps)
         return best
 
+    if "--stage" in sys.argv:
+        # the launches whose staging is batched (stage_issue / stage_copy, vae_dev.hpp), stand-alone, as one JSON line: run it from
+        # the parent's checkout and from this one, alternated in one call
+        aux_p = eng._bound[1].data_ptr()
+        stage_rows = [("encoder_fwd", "svgp_mnist_encoder_fwd", (cfg, th, img, ws, s)),
+                      ("encoder_kernel_matrix_fwd", "svgp_mnist_encoder_kernel_matrix_fwd", (cfg, th, img, aux_p, ws, s)),
+                      ("decoder_fwd_pre", "svgp_mnist_decoder_fwd_pre", (cfg, th, img, ws, s)),
+                      ("decoder_bwd_data_pre", "svgp_mnist_decoder_bwd_data_pre", (cfg, th, img, ws, st, s)),
+                      ("decoder_fwd_bwd_data_pre", "svgp_mnist_decoder_fwd_bwd_data_pre", (cfg, th, img, ws, st, s)),
+                      ("decoder_fwd_bwd_data_pre_tail", "svgp_mnist_decoder_fwd_bwd_data_pre_tail", (cfg, th, img, ws, st, s)),
+                      ("encoder_bwd", "svgp_mnist_encoder_bwd", (cfg, th, img, ws, s)),
+                      ("encoder_bwd_km_sum", "svgp_mnist_encoder_bwd_km_sum", (cfg, th, img, aux_p, ws, st, s)),
+                      ("gp_stats_factor_bwd_wgrad", "svgp_gp_stats_factor_bwd_wgrad", (cfg, img, ws, st, s))]
+        print(json.dumps({name: round(timeit(sym, args), 3) for name, sym, args in stage_rows}), flush=True)
+        return
     rows = [("decoder_bwd (one kernel)", "svgp_mnist_decoder_bwd", (cfg, th, img, ws, st, s)),
             ("decoder_bwd_data", "svgp_mnist_decoder_bwd_data", (cfg, th, img, ws, st, s)),
             ("decoder_bwd_data_pre", "svgp_mnist_decoder_bwd_data_pre", (cfg, th, img, ws, st, s)),
