@@ -257,7 +257,10 @@ int svgp_mnist_decoder_bwd_data_pre(const svgp_mnist_cfg*, const double* theta, 
  * svgp_gp_titsias_bwd adds the L_2 gradients to ybar, s2bar, Knbar, knnbar, Kbar.
  *   svgp_gp_titsias_stats : after svgp_gp_stats_fwd (phase 0)        -> ws[tit_S2], ws[tit_v2]
  *   svgp_gp_titsias_fwd   : after svgp_gp_posterior_fwd (phase 1)    -> ws[tit_Si], ws[tit_t], ws[tit_scal]
- *   svgp_gp_titsias_bwd   : after svgp_gp_posterior_bwd (phase 2), before svgp_kernel_matrix_bwd            */
+ *   svgp_gp_titsias_bwd   : after svgp_gp_posterior_bwd (phase 2), before svgp_kernel_matrix_bwd
+ * Scratch: stats ws[scr_bl], ws[scr_bm]; fwd ws[scr_inv]; bwd ws[scr_mm], ws[scr_bm], ws[scr_bl] and ws[Knbar_part], which every
+ * layout with cfg.titsias sizes as max(L b m, b m + 2 b L).  The Kbar increment is the same on every rank of a row-sharded step:
+ * at m > 64, where the kernel-matrix reverse pass takes Kbar as it is, it is scaled by cfg.rep_weight here.       */
 int svgp_gp_titsias_stats(const svgp_mnist_cfg*, double* ws, void* stream);
 int svgp_gp_titsias_fwd(const svgp_mnist_cfg*, double* ws, const double* state, void* stream);
 int svgp_gp_titsias_bwd(const svgp_mnist_cfg*, double* ws, const double* state, void* stream);

@@ -109,6 +109,41 @@ def gp_stats(Kn, w, a, bvec=None):
     return S, v1, v2
 
 
+# ------------------------------------------------------------------ Titsias L_2 in m x m space
+# The Woodbury form that the header of csrc/gp_titsias.hip describes, cut where its three stages are cut.  The oracle's own Titsias
+# branch (MnistSVGP.variational_loss) is the literal b x b form, a different algorithm: tests/test_titsias_restatement_cpu.py pins
+# this one against it, tests/test_gpu_titsias_stages.py holds the stages to it.  With d = var + j per (row, channel):
+#     log det C = sum_n log d_n + log det Sigma2 - log det(K + jI),   y^T C^-1 y = sum_n y_n^2 / d_n - v2 . t2
+def titsias_stats(Kn, y, var, jitter):
+    """svgp_gp_titsias_stats: S2[l] = sum_n k_n k_n^T / d_nl (L,m,m), v2[l] = sum_n y_nl k_n / d_nl (L,m).  y, var (b,L)."""
+    d = var + jitter
+    return torch.einsum('nl,ni,nj->lij', 1.0 / d, Kn, Kn), torch.einsum('nl,ni->li', y / d, Kn)
+
+
+def titsias_fwd(K, S2, v2, y, var, knn, q, jitter):
+    """svgp_gp_titsias_fwd: Sigma2^-1 (L,m,m), log det Sigma2 (L), t2 = Sigma2^-1 v2 (L,m), v2.t2 (L) and the row sum
+    sum_{n,l} [log d + y^2 / d + (k_nn - q_n) / var] (scalar), Sigma2 = K + jI + S2; q (b) = diag(Kn (K + jI)^-1 Kn^T)."""
+    Sig = K[None] + jitter * torch.eye(K.shape[0], dtype=DT)[None] + S2
+    Si2 = torch.linalg.inv(Sig)
+    ld2 = 2 * torch.log(torch.diagonal(torch.linalg.cholesky(Sig), dim1=-2, dim2=-1)).sum(-1)
+    t2 = torch.einsum('lij,lj->li', Si2, v2)
+    d = var + jitter
+    rows = (torch.log(d) + y * y / d + reciprocal_no_nan(var) * (knn - q)[:, None]).sum()
+    return Si2, ld2, t2, (v2 * t2).sum(1), rows
+
+
+def titsias_l2_sum(Kn, K, knn, y, var, jitter):
+    """sum_l L_2 (SVGPVAE_model.py:246-259) from the two stages above, differentiable in (Kn, K, knn, y, var): autograd of it
+    gives what svgp_gp_titsias_bwd adds to Knbar, Kbar, knnbar, ybar, s2bar per unit of d(objective)/d(inside-ELBO)."""
+    b, L = y.shape
+    Kj = K + jitter * torch.eye(K.shape[0], dtype=DT)
+    ldK = 2 * torch.log(torch.diagonal(torch.linalg.cholesky(Kj))).sum()
+    q = ((Kn @ torch.linalg.inv(Kj)) * Kn).sum(1)
+    S2, v2 = titsias_stats(Kn, y, var, jitter)
+    _, ld2, _, vt, rows = titsias_fwd(K, S2, v2, y, var, knn, q, jitter)
+    return -0.5 * (b * L * LOG_2PI + rows + ld2.sum() - L * ldK - vt.sum())
+
+
 # ------------------------------------------------------------------ m x m factor stage
 def gp_factor_fwd(K, S, v, jitter, c, kl_form=0):
     """svgp_gp_factor_fwd: shared Ki, ldK and per-channel Si, t, mu_hat, A_hat, G, Aji, u, KL.

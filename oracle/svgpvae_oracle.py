@@ -391,6 +391,10 @@ def forward_pass_SVGPVAE(data_batch, beta, vae, svgp, C_ma, lagrange_mult, alpha
                                               svgp.N_train, b_global=b_global)
         inside_elbo_recon = L3.sum()
         inside_elbo_kl = KL.sum()
+        if svgp.titsias:      # the m x m restatement of :246-259 (oracle/staged_gp.py) in the place of the b x b form
+            from . import staged_gp
+            inside_elbo_recon = staged_gp.titsias_l2_sum(Kn, K, knn, qnet_mu, qnet_var, svgp.jitter)
+            inside_elbo_kl = torch.zeros((), dtype=DT)
 
     if svgp.titsias:
         inside_elbo = inside_elbo_recon - inside_elbo_kl
@@ -456,12 +460,15 @@ def loss_and_grads(params, images, aux, epsilon, *, beta, C_ma, lagrange_mult, a
                    clipping_qs, GECO, jitter, N_train, L, formulation="literal",
                    K_obj_normalize=False, b_global=None, titsias=False):
     """Returns (16-tuple detached, grads dict) of the minimised objective:
-    GECO -> `elbo` slot itself, else `-elbo` (MNIST_experiment.py:202-205)."""
+    GECO -> `elbo` slot itself, else `-elbo` (MNIST_experiment.py:202-205).
+    With titsias the formulation is the literal one unless "mspace" is asked for: the efficient posterior with the Titsias L_2
+    restated in m x m space (staged_gp.titsias_l2_sum)."""
     leaf = {k: v.detach().clone().requires_grad_(True) for k, v in params.items()}
     vae, svgp = make_models(leaf, titsias, jitter, N_train, L, K_obj_normalize)
     out = forward_pass_SVGPVAE((images, aux), beta, vae, svgp, C_ma, lagrange_mult, alpha, kappa,
                                clipping_qs=clipping_qs, GECO=GECO, epsilon=epsilon,
-                               formulation="literal" if titsias else formulation, b_global=b_global)
+                               formulation="literal" if titsias and formulation != "mspace" else formulation,
+                               b_global=b_global)
     objective = out[0] if GECO else -out[0]
     names = list(leaf.keys())
     gs = torch.autograd.grad(objective, [leaf[k] for k in names], allow_unused=True)

@@ -144,7 +144,8 @@ int svgp_ws_layout_fill(const svgp_mnist_cfg* c, svgp_mnist_ws_layout* o, bool b
     o->statB = p; o->A2 = p; p += P * L * m * m; o->ud = p; p += P * L * m; o->td = p; p += P * L * m;
     o->statB_len = p - o->statB; take(0);
     o->Kbar = take(m * m); o->fb_part = take(ball_large ? svgp_ball_large_fb_part_elems(m, L) : 2 * L * m * m); o->Qm = take(big ? 0 : L * m * m); o->vbar = take(L * m);
-    o->Ssym = take(L * m * m); o->Knbar_part = take(ball_large ? std::max(L * b * m, b * m + 2 * b * L) : L * b * m);
+    // (the Titsias reverse stage keeps W | cA | cB, b m + 2 b L elements, here: more than L b m only when (L - 1) m < 2 L)
+    o->Ssym = take(L * m * m); o->Knbar_part = take(ball_large || c->titsias ? std::max(L * b * m, b * m + 2 * b * L) : L * b * m);
     // scratch of the large-m path (gp_large.hip)
     // m > 64: (L,b,m) scratch + the forward products [Kn; W] Si_l (L,2b,m), Kn Ki (b,m) kept for the reverse pass + X (b,2m)
     o->scr_bm = take(big ? 3 * L * b * m + 3 * b * m : L * b * m); o->scr_mm = take(4 * L * m * m);

@@ -95,7 +95,7 @@ extern "C" int svgp_ball_large_gp_bwd(const svgp_ball_large_cfg* q, const double
     RUNC(svgp_big_stats(&c, wl, ws, state, 1, stream));
     RUNC(svgp_big_factor_bwd(&c, wl, ws, state, stream, 0, c.L, SVGP_BWD_ALL));
     RUNC(svgp_big_posterior_bwd(&c, wl, ws, state, stream));
-    if (c.titsias) RUNC(svgp_titsias_bwd_wl(&c, wl, ws, state, stream, (long long)(wl.scr_bm - wl.Knbar_part)));
+    if (c.titsias) RUNC(svgp_titsias_bwd_wl(&c, wl, ws, state, stream));
     return svgp_se1d_kernel_matrix_bwd(c.b, c.m, times, ip, ls, ws + wl.Kbar, ws + wl.Knbar, d_ip, d_ls, stream);
 }
 

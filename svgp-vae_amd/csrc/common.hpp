@@ -144,9 +144,7 @@ static inline int64_t svgp_ball_large_fb_part_elems(int64_t m, int64_t L) {
 // gp_titsias.hip: the three Titsias stages on a workspace whose layout the caller supplies (no configuration check of their own)
 int svgp_titsias_stats_wl(const svgp_mnist_cfg* c, const svgp_mnist_ws_layout& wl, double* ws, void* stream);
 int svgp_titsias_fwd_wl(const svgp_mnist_cfg* c, const svgp_mnist_ws_layout& wl, double* ws, const double* state, void* stream);
-// (knbar_part_elems: what ws.Knbar_part holds when that is more than L b m)
-int svgp_titsias_bwd_wl(const svgp_mnist_cfg* c, const svgp_mnist_ws_layout& wl, double* ws, const double* state, void* stream,
-                        long long knbar_part_elems);
+int svgp_titsias_bwd_wl(const svgp_mnist_cfg* c, const svgp_mnist_ws_layout& wl, double* ws, const double* state, void* stream);
 // ball.hip: svgp_ball_elbo_assemble on two workspaces of layout wl
 int svgp_ball_assemble_wl(const svgp_mnist_cfg* cx, const svgp_mnist_ws_layout& wl, const double* ws_x, const double* ws_y,
                           const double* row_recon, const double* state, double* out, void* stream);

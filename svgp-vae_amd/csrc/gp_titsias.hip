@@ -144,8 +144,9 @@ __global__ __launch_bounds__(256) void k_tit_sum_l(int mm, int L, const real* __
     for (int l = 0; l < L; ++l) acc += S[(size_t)l * mm + o];
     out[o] = acc;
 }
-// Kbar += sum_l Sb_l + g2/2 (L Ki - T2)
-__global__ __launch_bounds__(256) void k_tit_kbar(int mm, int L, int flags, const real* __restrict__ state,
+// Kbar += w (sum_l Sb_l + g2/2 (L Ki - T2)).  Every term is a function of all-reduced quantities, the same on every rank of a
+// row-sharded step, and the ranks' Kbar shares add up in the gradient all-reduce: w is the weight of this replicated part.
+__global__ __launch_bounds__(256) void k_tit_kbar(int mm, int L, int flags, real w, const real* __restrict__ state,
                                                   const real* __restrict__ Sb, const real* __restrict__ Ki,
                                                   const real* __restrict__ T2, real* __restrict__ Kbar) {
     const int o = blockIdx.x * blockDim.x + threadIdx.x;
@@ -153,7 +154,7 @@ __global__ __launch_bounds__(256) void k_tit_kbar(int mm, int L, int flags, cons
     const real g2 = svgp_seed_T(flags, L, state);
     real acc = 0;
     for (int l = 0; l < L; ++l) acc += Sb[(size_t)l * mm + o];
-    Kbar[o] += acc + real(0.5) * g2 * ((real)L * Ki[o] - T2[o]);
+    Kbar[o] += w * (acc + real(0.5) * g2 * ((real)L * Ki[o] - T2[o]));
 }
 
 int layouts(const svgp_mnist_cfg* c, svgp_mnist_ws_layout* wl) {
@@ -218,10 +219,9 @@ int svgp_titsias_fwd_wl(const svgp_mnist_cfg* c, const svgp_mnist_ws_layout& wl,
 extern "C" int svgp_gp_titsias_bwd(const svgp_mnist_cfg* c, double* ws, const double* state, void* stream) {
     svgp_mnist_ws_layout wl;
     RUNC(layouts(c, &wl));
-    return svgp_titsias_bwd_wl(c, wl, ws, state, stream, 0);
+    return svgp_titsias_bwd_wl(c, wl, ws, state, stream);
 }
-int svgp_titsias_bwd_wl(const svgp_mnist_cfg* c, const svgp_mnist_ws_layout& wl, double* ws, const double* state, void* stream,
-                        long long knbar_part_elems) {
+int svgp_titsias_bwd_wl(const svgp_mnist_cfg* c, const svgp_mnist_ws_layout& wl, double* ws, const double* state, void* stream) {
     SVGP_REQUIRE(ws && state, SVGP_ERR_INVALID, "NULL device pointer");
     const int b = c->b, m = c->m, L = c->L, flags = SVGP_LOSS_FLAGS(c);
     const long long mm = (long long)m * m;
@@ -233,12 +233,13 @@ int svgp_titsias_bwd_wl(const svgp_mnist_cfg* c, const svgp_mnist_ws_layout& wl,
     real* U = ws + wl.scr_bm;                        // (L, b, m)
     real* Cb = ws + wl.scr_bl;                       // (b, L)
     real* W = ws + wl.Knbar_part;                    // (b, m)   Knbar_part is dead after svgp_gp_posterior_bwd
-    real* cA = W + (size_t)b * m;                    // (b, L)   (Knbar_part holds L b m >= b m + 2 b L for m >= 2 ... )
-    real* cB = cA + (size_t)b * L;
-    // (ws.Knbar_part holds L b m elements; the moving-ball large engine's layout, api.hip, sizes it for this at every m)
-    const long long room = std::max<long long>((long long)L * b * m, knbar_part_elems);
-    SVGP_REQUIRE(room >= (long long)b * m + 2LL * b * L, SVGP_ERR_UNSUPPORTED,
-                 "Titsias reverse pass needs (L - 1) m >= 2 L scratch elements per row (L=%d m=%d)", L, m);
+    real* cA = W + (size_t)b * m;                    // (b, L)
+    real* cB = cA + (size_t)b * L;                   // (b, L)
+    // every layout with cfg.titsias sizes ws.Knbar_part as max(L b m, b m + 2 b L) at the row capacity (svgp_ws_layout_fill); the
+    // field ends where ws.scr_bm begins.  A layout that does not is a defect of the library (tests/test_titsias_layout_cpu.py)
+    SVGP_REQUIRE(wl.scr_bm - wl.Knbar_part >= (long long)b * m + 2LL * b * L, SVGP_ERR_INVALID,
+                 "ws.Knbar_part holds %lld elements, the Titsias reverse stage keeps b m + 2 b L there (b=%d m=%d L=%d)",
+                 (long long)(wl.scr_bm - wl.Knbar_part), b, m, L);
     hipLaunchKernelGGL(k_tit_sb, dim3(nblk((long long)L * mm)), dim3(256), 0, st, m, L, flags, state, ws + wl.tit_Si,
                        ws + wl.tit_t, Sb);
     SVGP_LAUNCH_CHECK();
@@ -258,7 +259,10 @@ int svgp_titsias_bwd_wl(const svgp_mnist_cfg* c, const svgp_mnist_ws_layout& wl,
     SVGP_LAUNCH_CHECK();
     RUNC(svgp_dgemm_batched(0, 0, m, m, m, 1.0, ws + wl.Ki, m, 0, Ssum, m, 0, 0.0, T1, m, 0, 1, stream));
     RUNC(svgp_dgemm_batched(0, 0, m, m, m, 1.0, T1, m, 0, ws + wl.Ki, m, 0, 0.0, T2, m, 0, 1, stream));
-    hipLaunchKernelGGL(k_tit_kbar, dim3(nblk(mm)), dim3(256), 0, st, (int)mm, L, flags, state, Sb, ws + wl.Ki, T2,
+    // m <= 64: the kernel-matrix reverse pass multiplies the whole of Kbar by cfg.rep_weight.  m > 64: it takes Kbar as it is, with
+    // rank-local row sums in it unweighted (gp_large.hip header), so the replicated part added here carries the weight itself
+    const real w_rep = m > SVGP_M_MAX ? (real)c->rep_weight : real(1);
+    hipLaunchKernelGGL(k_tit_kbar, dim3(nblk(mm)), dim3(256), 0, st, (int)mm, L, flags, w_rep, state, Sb, ws + wl.Ki, T2,
                        ws + wl.Kbar);
     SVGP_LAUNCH_CHECK();
     return SVGP_OK;
