@@ -12,7 +12,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import BWD_PART, FWD_PART, STATE, STATE_LEN, MnistCfg, ParamLayout, WsLayout, call
+from ._lib import STATE, STATE_LEN, MnistCfg, ParamLayout, WsLayout, call
+from .gp_route import gp_block_route, run_gp_route
 
 VAE_PARAM_NAMES = ("enc_c1_w", "enc_c1_b", "enc_c2_w", "enc_c2_b", "enc_c3_w", "enc_c3_b", "enc_d_w", "enc_d_b",
                    "dec_d_w", "dec_d_b", "dec_c1_w", "dec_c1_b", "dec_c2_w", "dec_c2_b", "dec_c3_w", "dec_c3_b")
@@ -648,39 +649,24 @@ class MnistStepEngine:
             self.stream.cuda_stream
         im, ax, ep = images.data_ptr(), aux.data_ptr(), (eps.data_ptr() if eps is not None else None)
         plan = ShardedExchange(self.ws, self.wl, self.base["m"], self.base["L"], self.rank, self.world_size)
-        l0, nl = plan.l0, plan.nl
-        fork = not _lib.Schedule().side_off
-        side = self._side_stream() if fork else self.stream
-        with torch.cuda.stream(self.stream):
-            call("svgp_mnist_encoder_kernel_matrix_fwd", cp, th, im, ax, ws, s)
-            call("svgp_gp_stats_fwd", cp, ws, s)
-        yield plan.point(1)
-        with torch.cuda.stream(self.stream):
-            call("svgp_gp_factor_fwd_channels_part", cp, l0, nl, FWD_PART["HEAD"], ws, s)
-            plan.pack_window(s)
-            # the tail and the early reverse half go to the side branch, beside the all-gather, the row stage, the decoder and
-            # the reverse statistics: FORKED here, ISSUED behind the collective (below) -- enqueued first, the branch's GEMMs
-            # fill the chip and the collective's kernel waits for a slot
-            side.wait_stream(self.stream)
-        yield plan.point(2)
-        with torch.cuda.stream(self.stream):
-            call("svgp_gp_posterior_fwd", cp, ep, ws, st, s)              # (first: the caller's stream must not wait for the host)
-            call("svgp_gp_factor_fwd_channels_part", cp, l0, nl, FWD_PART["TAIL"], ws, side.cuda_stream)
-            if fork:
-                call("svgp_gp_factor_bwd_channels_part", cp, l0, nl, BWD_PART["EARLY"], ws, st, side.cuda_stream)
+        lanes = {"main": self.stream}
+        if not _lib.Schedule().side_off:
+            lanes["side0"] = self._side_stream()
+
+        def decoder():
             call("svgp_mnist_decoder_fwd", cp, th, im, ws, s)
             call("svgp_mnist_decoder_bwd", cp, th, im, ws, st, s)
-            call("svgp_gp_stats_bwd", cp, ws, st, s)
-        yield plan.point(3)
-        with torch.cuda.stream(self.stream):
-            self.stream.wait_stream(side)
-            call("svgp_gp_factor_bwd_channels_part", cp, l0, nl, BWD_PART["LATE" if fork else "ALL"], ws, st, s)
-        yield plan.point(4)
-        with torch.cuda.stream(self.stream):
-            call("svgp_gp_posterior_bwd", cp, ws, st, s)
-            call("svgp_kernel_matrix_bwd_partials", cp, th, ax, ws, s)
-            call("svgp_mnist_encoder_bwd", cp, th, im, ws, s)
-            call("svgp_mnist_grad_reduce_all", cp, ax, ws, s)
+
+        call("svgp_mnist_encoder_kernel_matrix_fwd", cp, th, im, ax, ws, s)
+        # the sharded route, no Ki-gradient branch (the tail and the early reverse half beside the all-gather, the row stage, the
+        # decoder and the reverse statistics: gp_block_route)
+        route = gp_block_route(self.base["m"], bool(self.base["titsias"]), True, len(lanes) - 1, False)
+        for k in run_gp_route(route, lanes, cp, ws, st, eps=ep, window=lambda: (plan.l0, plan.nl), networks=decoder,
+                              pack_window=lambda: plan.pack_window(s)):
+            yield plan.point(k)
+        call("svgp_kernel_matrix_bwd_partials", cp, th, ax, ws, s)
+        call("svgp_mnist_encoder_bwd", cp, th, im, ws, s)
+        call("svgp_mnist_grad_reduce_all", cp, ax, ws, s)
         yield [ExchangeOp("allreduce", self.block("gradC"))]
         self.phase(3, adam)
 

@@ -23,18 +23,22 @@ products.  The m x m factorisations / inverses, the scalar epilogue, Adam and th
 """
 import ctypes as C
 import math
+from types import SimpleNamespace
 
 import numpy as np
 import torch
 
 from . import _lib
-from ._lib import BWD_PART, FWD_PART, STATE, STATE_LEN, MnistCfg, SpritesKcfg, WsLayout, call
+from ._lib import STATE, STATE_LEN, MnistCfg, SpritesKcfg, WsLayout, call
 from .conv import ConvLayer, DeferredSums
 from .engine import ExchangeOp, ShardedExchange, concurrent_streams
+from .gp_route import SHARD_NEEDS, gp_block_route, run_gp_route
 
 _F64 = torch.float64
 ENC_STRIDES = (1, 2, 1, 2, 1, 2)
 DEC_UP = (True, False, True, False, True, False, False)
+# exchange point of the GP block's route -> the stage that phases() marks behind it (bench.py --full)
+_MARK_BEHIND = {"statA": "gp_fwd_factor", 1: "gp_fwd_factor", "statB": "gp_bwd_factor", 3: "gp_bwd_factor"}
 
 
 def aux_data_sprites_utils(batch_size, N, repeats):
@@ -182,7 +186,7 @@ class SpritesStepEngine:
         if channel_shard is None:
             channel_shard = world_size > 1 and self.m > 64 and self.L % world_size == 0 and not svgp.titsias
         if channel_shard and (self.m <= 64 or self.L % world_size or svgp.titsias):
-            raise _lib.SvgpError("channel_shard needs m > 64, L divisible by the number of ranks and the Hensman branch")
+            raise _lib.SvgpError(SHARD_NEEDS)
         self.chan_shard = bool(channel_shard)
         self.base = dict(m=self.m, L=self.L, M=1, n_obj=0, normalize_obj=0, clip_qs=int(clip_qs), geco=int(geco),
                          train_ip=1, train_gp=1, train_ov=0, b_cap=b_max, clip_pv=1, n_pix=64 * 64 * 3,
@@ -233,6 +237,9 @@ class SpritesStepEngine:
 
     # ------------------------------------------------------------------ helpers
     trace = None     # bench.py: a list -> (stage name, event) appended at the stage boundaries of phases()
+    exchange_trace = None      # bench.py: a list -> (event, event) around every exchange point of step()
+    freeze_repr = False        # --repr_nn_pretrain yes_fixed (SPRITES_experiment.py:214-216): the representation network stays
+    _blocks_checked = False    # step(): the exchange blocks have the same lengths on every rank
 
     def _mark(self, name):
         if self.trace is not None:
@@ -407,12 +414,12 @@ class SpritesStepEngine:
         the three exchange blocks are summed over ranks by `self.comm` between the phases."""
         if self.world_size > 1 and self.comm is None:
             raise _lib.SvgpError("world_size > 1 needs a communicator (engine.RcclComm)")
-        if self.world_size > 1 and not getattr(self, "_blocks_checked", False):
+        if self.world_size > 1 and not self._blocks_checked:
             # the exchange blocks' lengths are functions of the row capacity: every rank must have been built with the same b_max
             from .engine import agree_on_lengths
             self._blocks_checked = agree_on_lengths([self.wl.statA_len, self.wl.statB_len, self.wl.gradC_len], self.comm,
                                                     self.dev, self.stream)
-        tr = getattr(self, "exchange_trace", None)
+        tr = self.exchange_trace
         for ops in self.phases(images, action_ids, eps, adam, b_global):
             if self.comm is not None:
                 if tr is not None:           # bench.py: events around every exchange point (pack + grouped launch + unpack)
@@ -425,7 +432,10 @@ class SpritesStepEngine:
         return self
 
     def phases(self, images, action_ids, eps=None, adam=True, b_global=None):
-        """The step as a generator (see _phases_body).  Whatever ends it -- exhaustion, an exception in a stage, the caller
+        """The step as a generator: yields, at every exchange point, the list of engine.ExchangeOp to run across the ranks.
+        Three points (all-reduce of the forward statistics, the backward statistics, gradients + scalar sums) in the plain form;
+        five in the channel-sharded form (reduce-scatter S, v | all-gather Sigma^-1, t, u | reduce-scatter A2, ud, td |
+        all-gather Ssym, vbar | all-reduce gradients + sums).  Whatever ends it -- exhaustion, an exception in a stage, the caller
         abandoning it at an exchange point -- the per-step weight layouts of the layers are dropped, so that a later forward()
         / backward() can never pick up layouts of parameters that have changed in place since."""
         try:
@@ -434,22 +444,41 @@ class SpritesStepEngine:
             for lay in self.enc + self.dec + self.rep:
                 lay._prep = None
 
-    def _phases_body(self, images, action_ids, eps=None, adam=True, b_global=None):
-        """Generator over the step: yields, at every exchange point, the list of engine.ExchangeOp to run across the
-        ranks.  Three points (all-reduce of the forward statistics, the backward statistics, gradients + scalar sums) in
-        the plain form; five in the channel-sharded form (reduce-scatter S, v | all-gather Sigma^-1, t, u |
-        reduce-scatter A2, ud, td | all-gather Ssym, vbar | all-reduce gradients + sums)."""
+    def _phases_body(self, images, action_ids, eps, adam, b_global):
+        """The step's outline.  Which stage of the sparse-GP block goes to which stream, and where the side streams are forked
+        and joined, is gp_route.gp_block_route (pinned in tests/test_sprites_route_cpu.py)."""
         b = images.shape[0]
         assert b <= self.b_max and b % self.seg_len == 0
-        b_global = b * self.world_size if b_global is None else b_global
-        p, g, s, L = self.params, self.grads, self.stream.cuda_stream, self.L
-        pn, gn, sfx = self.np_, self.ng, self.sfx            # the networks' (possibly float32) parameters / gradients
-        nd = dict(dtype=self.ndt, device=self.dev)
-        cfg = MnistCfg(b=b, b_global=b_global, **self.base)
-        self.cfg = cfg
-        cp = C.byref(cfg)
-        ws, st = self.ws.data_ptr(), self.state.data_ptr()
-        f64 = dict(dtype=_F64, device=self.dev)
+        self.cfg = MnistCfg(b=b, b_global=b * self.world_size if b_global is None else b_global, **self.base)
+        eps = None if eps is None else eps.contiguous()
+        t = self._head(images, action_ids, b)
+        self._mark("gp_fwd_stats")
+        n_side = 0 if self.side is None else 1 + (self.side2 is not None)        # (bench.py drops the side streams between steps)
+        route = gp_block_route(self.m, self.svgp.titsias, self.chan_shard, n_side, _lib.Schedule().kbar_branch)
+        lanes = {"main": self.stream, "side0": self.side, "side1": self.side2}
+        plan = None
+        for k in run_gp_route(route, lanes, C.byref(self.cfg), self.ws.data_ptr(), self.state.data_ptr(),
+                              eps=None if eps is None else eps.data_ptr(), window=lambda: (plan.l0, plan.nl),
+                              networks=lambda: self._decoder_fwd_bwd(t),
+                              pack_window=lambda: plan.pack_window(self.stream.cuda_stream)):
+            if self.chan_shard:
+                # channel-sharded exchange (the sequence of svgp_mnist_train_step_dp): points 1-4, each ONE grouped RCCL launch.
+                # Built behind the launch of the forward statistics: the stream has work while the host slices the blocks
+                plan = plan or ShardedExchange(self.ws, self.wl, self.m, self.L, self.rank, self.world_size)
+                yield plan.point(k)
+            else:
+                off = getattr(self.wl, k)                      # statA / statB
+                yield [ExchangeOp("allreduce", self.ws[off:off + getattr(self.wl, k + "_len")])]
+            if k in _MARK_BEHIND:
+                self._mark(_MARK_BEHIND[k])
+        self._tail(t)
+        yield [ExchangeOp("allreduce", self.grad), ExchangeOp("allreduce", self.ws[self.wl.sums:self.wl.sums + 8])]
+        self._optimiser(t, adam)
+
+    def _head(self, images, action_ids, b):
+        """Weight layouts of the step, then its two opening chains of small launches: representation network -> auxiliary data
+        -> kernel matrices, and the encoder.  Returns the step's tensors for the later stages."""
+        p, pn = self.params, self.np_
         self.stream.wait_stream(torch.cuda.current_stream(self.dev))
         with torch.cuda.stream(self.stream):
             images = images.to(self.ndt).contiguous()
@@ -465,7 +494,6 @@ class SpritesStepEngine:
                     lay.prepare(pn[f"{grp}_c{i}_w"], prep_stream.cuda_stream, need_bwd=not (grp != "dec" and i == 1))
             prep_done = torch.cuda.Event()
             prep_done.record(prep_stream)      # (an event, not the stream: more work goes to that stream later in the step)
-            deferred = DeferredSums()          # every layer's closing partial sums: ONE launch at the end of the step
             self._mark("nets_fwd_enc")
             kc = SpritesKcfg(b=b, m=self.m, La=self.La, Lc=self.Lc, n_act=self.n_act,
                              normalize=int(self.svgp.K_obj_normalize), k_se=int(self.svgp.K_SE),
@@ -478,7 +506,7 @@ class SpritesStepEngine:
 
             def repr_and_kernel_matrices(strm):
                 r_, rvec = self._repr_forward(images, b, stream=strm)
-                aux_ = torch.empty(b, 1 + self.Lc, **f64)
+                aux_ = torch.empty(b, 1 + self.Lc, dtype=_F64, device=self.dev)
                 call("svgp_sprites_aux_fwd", b, self.seg_len, self.Lc, rvec.data_ptr(), aid.data_ptr(), aux_.data_ptr(),
                      strm.cuda_stream)
                 call("svgp_sprites_kernel_matrix_fwd", C.byref(kc), aux_.data_ptr(), p["inducing_index_points"].data_ptr(),
@@ -486,197 +514,115 @@ class SpritesStepEngine:
                      strm.cuda_stream)
                 return r_, aux_
 
-            # the step opens with two independent chains of small launches: representation network -> auxiliary data -> kernel
-            # matrices, and the encoder; the first goes to the side stream (one stream: in line)
+            # the first chain goes to the side stream (one stream: in line)
             if self.side is not None:
                 self.side.wait_stream(self.stream)
                 with torch.cuda.stream(self.side):
                     r, aux = repr_and_kernel_matrices(self.side)
-                a, enc, mu, var_raw, var = self._encoder_forward(images, b)
+                a, enc, _, var_raw, _ = self._encoder_forward(images, b)
                 self.stream.wait_stream(self.side)
             else:
-                a, enc, mu, var_raw, var = self._encoder_forward(images, b)
+                a, enc, _, var_raw, _ = self._encoder_forward(images, b)
                 r, aux = repr_and_kernel_matrices(self.stream)
-            # ---------------- sparse-GP block
-            self._mark("gp_fwd_stats")
-            call("svgp_gp_stats_fwd", cp, ws, s)
-            if self.svgp.titsias:
-                call("svgp_gp_titsias_stats", cp, ws, s)
-        # channel-sharded exchange (the sequence of svgp_mnist_train_step_dp): five points, each ONE grouped RCCL launch
-        plan = ShardedExchange(self.ws, self.wl, self.m, L, self.rank, self.world_size) if self.chan_shard else None
-        if self.chan_shard:
-            l0, nl = plan.l0, plan.nl
-            yield plan.point(1)
-        else:
-            yield [ExchangeOp("allreduce", self.ws[self.wl.statA:self.wl.statA + self.wl.statA_len])]
-        eps_ptr = None if eps is None else eps.contiguous().data_ptr()
-        # The side work of the forward factor stage -- its tail ((A_hat + jI)^-1, log det, KL_l: a whole batched inverse that only
-        # the reverse factor stage and the final scalars need; include/svgpvae_hip.h: svgp_gp_factor_fwd_aji_tail) and the early
-        # half of the reverse factor stage (no reverse statistic needed) -- runs beside the row stage, the decoder and the reverse
-        # statistics.  It is FORKED right behind the stage but ISSUED behind the row stage: its launches (two blocked factorisations)
-        # take the host ~0.5 ms to enqueue, and the caller's stream must not run dry meanwhile; the branch has the slack.
-        side_work = None
-        with torch.cuda.stream(self.stream):
-            self._mark("gp_fwd_factor")
-            if self.chan_shard:
-                call("svgp_gp_factor_fwd_channels_part", cp, l0, nl, FWD_PART["HEAD"], ws, s)
-                plan.pack_window(s)
-                sd = self.side if self.side is not None else self.stream
-                sd.wait_stream(self.stream)
+        # deferred: every layer's closing partial sums, ONE launch at the end of the step
+        return SimpleNamespace(b=b, images=images, kc=kc, a=a, enc=enc, var_raw=var_raw, r=r, aux=aux, deferred=DeferredSums(),
+                               prep_done=prep_done if prep_stream is not self.stream else None, recon=None)
 
-                def side_work():
-                    call("svgp_gp_factor_fwd_channels_part", cp, l0, nl, FWD_PART["TAIL"], ws, sd.cuda_stream)
-                    if self.side is not None:
-                        call("svgp_gp_factor_bwd_channels_part", cp, l0, nl, BWD_PART["EARLY"], ws, st, sd.cuda_stream)
-            elif self.m > 64 and self.side is not None and not self.svgp.titsias:
-                # (not with titsias: svgp_gp_titsias_fwd inverts through the same scratch, ws.scr_inv, on the main stream)
-                call("svgp_gp_factor_fwd_defer_aji", cp, ws, s)
-                self.side.wait_stream(self.stream)
-                if self.side2 is not None:
-                    self.side2.wait_stream(self.stream)
-
-                def side_work():
-                    call("svgp_gp_factor_fwd_aji_tail", cp, ws, self.side.cuda_stream)
-                    # the first part of the early reverse half beside the tail on a third stream (it does not need the tail's
-                    # inverse), its second part behind both
-                    if self.side2 is not None:
-                        call("svgp_gp_factor_bwd_early_a", cp, ws, st, self.side2.cuda_stream)
-                        self.side.wait_stream(self.side2)
-                        call("svgp_gp_factor_bwd_early_b", cp, ws, st, self.side.cuda_stream)
-                    else:
-                        call("svgp_gp_factor_bwd_early", cp, ws, st, self.side.cuda_stream)
-            else:
-                call("svgp_gp_factor_fwd", cp, ws, s)
-        if self.chan_shard:
-            yield plan.point(2)
+    def _decoder_fwd_bwd(self, t):
+        """The route's `networks` marker, between the row stage and the reverse statistics: decoder, squared error, and their
+        reverse pass down to zbar."""
+        b, L, s, sfx, pn, gn = t.b, self.L, self.stream.cuda_stream, self.sfx, self.np_, self.ng
+        st = self.state.data_ptr()
         with torch.cuda.stream(self.stream):
-            call("svgp_gp_posterior_fwd", cp, eps_ptr, ws, st, s)
-            if side_work is not None:
-                side_work()
-            if self.svgp.titsias:
-                call("svgp_gp_titsias_fwd", cp, ws, st, s)
-            # ---------------- decoder
             z = self._v("z", (b, L))
             self._mark("nets_fwd_dec")
-            if prep_stream is not self.stream:
-                self.stream.wait_event(prep_done)
+            if t.prep_done is not None:
+                self.stream.wait_event(t.prep_done)
             h0, d = self._decoder_forward(z, b)
-            x = d[-1]
-            recon = x
+            t.recon = recon = d[-1]
             tot = b * 64 * 64 * 3
-            call("svgp_sqerr_fwd" + sfx, tot, min(b, 256), images.data_ptr(), recon.data_ptr(),
+            call("svgp_sqerr_fwd" + sfx, tot, min(b, 256), t.images.data_ptr(), recon.data_ptr(),
                  self._v("part_sums", (1,)).data_ptr(), s)
             # ================ reverse
             self._mark("nets_bwd_dec")
             dx = torch.empty_like(recon)
-            call("svgp_sqerr_bwd" + sfx, tot, int(self.geco), b_global, 64 * 64 * 3, st, images.data_ptr(), recon.data_ptr(),
-                 dx.data_ptr(), s)
+            call("svgp_sqerr_bwd" + sfx, tot, int(self.geco), self.cfg.b_global, 64 * 64 * 3, st, t.images.data_ptr(),
+                 recon.data_ptr(), dx.data_ptr(), s)
             for i in range(7, 0, -1):
                 lay = self.dec[i - 1]
                 xin = d[i - 2] if i > 1 else h0.view(b, 8, 8, 16)
                 dx = lay.backward(xin, pn[f"dec_c{i}_w"], d[i - 1], dx, gn[f"dec_c{i}_w"], gn[f"dec_c{i}_b"],
-                                  self.lscratch[("dec", i)], s, nwg=self.nwg, deferred=deferred)
+                                  self.lscratch[("dec", i)], s, nwg=self.nwg, deferred=t.deferred)
             dh0 = dx.view(b, 1024)
             zn = self._to_net(z)
             self._gemm(1, 0, L, 1024, b, 1.0, zn, L, dh0, 1024, 0.0, gn["dec_d_w"], 1024)
             self._colsum(dh0, b, 1024, gn["dec_d_b"])
             zbar = self._v("zbar", (b, L))
             if self.f32:
-                zb = torch.empty(b, L, **nd)
+                zb = torch.empty(b, L, dtype=self.ndt, device=self.dev)
                 self._gemm(0, 1, b, L, 1024, 1.0, dh0, 1024, pn["dec_d_w"], 1024, 0.0, zb, L)
                 self._to_f64(zb, out=zbar)
             else:
                 self._gemm(0, 1, b, L, 1024, 1.0, dh0, 1024, pn["dec_d_w"], 1024, 0.0, zbar, L)
             self._mark("gp_bwd_stats")
-            call("svgp_gp_stats_bwd", cp, ws, st, s)
-        if self.chan_shard:
-            yield plan.point(3)
-        else:
-            yield [ExchangeOp("allreduce", self.ws[self.wl.statB:self.wl.statB + self.wl.statB_len])]
-        with torch.cuda.stream(self.stream):
-            self._mark("gp_bwd_factor")
-            if self.chan_shard:
-                if self.side is not None:
-                    self.stream.wait_stream(self.side)
-                call("svgp_gp_factor_bwd_channels_part", cp, l0, nl, BWD_PART["LATE" if self.side is not None else "ALL"], ws, st, s)
-            elif self.m > 64 and self.side is not None and not self.svgp.titsias:
-                # the part of the late half that reads nothing the side branch writes -- the vector chain and, with all rows local, X and
-                # the two full products Si X, (Si X) Si: 2.3 ms at m = 800 -- BEFORE the join: the caller's stream used to wait 0.8 ms
-                # there for the second inverse + early half with that work ready (kernel trace, round 5)
-                call("svgp_gp_factor_bwd_late_a", cp, ws, st, s)
-                self.stream.wait_stream(self.side)
-                if _lib.Schedule().kbar_branch:
-                    # round 6 (as csrc/api.hip does for the MNIST step): the single-matrix chain of the gradient of Ki on the branch that
-                    # has just been joined, beside the channel block
-                    self.side.wait_stream(self.stream)
-                    call("svgp_gp_factor_bwd_late_b_kbar", cp, ws, st, self.side.cuda_stream)
-                    call("svgp_gp_factor_bwd_late_b_channels", cp, ws, st, s)
-                    self.stream.wait_stream(self.side)
-                    call("svgp_gp_factor_bwd_late_b_final", cp, ws, st, s)
-                else:
-                    call("svgp_gp_factor_bwd_late_b", cp, ws, st, s)
-            else:
-                call("svgp_gp_factor_bwd", cp, ws, st, s)
-        if self.chan_shard:
-            yield plan.point(4)
-        with torch.cuda.stream(self.stream):
-            call("svgp_gp_posterior_bwd", cp, ws, st, s)
-            if self.svgp.titsias:
-                call("svgp_gp_titsias_bwd", cp, ws, st, s)
-            # The end of the step is two independent chains of small launches (5 - 7 us each, the GPU is waiting for the next one
-            # most of the time): kernel-matrix reverse pass -> representation network, and encoder head -> encoder.  Both need
-            # only the reverse row stage above, so the encoder chain goes to the side stream (idle since the reverse factor stage)
-            # with its own weight-gradient scratch: 1.12 -> 0.65 ms for this tail at m = 800.  SVGP_SIDE_STREAMS=0: in line.
-            enc_side = self.side is not None
 
-            def encoder_bwd(sx, scratch):
-                d_enc = torch.empty(b, 2 * L, **f64)
-                call("svgp_enc_head_bwd", b, L, int(self.clip_qs), var_raw.data_ptr(), self._v("ybar", (1,)).data_ptr(),
-                     self._v("s2bar", (1,)).data_ptr(), d_enc.data_ptr(), sx)
-                d_enc = self._to_net(d_enc, stream=sx)
-                a6 = a[5].view(b, 1024)
-                self._gemm(1, 0, 1024, 2 * L, b, 1.0, a6, 1024, d_enc, 2 * L, 0.0, gn["enc_d_w"], 2 * L, stream=sx)
-                self._colsum(d_enc, b, 2 * L, gn["enc_d_b"], stream=sx)
-                dxe = torch.empty(b, 8, 8, 16, **nd)
-                self._gemm(0, 1, b, 1024, 2 * L, 1.0, d_enc, 2 * L, pn["enc_d_w"], 2 * L, 0.0, dxe, 1024, stream=sx)
-                for i in range(6, 0, -1):
-                    xin = a[i - 2] if i > 1 else images
-                    dxe = self.enc[i - 1].backward(xin, pn[f"enc_c{i}_w"], a[i - 1], dxe, gn[f"enc_c{i}_w"], gn[f"enc_c{i}_b"],
-                                                   self.lscratch[("enc", i)], sx, need_dx=i > 1, nwg=self.nwg, deferred=deferred)
+    def _encoder_backward(self, t, sx):
+        """Encoder head and encoder, reverse, on stream handle `sx` (the caller has made that stream current)."""
+        b, L, pn, gn = t.b, self.L, self.np_, self.ng
+        d_enc = torch.empty(b, 2 * L, dtype=_F64, device=self.dev)
+        call("svgp_enc_head_bwd", b, L, int(self.clip_qs), t.var_raw.data_ptr(), self._v("ybar", (1,)).data_ptr(),
+             self._v("s2bar", (1,)).data_ptr(), d_enc.data_ptr(), sx)
+        d_enc = self._to_net(d_enc, stream=sx)
+        a6 = t.a[5].view(b, 1024)
+        self._gemm(1, 0, 1024, 2 * L, b, 1.0, a6, 1024, d_enc, 2 * L, 0.0, gn["enc_d_w"], 2 * L, stream=sx)
+        self._colsum(d_enc, b, 2 * L, gn["enc_d_b"], stream=sx)
+        dxe = torch.empty(b, 8, 8, 16, dtype=self.ndt, device=self.dev)
+        self._gemm(0, 1, b, 1024, 2 * L, 1.0, d_enc, 2 * L, pn["enc_d_w"], 2 * L, 0.0, dxe, 1024, stream=sx)
+        for i in range(6, 0, -1):
+            xin = t.a[i - 2] if i > 1 else t.images
+            dxe = self.enc[i - 1].backward(xin, pn[f"enc_c{i}_w"], t.a[i - 1], dxe, gn[f"enc_c{i}_w"], gn[f"enc_c{i}_b"],
+                                           self.lscratch[("enc", i)], sx, need_dx=i > 1, nwg=self.nwg, deferred=t.deferred)
 
-            if enc_side:
+    def _tail(self, t):
+        """The end of the step is two independent chains of small launches (5 - 7 us each, the GPU is waiting for the next one
+        most of the time): kernel-matrix reverse pass -> representation network, and encoder head -> encoder.  Both need only the
+        reverse row stage, so the encoder chain goes to the side stream (idle since the reverse factor stage): 1.12 -> 0.65 ms
+        for this tail at m = 800.  SVGP_SIDE_STREAMS=0: in line.  Then the deferred sums, the frozen groups, the scalar sums."""
+        b, s, p, g, pn, gn = t.b, self.stream.cuda_stream, self.params, self.grads, self.np_, self.ng
+        with torch.cuda.stream(self.stream):
+            if self.side is not None:
                 self.side.wait_stream(self.stream)
                 with torch.cuda.stream(self.side):
-                    encoder_bwd(self.side.cuda_stream, self.scratch2)
-            d_char = torch.empty(b, self.Lc, **f64)
-            call("svgp_sprites_kernel_matrix_bwd", C.byref(kc), aux.data_ptr(), p["inducing_index_points"].data_ptr(),
+                    self._encoder_backward(t, self.side.cuda_stream)
+            d_char = torch.empty(b, self.Lc, dtype=_F64, device=self.dev)
+            call("svgp_sprites_kernel_matrix_bwd", C.byref(t.kc), t.aux.data_ptr(), p["inducing_index_points"].data_ptr(),
                  p["GPLVM_action"].data_ptr(), p["se"].data_ptr(), self._v("Kbar", (1,)).data_ptr(),
                  self._v("Knbar", (1,)).data_ptr(), self._v("knnbar", (1,)).data_ptr(),
                  g["inducing_index_points"].data_ptr(), g["GPLVM_action"].data_ptr(), d_char.data_ptr(),
                  g["se"].data_ptr(), self.kscratch.data_ptr(), self.kscratch.numel(), s)
             self._mark("nets_bwd_enc")
-            d_rvec = torch.empty(b, self.Lc, **f64)
+            d_rvec = torch.empty(b, self.Lc, dtype=_F64, device=self.dev)
             call("svgp_sprites_aux_bwd", b, self.seg_len, self.Lc, d_char.data_ptr(), d_rvec.data_ptr(), s)
             d_rvec = self._to_net(d_rvec)
-            dx = torch.empty(b, 8, 8, self.Lc, **nd)
-            call("svgp_avgpool_bwd" + sfx, b, 64, self.Lc, d_rvec.data_ptr(), dx.data_ptr(), s)
+            dx = torch.empty(b, 8, 8, self.Lc, dtype=self.ndt, device=self.dev)
+            call("svgp_avgpool_bwd" + self.sfx, b, 64, self.Lc, d_rvec.data_ptr(), dx.data_ptr(), s)
             for i in range(3, 0, -1):
-                xin = r[i - 2] if i > 1 else images
-                dx = self.rep[i - 1].backward(xin, pn[f"repr_c{i}_w"], r[i - 1], dx, gn[f"repr_c{i}_w"], gn[f"repr_c{i}_b"],
-                                              self.lscratch[("rep", i)], s, need_dx=i > 1, nwg=self.nwg, deferred=deferred)
-            if enc_side:
+                xin = t.r[i - 2] if i > 1 else t.images
+                dx = self.rep[i - 1].backward(xin, pn[f"repr_c{i}_w"], t.r[i - 1], dx, gn[f"repr_c{i}_w"], gn[f"repr_c{i}_b"],
+                                              self.lscratch[("rep", i)], s, need_dx=i > 1, nwg=self.nwg, deferred=t.deferred)
+            if self.side is not None:
                 self.stream.wait_stream(self.side)
             else:
-                encoder_bwd(s, self.scratch)
+                self._encoder_backward(t, s)
             # every layer's weight / bias partial sums in one launch, then the folds of the up layers' effective-weight gradients;
             # the per-step weight layouts are dropped (the parameters change in the optimiser step below)
-            deferred.flush(s)
+            t.deferred.flush(s)
             for lay in self.enc + self.dec + self.rep:
                 lay._prep = None
             if self.f32:                                       # float32 network gradients -> the float64 gradient vector
                 call("svgp_cast_f32_f64", self.n_net, self.grad_n.data_ptr(), self.grad.data_ptr(), s)
             # frozen parameter groups (inverted flags of SPRITES_experiment.py:109-111)
-            if getattr(self, "freeze_repr", False):           # --repr_nn_pretrain yes_fixed (SPRITES_experiment.py:214-216)
+            if self.freeze_repr:
                 for k in g:
                     if k.startswith("repr_"):
                         g[k].zero_()
@@ -686,8 +632,10 @@ class SpritesStepEngine:
                 g["GPLVM_action"].zero_()
             if self.svgp.fixed_GP_params or not self.svgp.K_SE:
                 g["se"].zero_()
-            call("svgp_mnist_grad_reduce", cp, ws, s)           # scalar partial sums -> ws.sums
-        yield [ExchangeOp("allreduce", self.grad), ExchangeOp("allreduce", self.ws[self.wl.sums:self.wl.sums + 8])]
+            call("svgp_mnist_grad_reduce", C.byref(self.cfg), self.ws.data_ptr(), s)           # scalar partial sums -> ws.sums
+
+    def _optimiser(self, t, adam):
+        cp, ws, st, s = C.byref(self.cfg), self.ws.data_ptr(), self.state.data_ptr(), self.stream.cuda_stream
         with torch.cuda.stream(self.stream):
             self._mark("optim")
             if self.clip_grad is not None:
@@ -699,7 +647,8 @@ class SpritesStepEngine:
             else:
                 call("svgp_elbo_finalize_noadam", cp, ws, st, s)
             self._mark("end")
-            self.act = dict(recon=recon.double() if self.f32 else recon, aux=aux, enc=enc)     # (outputs(): not on the step's path)
+            # (outputs(): not on the step's path)
+            self.act = dict(recon=t.recon.double() if self.f32 else t.recon, aux=t.aux, enc=t.enc)
 
     def outputs(self):
         """The 16-tuple of forward_pass_SVGPVAE for the last step (mean_vectors slot = aux data)."""

@@ -102,16 +102,23 @@ def test_sprites_training_steps_reduce_the_loss():
     assert eng.scalars()["adam_t"] == 8.0
 
 
+_ONE_STREAM = {}     # net_dtype -> the one-stream engine's result, shared by the schedules of the test below
+
+
+@pytest.mark.parametrize("schedule", [{}, {"SVGP_SIDE_STREAMS": "2"}, {"SVGP_KBAR_BRANCH": "0"}],
+                         ids=lambda e: " ".join(f"{k[5:]}={v}" for k, v in e.items()) or "default")
 @pytest.mark.parametrize("net_dtype", [torch.float64, torch.float32])
-def test_sprites_side_streams_equal_one_stream(net_dtype):
+def test_sprites_side_streams_equal_one_stream(net_dtype, schedule, monkeypatch):
     """m > 64: three Adam steps with the side branches (forward-factor tail + early reverse half, and the encoder reverse pass
     beside the kernel-matrix / representation-network reverse pass) against the same engine with every launch on one stream:
-    identical parameters and Adam state, bit for bit (the same kernels on the same values, only the order of issue differs)."""
+    identical parameters and Adam state, bit for bit (the same kernels on the same values, only the order of issue differs).
+    schedule: two side streams (default), one (SVGP_SIDE_STREAMS=2: the early reverse half behind the forward tail), and the
+    late reverse half in one call on the caller's stream (SVGP_KBAR_BRANCH=0) -- the routes of tests/test_sprites_route_cpu.py."""
     from svgp_vae_amd import sprites as S
     b, frames, L, La, Lc, m, n_act = 24, 4, 6, 8, 16, 72, 9
     params, gp, images, ids, eps, seg, rep = _problem(b, frames, L, La, Lc, m, n_act, seed=5)
-    out = []
-    for one_stream in (False, True):
+
+    def run(one_stream):
         svgp = S.spritesSVGP(False, False, gp["inducing_index_points"].numpy(), 'main', 0.01, 100.0, La,
                              gp["GPLVM_action"].numpy(), Lc, L, K_obj_normalize=True)
         eng = S.SpritesStepEngine(S.spritesVAE(L), S.sprites_representation_network(Lc), svgp, b_max=b, seg_len=frames,
@@ -119,13 +126,20 @@ def test_sprites_side_streams_equal_one_stream(net_dtype):
         assert eng.side is not None and eng.scratch2 is not None
         if one_stream:
             eng.side = eng.side2 = None
+        else:
+            assert (eng.side2 is None) == (schedule.get("SVGP_SIDE_STREAMS") == "2")
         dev = eng.dev
         di, da, de = images.to(dev, net_dtype), ids.to(dev, DT), eps.to(dev)
         for _ in range(3):
             eng.step(di, da, de, adam=True)
         eng.stream.synchronize()
-        out.append((eng.theta.clone(), eng.adam_m.clone(), eng.adam_v.clone(), eng.state.clone()))
-    for x, y in zip(*out):
+        return eng.theta.clone(), eng.adam_m.clone(), eng.adam_v.clone(), eng.state.clone()
+
+    if net_dtype not in _ONE_STREAM:
+        _ONE_STREAM[net_dtype] = run(True)
+    for name, value in schedule.items():
+        monkeypatch.setenv(name, value)
+    for x, y in zip(run(False), _ONE_STREAM[net_dtype]):
         assert torch.equal(x, y)
 
 
