@@ -1071,6 +1071,33 @@ int svgp_mnist_generate(const svgp_mnist_cfg* cfg, const double* theta, const do
                         const double* eps, double* images_out, double* p_m_out, double* p_v_out, double* work, void* stream);
 int svgp_mnist_generate_route(const svgp_mnist_cfg* cfg, char* buf, int cap);
 
+/* ---- SPRITES: latent rows of a new character from a posterior cache (sprites_generate.hip) ---------
+ * The GP posterior of spritesSVGP.approximate_posterior_params_precomputed_GP_posterior_params (SVGPVAE_model.py:610-635)
+ * depends on the train set only through  w_l = Sigma_l^-1 K_mn (mu_l / var_l)  (L, m)  and  X_l = Sigma_l^-1 - K_mm^-1
+ * (L, m, m).  For the cfg->b query rows with kernel rows Kb (b, m) and prior variances kbb (b), per row i and channel l:
+ *   p_m[i,l] = Kb[i,:] . w_l      p_v[i,l] = clamp(kbb[i] + Kb[i,:] X_l Kb[i,:]^T, clip_lo, clip_hi)
+ *   z[i,l]   = p_m + eps[i,l] sqrt(p_v);  eps NULL: z = p_m (the decode of the posterior mean);  z NULL: not written.
+ * A workgroup owns 64 rows of one channel, walks column tiles of Kb X_l on the f64 MFMA, multiplies each accumulator tile by the
+ * matching Kb tile and keeps the row sums in registers: no buffer grows with b m.  m <= 256: ONE launch over all column tiles, no
+ * workspace (work may be NULL).  m > 256: the column tiles of a (row block, channel) are dealt to S <= 16 workgroups (about 1024
+ * workgroups in all; S = 1 where rows x channels alone give that many), each writes its partial row sums to work (S, b, L) and a
+ * second launch adds the S partials of an element in index order, clamps and draws; ..._workspace_elems returns S b L (0 for
+ * S = 1), at most 16 b L.  Of the outputs only their b L elements are written.  X is NOT assumed symmetric.  No atomics, fixed
+ * summation order: the same inputs give the same bits.  A NaN in p_v stays a NaN through the clamp (torch.clamp).
+ * ..._route: the kernels of one call as text, one name per line in launch order, from the same plan; needs no device.
+ * Accepted: 1 <= m <= 2048, 1 <= L <= 64, b >= 1, clip_lo <= clip_hi.  Outside that, a NULL cfg, a NULL Kb / kbb / w / X /
+ * p_m / p_v, or a NULL work where the size is non-zero: SVGP_ERR_INVALID with a message, before any launch.  Explicit stream,
+ * no allocation, no synchronisation.                                                                                          */
+typedef struct {
+    int32_t b, m, L;
+    double clip_lo, clip_hi;
+} svgp_posterior_rows_cfg;
+long long svgp_sprites_posterior_rows_workspace_elems(const svgp_posterior_rows_cfg* cfg);
+int svgp_sprites_posterior_rows(const svgp_posterior_rows_cfg* cfg, const double* Kb, const double* kbb, const double* w,
+                                const double* X, const double* eps, double* p_m, double* p_v, double* z, double* work,
+                                void* stream);
+int svgp_sprites_posterior_rows_route(const svgp_posterior_rows_cfg* cfg, char* buf, int cap);
+
 /* ---- runtime helpers: HIP graphs and events without going through torch ---------------------*/
 int svgp_stream_create(void** stream_out);
 /* HIP maps streams onto a small pool of hardware queues (GPU_MAX_HW_QUEUES) in creation order; two streams on one queue run

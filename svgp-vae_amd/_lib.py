@@ -104,6 +104,11 @@ class CacheLayout(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("acc_S", "acc_v", "acc_rows", "w", "X", "total")]
 
 
+class PosteriorRowsCfg(C.Structure):
+    """svgp_posterior_rows_cfg (include/svgpvae_hip.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("b", "m", "L")] + [(n, C.c_double) for n in ("clip_lo", "clip_hi")]
+
+
 STATE = dict(C_MA=0, LAGRANGE=1, ALPHA=2, ADAM_T=3, LR=4, BETA=5, ELBO=6, RECON_LOSS=7, KL_TERM=8,
              INSIDE_ELBO=9, CE_TERM=10, INSIDE_RECON=11, INSIDE_KL=12, RNG_CTR=13)
 STATE_LEN = 16
@@ -308,6 +313,8 @@ SIGNATURES = {
     "svgp_mnist_cache_build": [_CFG, _P, _P, _P, _P],
     "svgp_mnist_generate": [_CFG, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P],
     "svgp_mnist_generate_route": [_CFG, C.c_char_p, C.c_int],
+    "svgp_sprites_posterior_rows": [C.POINTER(PosteriorRowsCfg)] + [_P] * 10,
+    "svgp_sprites_posterior_rows_route": [C.POINTER(PosteriorRowsCfg), C.c_char_p, C.c_int],
     "svgp_stream_create": [C.POINTER(_P)],
     "svgp_stream_destroy": [_P],
     "svgp_stream_sync": [_P],
@@ -345,6 +352,7 @@ NON_STATUS = {"svgp_version": ([], C.c_int), "svgp_last_error": ([], C.c_char_p)
               "svgp_svigp_workspace_elems": ([C.c_int, C.c_int, C.c_int], C.c_longlong),
               "svgp_mnist_cache_workspace_elems": ([_CFG], C.c_longlong),
               "svgp_mnist_generate_workspace_elems": ([_CFG], C.c_longlong),
+              "svgp_sprites_posterior_rows_workspace_elems": ([C.POINTER(PosteriorRowsCfg)], C.c_longlong),
               "svgp_svigp_scale_offset": ([C.c_int, C.c_int, C.c_int], C.c_longlong)}
 
 _lib = None
