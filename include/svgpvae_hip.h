@@ -189,7 +189,8 @@ const char* svgp_last_error(void);
 /* sizeof() of the ABI structs as compiled into the library, so a binding can verify its own mirror of a struct at load
  * time (a stale mirror shifts every later field silently): which = 0 svgp_mnist_cfg, 1 svgp_mnist_param_layout,
  * 2 svgp_mnist_ws_layout, 3 svgp_stream_kdesc, 4 svgp_conv_desc, 5 svgp_sprites_kcfg, 6 svgp_pearce_bufs,
- * 7 svgp_sum_job, 8 svgp_casale_cfg, 9 svgp_casale_layout, 10 svgp_ball_large_cfg, 11 svgp_mnist_cache_layout; -1 otherwise. */
+ * 7 svgp_sum_job, 8 svgp_casale_cfg, 9 svgp_casale_layout, 10 svgp_ball_large_cfg, 11 svgp_mnist_cache_layout,
+ * 13 svgp_ball_predict_cfg, 14 svgp_ball_predict_bufs; -1 otherwise (12 is not assigned). */
 int         svgp_struct_sizeof(int which);
 
 int svgp_mnist_param_layout_get(const svgp_mnist_cfg* cfg, svgp_mnist_param_layout* out);
@@ -1097,6 +1098,51 @@ int svgp_sprites_posterior_rows(const svgp_posterior_rows_cfg* cfg, const double
                                 const double* X, const double* eps, double* p_m, double* p_v, double* z, double* work,
                                 void* stream);
 int svgp_sprites_posterior_rows_route(const svgp_posterior_rows_cfg* cfg, char* buf, int cap);
+
+/* ---- moving ball: fill dropped frames, resample in time (ball_predict.hip) --------------------------
+ * The sparse-GP posterior of SVGP.approximate_posterior_params (SVGPVAE_model.py:142-171) at arbitrary query times tq (Q) -- any
+ * reals, unsorted, inside or outside the frame times -- from the frames a mask keeps.  Per video b and latent coordinate, with
+ * SE(a, b) = exp(-(a - b)^2 / (2 ls^2)), p = mask * reciprocal_no_nan(var) (a dropped frame has precision 0; where p = 0 the
+ * product p mu counts as 0), K = SE(ip, ip), Kn = SE(times, ip), k = SE(tq, ip):
+ *   Sig = K + Kn^T diag(p) Kn    Si = (Sig + jitter I)^-1    Ki = (K + jitter I)^-1    w = Si Kn^T (p mu)    X = Si - Ki
+ *   p_m = k w      p_v = 1 + diag(k X k^T)  (reported unclamped)      z = p_m + eps sqrt(clamp(p_v, clip_lo, clip_hi))  (:701)
+ * mu, var and mask are (T, B), the frame-major layout svgp_ball_head_fwd writes; mask (values 0 / 1) is shared by the two
+ * coordinates, NULL = all ones.  eps and the outputs p_m, p_v, z are (Q, B) per coordinate.  eps NULL: z = p_m; z NULL: not written.
+ * A video with every frame dropped gives the prior, p_m = 0 and p_v = 1.
+ * svgp_ball_predict: 1 <= m <= 64, 1 <= T <= 16384, B, Q >= 1.  ONE launch, a workgroup per (video, coordinate): K in LDS, the
+ *   frames streamed in order (no (T, m) matrix), both inverses by the same LDS sweep (X = 0 exactly for the all-dropped video), then
+ *   the query times.  No workspace, no atomics, fixed summation order: the same inputs give the same bits, and a query time's
+ *   outputs do not depend on its position in tq.
+ * svgp_ball_predict_large: 1 <= m <= 2048, 1 <= T <= 2048: the same results up to rounding from svgp_se1d_kernel_matrix_fwd, a
+ *   row-scaling kernel + svgp_dgemm_batched (Sig_b, Kn^T (p mu)), svgp_spd_inverse_batched on the Sig_b + jitter I of a chunk and on
+ *   K + jitter I, a batched product (w), a subtraction (X) and svgp_sprites_posterior_rows with the videos of the chunk as channels
+ *   (kbb = 1).  The videos are walked in chunks of 64 (one rows call each) and the query rows in chunks of 4096; work holds
+ *   svgp_ball_predict_large_workspace_elems(cfg) doubles (0 for a refused cfg), which grows with neither B beyond 64 nor Q beyond
+ *   4096.  The rows kernel gets an unbounded clip range and draws nothing: the clamp applies to the sample only and is taken by
+ *   this entry's closing kernel.
+ * svgp_ball_predict_route: the kernels (library entry points for the shared pieces) of one call as text, one name per line in
+ *   launch order, from the same plan as the launch code; needs no device.  SVGP_ERR_INVALID when cap bytes do not hold the text.
+ * Refused with a message before any launch: a NULL cfg / bufs / pointer (mask, eps_x/y and z_x/y excepted), B, T, m or Q < 1,
+ *   clip_lo > clip_hi, NULL work (SVGP_ERR_INVALID); m or T beyond the entry's range (SVGP_ERR_UNSUPPORTED).
+ * Explicit stream, no allocation, no synchronisation.                                                                          */
+typedef struct {
+    int32_t B, T, m, Q;
+    double jitter, clip_lo, clip_hi;
+} svgp_ball_predict_cfg;
+typedef struct {
+    const double *times, *tq;                 /* (T), (Q) */
+    const double *ip_x, *ip_y;                /* (m) */
+    const double *ls_x, *ls_y;                /* scalars */
+    const double *mu_x, *mu_y, *var_x, *var_y;/* (T, B) */
+    const double *mask;                       /* (T, B) or NULL */
+    const double *eps_x, *eps_y;              /* (Q, B) or NULL */
+    double *p_m_x, *p_m_y, *p_v_x, *p_v_y;    /* (Q, B) */
+    double *z_x, *z_y;                        /* (Q, B) or NULL */
+} svgp_ball_predict_bufs;
+int svgp_ball_predict(const svgp_ball_predict_cfg* cfg, const svgp_ball_predict_bufs* bufs, void* stream);
+long long svgp_ball_predict_large_workspace_elems(const svgp_ball_predict_cfg* cfg);
+int svgp_ball_predict_large(const svgp_ball_predict_cfg* cfg, const svgp_ball_predict_bufs* bufs, double* work, void* stream);
+int svgp_ball_predict_route(const svgp_ball_predict_cfg* cfg, int large, char* buf, int cap);
 
 /* ---- runtime helpers: HIP graphs and events without going through torch ---------------------*/
 int svgp_stream_create(void** stream_out);

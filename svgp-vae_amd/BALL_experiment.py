@@ -11,7 +11,8 @@ SVGP objects with the inverted `fixed_*` flags (:100-103), loss = -mean(elbo) wi
 clip (:116-136), and every `--eval_every` (reference: 1000) steps the test-batch diagnostics at beta = 1 (:219-247):
 ELBO terms, posterior ranges, MSE of the affinely rotated latent paths (MSE_rotation), appended to
 <chkpnt>/res/ELBO_log.jsonl when --save.  Plotting / pandas logging / TF checkpoints are not reproduced; --save_model
-writes the flat parameter vector + Adam moments (BALL_experiment.py:270-272 saves every 50000 steps).
+writes the flat parameter vector + Adam moments (BALL_experiment.py:270-272 saves every 50000 steps) and a "meta" dict with the
+model's shape, from which svgp_vae_amd.ball_predict rebuilds the model.
 """
 import argparse
 import json
@@ -161,7 +162,10 @@ def run_experiment(args):
     if args.save_model and chk:
         eng.stream.synchronize()
         torch.save({"theta": eng.theta.cpu(), "adam_m": eng.adam_m.cpu(), "adam_v": eng.adam_v.cpu(),
-                    "state": eng.state.cpu(), "shapes": eng.shapes}, chk + "model.pt")
+                    "state": eng.state.cpu(), "shapes": eng.shapes,
+                    # what svgp_vae_amd.ball_predict needs to rebuild the model (additive: the keys above are unchanged)
+                    "meta": dict(elbo=args.elbo, tmax=args.tmax, m=args.m, hidden=args.hidden, px=px, py=py, jitter=args.jitter,
+                                 clip_qs=bool(args.clip_qs), vidlt=args.vidlt)}, chk + "model.pt")
         print("\n\nModel Saved: " + chk + "\n\n")
     return log
 

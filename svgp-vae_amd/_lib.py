@@ -109,6 +109,17 @@ class PosteriorRowsCfg(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("b", "m", "L")] + [(n, C.c_double) for n in ("clip_lo", "clip_hi")]
 
 
+class BallPredictCfg(C.Structure):
+    """svgp_ball_predict_cfg (include/svgpvae_hip.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("B", "T", "m", "Q")] + [(n, C.c_double) for n in ("jitter", "clip_lo", "clip_hi")]
+
+
+class BallPredictBufs(C.Structure):
+    """svgp_ball_predict_bufs (include/svgpvae_hip.h)."""
+    _fields_ = [(n, C.c_void_p) for n in ("times", "tq", "ip_x", "ip_y", "ls_x", "ls_y", "mu_x", "mu_y", "var_x", "var_y", "mask",
+                                          "eps_x", "eps_y", "p_m_x", "p_m_y", "p_v_x", "p_v_y", "z_x", "z_y")]
+
+
 STATE = dict(C_MA=0, LAGRANGE=1, ALPHA=2, ADAM_T=3, LR=4, BETA=5, ELBO=6, RECON_LOSS=7, KL_TERM=8,
              INSIDE_ELBO=9, CE_TERM=10, INSIDE_RECON=11, INSIDE_KL=12, RNG_CTR=13)
 STATE_LEN = 16
@@ -315,6 +326,9 @@ SIGNATURES = {
     "svgp_mnist_generate_route": [_CFG, C.c_char_p, C.c_int],
     "svgp_sprites_posterior_rows": [C.POINTER(PosteriorRowsCfg)] + [_P] * 10,
     "svgp_sprites_posterior_rows_route": [C.POINTER(PosteriorRowsCfg), C.c_char_p, C.c_int],
+    "svgp_ball_predict": [C.POINTER(BallPredictCfg), C.POINTER(BallPredictBufs), _P],
+    "svgp_ball_predict_large": [C.POINTER(BallPredictCfg), C.POINTER(BallPredictBufs), _P, _P],
+    "svgp_ball_predict_route": [C.POINTER(BallPredictCfg), C.c_int, C.c_char_p, C.c_int],
     "svgp_stream_create": [C.POINTER(_P)],
     "svgp_stream_destroy": [_P],
     "svgp_stream_sync": [_P],
@@ -353,6 +367,7 @@ NON_STATUS = {"svgp_version": ([], C.c_int), "svgp_last_error": ([], C.c_char_p)
               "svgp_mnist_cache_workspace_elems": ([_CFG], C.c_longlong),
               "svgp_mnist_generate_workspace_elems": ([_CFG], C.c_longlong),
               "svgp_sprites_posterior_rows_workspace_elems": ([C.POINTER(PosteriorRowsCfg)], C.c_longlong),
+              "svgp_ball_predict_large_workspace_elems": ([C.POINTER(BallPredictCfg)], C.c_longlong),
               "svgp_svigp_scale_offset": ([C.c_int, C.c_int, C.c_int], C.c_longlong)}
 
 _lib = None
@@ -381,8 +396,10 @@ def load_library(path=None):
         fn.argtypes = argtypes
         fn.restype = restype
     # the ctypes mirrors must have the layout the library was compiled with (svgp_struct_sizeof)
-    for which, cls in enumerate((MnistCfg, ParamLayout, WsLayout, StreamKdesc, ConvDesc, SpritesKcfg, PearceBufs, SumJob,
-                                 CasaleCfg, CasaleLayout, BallLargeCfg, CacheLayout)):
+    mirrors = dict(enumerate((MnistCfg, ParamLayout, WsLayout, StreamKdesc, ConvDesc, SpritesKcfg, PearceBufs, SumJob,
+                              CasaleCfg, CasaleLayout, BallLargeCfg, CacheLayout)))
+    mirrors.update({13: BallPredictCfg, 14: BallPredictBufs})          # code 12 is not assigned
+    for which, cls in mirrors.items():
         if lib.svgp_struct_sizeof(which) != C.sizeof(cls):
             raise SvgpError(f"{p}: sizeof({cls.__name__}) is {lib.svgp_struct_sizeof(which)} in the library but "
                             f"{C.sizeof(cls)} in the binding; rebuild the library or update _lib.py")

@@ -245,9 +245,8 @@ class _BallMlpEngine:
         self._gemm(0, 0, R, 4, H, h1, H, p["encW2"], 4, h2, 4)
         return h1, h2
 
-    def _decode_recon(self, z, X, want_grad, row_weights=None):
-        """z (R,2) -> logits, pred = sigmoid, per-frame reconstruction term, dlogits (VAE_utils.py:73-94,
-        SVGPVAE_model.py:697-700).  row_weights (R): frames whose reconstruction term counts (NP targets)."""
+    def _decode_logits(self, z):
+        """z (R,2) -> g1 (R,H) post-tanh, logits (R,P) (VAE_utils.py:73-94); the decoder half that needs no labels."""
         R, P, H, p, s = z.shape[0], self.P, self.H, self.params, self.stream.cuda_stream
         f64 = dict(dtype=_F64, device=self.dev)
         g1 = torch.empty(R, H, **f64)
@@ -256,6 +255,14 @@ class _BallMlpEngine:
         logits = torch.empty(R, P, **f64)
         self._gemm(0, 0, R, P, H, g1, H, p["decW2"], P, logits, P)
         call("svgp_bias_act_fwd", R, P, 0, p["decB2"].data_ptr(), logits.data_ptr(), s)
+        return g1, logits
+
+    def _decode_recon(self, z, X, want_grad, row_weights=None):
+        """z (R,2) -> logits, pred = sigmoid, per-frame reconstruction term, dlogits (VAE_utils.py:73-94,
+        SVGPVAE_model.py:697-700).  row_weights (R): frames whose reconstruction term counts (NP targets)."""
+        R, P, s = z.shape[0], self.P, self.stream.cuda_stream
+        f64 = dict(dtype=_F64, device=self.dev)
+        g1, logits = self._decode_logits(z)
         pred, row_recon = torch.empty(R, P, **f64), torch.empty(R, **f64)
         dlog = torch.empty(R, P, **f64) if want_grad else None
         call("svgp_sigmoid_xent", R, P, 1.0 / self.B, logits.data_ptr(), X.data_ptr(), pred.data_ptr(),
@@ -541,6 +548,14 @@ def sparse_engine_class(m, batch):
 
 
 SPARSE_ENGINES = (BallStepEngine, BallLargeStepEngine)
+
+
+def __getattr__(name):
+    """BallPredictor lives in ball_predict.py (which imports this module); re-exported here on first use."""
+    if name == "BallPredictor":
+        from .ball_predict import BallPredictor
+        return BallPredictor
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 class _PearceEngineBase(_BallMlpEngine):

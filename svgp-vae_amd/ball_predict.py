@@ -1,0 +1,275 @@
+"""Moving-ball SVGP-VAE after training: reconstruct dropped frames, render a video at another time grid,
+extrapolate a few frames -- from a `BALL_experiment --save_model` checkpoint.
+
+    python -m svgp_vae_amd.ball_predict --checkpoint RUN/model.pt (--videos F.npy | --test_batch K --base_dir D)
+        [--drop 0.5 --drop_seed S | --observed mask.npy] [--upsample R | --query_times t1 t2 ..] [--sample --seed S] --out frames.npy
+
+The GP posterior of SVGP.approximate_posterior_params (SVGPVAE_model.py:142-171) is evaluated at arbitrary query times from the
+frames that are observed (a dropped frame is a frame of precision 0): svgp_ball_predict, ONE launch per batch for m <= 64 whatever
+the number of videos and query times, svgp_ball_predict_large beyond.  Encoder and decoder are those of the training engines
+(ball._BallMlpEngine).  Only the sparse-GP models (SVGPVAE_Hensman / SVGPVAE_Titsias) are handled; forward only: no gradient, no
+Adam state, no random-number state is touched."""
+import argparse
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import BallPredictBufs, BallPredictCfg, call
+from .ball import _BallMlpEngine, mlp_param_shapes
+
+_F64 = torch.float64
+CLIP_PV = (1e-4, 1000.0)                                  # SVGPVAE_model.py:701: only the sample clamps
+FUSED_M_MAX = 64
+META_KEYS = ("tmax", "m", "hidden", "px", "py", "jitter", "clip_qs")
+_PEARCE_ELBOS = ("GPVAE_Pearce", "NP", "VAE")
+
+
+def route(shape):
+    """The kernels of the GP stage of one `predict` call of shape (B, T, m, Q), in launch order (svgp_ball_predict_route); needs
+    no device."""
+    B, T, m, Q = shape
+    buf = C.create_string_buffer(1 << 16)
+    cfg = BallPredictCfg(B=int(B), T=int(T), m=int(m), Q=int(Q), jitter=0.0, clip_lo=CLIP_PV[0], clip_hi=CLIP_PV[1])
+    call("svgp_ball_predict_route", C.byref(cfg), int(m > FUSED_M_MAX), buf, len(buf))
+    return buf.value.decode().split()
+
+
+def param_shapes(m, px=32, py=32, hidden=500):
+    """The flat parameter vector of the sparse-GP ball engines: the MLPs, then ip_x, l_x, ip_y, l_y."""
+    sh = dict(mlp_param_shapes(px, py, hidden))
+    sh.update(ip_x=(m,), l_x=(1,), ip_y=(m,), l_y=(1,))
+    return sh
+
+
+class BallPredictor(_BallMlpEngine):
+    """A trained moving-ball SVGP-VAE, forward only.  `params`: name -> array for every entry of param_shapes(m, px, py, hidden)."""
+
+    def __init__(self, params, *, tmax, m, hidden=500, px=32, py=32, jitter, clip_qs, device="cuda:0"):
+        self.shapes = param_shapes(int(m), int(px), int(py), int(hidden))
+        missing = [k for k in self.shapes if k not in params]
+        if missing:
+            raise ValueError(f"BallPredictor: parameters {missing} are missing (a sparse-GP ball model has {list(self.shapes)})")
+        flat = []
+        for k, s in self.shapes.items():
+            v = params[k]
+            v = torch.as_tensor(np.asarray(v) if not torch.is_tensor(v) else v.detach().cpu(), dtype=_F64).reshape(-1)
+            if v.numel() != int(np.prod(s)):
+                raise ValueError(f"BallPredictor: {k} has {v.numel()} elements, the model's shape {s} needs {int(np.prod(s))}")
+            flat.append(v)
+        self.lib = _lib.load_library()
+        if not torch.cuda.is_available():
+            raise _lib.SvgpError("BallPredictor needs a HIP device; there is no CPU execution path")
+        self.dev = torch.device(device)
+        self.tmax, self.m, self.px, self.py, self.P, self.H = int(tmax), int(m), int(px), int(py), int(px) * int(py), int(hidden)
+        self.jitter, self.clip_qs = float(jitter), bool(clip_qs)
+        self.stream = torch.cuda.Stream(device=self.dev)
+        with torch.cuda.stream(self.stream):
+            self.theta = torch.cat(flat).to(self.dev)
+        self.params, off = {}, 0
+        for k, s in self.shapes.items():
+            n = int(np.prod(s))
+            self.params[k] = self.theta[off:off + n].view(s)
+            off += n
+        self._gemm_scratch = torch.empty(0, dtype=_F64, device=self.dev)
+        self._work = torch.empty(0, dtype=_F64, device=self.dev)
+        self.stream.synchronize()
+
+    # ------------------------------------------------------------------ checkpoints
+    @classmethod
+    def load(cls, path, **overrides):
+        """A predictor from the `model.pt` of `BALL_experiment --save_model`.  The model's shape comes from the checkpoint's "meta"
+        dict; keywords override it, and stand in for it where an older checkpoint has none."""
+        ck = torch.load(path, map_location="cpu")
+        if not isinstance(ck, dict) or "theta" not in ck or "shapes" not in ck:
+            raise ValueError(f"{path}: not a checkpoint of the moving-ball driver (needs theta and shapes)")
+        meta = dict(ck.get("meta") or {})
+        device = overrides.pop("device", "cuda:0")
+        meta.update(overrides)
+        shapes = dict(ck["shapes"])
+        if meta.get("elbo") in _PEARCE_ELBOS or "ip_x" not in shapes:
+            raise ValueError(f"{path}: a checkpoint of an exact-GP baseline (GPVAE_Pearce / NP / VAE: no inducing points); "
+                             f"ball_predict handles the sparse-GP models SVGPVAE_Hensman / SVGPVAE_Titsias only")
+        missing = [k for k in META_KEYS if k not in meta]
+        if missing:
+            raise ValueError(f"{path}: the checkpoint has no meta entry for {', '.join(missing)}; pass "
+                             f"{', '.join(k + '=...' for k in missing)} to BallPredictor.load")
+        want = param_shapes(int(meta["m"]), int(meta["px"]), int(meta["py"]), int(meta["hidden"]))
+        got = {k: tuple(v) for k, v in shapes.items()}
+        if got != {k: tuple(v) for k, v in want.items()}:
+            bad = sorted(k for k in set(got) | set(want) if got.get(k) != tuple(want.get(k, ())))
+            raise ValueError(f"{path}: the checkpoint's shapes do not fit m={meta['m']} hidden={meta['hidden']} px={meta['px']} "
+                             f"py={meta['py']} (differing: {bad})")
+        theta = torch.as_tensor(ck["theta"], dtype=_F64).reshape(-1)
+        need = sum(int(np.prod(s)) for s in want.values())
+        if theta.numel() != need:
+            raise ValueError(f"{path}: theta has {theta.numel()} elements, the shapes describe {need}")
+        params, off = {}, 0
+        for k, s in shapes.items():
+            n = int(np.prod(s))
+            params[k] = theta[off:off + n]
+            off += n
+        return cls(params, device=device, **{k: meta[k] for k in META_KEYS})
+
+    def route(self, B, T, Q):
+        return route((B, T, self.m, Q))
+
+    # ------------------------------------------------------------------ the GP stage alone
+    def _gp(self, mu, var, times, tq, mask, eps_c):
+        """mu, var: two (T, B) tensors each; mask (T, B) or None; eps_c: two (Q, B) tensors or None.  Returns p_m, p_v, z lists."""
+        T, B = mu[0].shape
+        Q, p, s = tq.numel(), self.params, self.stream.cuda_stream
+        f64 = dict(dtype=_F64, device=self.dev)
+        out = {k: [torch.empty(Q, B, **f64) for _ in range(2)] for k in ("p_m", "p_v", "z")}
+        cfg = BallPredictCfg(B=B, T=T, m=self.m, Q=Q, jitter=self.jitter, clip_lo=CLIP_PV[0], clip_hi=CLIP_PV[1])
+        q = BallPredictBufs()
+        q.times, q.tq, q.mask = times.data_ptr(), tq.data_ptr(), None if mask is None else mask.data_ptr()
+        for c, cn in enumerate("xy"):
+            setattr(q, f"ip_{cn}", p[f"ip_{cn}"].data_ptr()); setattr(q, f"ls_{cn}", p[f"l_{cn}"].data_ptr())
+            setattr(q, f"mu_{cn}", mu[c].data_ptr()); setattr(q, f"var_{cn}", var[c].data_ptr())
+            setattr(q, f"eps_{cn}", None if eps_c is None else eps_c[c].data_ptr())
+            setattr(q, f"p_m_{cn}", out["p_m"][c].data_ptr()); setattr(q, f"p_v_{cn}", out["p_v"][c].data_ptr())
+            setattr(q, f"z_{cn}", out["z"][c].data_ptr())
+        if self.m <= FUSED_M_MAX:
+            call("svgp_ball_predict", C.byref(cfg), C.byref(q), s)
+        else:
+            need = int(self.lib.svgp_ball_predict_large_workspace_elems(C.byref(cfg)))      # 0: a shape the entry refuses (it says why)
+            if self._work.numel() < need:
+                self._work = torch.empty(need, **f64)                                     # grows once per shape
+            call("svgp_ball_predict_large", C.byref(cfg), C.byref(q), self._work.data_ptr() if need else None, s)
+        return out["p_m"], out["p_v"], out["z"]
+
+    # ------------------------------------------------------------------ frames
+    def predict(self, videos, query_times, observed=None, frame_times=None, eps=None):
+        """videos (B, T, px, py); query_times (Q) arbitrary reals; observed (B, T) bool, default all; frame_times (T), default 1..T;
+        eps (B, Q, 2) or None (decode the posterior mean).  Returns dict(frames (B, Q, px, py) in [0, 1], p_m, p_v, z (B, Q, 2))."""
+        videos = torch.as_tensor(np.asarray(videos) if not torch.is_tensor(videos) else videos)
+        if videos.dim() != 4 or tuple(videos.shape[2:]) != (self.px, self.py):
+            raise ValueError(f"videos must be (B, T, {self.px}, {self.py}), got {tuple(videos.shape)}")
+        B, T = int(videos.shape[0]), int(videos.shape[1])
+        tq = torch.as_tensor(np.asarray(query_times, dtype=np.float64) if not torch.is_tensor(query_times) else query_times,
+                             dtype=_F64).reshape(-1)
+        Q = int(tq.numel())
+        if B < 1 or T < 1 or Q < 1:
+            raise ValueError(f"need at least one video, frame and query time (B={B} T={T} Q={Q})")
+        if not bool(torch.isfinite(tq).all()):
+            raise ValueError("query_times must be finite")
+        if observed is not None:
+            observed = torch.as_tensor(np.asarray(observed) if not torch.is_tensor(observed) else observed)
+            if tuple(observed.shape) != (B, T):
+                raise ValueError(f"observed must be (B, T) = ({B}, {T}), got {tuple(observed.shape)}")
+        if frame_times is not None:
+            frame_times = torch.as_tensor(np.asarray(frame_times, dtype=np.float64) if not torch.is_tensor(frame_times)
+                                          else frame_times, dtype=_F64).reshape(-1)
+            if frame_times.numel() != T:
+                raise ValueError(f"frame_times must have T = {T} entries, got {frame_times.numel()}")
+        if eps is not None:
+            eps = torch.as_tensor(np.asarray(eps) if not torch.is_tensor(eps) else eps, dtype=_F64)
+            if tuple(eps.shape) != (B, Q, 2):
+                raise ValueError(f"eps must be (B, Q, 2) = ({B}, {Q}, 2), got {tuple(eps.shape)}")
+        p, s, P = self.params, self.stream.cuda_stream, self.P
+        f64 = dict(dtype=_F64, device=self.dev)
+        self.stream.wait_stream(torch.cuda.current_stream(self.dev))
+        with torch.cuda.stream(self.stream):
+            X = videos.to(self.dev, _F64).contiguous().view(B * T, P)
+            times = torch.arange(1, T + 1, **f64) if frame_times is None else frame_times.to(self.dev).contiguous()
+            tq = tq.to(self.dev).contiguous()
+            mask = None if observed is None else observed.to(self.dev).to(_F64).t().contiguous()
+            eps_c = None if eps is None else [eps[:, :, c].to(self.dev).t().contiguous() for c in range(2)]
+            _, h2 = self._encode(X)
+            mu, var_raw, var = ([torch.empty(T, B, **f64) for _ in range(2)] for _ in range(3))
+            call("svgp_ball_head_fwd", B, T, int(self.clip_qs), p["encB2"].data_ptr(), h2.data_ptr(), mu[0].data_ptr(),
+                 var_raw[0].data_ptr(), var[0].data_ptr(), mu[1].data_ptr(), var_raw[1].data_ptr(), var[1].data_ptr(), s)
+            p_m, p_v, zc = self._gp(mu, var, times, tq, mask, eps_c)
+            z = torch.empty(B * Q, 2, **f64)
+            call("svgp_ball_pack_z", B, Q, zc[0].data_ptr(), zc[1].data_ptr(), z.data_ptr(), s)
+            _, logits = self._decode_logits(z)
+            # sigmoid by the training engines' kernel; its cross-entropy row sums (against the logits themselves) are not used
+            frames, row = torch.empty(B * Q, P, **f64), torch.empty(B * Q, **f64)
+            call("svgp_sigmoid_xent", B * Q, P, 1.0, logits.data_ptr(), logits.data_ptr(), frames.data_ptr(), row.data_ptr(),
+                 None, s)
+            st2 = lambda v: torch.stack([v[0].t(), v[1].t()], 2).contiguous()
+            out = dict(frames=frames.view(B, Q, self.px, self.py), p_m=st2(p_m), p_v=st2(p_v), z=z.view(B, Q, 2))
+        self.stream.synchronize()
+        return out
+
+
+# ---------------------------------------------------------------------------------------------- command line
+def build_parser():
+    p = argparse.ArgumentParser(description="Fill dropped frames / resample in time with a trained moving-ball SVGP-VAE.")
+    p.add_argument("--checkpoint", required=True, help="RUN/model.pt of BALL_experiment --save_model")
+    src = p.add_mutually_exclusive_group(required=True)
+    src.add_argument("--videos", type=str, default=None, help=".npy of videos (B, T, px, py)")
+    src.add_argument("--test_batch", type=int, default=None, help="index 0..9 of the driver's fixed test batches (needs --base_dir)")
+    p.add_argument("--base_dir", type=str, default=None, help="where the driver keeps Test_Batches_<vidlt>_<tmax>.pkl")
+    obs = p.add_mutually_exclusive_group()
+    obs.add_argument("--drop", type=float, default=None, help="fraction of frames to drop at random (with --drop_seed)")
+    obs.add_argument("--observed", type=str, default=None, help=".npy of a (B, T) mask, non-zero = observed")
+    p.add_argument("--drop_seed", type=int, default=0)
+    qt = p.add_mutually_exclusive_group()
+    qt.add_argument("--upsample", type=int, default=None, help="R: the frame times with R - 1 new times between neighbours")
+    qt.add_argument("--query_times", type=float, nargs="+", default=None)
+    p.add_argument("--sample", action="store_true", help="z = p_m + eps sqrt(p_v) with eps from --seed; default: the posterior mean")
+    p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--device", type=str, default="cuda:0")
+    p.add_argument("--out", required=True)
+    return p
+
+
+def parse_args(argv=None):
+    p = build_parser()
+    args = p.parse_args(argv)
+    if args.test_batch is not None and args.base_dir is None:
+        p.error("--test_batch needs --base_dir")
+    if args.test_batch is not None and not 0 <= args.test_batch < 10:
+        p.error("--test_batch must be in 0..9")
+    if args.drop is not None and not 0.0 <= args.drop < 1.0:
+        p.error("--drop must be in [0, 1)")
+    if args.upsample is not None and args.upsample < 1:
+        p.error("--upsample must be at least 1")
+    return args
+
+
+def query_grid(T, upsample=None, query_times=None):
+    """(query times, index of every frame time in them or None)."""
+    if query_times is not None:
+        return np.asarray(query_times, dtype=np.float64), None
+    R = 1 if upsample is None else int(upsample)
+    return np.linspace(1.0, float(T), R * (T - 1) + 1), np.arange(T) * R
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    pred = BallPredictor.load(args.checkpoint, device=args.device)
+    if args.videos is not None:
+        videos = np.load(args.videos)
+    else:
+        from .BALL_experiment import load_or_make_test_batches
+        meta = torch.load(args.checkpoint, map_location="cpu").get("meta") or {}
+        if "vidlt" not in meta:
+            raise SystemExit(f"{args.checkpoint}: no meta entry for vidlt; --test_batch needs it, use --videos")
+        tb = load_or_make_test_batches(args.base_dir, meta["vidlt"], pred.tmax, pred.px, pred.py, 35, 3)
+        videos = np.asarray(tb[args.test_batch][1], dtype=np.float64)
+    B, T = videos.shape[:2]
+    observed = None
+    if args.observed is not None:
+        observed = np.load(args.observed) != 0
+    elif args.drop is not None:
+        observed = np.random.RandomState(args.drop_seed).rand(B, T) >= args.drop
+    tq, at_frames = query_grid(T, args.upsample, args.query_times)
+    eps = np.random.RandomState(args.seed).randn(B, tq.size, 2) if args.sample else None
+    out = pred.predict(videos, tq, observed=observed, eps=eps)
+    frames = out["frames"].cpu().numpy()
+    np.save(args.out, frames)
+    names = pred.route(B, T, tq.size)
+    print(f"{B} videos x {tq.size} query times -> {args.out}   route ({len(names)} GP launch{'es' if len(names) != 1 else ''}): "
+          f"{' '.join(names)}")
+    if args.test_batch is not None and observed is not None and at_frames is not None and not observed.all():
+        err = (frames[:, at_frames] - videos)[~observed]
+        print(f"MSE of the {int((~observed).sum())} filled-in frames against the held-back ones: {float((err ** 2).mean()):.6g}")
+    return frames
+
+
+if __name__ == "__main__":
+    main()

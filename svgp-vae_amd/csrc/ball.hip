@@ -12,6 +12,7 @@
 //   per-video ELBO assembly + scalar epilogue             SVGPVAE_model.py:677-705, BALL_experiment.py:116-123
 //   exact per-video GP of the Pearce baseline + VJP       GPVAE_Pearce_model.py:8-86
 #include "common.hpp"
+#include "lds_spd_inverse.hpp"
 
 namespace {
 
@@ -274,41 +275,7 @@ struct PearceArgs {
 // lane i0 = tid / CW of RL = 256 / CW; a thread owns the elements (i0 + RL r, j).  No integer division in the loops.
 #define PEARCE_IJ for (int i = i0; i < n; i += RL) if (j < n)
 
-// in-place Gauss-Jordan inverse of an SPD n x n LDS matrix (leading dimension ld, n <= 64), no pivoting; returns log det
-template <int CW>
-__device__ real lds_spd_inverse(real* A, int ld, int n, real* pivbuf) {
-    constexpr int RL = 256 / CW, RMAX = CW / RL;
-    const int j = threadIdx.x & (CW - 1), i0 = threadIdx.x / CW;
-    real logdet = 0;
-    for (int k = 0; k < n; ++k) {
-        __syncthreads();
-        const real piv = A[k * ld + k], ip = real(1) / piv;
-        const real rowk = j < n ? A[k * ld + j] : real(0);
-        real f[RMAX];
-#pragma unroll
-        for (int r = 0; r < RMAX; ++r) { const int i = i0 + RL * r; f[r] = i < n ? A[i * ld + k] * ip : real(0); }
-        if (threadIdx.x == 0) pivbuf[k] = piv;           // the logs are taken once, in parallel, after the sweep
-        __syncthreads();
-        if (j < n) {
-#pragma unroll
-            for (int r = 0; r < RMAX; ++r) {
-                const int i = i0 + RL * r;
-                if (i < n && i != k) A[i * ld + j] = (j == k) ? -f[r] : A[i * ld + j] - f[r] * rowk;
-            }
-            if (i0 == 0) A[k * ld + j] = (j == k) ? ip : rowk * ip;
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x < 64) {                              // n <= 64: one wave, fixed-order shuffle sum
-        const real lg = wave_sum((int)threadIdx.x < n ? log(pivbuf[threadIdx.x]) : real(0));
-        if (threadIdx.x == 0) pivbuf[0] = lg;
-    }
-    __syncthreads();
-    logdet = pivbuf[0];
-    __syncthreads();
-    return logdet;
-}
-
+// (lds_spd_inverse: lds_spd_inverse.hpp, shared with ball_predict.hip)
 __device__ __forceinline__ real pearce_time(const PearceArgs& a, int b, int i) {
     return a.idx ? a.times[a.idx[(size_t)b * a.n + i]] : a.times[i];
 }

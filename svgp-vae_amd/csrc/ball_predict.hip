@@ -1,0 +1,388 @@
+// Moving-ball SVGP-VAE after training: the sparse-GP posterior of a video at ARBITRARY query times, from the
+// frames that were observed.  Per video b and latent coordinate c, with SE(a, b) = exp(-(a - b)^2 / (2 ls^2)):
+//   p   = mask * reciprocal_no_nan(s2)                         (a dropped frame is a frame of precision 0)
+//   K   = SE(z, z)       Kn = SE(t, z)
+//   Sig = K + Kn^T diag(p) Kn       Si = (Sig + j I)^-1        Ki = (K + j I)^-1
+//   w   = Si Kn^T (p y)             X  = Si - Ki
+//   k   = SE(tau, z)     p_m = k w     p_v = 1 + diag(k X k^T)     z = p_m + eps sqrt(clamp(p_v, clip_lo, clip_hi))
+// which for tau = t and mask = 1 is SVGP.approximate_posterior_params (SVGPVAE_model.py:142-171; mean and diag(B)) and the draw of
+// :701.  p_v is reported unclamped.  Where p = 0 the product p y is taken as 0 whatever y holds.
+//
+// svgp_ball_predict (m <= 64): ONE launch, a workgroup of 256 threads per (video, coordinate).  K in LDS; the frames are streamed
+// in chunks of BP_TC: the chunk's kernel rows k_t are formed from times[t] into LDS, every thread adds p_t k_t[i] k_t[j] to the
+// elements (i, j) it owns (registers) in frame order, so Sig and Kn^T (p y) have a fixed summation order and no (T, m) matrix
+// exists.  Both matrices are inverted by lds_spd_inverse; a video without a kept frame has Sig + j I == K + j I bit for bit, hence
+// X = 0 and w = 0 exactly.  The query times are walked in chunks of 16: 16 lanes share a query, each takes the rows i = lane,
+// lane + 16, ... of k^T X k and of k . w, and an xor-shuffle adds the 16 partials; a query's bits do not depend on where it stands.
+// LDS at m = 64: two 64 x 65 matrices, the 16 x 65 chunk and 4 x 64 + 32 values = 77 184 bytes (two workgroups per CU).
+//
+// svgp_ball_predict_large (m <= 2048, T <= 2048): the same quantities from the library's global-memory pieces, walked in chunks of
+// BPL_NB videos and BPL_QC query rows so that the workspace grows with neither B nor Q (bp_walk below is the one plan both the
+// launch code and svgp_ball_predict_route follow).  svgp_sprites_posterior_rows runs with the videos of a chunk as its channels
+// (kbb = 1), an unbounded clip range and no draw: the clamp applies to the sample only and is taken in k_bp_finish.
+#include "common.hpp"
+#include "lds_spd_inverse.hpp"
+
+#include <cmath>
+
+namespace {
+
+constexpr int BP_TC = 16;            // frames (and query times) of a chunk of the fused kernel
+constexpr int BP_M_MAX = 64, BP_T_MAX = 16384;
+constexpr int BPL_T_MAX = 2048;
+constexpr int BPL_NB = 64;           // videos of a chunk of the large form = channels of one svgp_sprites_posterior_rows call
+constexpr int BPL_QC = 4096;         // query rows of a chunk of the large form
+
+struct BpArgs {
+    int B, T, m, Q;
+    real jitter, lo, hi;
+    const real* times; const real* tq; const real* mask;
+    const real* ip[2]; const real* ls[2]; const real* mu[2]; const real* var[2]; const real* eps[2];
+    real* p_m[2]; real* p_v[2]; real* z[2];
+};
+
+__device__ __forceinline__ void bp_precision(const BpArgs& a, int c, size_t e, real& p, real& py) {
+    p = recip_no_nan(a.var[c][e]);
+    if (a.mask) p *= a.mask[e];
+    py = p == real(0) ? real(0) : p * a.mu[c][e];
+}
+
+// Thread layout as in lds_spd_inverse: column j = tid & (CW - 1), row lane i0 = tid / CW; a thread owns (i0 + RL r, j).
+template <int CW>
+__global__ __launch_bounds__(256) void k_ball_predict(BpArgs a) {
+    extern __shared__ __align__(16) real smem[];
+    constexpr int RL = 256 / CW, RMAX = CW / RL, KS = CW + 1;
+    const int tid = threadIdx.x, j = tid & (CW - 1), i0 = tid / CW;
+    const int b = blockIdx.x, c = blockIdx.y, m = a.m, ld = m + 1, B = a.B, T = a.T, Q = a.Q;
+    real* Km = smem;                 // m x ld : K, K + j I, its inverse
+    real* Sg = Km + m * ld;          // m x ld : Sig + j I, its inverse, X
+    real* kt = Sg + m * ld;          // BP_TC x KS : kernel rows of a chunk of frames / of query times, columns >= m zero
+    real* zv = kt + BP_TC * KS;      // CW : inducing points
+    real* vv = zv + CW;              // CW : Kn^T (p y)
+    real* wv = vv + CW;              // CW : w
+    real* piv = wv + CW;             // CW : pivots of the sweep
+    real* pc = piv + CW;             // BP_TC : p of the chunk
+    real* pyc = pc + BP_TC;          // BP_TC : p y of the chunk
+    const real* __restrict__ times = a.times;
+    const real* __restrict__ tq = a.tq;
+    const real* __restrict__ eps = a.eps[c];
+    real* __restrict__ o_pm = a.p_m[c];
+    real* __restrict__ o_pv = a.p_v[c];
+    real* __restrict__ o_z = a.z[c];
+    const real l = *a.ls[c], il2 = real(-0.5) / (l * l);
+    if (tid < CW) zv[tid] = tid < m ? a.ip[c][tid] : real(0);
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < RMAX; ++r) {
+        const int i = i0 + RL * r;
+        if (i < m && j < m) { const real d = zv[i] - zv[j]; Km[i * ld + j] = exp(d * d * il2); }
+    }
+    // ---- the frames, in order
+    real acc[RMAX], vacc = 0;
+#pragma unroll
+    for (int r = 0; r < RMAX; ++r) acc[r] = 0;
+    for (int t0 = 0; t0 < T; t0 += BP_TC) {
+        const int cnt = T - t0 < BP_TC ? T - t0 : BP_TC;
+        __syncthreads();             // the previous chunk is consumed
+        if (tid < BP_TC) {
+            real p = 0, py = 0;
+            if (tid < cnt) bp_precision(a, c, (size_t)(t0 + tid) * B + b, p, py);
+            pc[tid] = p; pyc[tid] = py;
+        }
+#pragma unroll
+        for (int r = 0; r < BP_TC / RL; ++r) {
+            const int tc = i0 + RL * r;
+            real k = 0;
+            if (tc < cnt && j < m) { const real d = times[t0 + tc] - zv[j]; k = exp(d * d * il2); }
+            kt[tc * KS + j] = k;
+        }
+        __syncthreads();
+#pragma unroll 2
+        for (int tc = 0; tc < cnt; ++tc) {
+            const real* kr = kt + tc * KS;
+            const real kj = kr[j], pk = pc[tc] * kj;
+#pragma unroll
+            for (int r = 0; r < RMAX; ++r) acc[r] += pk * kr[i0 + RL * r];
+            if (i0 == 0) vacc += pyc[tc] * kj;
+        }
+    }
+    // Sig + j I beside K + j I: equal bit for bit where every p was 0
+#pragma unroll
+    for (int r = 0; r < RMAX; ++r) {
+        const int i = i0 + RL * r;
+        if (i < m && j < m) {
+            const real k = Km[i * ld + j], jit = i == j ? a.jitter : real(0);
+            Sg[i * ld + j] = (k + acc[r]) + jit;
+            Km[i * ld + j] = k + jit;
+        }
+    }
+    if (i0 == 0) vv[j] = vacc;
+#pragma unroll 1
+    for (int which = 0; which < 2; ++which) lds_spd_inverse<CW>(which ? Sg : Km, ld, m, piv);      // one copy of the sweep's code
+    if (tid < CW) {
+        real s = 0;
+        if (tid < m) {
+#pragma unroll 4
+            for (int k = 0; k < m; ++k) s += Sg[tid * ld + k] * vv[k];
+        }
+        wv[tid] = s;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < RMAX; ++r) {
+        const int i = i0 + RL * r;
+        if (i < m && j < m) Sg[i * ld + j] -= Km[i * ld + j];
+    }
+    // ---- the query times: 16 per chunk, 16 lanes per query
+    const int qc = tid >> 4, l16 = tid & 15;
+    for (int q0 = 0; q0 < Q; q0 += BP_TC) {
+        __syncthreads();             // X is complete / the previous chunk is consumed
+#pragma unroll
+        for (int r = 0; r < BP_TC / RL; ++r) {
+            const int qq = i0 + RL * r;
+            real k = 0;
+            if (q0 + qq < Q && j < m) { const real d = tq[q0 + qq] - zv[j]; k = exp(d * d * il2); }
+            kt[qq * KS + j] = k;
+        }
+        __syncthreads();
+        const real* kr = kt + qc * KS;
+        real pm = 0, qs = 0;
+        for (int i = l16; i < m; i += 16) {
+            const real* xr = Sg + i * ld;
+            real row = 0;
+#pragma unroll 4
+            for (int k = 0; k < m; ++k) row += xr[k] * kr[k];
+            qs += kr[i] * row;
+            pm += kr[i] * wv[i];
+        }
+#pragma unroll
+        for (int o = 1; o < 16; o <<= 1) { pm += __shfl_xor(pm, o, 64); qs += __shfl_xor(qs, o, 64); }
+        if (l16 == 0 && q0 + qc < Q) {
+            const size_t e = (size_t)(q0 + qc) * B + b;
+            const real pv = real(1) + qs;
+            o_pm[e] = pm; o_pv[e] = pv;
+            if (o_z) o_z[e] = eps ? pm + eps[e] * sqrt(clip_keep_nan(pv, a.lo, a.hi)) : pm;
+        }
+    }
+}
+
+inline size_t bp_lds_bytes(int m, int CW) { return ((size_t)2 * m * (m + 1) + BP_TC * (CW + 1) + 4 * CW + 2 * BP_TC) * sizeof(real); }
+static_assert(((size_t)2 * 64 * 65 + BP_TC * 65 + 4 * 64 + 2 * BP_TC) * sizeof(real) <= SVGP_LDS_MAX_BYTES / 2, "two workgroups per CU at m = 64");
+
+// ---------------------------------------------------------------------------------------------------------
+// the large form's own kernels
+// ---------------------------------------------------------------------------------------------------------
+// KnP (nb, T, m) = diag(p_l) Kn per video l = b0 + .. of the chunk, PY (T, nb) = p y
+__global__ __launch_bounds__(SVGP_BLOCK) void k_bp_scale_rows(BpArgs a, int c, int b0, int nb, const real* __restrict__ Kn,
+                                                              real* __restrict__ KnP, real* __restrict__ PY) {
+    const long long tot = (long long)nb * a.T * a.m, e = (long long)blockIdx.x * SVGP_BLOCK + threadIdx.x;
+    if (e >= tot) return;
+    const int i = (int)(e % a.m), t = (int)((e / a.m) % a.T), l = (int)(e / ((long long)a.m * a.T));
+    real p, py;
+    bp_precision(a, c, (size_t)t * a.B + b0 + l, p, py);
+    KnP[e] = p * Kn[(size_t)t * a.m + i];
+    if (i == 0) PY[(size_t)t * nb + l] = py;
+}
+// Mats (nb + 1, m, m): the first nb hold Kn^T diag(p_l) Kn and become Sig_l + j I, the last becomes K + j I
+__global__ __launch_bounds__(SVGP_BLOCK) void k_bp_add_prior(int m, int nb, real jitter, const real* __restrict__ K, real* __restrict__ Mats) {
+    const long long mm = (long long)m * m, tot = (nb + 1) * mm, e = (long long)blockIdx.x * SVGP_BLOCK + threadIdx.x;
+    if (e >= tot) return;
+    const long long o = e % mm;
+    const real k = K[o], jit = (o / m == o % m) ? jitter : real(0);
+    Mats[e] = e < nb * mm ? (k + Mats[e]) + jit : k + jit;
+}
+// X_l = Si_l - Ki in place
+__global__ __launch_bounds__(SVGP_BLOCK) void k_bp_subtract(int m, int nb, real* __restrict__ Mats) {
+    const long long mm = (long long)m * m, tot = nb * mm, e = (long long)blockIdx.x * SVGP_BLOCK + threadIdx.x;
+    if (e < tot) Mats[e] -= Mats[tot + e % mm];
+}
+// (nq, nb) rows of a chunk -> the (Q, B) outputs; the draw with the clamped variance
+__global__ __launch_bounds__(SVGP_BLOCK) void k_bp_finish(BpArgs a, int c, int b0, int nb, int q0, int nq, const real* __restrict__ tpm,
+                                                          const real* __restrict__ tpv) {
+    const long long tot = (long long)nq * nb, e = (long long)blockIdx.x * SVGP_BLOCK + threadIdx.x;
+    if (e >= tot) return;
+    const size_t o = (size_t)(q0 + e / nb) * a.B + b0 + e % nb;
+    const real pm = tpm[e], pv = tpv[e];
+    a.p_m[c][o] = pm; a.p_v[c][o] = pv;
+    if (a.z[c]) a.z[c][o] = a.eps[c] ? pm + a.eps[c][o] * sqrt(clip_keep_nan(pv, a.lo, a.hi)) : pm;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// one plan for the launch code and the route text
+// ---------------------------------------------------------------------------------------------------------
+enum BpOp { BP_FUSED, BP_KMAT, BP_SCALE, BP_SIGMA, BP_PRIOR, BP_V, BP_INVERSE, BP_W, BP_SUB, BP_KQ, BP_ROWS, BP_FINISH };
+const char* const BP_NAME[] = {"k_ball_predict", "svgp_se1d_kernel_matrix_fwd", "k_bp_scale_rows", "svgp_dgemm_batched", "k_bp_add_prior",
+                               "svgp_dgemm_batched", "svgp_spd_inverse_batched", "svgp_dgemm_batched", "k_bp_subtract",
+                               "svgp_se1d_kernel_matrix_fwd", "svgp_sprites_posterior_rows", "k_bp_finish"};
+struct BpStep { BpOp op; int c, b0, nb, q0, nq; };
+
+// calls f(step) for every launch group of one call, in order; stops at the first non-zero return
+template <class F>
+int bp_walk(const svgp_ball_predict_cfg* g, bool large, F f) {
+    int rc;
+    if (!large) return f(BpStep{BP_FUSED, 0, 0, g->B, 0, g->Q});
+    for (int c = 0; c < 2; ++c) {
+        if ((rc = f(BpStep{BP_KMAT, c, 0, 0, 0, 0}))) return rc;
+        for (int b0 = 0; b0 < g->B; b0 += BPL_NB) {
+            const int nb = g->B - b0 < BPL_NB ? g->B - b0 : BPL_NB;
+            for (BpOp op : {BP_SCALE, BP_SIGMA, BP_PRIOR, BP_V, BP_INVERSE, BP_W, BP_SUB})
+                if ((rc = f(BpStep{op, c, b0, nb, 0, 0}))) return rc;
+            for (int q0 = 0; q0 < g->Q; q0 += BPL_QC) {
+                const int nq = g->Q - q0 < BPL_QC ? g->Q - q0 : BPL_QC;
+                for (BpOp op : {BP_KQ, BP_ROWS, BP_FINISH})
+                    if ((rc = f(BpStep{op, c, b0, nb, q0, nq}))) return rc;
+            }
+        }
+    }
+    return SVGP_OK;
+}
+
+int bp_check(const svgp_ball_predict_cfg* g, bool large) {
+    SVGP_REQUIRE(g != nullptr, SVGP_ERR_INVALID, "cfg is NULL");
+    SVGP_REQUIRE(g->B >= 1 && g->T >= 1 && g->m >= 1 && g->Q >= 1, SVGP_ERR_INVALID, "need B, T, m, Q >= 1 (B=%d T=%d m=%d Q=%d)", g->B,
+                 g->T, g->m, g->Q);
+    const int m_max = large ? SVGP_M_LIMIT : BP_M_MAX, t_max = large ? BPL_T_MAX : BP_T_MAX;
+    SVGP_REQUIRE(g->m <= m_max, SVGP_ERR_UNSUPPORTED, "m=%d: %s takes m <= %d", g->m, large ? "svgp_ball_predict_large" : "svgp_ball_predict", m_max);
+    SVGP_REQUIRE(g->T <= t_max, SVGP_ERR_UNSUPPORTED, "T=%d: %s takes T <= %d", g->T, large ? "svgp_ball_predict_large" : "svgp_ball_predict", t_max);
+    SVGP_REQUIRE(g->clip_lo <= g->clip_hi, SVGP_ERR_INVALID, "need clip_lo <= clip_hi (%g, %g)", g->clip_lo, g->clip_hi);
+    return SVGP_OK;
+}
+
+int bp_args(const svgp_ball_predict_cfg* g, const svgp_ball_predict_bufs* q, BpArgs* a) {
+    SVGP_REQUIRE(q != nullptr, SVGP_ERR_INVALID, "bufs is NULL");
+    const void* need[] = {q->times, q->tq, q->ip_x, q->ip_y, q->ls_x, q->ls_y, q->mu_x, q->mu_y, q->var_x, q->var_y,
+                          q->p_m_x, q->p_m_y, q->p_v_x, q->p_v_y};
+    for (const void* p : need) SVGP_REQUIRE(p != nullptr, SVGP_ERR_INVALID, "NULL device pointer");
+    a->B = g->B; a->T = g->T; a->m = g->m; a->Q = g->Q; a->jitter = g->jitter; a->lo = g->clip_lo; a->hi = g->clip_hi;
+    a->times = q->times; a->tq = q->tq; a->mask = q->mask;
+    a->ip[0] = q->ip_x; a->ip[1] = q->ip_y; a->ls[0] = q->ls_x; a->ls[1] = q->ls_y; a->mu[0] = q->mu_x; a->mu[1] = q->mu_y;
+    a->var[0] = q->var_x; a->var[1] = q->var_y; a->eps[0] = q->eps_x; a->eps[1] = q->eps_y;
+    a->p_m[0] = q->p_m_x; a->p_m[1] = q->p_m_y; a->p_v[0] = q->p_v_x; a->p_v[1] = q->p_v_y; a->z[0] = q->z_x; a->z[1] = q->z_y;
+    return SVGP_OK;
+}
+
+inline int64_t bp_al16(int64_t n) { return (n + 15) / 16 * 16; }
+struct BpWork { int64_t K, Kn, knn, K2, Kq, kbb, KnP, PY, Mats, V, W, logdet, inv, tpm, tpv, rows, total; };
+BpWork bp_work(const svgp_ball_predict_cfg* g) {
+    const int64_t m = g->m, T = g->T, nb = g->B < BPL_NB ? g->B : BPL_NB, nq = g->Q < BPL_QC ? g->Q : BPL_QC;
+    int64_t p = 0;
+    auto take = [&](int64_t n) { int64_t r = p; p += bp_al16(n); return r; };
+    BpWork o;
+    o.K = take(m * m); o.Kn = take(T * m); o.knn = take(T); o.K2 = take(m * m); o.Kq = take(nq * m); o.kbb = take(nq);
+    o.KnP = take(nb * T * m); o.PY = take(T * nb); o.Mats = take((nb + 1) * m * m); o.V = take(m * nb); o.W = take(nb * m);
+    o.logdet = take(nb + 1); o.inv = take((int64_t)svgp_spd_inverse_workspace_elems((int)m, (int)nb + 1));
+    o.tpm = take(nq * nb); o.tpv = take(nq * nb);
+    o.rows = take(m > 256 ? 16 * nq * nb : 0);      // svgp_sprites_posterior_rows_workspace_elems: at most 16 b L, 0 up to m = 256
+    o.total = p;
+    return o;
+}
+
+inline unsigned bp_blocks(long long n) { return (unsigned)((n + SVGP_BLOCK - 1) / SVGP_BLOCK); }
+
+}  // namespace
+
+extern "C" int svgp_ball_predict_route(const svgp_ball_predict_cfg* g, int large, char* buf, int cap) {
+    SVGP_REQUIRE(buf && cap >= 1, SVGP_ERR_INVALID, "bad argument");
+    int rc = bp_check(g, large != 0);
+    if (rc) return rc;
+    int pos = 0;
+    buf[0] = 0;
+    return bp_walk(g, large != 0, [&](const BpStep& s) -> int {
+        if (s.op == BP_ROWS) {       // the rows entry prints its own one or two kernels
+            const svgp_posterior_rows_cfg rc_ = {s.nq, g->m, s.nb, -INFINITY, INFINITY};
+            char sub[128];
+            int r = svgp_sprites_posterior_rows_route(&rc_, sub, (int)sizeof(sub));
+            if (r) return r;
+            pos += snprintf(buf + pos, cap - pos, "%s", sub);
+        } else {
+            pos += snprintf(buf + pos, cap - pos, "%s\n", BP_NAME[s.op]);
+        }
+        SVGP_REQUIRE(pos < cap, SVGP_ERR_INVALID, "route text needs more than %d bytes", cap);
+        return (int)SVGP_OK;
+    });
+}
+
+extern "C" int svgp_ball_predict(const svgp_ball_predict_cfg* g, const svgp_ball_predict_bufs* q, void* stream) {
+    int rc = bp_check(g, false);
+    if (rc) return rc;
+    BpArgs a;
+    rc = bp_args(g, q, &a);
+    if (rc) return rc;
+    return bp_walk(g, false, [&](const BpStep&) -> int {
+        const dim3 grid((unsigned)a.B, 2);
+        if (a.m <= 32) {
+            const size_t lds = bp_lds_bytes(a.m, 32);
+            SVGP_CHECK_HIP(hipFuncSetAttribute((const void*)k_ball_predict<32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            hipLaunchKernelGGL(k_ball_predict<32>, grid, dim3(256), lds, (hipStream_t)stream, a);
+        } else {
+            const size_t lds = bp_lds_bytes(a.m, 64);
+            SVGP_CHECK_HIP(hipFuncSetAttribute((const void*)k_ball_predict<64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            hipLaunchKernelGGL(k_ball_predict<64>, grid, dim3(256), lds, (hipStream_t)stream, a);
+        }
+        SVGP_LAUNCH_CHECK();
+        return (int)SVGP_OK;
+    });
+}
+
+extern "C" long long svgp_ball_predict_large_workspace_elems(const svgp_ball_predict_cfg* g) {
+    if (bp_check(g, true)) return 0;
+    return bp_work(g).total;
+}
+
+extern "C" int svgp_ball_predict_large(const svgp_ball_predict_cfg* g, const svgp_ball_predict_bufs* q, double* work, void* stream) {
+    int rc = bp_check(g, true);
+    if (rc) return rc;
+    BpArgs a;
+    rc = bp_args(g, q, &a);
+    if (rc) return rc;
+    const BpWork w = bp_work(g);
+    SVGP_REQUIRE(work != nullptr, SVGP_ERR_INVALID, "work is NULL (B = %d, T = %d, m = %d, Q = %d needs %lld doubles)", g->B, g->T, g->m,
+                 g->Q, (long long)w.total);
+    const int m = a.m, T = a.T;
+    const long long mm = (long long)m * m;
+    hipStream_t st = (hipStream_t)stream;
+    return bp_walk(g, true, [&](const BpStep& s) -> int {
+        const int c = s.c, nb = s.nb;
+        switch (s.op) {
+        case BP_FUSED: break;
+        case BP_KMAT:
+            return svgp_se1d_kernel_matrix_fwd(T, m, a.times, a.ip[c], a.ls[c], work + w.K, work + w.Kn, work + w.knn, stream);
+        case BP_SCALE:
+            hipLaunchKernelGGL(k_bp_scale_rows, dim3(bp_blocks((long long)nb * T * m)), dim3(SVGP_BLOCK), 0, st, a, c, s.b0, nb, work + w.Kn,
+                               work + w.KnP, work + w.PY);
+            SVGP_LAUNCH_CHECK();
+            break;
+        case BP_SIGMA:      // Kn^T diag(p_l) Kn: the shared Kn has stride 0
+            return svgp_dgemm_batched(1, 0, m, m, T, 1.0, work + w.Kn, m, 0, work + w.KnP, m, (long long)T * m, 0.0, work + w.Mats, m, mm, nb,
+                                      stream);
+        case BP_PRIOR:
+            hipLaunchKernelGGL(k_bp_add_prior, dim3(bp_blocks((nb + 1) * mm)), dim3(SVGP_BLOCK), 0, st, m, nb, a.jitter, work + w.K,
+                               work + w.Mats);
+            SVGP_LAUNCH_CHECK();
+            break;
+        case BP_V:          // V (m, nb) = Kn^T PY
+            return svgp_dgemm_batched(1, 0, m, nb, T, 1.0, work + w.Kn, m, 0, work + w.PY, nb, 0, 0.0, work + w.V, nb, 0, 1, stream);
+        case BP_INVERSE:
+            return svgp_spd_inverse_batched(m, nb + 1, work + w.Mats, work + w.logdet, work + w.inv, stream);
+        case BP_W:          // w_l = Si_l V[:, l]
+            return svgp_dgemm_batched(0, 0, m, 1, m, 1.0, work + w.Mats, m, mm, work + w.V, nb, 1, 0.0, work + w.W, 1, m, nb, stream);
+        case BP_SUB:
+            hipLaunchKernelGGL(k_bp_subtract, dim3(bp_blocks(nb * mm)), dim3(SVGP_BLOCK), 0, st, m, nb, work + w.Mats);
+            SVGP_LAUNCH_CHECK();
+            break;
+        case BP_KQ:
+            return svgp_se1d_kernel_matrix_fwd(s.nq, m, a.tq + s.q0, a.ip[c], a.ls[c], work + w.K2, work + w.Kq, work + w.kbb, stream);
+        case BP_ROWS: {
+            const svgp_posterior_rows_cfg rc_ = {s.nq, m, nb, -INFINITY, INFINITY};
+            return svgp_sprites_posterior_rows(&rc_, work + w.Kq, work + w.kbb, work + w.W, work + w.Mats, nullptr, work + w.tpm, work + w.tpv,
+                                               nullptr, work + w.rows, stream);
+        }
+        case BP_FINISH:
+            hipLaunchKernelGGL(k_bp_finish, dim3(bp_blocks((long long)s.nq * nb)), dim3(SVGP_BLOCK), 0, st, a, c, s.b0, nb, s.q0, s.nq,
+                               work + w.tpm, work + w.tpv);
+            SVGP_LAUNCH_CHECK();
+            break;
+        }
+        return (int)SVGP_OK;
+    });
+}
