@@ -190,7 +190,8 @@ const char* svgp_last_error(void);
  * time (a stale mirror shifts every later field silently): which = 0 svgp_mnist_cfg, 1 svgp_mnist_param_layout,
  * 2 svgp_mnist_ws_layout, 3 svgp_stream_kdesc, 4 svgp_conv_desc, 5 svgp_sprites_kcfg, 6 svgp_pearce_bufs,
  * 7 svgp_sum_job, 8 svgp_casale_cfg, 9 svgp_casale_layout, 10 svgp_ball_large_cfg, 11 svgp_mnist_cache_layout,
- * 13 svgp_ball_predict_cfg, 14 svgp_ball_predict_bufs; -1 otherwise (12 is not assigned). */
+ * 13 svgp_ball_predict_cfg, 14 svgp_ball_predict_bufs, 15 svgp_pearce_predict_cfg, 16 svgp_pearce_predict_bufs; -1 otherwise
+ * (12 is not assigned). */
 int         svgp_struct_sizeof(int which);
 
 int svgp_mnist_param_layout_get(const svgp_mnist_cfg* cfg, svgp_mnist_param_layout* out);
@@ -801,7 +802,8 @@ int svgp_state_add(double* state, int slot, double v, void* stream);
 int svgp_ball_rasterize(long long frames, int px, int py, double r, const double* paths, double* vid, void* stream);
 
 /* ---- Pearce baseline of the moving-ball experiment: BALL_experiment.py --elbo GPVAE_Pearce | VAE | NP ----------
- * build_1d_gp (GPVAE_Pearce_model.py:8-86) with X_test = X: exact GP regression per (video, latent coordinate),
+ * build_1d_gp (GPVAE_Pearce_model.py:8-86) with X_test = X (a general X_test, after training: svgp_pearce_predict
+ * further down): exact GP regression per (video, latent coordinate),
  * one workgroup each, n <= 64 points:  A = K_SE(l) + diag(var), alpha = A^-1 y,
  *   lhood = -1/2 (n log 2pi + y.alpha + log det A),  p_m = K alpha,  p_v = 1 - diag(K A^-1 K),
  *   z = p_m + eps sqrt(p_v), per-frame -gauss_cross_entropy (utils.py:483-504) and their sums.
@@ -1143,6 +1145,53 @@ int svgp_ball_predict(const svgp_ball_predict_cfg* cfg, const svgp_ball_predict_
 long long svgp_ball_predict_large_workspace_elems(const svgp_ball_predict_cfg* cfg);
 int svgp_ball_predict_large(const svgp_ball_predict_cfg* cfg, const svgp_ball_predict_bufs* bufs, double* work, void* stream);
 int svgp_ball_predict_route(const svgp_ball_predict_cfg* cfg, int large, char* buf, int cap);
+
+/* ---- moving ball, exact-GP baselines: fill dropped frames, resample in time (pearce_predict.hip) ------
+ * build_1d_gp(X, Y, varY, X_test) (GPVAE_Pearce_model.py:8-86) with a general X_test: the exact per-video GP posterior at
+ * arbitrary query times tq (Q) -- any finite reals, unsorted -- from the frames a mask keeps.  Per video b and latent coordinate c,
+ * with SE(s, t) = exp(-(s - t)^2 / (2 ls_c^2)) and O the kept frames of the video (mask != 0, n of them; mask NULL keeps all):
+ *   A = SE(t_O, t_O) + diag(var_O)  (no jitter, as in the reference)    alpha = A^-1 mu_O
+ *   lh = -1/2 (n log 2pi + mu_O . alpha + log det A)                    k = SE(tq, t_O)
+ *   p_m = k . alpha      p_v = 1 - k^T A^-1 k  (reported as computed)   z = p_m + eps sqrt(max(p_v, 0))
+ * The reference takes sqrt(p_v) unguarded; the max(., 0) is this library's and applies to the sample only.  A dropped frame is
+ * absent: its mu / var are never read (a NaN there reaches no output).  A video with every frame dropped gives the prior,
+ * p_m = 0, p_v = 1, lh = 0.  mu, var and mask are (T, B), the frame-major layout svgp_ball_head_fwd writes; mask is shared by the
+ * two coordinates.  eps and the outputs p_m, p_v, z are (Q, B) per coordinate, lh is (2, B).  eps NULL: z = p_m; z / lh NULL: not
+ * written.
+ * svgp_pearce_predict: 1 <= T <= 64, B, Q >= 1.  ONE launch, grid (B, 2, S): a workgroup compacts the kept frames of its video,
+ *   builds A in LDS, inverts it in place (the LDS sweep of the training kernels, which also gives log det), forms alpha and serves
+ *   its slice of the query times, a wave per query.  S query slices let a call with few videos and many query times fill the
+ *   device; every slice repeats the inverse.  q_slices = 0: the launch plan chooses S (about 512 workgroups, at least four
+ *   queries a slice); q_slices > 0 forces S.  No workspace, no atomics, fixed summation order: the same inputs give the same bits,
+ *   and a query time's outputs depend neither on its position in tq nor on S.
+ * svgp_pearce_predict_long: 1 <= T <= 2048: the same results up to rounding from global-memory pieces, both coordinates of 8
+ *   videos per chunk: a kernel builds the masked full-size A (rows / columns of dropped frames are those of the identity: log det
+ *   and the inverse of the kept block are unaffected), svgp_spd_inverse_batched inverts it in place, a row pass forms alpha, a
+ *   reduction lh (not launched when lh is NULL); per chunk of 512 query rows a kernel forms the masked k, svgp_dgemm_batched
+ *   k^T A^-1, and a closing kernel the row dot products and z.  work holds svgp_pearce_predict_long_workspace_elems(cfg) doubles
+ *   (0 for a refused cfg), which grows with neither B beyond 8 nor Q beyond 512.  q_slices is checked and otherwise unused.
+ * svgp_pearce_predict_route: the kernels (library entry points for the shared pieces) of one call as text, one name per line in
+ *   launch order, from the same plan as the launch code; needs no device.  SVGP_ERR_INVALID when cap bytes do not hold the text.
+ * Refused with a message before any launch: a NULL cfg / bufs / pointer (mask, eps_x/y, z_x/y and lh excepted), B, T or Q < 1,
+ *   q_slices < 0 or > min(Q, 65535), NULL work (SVGP_ERR_INVALID); T beyond the entry's range (SVGP_ERR_UNSUPPORTED).
+ * Explicit stream, no allocation, no synchronisation.                                                                          */
+typedef struct {
+    int32_t B, T, Q, q_slices;
+} svgp_pearce_predict_cfg;
+typedef struct {
+    const double *times, *tq;                 /* (T), (Q) */
+    const double *ls_x, *ls_y;                /* scalars */
+    const double *mu_x, *mu_y, *var_x, *var_y;/* (T, B) */
+    const double *mask;                       /* (T, B) or NULL */
+    const double *eps_x, *eps_y;              /* (Q, B) or NULL */
+    double *p_m_x, *p_m_y, *p_v_x, *p_v_y;    /* (Q, B) */
+    double *z_x, *z_y;                        /* (Q, B) or NULL */
+    double *lh;                               /* (2, B) or NULL */
+} svgp_pearce_predict_bufs;
+int svgp_pearce_predict(const svgp_pearce_predict_cfg* cfg, const svgp_pearce_predict_bufs* bufs, void* stream);
+long long svgp_pearce_predict_long_workspace_elems(const svgp_pearce_predict_cfg* cfg);
+int svgp_pearce_predict_long(const svgp_pearce_predict_cfg* cfg, const svgp_pearce_predict_bufs* bufs, double* work, void* stream);
+int svgp_pearce_predict_route(const svgp_pearce_predict_cfg* cfg, int long_form, char* buf, int cap);
 
 /* ---- runtime helpers: HIP graphs and events without going through torch ---------------------*/
 int svgp_stream_create(void** stream_out);

@@ -120,6 +120,17 @@ class BallPredictBufs(C.Structure):
                                           "eps_x", "eps_y", "p_m_x", "p_m_y", "p_v_x", "p_v_y", "z_x", "z_y")]
 
 
+class PearcePredictCfg(C.Structure):
+    """svgp_pearce_predict_cfg (include/svgpvae_hip.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("B", "T", "Q", "q_slices")]
+
+
+class PearcePredictBufs(C.Structure):
+    """svgp_pearce_predict_bufs (include/svgpvae_hip.h)."""
+    _fields_ = [(n, C.c_void_p) for n in ("times", "tq", "ls_x", "ls_y", "mu_x", "mu_y", "var_x", "var_y", "mask", "eps_x", "eps_y",
+                                          "p_m_x", "p_m_y", "p_v_x", "p_v_y", "z_x", "z_y", "lh")]
+
+
 STATE = dict(C_MA=0, LAGRANGE=1, ALPHA=2, ADAM_T=3, LR=4, BETA=5, ELBO=6, RECON_LOSS=7, KL_TERM=8,
              INSIDE_ELBO=9, CE_TERM=10, INSIDE_RECON=11, INSIDE_KL=12, RNG_CTR=13)
 STATE_LEN = 16
@@ -329,6 +340,9 @@ SIGNATURES = {
     "svgp_ball_predict": [C.POINTER(BallPredictCfg), C.POINTER(BallPredictBufs), _P],
     "svgp_ball_predict_large": [C.POINTER(BallPredictCfg), C.POINTER(BallPredictBufs), _P, _P],
     "svgp_ball_predict_route": [C.POINTER(BallPredictCfg), C.c_int, C.c_char_p, C.c_int],
+    "svgp_pearce_predict": [C.POINTER(PearcePredictCfg), C.POINTER(PearcePredictBufs), _P],
+    "svgp_pearce_predict_long": [C.POINTER(PearcePredictCfg), C.POINTER(PearcePredictBufs), _P, _P],
+    "svgp_pearce_predict_route": [C.POINTER(PearcePredictCfg), C.c_int, C.c_char_p, C.c_int],
     "svgp_stream_create": [C.POINTER(_P)],
     "svgp_stream_destroy": [_P],
     "svgp_stream_sync": [_P],
@@ -368,6 +382,7 @@ NON_STATUS = {"svgp_version": ([], C.c_int), "svgp_last_error": ([], C.c_char_p)
               "svgp_mnist_generate_workspace_elems": ([_CFG], C.c_longlong),
               "svgp_sprites_posterior_rows_workspace_elems": ([C.POINTER(PosteriorRowsCfg)], C.c_longlong),
               "svgp_ball_predict_large_workspace_elems": ([C.POINTER(BallPredictCfg)], C.c_longlong),
+              "svgp_pearce_predict_long_workspace_elems": ([C.POINTER(PearcePredictCfg)], C.c_longlong),
               "svgp_svigp_scale_offset": ([C.c_int, C.c_int, C.c_int], C.c_longlong)}
 
 _lib = None
@@ -398,7 +413,7 @@ def load_library(path=None):
     # the ctypes mirrors must have the layout the library was compiled with (svgp_struct_sizeof)
     mirrors = dict(enumerate((MnistCfg, ParamLayout, WsLayout, StreamKdesc, ConvDesc, SpritesKcfg, PearceBufs, SumJob,
                               CasaleCfg, CasaleLayout, BallLargeCfg, CacheLayout)))
-    mirrors.update({13: BallPredictCfg, 14: BallPredictBufs})          # code 12 is not assigned
+    mirrors.update({13: BallPredictCfg, 14: BallPredictBufs, 15: PearcePredictCfg, 16: PearcePredictBufs})     # code 12 is not assigned
     for which, cls in mirrors.items():
         if lib.svgp_struct_sizeof(which) != C.sizeof(cls):
             raise SvgpError(f"{p}: sizeof({cls.__name__}) is {lib.svgp_struct_sizeof(which)} in the library but "

@@ -551,10 +551,10 @@ SPARSE_ENGINES = (BallStepEngine, BallLargeStepEngine)
 
 
 def __getattr__(name):
-    """BallPredictor lives in ball_predict.py (which imports this module); re-exported here on first use."""
-    if name == "BallPredictor":
-        from .ball_predict import BallPredictor
-        return BallPredictor
+    """BallPredictor and PearcePredictor live in ball_predict.py (which imports this module); re-exported here on first use."""
+    if name in ("BallPredictor", "PearcePredictor"):
+        from . import ball_predict
+        return getattr(ball_predict, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

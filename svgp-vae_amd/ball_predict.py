@@ -1,14 +1,16 @@
-"""Moving-ball SVGP-VAE after training: reconstruct dropped frames, render a video at another time grid,
+"""Moving-ball models after training (DESIGN.md sections 9h, 9i): reconstruct dropped frames, render a video at another time grid,
 extrapolate a few frames -- from a `BALL_experiment --save_model` checkpoint.
 
     python -m svgp_vae_amd.ball_predict --checkpoint RUN/model.pt (--videos F.npy | --test_batch K --base_dir D)
         [--drop 0.5 --drop_seed S | --observed mask.npy] [--upsample R | --query_times t1 t2 ..] [--sample --seed S] --out frames.npy
 
-The GP posterior of SVGP.approximate_posterior_params (SVGPVAE_model.py:142-171) is evaluated at arbitrary query times from the
-frames that are observed (a dropped frame is a frame of precision 0): svgp_ball_predict, ONE launch per batch for m <= 64 whatever
-the number of videos and query times, svgp_ball_predict_large beyond.  Encoder and decoder are those of the training engines
-(ball._BallMlpEngine).  Only the sparse-GP models (SVGPVAE_Hensman / SVGPVAE_Titsias) are handled; forward only: no gradient, no
-Adam state, no random-number state is touched."""
+BallPredictor (SVGPVAE_Hensman / SVGPVAE_Titsias): the GP posterior of SVGP.approximate_posterior_params (SVGPVAE_model.py:142-171)
+is evaluated at arbitrary query times from the frames that are observed (a dropped frame is a frame of precision 0):
+svgp_ball_predict, ONE launch per batch for m <= 64 whatever the number of videos and query times, svgp_ball_predict_large beyond.
+PearcePredictor (the exact-GP baselines GPVAE_Pearce / NP / VAE): build_1d_gp (GPVAE_Pearce_model.py:8-86) with a general X_test on
+the observed frames of each video: svgp_pearce_predict, ONE launch, up to 64 frames, svgp_pearce_predict_long beyond.
+load_predictor picks the class from the checkpoint, so the command line serves all five --elbo values.  Encoder and decoder are
+those of the training engines (ball._BallMlpEngine).  Forward only: no gradient, no Adam state, no random-number state is touched."""
 import argparse
 import ctypes as C
 
@@ -16,13 +18,15 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import BallPredictBufs, BallPredictCfg, call
+from ._lib import BallPredictBufs, BallPredictCfg, PearcePredictBufs, PearcePredictCfg, call
 from .ball import _BallMlpEngine, mlp_param_shapes
 
 _F64 = torch.float64
 CLIP_PV = (1e-4, 1000.0)                                  # SVGPVAE_model.py:701: only the sample clamps
 FUSED_M_MAX = 64
+PEARCE_FUSED_T_MAX = 64
 META_KEYS = ("tmax", "m", "hidden", "px", "py", "jitter", "clip_qs")
+PEARCE_META_KEYS = ("tmax", "hidden", "px", "py")          # all an exact-GP model's shape needs; m, jitter, clip_qs are ignored
 _PEARCE_ELBOS = ("GPVAE_Pearce", "NP", "VAE")
 
 
@@ -36,6 +40,16 @@ def route(shape):
     return buf.value.decode().split()
 
 
+def pearce_route(shape, q_slices=0):
+    """The kernels of the GP stage of one `PearcePredictor.predict` call of shape (B, T, Q), in launch order
+    (svgp_pearce_predict_route); needs no device."""
+    B, T, Q = shape
+    buf = C.create_string_buffer(1 << 16)
+    cfg = PearcePredictCfg(B=int(B), T=int(T), Q=int(Q), q_slices=int(q_slices))
+    call("svgp_pearce_predict_route", C.byref(cfg), int(T > PEARCE_FUSED_T_MAX), buf, len(buf))
+    return buf.value.decode().split()
+
+
 def param_shapes(m, px=32, py=32, hidden=500):
     """The flat parameter vector of the sparse-GP ball engines: the MLPs, then ip_x, l_x, ip_y, l_y."""
     sh = dict(mlp_param_shapes(px, py, hidden))
@@ -43,27 +57,60 @@ def param_shapes(m, px=32, py=32, hidden=500):
     return sh
 
 
-class BallPredictor(_BallMlpEngine):
-    """A trained moving-ball SVGP-VAE, forward only.  `params`: name -> array for every entry of param_shapes(m, px, py, hidden)."""
+def pearce_param_shapes(px=32, py=32, hidden=500):
+    """The flat parameter vector of the exact-GP ball engines: the MLPs, then l_x, l_y."""
+    sh = dict(mlp_param_shapes(px, py, hidden))
+    sh.update(l_x=(1,), l_y=(1,))
+    return sh
 
-    def __init__(self, params, *, tmax, m, hidden=500, px=32, py=32, jitter, clip_qs, device="cuda:0"):
-        self.shapes = param_shapes(int(m), int(px), int(py), int(hidden))
+
+def _read_checkpoint(path):
+    """(checkpoint dict, its shapes as name -> tuple) of a `model.pt` of the moving-ball driver."""
+    ck = torch.load(path, map_location="cpu")
+    if not isinstance(ck, dict) or "theta" not in ck or "shapes" not in ck:
+        raise ValueError(f"{path}: not a checkpoint of the moving-ball driver (needs theta and shapes)")
+    return ck, {k: tuple(v) for k, v in dict(ck["shapes"]).items()}
+
+
+def _split_theta(path, ck, got, want, what):
+    """name -> slice of the checkpoint's theta, after its shapes were checked against the model's (`what` describes the model)."""
+    want = {k: tuple(v) for k, v in want.items()}
+    if got != want:
+        bad = sorted(k for k in set(got) | set(want) if got.get(k) != want.get(k, ()))
+        raise ValueError(f"{path}: the checkpoint's shapes do not fit {what} (differing: {bad})")
+    theta = torch.as_tensor(ck["theta"], dtype=_F64).reshape(-1)
+    need = sum(int(np.prod(s)) for s in want.values())
+    if theta.numel() != need:
+        raise ValueError(f"{path}: theta has {theta.numel()} elements, the shapes describe {need}")
+    params, off = {}, 0
+    for k, s in got.items():
+        n = int(np.prod(s))
+        params[k] = theta[off:off + n]
+        off += n
+    return params
+
+
+class _Predictor(_BallMlpEngine):
+    """What the two predictors share: the flat parameter vector on the device and `predict` around the GP stage.  A subclass sets
+    `shapes` and `clip_qs` (the clamp of the encoder head) before _setup and provides _gp_stage."""
+
+    def _setup(self, params, kind, *, tmax, hidden, px, py, device):
+        name = type(self).__name__
         missing = [k for k in self.shapes if k not in params]
         if missing:
-            raise ValueError(f"BallPredictor: parameters {missing} are missing (a sparse-GP ball model has {list(self.shapes)})")
+            raise ValueError(f"{name}: parameters {missing} are missing ({kind} ball model has {list(self.shapes)})")
         flat = []
         for k, s in self.shapes.items():
             v = params[k]
             v = torch.as_tensor(np.asarray(v) if not torch.is_tensor(v) else v.detach().cpu(), dtype=_F64).reshape(-1)
             if v.numel() != int(np.prod(s)):
-                raise ValueError(f"BallPredictor: {k} has {v.numel()} elements, the model's shape {s} needs {int(np.prod(s))}")
+                raise ValueError(f"{name}: {k} has {v.numel()} elements, the model's shape {s} needs {int(np.prod(s))}")
             flat.append(v)
         self.lib = _lib.load_library()
         if not torch.cuda.is_available():
-            raise _lib.SvgpError("BallPredictor needs a HIP device; there is no CPU execution path")
+            raise _lib.SvgpError(f"{name} needs a HIP device; there is no CPU execution path")
         self.dev = torch.device(device)
-        self.tmax, self.m, self.px, self.py, self.P, self.H = int(tmax), int(m), int(px), int(py), int(px) * int(py), int(hidden)
-        self.jitter, self.clip_qs = float(jitter), bool(clip_qs)
+        self.tmax, self.px, self.py, self.P, self.H = int(tmax), int(px), int(py), int(px) * int(py), int(hidden)
         self.stream = torch.cuda.Stream(device=self.dev)
         with torch.cuda.stream(self.stream):
             self.theta = torch.cat(flat).to(self.dev)
@@ -76,74 +123,11 @@ class BallPredictor(_BallMlpEngine):
         self._work = torch.empty(0, dtype=_F64, device=self.dev)
         self.stream.synchronize()
 
-    # ------------------------------------------------------------------ checkpoints
-    @classmethod
-    def load(cls, path, **overrides):
-        """A predictor from the `model.pt` of `BALL_experiment --save_model`.  The model's shape comes from the checkpoint's "meta"
-        dict; keywords override it, and stand in for it where an older checkpoint has none."""
-        ck = torch.load(path, map_location="cpu")
-        if not isinstance(ck, dict) or "theta" not in ck or "shapes" not in ck:
-            raise ValueError(f"{path}: not a checkpoint of the moving-ball driver (needs theta and shapes)")
-        meta = dict(ck.get("meta") or {})
-        device = overrides.pop("device", "cuda:0")
-        meta.update(overrides)
-        shapes = dict(ck["shapes"])
-        if meta.get("elbo") in _PEARCE_ELBOS or "ip_x" not in shapes:
-            raise ValueError(f"{path}: a checkpoint of an exact-GP baseline (GPVAE_Pearce / NP / VAE: no inducing points); "
-                             f"ball_predict handles the sparse-GP models SVGPVAE_Hensman / SVGPVAE_Titsias only")
-        missing = [k for k in META_KEYS if k not in meta]
-        if missing:
-            raise ValueError(f"{path}: the checkpoint has no meta entry for {', '.join(missing)}; pass "
-                             f"{', '.join(k + '=...' for k in missing)} to BallPredictor.load")
-        want = param_shapes(int(meta["m"]), int(meta["px"]), int(meta["py"]), int(meta["hidden"]))
-        got = {k: tuple(v) for k, v in shapes.items()}
-        if got != {k: tuple(v) for k, v in want.items()}:
-            bad = sorted(k for k in set(got) | set(want) if got.get(k) != tuple(want.get(k, ())))
-            raise ValueError(f"{path}: the checkpoint's shapes do not fit m={meta['m']} hidden={meta['hidden']} px={meta['px']} "
-                             f"py={meta['py']} (differing: {bad})")
-        theta = torch.as_tensor(ck["theta"], dtype=_F64).reshape(-1)
-        need = sum(int(np.prod(s)) for s in want.values())
-        if theta.numel() != need:
-            raise ValueError(f"{path}: theta has {theta.numel()} elements, the shapes describe {need}")
-        params, off = {}, 0
-        for k, s in shapes.items():
-            n = int(np.prod(s))
-            params[k] = theta[off:off + n]
-            off += n
-        return cls(params, device=device, **{k: meta[k] for k in META_KEYS})
-
-    def route(self, B, T, Q):
-        return route((B, T, self.m, Q))
-
-    # ------------------------------------------------------------------ the GP stage alone
-    def _gp(self, mu, var, times, tq, mask, eps_c):
-        """mu, var: two (T, B) tensors each; mask (T, B) or None; eps_c: two (Q, B) tensors or None.  Returns p_m, p_v, z lists."""
-        T, B = mu[0].shape
-        Q, p, s = tq.numel(), self.params, self.stream.cuda_stream
-        f64 = dict(dtype=_F64, device=self.dev)
-        out = {k: [torch.empty(Q, B, **f64) for _ in range(2)] for k in ("p_m", "p_v", "z")}
-        cfg = BallPredictCfg(B=B, T=T, m=self.m, Q=Q, jitter=self.jitter, clip_lo=CLIP_PV[0], clip_hi=CLIP_PV[1])
-        q = BallPredictBufs()
-        q.times, q.tq, q.mask = times.data_ptr(), tq.data_ptr(), None if mask is None else mask.data_ptr()
-        for c, cn in enumerate("xy"):
-            setattr(q, f"ip_{cn}", p[f"ip_{cn}"].data_ptr()); setattr(q, f"ls_{cn}", p[f"l_{cn}"].data_ptr())
-            setattr(q, f"mu_{cn}", mu[c].data_ptr()); setattr(q, f"var_{cn}", var[c].data_ptr())
-            setattr(q, f"eps_{cn}", None if eps_c is None else eps_c[c].data_ptr())
-            setattr(q, f"p_m_{cn}", out["p_m"][c].data_ptr()); setattr(q, f"p_v_{cn}", out["p_v"][c].data_ptr())
-            setattr(q, f"z_{cn}", out["z"][c].data_ptr())
-        if self.m <= FUSED_M_MAX:
-            call("svgp_ball_predict", C.byref(cfg), C.byref(q), s)
-        else:
-            need = int(self.lib.svgp_ball_predict_large_workspace_elems(C.byref(cfg)))      # 0: a shape the entry refuses (it says why)
-            if self._work.numel() < need:
-                self._work = torch.empty(need, **f64)                                     # grows once per shape
-            call("svgp_ball_predict_large", C.byref(cfg), C.byref(q), self._work.data_ptr() if need else None, s)
-        return out["p_m"], out["p_v"], out["z"]
-
     # ------------------------------------------------------------------ frames
     def predict(self, videos, query_times, observed=None, frame_times=None, eps=None):
         """videos (B, T, px, py); query_times (Q) arbitrary reals; observed (B, T) bool, default all; frame_times (T), default 1..T;
-        eps (B, Q, 2) or None (decode the posterior mean).  Returns dict(frames (B, Q, px, py) in [0, 1], p_m, p_v, z (B, Q, 2))."""
+        eps (B, Q, 2) or None (decode the posterior mean).  Returns dict(frames (B, Q, px, py) in [0, 1], p_m, p_v, z (B, Q, 2));
+        PearcePredictor adds lh (B, 2)."""
         videos = torch.as_tensor(np.asarray(videos) if not torch.is_tensor(videos) else videos)
         if videos.dim() != 4 or tuple(videos.shape[2:]) != (self.px, self.py):
             raise ValueError(f"videos must be (B, T, {self.px}, {self.py}), got {tuple(videos.shape)}")
@@ -181,7 +165,7 @@ class BallPredictor(_BallMlpEngine):
             mu, var_raw, var = ([torch.empty(T, B, **f64) for _ in range(2)] for _ in range(3))
             call("svgp_ball_head_fwd", B, T, int(self.clip_qs), p["encB2"].data_ptr(), h2.data_ptr(), mu[0].data_ptr(),
                  var_raw[0].data_ptr(), var[0].data_ptr(), mu[1].data_ptr(), var_raw[1].data_ptr(), var[1].data_ptr(), s)
-            p_m, p_v, zc = self._gp(mu, var, times, tq, mask, eps_c)
+            p_m, p_v, zc, extra = self._gp_stage(mu, var, times, tq, mask, eps_c)
             z = torch.empty(B * Q, 2, **f64)
             call("svgp_ball_pack_z", B, Q, zc[0].data_ptr(), zc[1].data_ptr(), z.data_ptr(), s)
             _, logits = self._decode_logits(z)
@@ -190,14 +174,152 @@ class BallPredictor(_BallMlpEngine):
             call("svgp_sigmoid_xent", B * Q, P, 1.0, logits.data_ptr(), logits.data_ptr(), frames.data_ptr(), row.data_ptr(),
                  None, s)
             st2 = lambda v: torch.stack([v[0].t(), v[1].t()], 2).contiguous()
-            out = dict(frames=frames.view(B, Q, self.px, self.py), p_m=st2(p_m), p_v=st2(p_v), z=z.view(B, Q, 2))
+            out = dict(frames=frames.view(B, Q, self.px, self.py), p_m=st2(p_m), p_v=st2(p_v), z=z.view(B, Q, 2), **extra)
         self.stream.synchronize()
         return out
 
 
+class BallPredictor(_Predictor):
+    """A trained moving-ball SVGP-VAE, forward only.  `params`: name -> array for every entry of param_shapes(m, px, py, hidden)."""
+
+    def __init__(self, params, *, tmax, m, hidden=500, px=32, py=32, jitter, clip_qs, device="cuda:0"):
+        self.shapes = param_shapes(int(m), int(px), int(py), int(hidden))
+        self.m, self.jitter, self.clip_qs = int(m), float(jitter), bool(clip_qs)
+        self._setup(params, "a sparse-GP", tmax=tmax, hidden=hidden, px=px, py=py, device=device)
+
+    # ------------------------------------------------------------------ checkpoints
+    @classmethod
+    def load(cls, path, **overrides):
+        """A predictor from the `model.pt` of `BALL_experiment --save_model`.  The model's shape comes from the checkpoint's "meta"
+        dict; keywords override it, and stand in for it where an older checkpoint has none."""
+        ck, shapes = _read_checkpoint(path)
+        meta = dict(ck.get("meta") or {})
+        device = overrides.pop("device", "cuda:0")
+        meta.update(overrides)
+        if meta.get("elbo") in _PEARCE_ELBOS or "ip_x" not in shapes:
+            raise ValueError(f"{path}: a checkpoint of an exact-GP baseline (GPVAE_Pearce / NP / VAE: no inducing points); "
+                             f"BallPredictor handles the sparse-GP models SVGPVAE_Hensman / SVGPVAE_Titsias only, use PearcePredictor")
+        missing = [k for k in META_KEYS if k not in meta]
+        if missing:
+            raise ValueError(f"{path}: the checkpoint has no meta entry for {', '.join(missing)}; pass "
+                             f"{', '.join(k + '=...' for k in missing)} to BallPredictor.load")
+        want = param_shapes(int(meta["m"]), int(meta["px"]), int(meta["py"]), int(meta["hidden"]))
+        params = _split_theta(path, ck, shapes, want, f"m={meta['m']} hidden={meta['hidden']} px={meta['px']} py={meta['py']}")
+        return cls(params, device=device, **{k: meta[k] for k in META_KEYS})
+
+    def route(self, B, T, Q):
+        return route((B, T, self.m, Q))
+
+    # ------------------------------------------------------------------ the GP stage alone
+    def _gp(self, mu, var, times, tq, mask, eps_c):
+        """mu, var: two (T, B) tensors each; mask (T, B) or None; eps_c: two (Q, B) tensors or None.  Returns p_m, p_v, z lists."""
+        T, B = mu[0].shape
+        Q, p, s = tq.numel(), self.params, self.stream.cuda_stream
+        f64 = dict(dtype=_F64, device=self.dev)
+        out = {k: [torch.empty(Q, B, **f64) for _ in range(2)] for k in ("p_m", "p_v", "z")}
+        cfg = BallPredictCfg(B=B, T=T, m=self.m, Q=Q, jitter=self.jitter, clip_lo=CLIP_PV[0], clip_hi=CLIP_PV[1])
+        q = BallPredictBufs()
+        q.times, q.tq, q.mask = times.data_ptr(), tq.data_ptr(), None if mask is None else mask.data_ptr()
+        for c, cn in enumerate("xy"):
+            setattr(q, f"ip_{cn}", p[f"ip_{cn}"].data_ptr()); setattr(q, f"ls_{cn}", p[f"l_{cn}"].data_ptr())
+            setattr(q, f"mu_{cn}", mu[c].data_ptr()); setattr(q, f"var_{cn}", var[c].data_ptr())
+            setattr(q, f"eps_{cn}", None if eps_c is None else eps_c[c].data_ptr())
+            setattr(q, f"p_m_{cn}", out["p_m"][c].data_ptr()); setattr(q, f"p_v_{cn}", out["p_v"][c].data_ptr())
+            setattr(q, f"z_{cn}", out["z"][c].data_ptr())
+        if self.m <= FUSED_M_MAX:
+            call("svgp_ball_predict", C.byref(cfg), C.byref(q), s)
+        else:
+            need = int(self.lib.svgp_ball_predict_large_workspace_elems(C.byref(cfg)))      # 0: a shape the entry refuses (it says why)
+            if self._work.numel() < need:
+                self._work = torch.empty(need, **f64)                                     # grows once per shape
+            call("svgp_ball_predict_large", C.byref(cfg), C.byref(q), self._work.data_ptr() if need else None, s)
+        return out["p_m"], out["p_v"], out["z"]
+
+    def _gp_stage(self, mu, var, times, tq, mask, eps_c):
+        return self._gp(mu, var, times, tq, mask, eps_c) + ({},)
+
+
+class PearcePredictor(_Predictor):
+    """A trained exact-GP moving-ball baseline (BALL_experiment --elbo GPVAE_Pearce | NP | VAE), forward only.  `params`: name ->
+    array for every entry of pearce_param_shapes(px, py, hidden).
+
+    The posterior of a video at the query times is build_1d_gp (GPVAE_Pearce_model.py:8-86) on its observed frames with X_test =
+    the query times; `predict` additionally returns lh (B, 2), the marginal likelihood of the observed frames per coordinate.  The
+    encoder head is not clamped, as in _PearceEngineBase.step.  `frame_times` defaults to 1..T like BallPredictor's; the training
+    engines count 0..T-1, and since the SE kernel is stationary the posterior at a frame (and lh) is the same under either
+    convention.  A checkpoint of --elbo VAE carries the length scale 0.001: a query time that is not an observed frame time gets
+    the prior N(0, 1), which is the point of that baseline."""
+
+    clip_qs = False
+
+    def __init__(self, params, *, tmax, hidden=500, px=32, py=32, device="cuda:0"):
+        self.shapes = pearce_param_shapes(int(px), int(py), int(hidden))
+        self._setup(params, "an exact-GP", tmax=tmax, hidden=hidden, px=px, py=py, device=device)
+
+    @classmethod
+    def load(cls, path, **overrides):
+        """A predictor from the `model.pt` of `BALL_experiment --save_model` with --elbo GPVAE_Pearce | NP | VAE.  Of the "meta"
+        dict only tmax, hidden, px, py are needed; keywords override them, and stand in for them where a checkpoint has none."""
+        ck, shapes = _read_checkpoint(path)
+        meta = dict(ck.get("meta") or {})
+        device = overrides.pop("device", "cuda:0")
+        meta.update(overrides)
+        if "ip_x" in shapes or ("elbo" in meta and meta["elbo"] not in _PEARCE_ELBOS):
+            raise ValueError(f"{path}: a checkpoint of a sparse-GP model (SVGPVAE_Hensman / SVGPVAE_Titsias: it has inducing points); "
+                             f"PearcePredictor handles the exact-GP baselines GPVAE_Pearce / NP / VAE only, use BallPredictor")
+        missing = [k for k in PEARCE_META_KEYS if k not in meta]
+        if missing:
+            raise ValueError(f"{path}: the checkpoint has no meta entry for {', '.join(missing)}; pass "
+                             f"{', '.join(k + '=...' for k in missing)} to PearcePredictor.load")
+        want = pearce_param_shapes(int(meta["px"]), int(meta["py"]), int(meta["hidden"]))
+        params = _split_theta(path, ck, shapes, want, f"hidden={meta['hidden']} px={meta['px']} py={meta['py']}")
+        return cls(params, device=device, **{k: meta[k] for k in PEARCE_META_KEYS})
+
+    def route(self, B, T, Q):
+        return pearce_route((B, T, Q))
+
+    # ------------------------------------------------------------------ the GP stage alone
+    def _gp(self, mu, var, times, tq, mask, eps_c, q_slices=0):
+        """mu, var: two (T, B) tensors each; mask (T, B) or None; eps_c: two (Q, B) tensors or None.  Returns the p_m, p_v, z lists
+        and lh (2, B)."""
+        T, B = mu[0].shape
+        Q, p, s = tq.numel(), self.params, self.stream.cuda_stream
+        f64 = dict(dtype=_F64, device=self.dev)
+        out = {k: [torch.empty(Q, B, **f64) for _ in range(2)] for k in ("p_m", "p_v", "z")}
+        lh = torch.empty(2, B, **f64)
+        cfg = PearcePredictCfg(B=B, T=T, Q=Q, q_slices=int(q_slices))
+        q = PearcePredictBufs()
+        q.times, q.tq, q.mask, q.lh = times.data_ptr(), tq.data_ptr(), None if mask is None else mask.data_ptr(), lh.data_ptr()
+        for c, cn in enumerate("xy"):
+            setattr(q, f"ls_{cn}", p[f"l_{cn}"].data_ptr())
+            setattr(q, f"mu_{cn}", mu[c].data_ptr()); setattr(q, f"var_{cn}", var[c].data_ptr())
+            setattr(q, f"eps_{cn}", None if eps_c is None else eps_c[c].data_ptr())
+            setattr(q, f"p_m_{cn}", out["p_m"][c].data_ptr()); setattr(q, f"p_v_{cn}", out["p_v"][c].data_ptr())
+            setattr(q, f"z_{cn}", out["z"][c].data_ptr())
+        if T <= PEARCE_FUSED_T_MAX:
+            call("svgp_pearce_predict", C.byref(cfg), C.byref(q), s)
+        else:
+            need = int(self.lib.svgp_pearce_predict_long_workspace_elems(C.byref(cfg)))     # 0: a shape the entry refuses (it says why)
+            if self._work.numel() < need:
+                self._work = torch.empty(need, **f64)                                     # grows once per shape
+            call("svgp_pearce_predict_long", C.byref(cfg), C.byref(q), self._work.data_ptr() if need else None, s)
+        return out["p_m"], out["p_v"], out["z"], lh
+
+    def _gp_stage(self, mu, var, times, tq, mask, eps_c):
+        p_m, p_v, z, lh = self._gp(mu, var, times, tq, mask, eps_c)
+        return p_m, p_v, z, dict(lh=lh.t().contiguous())
+
+
+def load_predictor(path, **kw):
+    """BallPredictor or PearcePredictor, whichever model the checkpoint holds (told by its inducing points); the class's own load
+    does the checking."""
+    _, shapes = _read_checkpoint(path)
+    return (BallPredictor if "ip_x" in shapes else PearcePredictor).load(path, **kw)
+
+
 # ---------------------------------------------------------------------------------------------- command line
 def build_parser():
-    p = argparse.ArgumentParser(description="Fill dropped frames / resample in time with a trained moving-ball SVGP-VAE.")
+    p = argparse.ArgumentParser(description="Fill dropped frames / resample in time with a trained moving-ball model.")
     p.add_argument("--checkpoint", required=True, help="RUN/model.pt of BALL_experiment --save_model")
     src = p.add_mutually_exclusive_group(required=True)
     src.add_argument("--videos", type=str, default=None, help=".npy of videos (B, T, px, py)")
@@ -241,7 +363,7 @@ def query_grid(T, upsample=None, query_times=None):
 
 def main(argv=None):
     args = parse_args(argv)
-    pred = BallPredictor.load(args.checkpoint, device=args.device)
+    pred = load_predictor(args.checkpoint, device=args.device)
     if args.videos is not None:
         videos = np.load(args.videos)
     else:

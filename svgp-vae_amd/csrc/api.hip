@@ -36,6 +36,8 @@ extern "C" int svgp_struct_sizeof(int which) {
     case 11: return (int)sizeof(svgp_mnist_cache_layout);
     case 13: return (int)sizeof(svgp_ball_predict_cfg);       // (12 stays unassigned: tests/test_generate_cpu.py pins it to -1)
     case 14: return (int)sizeof(svgp_ball_predict_bufs);
+    case 15: return (int)sizeof(svgp_pearce_predict_cfg);
+    case 16: return (int)sizeof(svgp_pearce_predict_bufs);
     default: return -1;
     }
 }

@@ -2,7 +2,9 @@
 
 Shapes (B videos, T frames, m inducing points, Q query times): the reference batch at its own frame rate (35, 30, 15, 30) and at
 eight times that rate (35, 30, 15, 240), the largest fused shape (256, 64, 64, 512), and one shape of the large route
-(35, 64, 256, 128).  Frames 32 x 32, hidden 500, 40 % of the frames dropped.  The GP stage is timed between device events (its own
+(35, 64, 256, 128).  Beside each, the exact-GP predictor (PearcePredictor) at the same (B, T, Q): svgp_pearce_predict for these
+T <= 64, and svgp_pearce_predict_long forced onto the same shape; plus one shape only the long entry takes, (35, 256, -, 512).
+Frames 32 x 32, hidden 500, 40 % of the frames dropped.  The GP stage is timed between device events (its own
 launches only, inputs resident), `predict` by the wall clock around a call that ends in a device synchronise; medians and minima
 over --reps calls after a warm-up of each.  Information only, no threshold; needs a GPU and fails without one.
 
@@ -21,7 +23,72 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 SHAPES = [(35, 30, 15, 30), (35, 30, 15, 240), (256, 64, 64, 512), (35, 64, 256, 128)]
+PEARCE_LONG_ONLY = [(35, 256, 512)]
 PX, HIDDEN = 32, 500
+
+
+def _device_times(stream, fn, reps):
+    """Seconds between device events around `fn`, per call, after one warm-up call."""
+    fn()
+    torch.cuda.synchronize()
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)]
+    for e0, e1 in ev:
+        e0.record(stream); fn(); e1.record(stream)
+    torch.cuda.synchronize()
+    return [e0.elapsed_time(e1) * 1e-3 for e0, e1 in ev]
+
+
+def pearce_rows(B, T, Q, reps, vid=None, observed=None):
+    """The exact-GP predictor at (B, T, Q): the GP stage of each entry that takes T, and the whole predict."""
+    import ctypes as C
+
+    from svgp_vae_amd import _lib, ball
+    from svgp_vae_amd.ball_predict import PEARCE_FUSED_T_MAX, PearcePredictor
+    rs = np.random.RandomState(0)
+    params = dict(ball.truncated_normal_mlp_params(PX, PX, HIDDEN, 0))
+    params.update(l_x=[2.0], l_y=[2.0 / 1.1])
+    pred = PearcePredictor(params, tmax=T, hidden=HIDDEN, px=PX, py=PX)
+    f64 = dict(dtype=torch.float64, device=pred.dev)
+    if observed is None:
+        observed = rs.rand(B, T) >= 0.4
+        observed[:, 0] = True
+    tq = np.linspace(1.0, float(T), Q)
+    mu = [torch.randn(T, B, **f64) for _ in range(2)]
+    var = [torch.rand(T, B, **f64) * 0.5 + 1e-3 for _ in range(2)]
+    times, tqd = torch.arange(1, T + 1, **f64), torch.as_tensor(tq, **f64)
+    mask = torch.as_tensor(observed, **f64).t().contiguous()
+    out = [torch.empty(Q, B, **f64) for _ in range(6)]
+    lh = torch.empty(2, B, **f64)
+    cfg = _lib.PearcePredictCfg(B=B, T=T, Q=Q, q_slices=0)
+    q = _lib.PearcePredictBufs()
+    q.times, q.tq, q.mask, q.lh = times.data_ptr(), tqd.data_ptr(), mask.data_ptr(), lh.data_ptr()
+    for c, cn in enumerate("xy"):
+        setattr(q, f"ls_{cn}", pred.params[f"l_{cn}"].data_ptr())
+        setattr(q, f"mu_{cn}", mu[c].data_ptr()); setattr(q, f"var_{cn}", var[c].data_ptr())
+        setattr(q, f"p_m_{cn}", out[c].data_ptr()); setattr(q, f"p_v_{cn}", out[2 + c].data_ptr()); setattr(q, f"z_{cn}", out[4 + c].data_ptr())
+    work = torch.empty(int(pred.lib.svgp_pearce_predict_long_workspace_elems(C.byref(cfg))), **f64)
+    s = pred.stream.cuda_stream
+    row = dict(model="exact-GP", B=B, T=T, Q=Q, reps=reps)
+    if T <= PEARCE_FUSED_T_MAX:
+        t = _device_times(pred.stream, lambda: _lib.call("svgp_pearce_predict", C.byref(cfg), C.byref(q), s), reps)
+        row.update(gp_lds_device_s=float(np.median(t)), gp_lds_device_min_s=float(np.min(t)))
+    t = _device_times(pred.stream, lambda: _lib.call("svgp_pearce_predict_long", C.byref(cfg), C.byref(q), work.data_ptr(), s), reps)
+    buf = C.create_string_buffer(1 << 16)
+    _lib.call("svgp_pearce_predict_route", C.byref(cfg), 1, buf, len(buf))
+    names = buf.value.decode().split()
+    row.update(gp_long_device_s=float(np.median(t)), gp_long_device_min_s=float(np.min(t)), gp_long_launches=len(names))
+    if vid is None:
+        _, vid = ball.Make_Video_batch(tmax=T, px=PX, py=PX, lt=2, batch=B, seed=0)
+        vid = torch.as_tensor(vid, dtype=torch.float64, device=pred.dev)
+    pred.predict(vid, tq, observed=observed)
+    t_all = []
+    for _ in range(reps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        pred.predict(vid, tq, observed=observed)
+        t_all.append(time.perf_counter() - t0)
+    row.update(predict_s=float(np.median(t_all)), predict_min_s=float(np.min(t_all)), route=pred.route(B, T, Q)[:3])
+    return row
 
 
 def main(argv=None):
@@ -78,6 +145,13 @@ def main(argv=None):
         rows.append(row)
         print(json.dumps(row), flush=True)
         del pred
+        torch.cuda.empty_cache()
+        rows.append(pearce_rows(B, T, Q, args.reps, vid=vid, observed=observed))
+        print(json.dumps(rows[-1]), flush=True)
+        torch.cuda.empty_cache()
+    for B, T, Q in PEARCE_LONG_ONLY:
+        rows.append(pearce_rows(B, T, Q, args.reps))
+        print(json.dumps(rows[-1]), flush=True)
         torch.cuda.empty_cache()
     if args.out:
         with open(args.out, "w") as f:
