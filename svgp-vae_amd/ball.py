@@ -168,42 +168,68 @@ def truncated_normal_mlp_params(px=32, py=32, hidden=500, seed=0):
 
 
 class _BallMlpEngine:
-    """Shared part of the two moving-ball engines: flat parameters, the MLP encoder / decoder
+    """Shared part of the moving-ball engines and predictors: flat parameters, the MLP encoder / decoder
     (build_MLP_inference_graph / build_MLP_decoder_graph, VAE_utils.py:9-96) forward and reverse, the Bernoulli
-    reconstruction term, gradient clip + TF1 Adam (BALL_experiment.py:116-136)."""
+    reconstruction term, gradient clip + TF1 Adam (BALL_experiment.py:116-136), and the one training step.  What a step leaves
+    to the subclass: `fld` (the (T, B) field tensors of the two coordinates the head and pack / unpack kernels read and write:
+    mu, var_raw, var, z, zbar, ybar, s2bar), `clip_qs` (the clamp of the encoder head), _gp_forward / _gp_reverse, _assemble,
+    and _row_weights (the frames whose reconstruction term counts)."""
 
-    def _init_common(self, extra_shapes, init, *, batch, tmax, px, py, hidden, beta, lr, clip_grad, device, seed):
-        self.lib = _lib.load_library()
-        if not torch.cuda.is_available():
-            raise _lib.SvgpError(f"{type(self).__name__} needs a HIP device; there is no CPU execution path")
-        self.dev = torch.device(device)
-        self.B, self.T, self.px, self.py, self.P, self.H = batch, tmax, px, py, px * py, hidden
-        self.clip_grad = bool(clip_grad)
-        self.stream = torch.cuda.Stream(device=self.dev)
-        f64 = dict(dtype=_F64, device=self.dev)
-        self.shapes = dict(mlp_param_shapes(px, py, hidden))
-        self.shapes.update(extra_shapes)
-        n_tot = sum(int(np.prod(s)) for s in self.shapes.values())
-        self.theta, self.grad = torch.zeros(n_tot, **f64), torch.zeros(n_tot, **f64)
-        self.adam_m, self.adam_v = torch.zeros(n_tot, **f64), torch.zeros(n_tot, **f64)
-        self.params, self.grads, off = {}, {}, 0
+    def _views(self, flat):
+        views, off = {}, 0
         for k, s in self.shapes.items():
             n = int(np.prod(s))
-            self.params[k], self.grads[k] = self.theta[off:off + n].view(s), self.grad[off:off + n].view(s)
+            views[k] = flat[off:off + n].view(s)
             off += n
+        return views
+
+    def _init_params(self, shapes, values, kind, *, px, py, hidden, device):
+        """The flat parameter vector `theta` on the device and its named views `params`, filled from `values` (name -> array).
+        `kind` names the model family where a name is missing."""
+        name = type(self).__name__
+        self.shapes = dict(shapes)
+        missing = [k for k in self.shapes if k not in values]
+        if missing:
+            raise ValueError(f"{name}: parameters {missing} are missing ({kind} ball model has {list(self.shapes)})")
+        flat = []
+        for k, s in self.shapes.items():
+            v = values[k]
+            v = torch.as_tensor(np.asarray(v) if not torch.is_tensor(v) else v.detach().cpu(), dtype=_F64).reshape(-1)
+            if v.numel() != int(np.prod(s)):
+                raise ValueError(f"{name}: {k} has {v.numel()} elements, the model's shape {s} needs {int(np.prod(s))}")
+            flat.append(v)
+        self.lib = _lib.load_library()
+        if not torch.cuda.is_available():
+            raise _lib.SvgpError(f"{name} needs a HIP device; there is no CPU execution path")
+        self.dev = torch.device(device)
+        self.px, self.py, self.P, self.H = int(px), int(py), int(px) * int(py), int(hidden)
+        self.stream = torch.cuda.Stream(device=self.dev)
+        self.theta = torch.empty(sum(v.numel() for v in flat), dtype=_F64, device=self.dev)
+        self.stream.wait_stream(torch.cuda.current_stream(self.dev))     # the block may be a recycled one still in use there
+        with torch.cuda.stream(self.stream):
+            self.theta.copy_(torch.cat(flat))
+        self.params = self._views(self.theta)
+        self._gemm_scratch = torch.empty(0, dtype=_F64, device=self.dev)
+        self.stream.synchronize()
+
+    def _init_common(self, extra_shapes, init, kind, *, batch, tmax, px, py, hidden, beta, lr, clip_grad, device, seed):
+        """_init_params from truncated-normal MLP weights overlaid with `init`, then what only training needs: gradients, Adam
+        moments, the state vector and the output rows."""
+        shapes = dict(mlp_param_shapes(px, py, hidden))
+        shapes.update(extra_shapes)
         full = dict(truncated_normal_mlp_params(px, py, hidden, seed))
         full.update(init)
-        self.stream.wait_stream(torch.cuda.current_stream(self.dev))     # zero-fills ran on torch's stream
-        with torch.cuda.stream(self.stream):
-            for k, s in self.shapes.items():
-                v = full[k]
-                self.params[k].copy_(torch.as_tensor(np.asarray(v) if not torch.is_tensor(v) else v.detach().cpu(),
-                                                     dtype=_F64).reshape(s))
+        self._init_params(shapes, full, kind, px=px, py=py, hidden=hidden, device=device)
+        self.B, self.T = batch, tmax
+        self.clip_grad = bool(clip_grad)
+        f64 = dict(dtype=_F64, device=self.dev)
+        self.grad = torch.zeros_like(self.theta)
+        self.adam_m, self.adam_v = torch.zeros_like(self.theta), torch.zeros_like(self.theta)
+        self.grads = self._views(self.grad)
         self.state = torch.zeros(STATE_LEN, **f64)
         self.out = torch.zeros(len(OUT_ROWS), batch, **f64)
-        self._gemm_scratch = torch.empty(0, **f64)
         self.part = torch.zeros(int(self.lib.svgp_act_bwd_bias_scratch_elems(max(self.P, hidden))), **f64)
-        self.stream.wait_stream(torch.cuda.current_stream(self.dev))
+        self.stream.wait_stream(torch.cuda.current_stream(self.dev))     # zero-fills ran on torch's stream
         st = torch.zeros(STATE_LEN, dtype=_F64)
         st[STATE["LR"]], st[STATE["BETA"]], st[STATE["LAGRANGE"]] = lr, beta, 1.0
         with torch.cuda.stream(self.stream):
@@ -303,9 +329,60 @@ class _BallMlpEngine:
             call("svgp_adam_tf1_step", self.theta.numel(), self.theta.data_ptr(), self.grad.data_ptr(),
                  self.adam_m.data_ptr(), self.adam_v.data_ptr(), self.state.data_ptr(), 0.9, 0.999, 1e-8, s)
 
+    def _row_weights(self):
+        return None
 
-class BallStepEngine(_BallMlpEngine):
-    """Buffers + kernel schedule of one moving-ball training step (SVGPVAE_Hensman / SVGPVAE_Titsias)."""
+    # ------------------------------------------------------------------ one step
+    def step(self, vid_batch, epsilon=None, adam=True, backward=True):
+        """vid_batch (batch,tmax,px,py) float64 CUDA tensor; epsilon (batch,tmax,2) or None (on-device N(0,1)).
+        Forward, reverse, optional gradient clip, TF1 Adam when `adam`, per-video ELBO terms and their means."""
+        B, T, P = self.B, self.T, self.P
+        assert tuple(vid_batch.shape) == (B, T, self.px, self.py)
+        p, s, st, f = self.params, self.stream.cuda_stream, self.state.data_ptr(), self.fld
+        f64 = dict(dtype=_F64, device=self.dev)
+        R, clamp = B * T, int(self.clip_qs)
+        self.stream.wait_stream(torch.cuda.current_stream(self.dev))
+        with torch.cuda.stream(self.stream):
+            row_weights = self._row_weights()
+            X = vid_batch.to(self.dev, _F64).contiguous().view(R, P)
+            h1, h2 = self._encode(X)
+            call("svgp_ball_head_fwd", B, T, clamp, p["encB2"].data_ptr(), h2.data_ptr(), f["mu"][0].data_ptr(),
+                 f["var_raw"][0].data_ptr(), f["var"][0].data_ptr(), f["mu"][1].data_ptr(), f["var_raw"][1].data_ptr(),
+                 f["var"][1].data_ptr(), s)
+            eps_c = [None, None]
+            if epsilon is not None:
+                e = epsilon.to(self.dev, _F64)
+                eps_c = [e[:, :, c].t().contiguous() for c in range(2)]
+            self._gp_forward(eps_c)
+            # ---------------- decoder MLP + Bernoulli reconstruction term (SVGPVAE_model.py:693-700)
+            z = torch.empty(R, 2, **f64)
+            call("svgp_ball_pack_z", B, T, f["z"][0].data_ptr(), f["z"][1].data_ptr(), z.data_ptr(), s)
+            g1, pred, row_recon, dlog = self._decode_recon(z, X, backward, row_weights)
+            self.act = dict(pred=pred.view(B, T, self.px, self.py), z=z.view(B, T, 2))
+            if backward:
+                dz = self._decoder_backward(z, g1, dlog)
+                call("svgp_ball_unpack_zbar", B, T, dz.data_ptr(), f["zbar"][0].data_ptr(), f["zbar"][1].data_ptr(), s)
+                self._gp_reverse()
+                dh2 = torch.empty(R, 4, **f64)
+                call("svgp_ball_head_bwd", B, T, clamp, f["var_raw"][0].data_ptr(), f["ybar"][0].data_ptr(),
+                     f["s2bar"][0].data_ptr(), f["var_raw"][1].data_ptr(), f["ybar"][1].data_ptr(),
+                     f["s2bar"][1].data_ptr(), dh2.data_ptr(), s)
+                self._encoder_backward(X, h1, dh2)
+                self._clip_and_adam(adam)
+            self._assemble(row_recon)
+            call("svgp_ball_finalize", B, int(bool(adam and backward)), 1, self.out.data_ptr(), st, s)
+            self._keep = eps_c
+        return self
+
+    train_step = step
+
+
+class _SparseEngineBase(_BallMlpEngine):
+    """SVGPVAE_Hensman / SVGPVAE_Titsias: the two sparse GPs of build_SVGPVAE_elbo_graph, one workspace per latent coordinate
+    (rows = frames, channels = videos).  A subclass makes the cfg struct (_make_cfg), names its layout and assemble entries and
+    issues the GP calls of one coordinate (_gp_fwd_c / _gp_bwd_c)."""
+
+    _FIELDS = dict(mu="qnet_mu", var_raw="qnet_var_raw", var="qnet_var", z="z", zbar="zbar", ybar="ybar", s2bar="s2bar")
 
     def __init__(self, svgp_x, svgp_y, *, batch=35, tmax=30, px=32, py=32, hidden=500, clip_qs=False, beta=1.0,
                  lr=1e-3, clip_grad=False, device="cuda:0", params=None, seed=0):
@@ -316,105 +393,54 @@ class BallStepEngine(_BallMlpEngine):
         self.m, self.titsias = svgp_x.num_inducing_points, svgp_x.titsias
         self.svgp = (svgp_x, svgp_y)
         self.clip_qs = bool(clip_qs)
-        # ---- one GP workspace per latent coordinate: rows = frames, channels = videos (validated before any allocation)
-        self.cfg = MnistCfg(b=tmax, b_global=tmax, m=self.m, L=batch, M=1, n_obj=0, normalize_obj=0, clip_qs=0, geco=0,
-                            train_ip=1, train_gp=1, train_ov=0, b_cap=tmax, clip_pv=2, n_pix=px * py,
-                            titsias=int(self.titsias), kl_form=1, single_stat_block=0, N_train=float(tmax),
-                            jitter=svgp_x.jitter, kappa_squared=0.0, alpha=0.0, rep_weight=1.0)
+        self.cfg = self._make_cfg(batch, tmax, px * py, svgp_x.jitter)
         _lib.load_library()
         self.wl = WsLayout()
-        call("svgp_mnist_ws_layout_get", C.byref(self.cfg), C.byref(self.wl))
+        call(self._LAYOUT, C.byref(self.cfg), C.byref(self.wl))         # validates the shape before any allocation
+        if not torch.cuda.is_available():
+            raise _lib.SvgpError(f"{type(self).__name__} needs a HIP device; there is no CPU execution path")
+        self._check_memory(batch, tmax, px * py, hidden, torch.device(device))
         init = dict(params or {})
         for c, sv in zip("xy", self.svgp):
             init.setdefault(f"ip_{c}", sv.inducing_index_points)
             init.setdefault(f"l_{c}", sv.l_GP)
-        self._init_common(dict(ip_x=(self.m,), l_x=(1,), ip_y=(self.m,), l_y=(1,)), init, batch=batch, tmax=tmax, px=px,
-                          py=py, hidden=hidden, beta=beta, lr=lr, clip_grad=clip_grad, device=device, seed=seed)
+        self._init_common(dict(ip_x=(self.m,), l_x=(1,), ip_y=(self.m,), l_y=(1,)), init, "a sparse-GP", batch=batch,
+                          tmax=tmax, px=px, py=py, hidden=hidden, beta=beta, lr=lr, clip_grad=clip_grad, device=device, seed=seed)
         for c, sv in zip("xy", self.svgp):
             sv.inducing_index_points, sv.l_GP = self.params[f"ip_{c}"], self.params[f"l_{c}"]
         f64 = dict(dtype=_F64, device=self.dev)
         self.ws = [torch.zeros(self.wl.total, **f64) for _ in range(2)]
+        self.fld = {k: [self._v(c, n, (tmax, batch)) for c in range(2)] for k, n in self._FIELDS.items()}
         self.times = torch.arange(1, tmax + 1, **f64)                   # SVGPVAE_model.py:663
         self.stream.wait_stream(torch.cuda.current_stream(self.dev))
         self.stream.synchronize()
+
+    def _check_memory(self, batch, tmax, n_pix, hidden, dev):
+        pass
 
     def _v(self, c, name, shape):
         off = getattr(self.wl, name)
         return self.ws[c][off:off + int(np.prod(shape))].view(shape)
 
-    # ------------------------------------------------------------------ one step
-    def step(self, vid_batch, epsilon=None, adam=True, backward=True):
-        """vid_batch (batch,tmax,px,py) float64 CUDA tensor; epsilon (batch,tmax,2) or None (on-device N(0,1)).
-        Forward, reverse, optional gradient clip, TF1 Adam when `adam`, per-video ELBO terms and their means."""
-        B, T, P, m = self.B, self.T, self.P, self.m
-        assert tuple(vid_batch.shape) == (B, T, self.px, self.py)
-        p, g, s = self.params, self.grads, self.stream.cuda_stream
-        cp, st = C.byref(self.cfg), self.state.data_ptr()
-        f64 = dict(dtype=_F64, device=self.dev)
-        R = B * T
-        self.stream.wait_stream(torch.cuda.current_stream(self.dev))
-        with torch.cuda.stream(self.stream):
-            X = vid_batch.to(self.dev, _F64).contiguous().view(R, P)
-            h1, h2 = self._encode(X)
-            fld = lambda n: [self._v(c, n, (T, B)) for c in range(2)]
-            mu, var_raw, var = fld("qnet_mu"), fld("qnet_var_raw"), fld("qnet_var")
-            call("svgp_ball_head_fwd", B, T, int(self.clip_qs), p["encB2"].data_ptr(), h2.data_ptr(), mu[0].data_ptr(),
-                 var_raw[0].data_ptr(), var[0].data_ptr(), mu[1].data_ptr(), var_raw[1].data_ptr(), var[1].data_ptr(), s)
-            # ---------------- the two sparse GPs (SVGPVAE_model.py:673-681)
-            eps_c = [None, None]
-            if epsilon is not None:
-                e = epsilon.to(self.dev, _F64)
-                eps_c = [e[:, :, c].t().contiguous() for c in range(2)]
-            for c, cn in enumerate("xy"):
-                ws = self.ws[c].data_ptr()
-                call("svgp_se1d_kernel_matrix_fwd", T, m, self.times.data_ptr(), p[f"ip_{cn}"].data_ptr(),
-                     p[f"l_{cn}"].data_ptr(), self._v(c, "K", (1,)).data_ptr(), self._v(c, "Kn", (1,)).data_ptr(),
-                     self._v(c, "knn", (1,)).data_ptr(), s)
-                call("svgp_gp_stats_fwd", cp, ws, s)
-                if self.titsias:
-                    call("svgp_gp_titsias_stats", cp, ws, s)
-                call("svgp_gp_factor_fwd", cp, ws, s)
-                call("svgp_gp_posterior_fwd", cp, None if eps_c[c] is None else eps_c[c].data_ptr(), ws, st, s)
-                if self.titsias:
-                    call("svgp_gp_titsias_fwd", cp, ws, st, s)
-                if c == 0:
-                    call("svgp_state_add", st, STATE["RNG_CTR"], 1.0, s)      # fresh samples for the y coordinate
-            # ---------------- decoder MLP + Bernoulli reconstruction term (:693-700)
-            z = torch.empty(R, 2, **f64)
-            call("svgp_ball_pack_z", B, T, self._v(0, "z", (1,)).data_ptr(), self._v(1, "z", (1,)).data_ptr(),
-                 z.data_ptr(), s)
-            g1, pred, row_recon, dlog = self._decode_recon(z, X, backward)
-            self.act = dict(pred=pred.view(B, T, self.px, self.py), z=z.view(B, T, 2))
-            if backward:
-                dz = self._decoder_backward(z, g1, dlog)
-                call("svgp_ball_unpack_zbar", B, T, dz.data_ptr(), self._v(0, "zbar", (1,)).data_ptr(),
-                     self._v(1, "zbar", (1,)).data_ptr(), s)
-                for c, cn in enumerate("xy"):
-                    ws = self.ws[c].data_ptr()
-                    call("svgp_gp_stats_bwd", cp, ws, st, s)
-                    call("svgp_gp_factor_bwd", cp, ws, st, s)
-                    call("svgp_gp_posterior_bwd", cp, ws, st, s)
-                    if self.titsias:
-                        call("svgp_gp_titsias_bwd", cp, ws, st, s)
-                    call("svgp_se1d_kernel_matrix_bwd", T, m, self.times.data_ptr(), p[f"ip_{cn}"].data_ptr(),
-                         p[f"l_{cn}"].data_ptr(), self._v(c, "Kbar", (1,)).data_ptr(), self._v(c, "Knbar", (1,)).data_ptr(),
-                         g[f"ip_{cn}"].data_ptr(), g[f"l_{cn}"].data_ptr(), s)
-                    if self.svgp[c].fixed_inducing_points:
-                        g[f"ip_{cn}"].zero_()
-                    if self.svgp[c].fixed_gp_params:
-                        g[f"l_{cn}"].zero_()
-                dh2 = torch.empty(R, 4, **f64)
-                yb, sb = fld("ybar"), fld("s2bar")
-                call("svgp_ball_head_bwd", B, T, int(self.clip_qs), var_raw[0].data_ptr(), yb[0].data_ptr(),
-                     sb[0].data_ptr(), var_raw[1].data_ptr(), yb[1].data_ptr(), sb[1].data_ptr(), dh2.data_ptr(), s)
-                self._encoder_backward(X, h1, dh2)
-                self._clip_and_adam(adam)
-            call("svgp_ball_elbo_assemble", cp, self.ws[0].data_ptr(), self.ws[1].data_ptr(), row_recon.data_ptr(), st,
-                 self.out.data_ptr(), s)
-            call("svgp_ball_finalize", B, int(bool(adam and backward)), 1, self.out.data_ptr(), st, s)
-        return self
+    def _gp_forward(self, eps_c):
+        """The two sparse GPs (SVGPVAE_model.py:673-681)."""
+        for c, cn in enumerate("xy"):
+            self._gp_fwd_c(c, cn, None if eps_c[c] is None else eps_c[c].data_ptr())
+            if c == 0:                                                  # fresh samples for the y coordinate
+                call("svgp_state_add", self.state.data_ptr(), STATE["RNG_CTR"], 1.0, self.stream.cuda_stream)
 
-    train_step = step
+    def _gp_reverse(self):
+        g = self.grads
+        for c, cn in enumerate("xy"):
+            self._gp_bwd_c(c, cn)
+            if self.svgp[c].fixed_inducing_points:
+                g[f"ip_{cn}"].zero_()
+            if self.svgp[c].fixed_gp_params:
+                g[f"l_{cn}"].zero_()
+
+    def _assemble(self, row_recon):
+        call(self._ASSEMBLE, C.byref(self.cfg), self.ws[0].data_ptr(), self.ws[1].data_ptr(), row_recon.data_ptr(),
+             self.state.data_ptr(), self.out.data_ptr(), self.stream.cuda_stream)
 
     def outputs(self):
         """build_SVGPVAE_elbo_graph's return tuple for the last step (the trailing globals() slot holds the engine)."""
@@ -437,108 +463,76 @@ class BallStepEngine(_BallMlpEngine):
                 o["inside_elbo_kl"], p["ip_x"].clone(), p["ip_y"].clone(), cov[0], cov[1], self)
 
 
-class BallLargeStepEngine(_BallMlpEngine):
+class BallStepEngine(_SparseEngineBase):
+    """Buffers + kernel schedule of one moving-ball training step (SVGPVAE_Hensman / SVGPVAE_Titsias) on the LDS-resident GP
+    stage kernels: a chain of stage calls per latent coordinate."""
+
+    _LAYOUT, _ASSEMBLE = "svgp_mnist_ws_layout_get", "svgp_ball_elbo_assemble"
+
+    def _make_cfg(self, batch, tmax, n_pix, jitter):
+        return MnistCfg(b=tmax, b_global=tmax, m=self.m, L=batch, M=1, n_obj=0, normalize_obj=0, clip_qs=0, geco=0,
+                        train_ip=1, train_gp=1, train_ov=0, b_cap=tmax, clip_pv=2, n_pix=n_pix,
+                        titsias=int(self.titsias), kl_form=1, single_stat_block=0, N_train=float(tmax),
+                        jitter=jitter, kappa_squared=0.0, alpha=0.0, rep_weight=1.0)
+
+    def _gp_fwd_c(self, c, cn, eps):
+        p, s, cp, ws, st = self.params, self.stream.cuda_stream, C.byref(self.cfg), self.ws[c].data_ptr(), self.state.data_ptr()
+        call("svgp_se1d_kernel_matrix_fwd", self.T, self.m, self.times.data_ptr(), p[f"ip_{cn}"].data_ptr(),
+             p[f"l_{cn}"].data_ptr(), self._v(c, "K", (1,)).data_ptr(), self._v(c, "Kn", (1,)).data_ptr(),
+             self._v(c, "knn", (1,)).data_ptr(), s)
+        call("svgp_gp_stats_fwd", cp, ws, s)
+        if self.titsias:
+            call("svgp_gp_titsias_stats", cp, ws, s)
+        call("svgp_gp_factor_fwd", cp, ws, s)
+        call("svgp_gp_posterior_fwd", cp, eps, ws, st, s)
+        if self.titsias:
+            call("svgp_gp_titsias_fwd", cp, ws, st, s)
+
+    def _gp_bwd_c(self, c, cn):
+        p, g, s = self.params, self.grads, self.stream.cuda_stream
+        cp, ws, st = C.byref(self.cfg), self.ws[c].data_ptr(), self.state.data_ptr()
+        call("svgp_gp_stats_bwd", cp, ws, st, s)
+        call("svgp_gp_factor_bwd", cp, ws, st, s)
+        call("svgp_gp_posterior_bwd", cp, ws, st, s)
+        if self.titsias:
+            call("svgp_gp_titsias_bwd", cp, ws, st, s)
+        call("svgp_se1d_kernel_matrix_bwd", self.T, self.m, self.times.data_ptr(), p[f"ip_{cn}"].data_ptr(),
+             p[f"l_{cn}"].data_ptr(), self._v(c, "Kbar", (1,)).data_ptr(), self._v(c, "Knbar", (1,)).data_ptr(),
+             g[f"ip_{cn}"].data_ptr(), g[f"l_{cn}"].data_ptr(), s)
+
+
+class BallLargeStepEngine(_SparseEngineBase):
     """The same step -- constructor arguments, step() and the outputs() tuple of BallStepEngine -- beyond the LDS-resident GP
     stages: 1 <= m <= 2048 inducing points, up to _lib.BALL_LARGE_MAX_VIDEOS videos per batch (csrc/ball_large.hip: the large-m
     stages of gp_large.hip with the moving-ball KL form, all videos channels of one workspace per latent coordinate).  One
     library call per coordinate forward and one reverse instead of a chain of stage calls.  Everything is sized here, once; a
     configuration whose (batch, m, m) blocks do not fit the device is refused here with the figures."""
 
-    def __init__(self, svgp_x, svgp_y, *, batch=35, tmax=30, px=32, py=32, hidden=500, clip_qs=False, beta=1.0,
-                 lr=1e-3, clip_grad=False, device="cuda:0", params=None, seed=0):
-        if svgp_x.titsias != svgp_y.titsias or svgp_x.num_inducing_points != svgp_y.num_inducing_points:
-            raise ValueError("svgp_x and svgp_y must agree on the ELBO branch and on the number of inducing points")
-        if svgp_x.jitter != svgp_y.jitter:
-            raise ValueError("svgp_x and svgp_y must use the same jitter")
-        self.m, self.titsias = svgp_x.num_inducing_points, svgp_x.titsias
-        self.svgp = (svgp_x, svgp_y)
-        self.clip_qs = bool(clip_qs)
-        self.cfg = _lib.BallLargeCfg(T=tmax, B=batch, m=self.m, titsias=int(self.titsias), kl_form=1, clip_pv=2,
-                                     jitter=svgp_x.jitter)
-        _lib.load_library()
-        self.wl = WsLayout()
-        call("svgp_ball_large_ws_layout_get", C.byref(self.cfg), C.byref(self.wl))     # validates before any allocation
-        if not torch.cuda.is_available():
-            raise _lib.SvgpError(f"{type(self).__name__} needs a HIP device; there is no CPU execution path")
+    _LAYOUT, _ASSEMBLE = "svgp_ball_large_ws_layout_get", "svgp_ball_large_elbo_assemble"
+
+    def _make_cfg(self, batch, tmax, n_pix, jitter):
+        return _lib.BallLargeCfg(T=tmax, B=batch, m=self.m, titsias=int(self.titsias), kl_form=1, clip_pv=2, jitter=jitter)
+
+    def _check_memory(self, B, T, n_pix, hidden, dev):
         # the two workspaces + what one step allocates on top (encoder / decoder activations and their gradients)
-        B, T, m, dev = batch, tmax, self.m, torch.device(device)
-        step = B * T * (4 * px * py + 4 * hidden + 16)
+        m = self.m
+        step = B * T * (4 * n_pix + 4 * hidden + 16)
         need, (free, _) = 8 * (2 * self.wl.total + step), torch.cuda.mem_get_info(dev)
         if need > free:
             raise _lib.SvgpError(f"batch={B} tmax={T} m={m}: the sparse GP step needs {need / 2 ** 30:.1f} GiB "
                                  f"(2 workspaces of {8 * self.wl.total / 2 ** 30:.1f} GiB, about 16 (batch, m, m) blocks of "
                                  f"{8 * B * m * m / 2 ** 30:.2f} GiB each), {free / 2 ** 30:.1f} GiB are free on {dev}")
-        init = dict(params or {})
-        for c, sv in zip("xy", self.svgp):
-            init.setdefault(f"ip_{c}", sv.inducing_index_points)
-            init.setdefault(f"l_{c}", sv.l_GP)
-        self._init_common(dict(ip_x=(m,), l_x=(1,), ip_y=(m,), l_y=(1,)), init, batch=batch, tmax=tmax, px=px,
-                          py=py, hidden=hidden, beta=beta, lr=lr, clip_grad=clip_grad, device=device, seed=seed)
-        for c, sv in zip("xy", self.svgp):
-            sv.inducing_index_points, sv.l_GP = self.params[f"ip_{c}"], self.params[f"l_{c}"]
-        f64 = dict(dtype=_F64, device=self.dev)
-        self.ws = [torch.zeros(self.wl.total, **f64) for _ in range(2)]
-        self.times = torch.arange(1, tmax + 1, **f64)                   # SVGPVAE_model.py:663
-        self.stream.wait_stream(torch.cuda.current_stream(self.dev))
-        self.stream.synchronize()
 
-    _v = BallStepEngine._v
-    outputs = BallStepEngine.outputs
+    def _gp_fwd_c(self, c, cn, eps):
+        p = self.params
+        call("svgp_ball_large_gp_fwd", C.byref(self.cfg), self.times.data_ptr(), p[f"ip_{cn}"].data_ptr(),
+             p[f"l_{cn}"].data_ptr(), eps, self.ws[c].data_ptr(), self.state.data_ptr(), self.stream.cuda_stream)
 
-    def step(self, vid_batch, epsilon=None, adam=True, backward=True):
-        """As BallStepEngine.step."""
-        B, T, P = self.B, self.T, self.P
-        assert tuple(vid_batch.shape) == (B, T, self.px, self.py)
-        p, g, s = self.params, self.grads, self.stream.cuda_stream
-        cp, st = C.byref(self.cfg), self.state.data_ptr()
-        f64 = dict(dtype=_F64, device=self.dev)
-        R = B * T
-        self.stream.wait_stream(torch.cuda.current_stream(self.dev))
-        with torch.cuda.stream(self.stream):
-            X = vid_batch.to(self.dev, _F64).contiguous().view(R, P)
-            h1, h2 = self._encode(X)
-            fld = lambda n: [self._v(c, n, (T, B)) for c in range(2)]
-            mu, var_raw, var = fld("qnet_mu"), fld("qnet_var_raw"), fld("qnet_var")
-            call("svgp_ball_head_fwd", B, T, int(self.clip_qs), p["encB2"].data_ptr(), h2.data_ptr(), mu[0].data_ptr(),
-                 var_raw[0].data_ptr(), var[0].data_ptr(), mu[1].data_ptr(), var_raw[1].data_ptr(), var[1].data_ptr(), s)
-            eps_c = [None, None]
-            if epsilon is not None:
-                e = epsilon.to(self.dev, _F64)
-                eps_c = [e[:, :, c].t().contiguous() for c in range(2)]
-            for c, cn in enumerate("xy"):
-                call("svgp_ball_large_gp_fwd", cp, self.times.data_ptr(), p[f"ip_{cn}"].data_ptr(), p[f"l_{cn}"].data_ptr(),
-                     None if eps_c[c] is None else eps_c[c].data_ptr(), self.ws[c].data_ptr(), st, s)
-                if c == 0:
-                    call("svgp_state_add", st, STATE["RNG_CTR"], 1.0, s)      # fresh samples for the y coordinate
-            z = torch.empty(R, 2, **f64)
-            call("svgp_ball_pack_z", B, T, self._v(0, "z", (1,)).data_ptr(), self._v(1, "z", (1,)).data_ptr(),
-                 z.data_ptr(), s)
-            g1, pred, row_recon, dlog = self._decode_recon(z, X, backward)
-            self.act = dict(pred=pred.view(B, T, self.px, self.py), z=z.view(B, T, 2))
-            if backward:
-                dz = self._decoder_backward(z, g1, dlog)
-                call("svgp_ball_unpack_zbar", B, T, dz.data_ptr(), self._v(0, "zbar", (1,)).data_ptr(),
-                     self._v(1, "zbar", (1,)).data_ptr(), s)
-                for c, cn in enumerate("xy"):
-                    call("svgp_ball_large_gp_bwd", cp, self.times.data_ptr(), p[f"ip_{cn}"].data_ptr(),
-                         p[f"l_{cn}"].data_ptr(), self.ws[c].data_ptr(), st, g[f"ip_{cn}"].data_ptr(),
-                         g[f"l_{cn}"].data_ptr(), s)
-                    if self.svgp[c].fixed_inducing_points:
-                        g[f"ip_{cn}"].zero_()
-                    if self.svgp[c].fixed_gp_params:
-                        g[f"l_{cn}"].zero_()
-                dh2 = torch.empty(R, 4, **f64)
-                yb, sb = fld("ybar"), fld("s2bar")
-                call("svgp_ball_head_bwd", B, T, int(self.clip_qs), var_raw[0].data_ptr(), yb[0].data_ptr(),
-                     sb[0].data_ptr(), var_raw[1].data_ptr(), yb[1].data_ptr(), sb[1].data_ptr(), dh2.data_ptr(), s)
-                self._encoder_backward(X, h1, dh2)
-                self._clip_and_adam(adam)
-            call("svgp_ball_large_elbo_assemble", cp, self.ws[0].data_ptr(), self.ws[1].data_ptr(), row_recon.data_ptr(),
-                 st, self.out.data_ptr(), s)
-            call("svgp_ball_finalize", B, int(bool(adam and backward)), 1, self.out.data_ptr(), st, s)
-        return self
-
-    train_step = step
+    def _gp_bwd_c(self, c, cn):
+        p, g = self.params, self.grads
+        call("svgp_ball_large_gp_bwd", C.byref(self.cfg), self.times.data_ptr(), p[f"ip_{cn}"].data_ptr(),
+             p[f"l_{cn}"].data_ptr(), self.ws[c].data_ptr(), self.state.data_ptr(), g[f"ip_{cn}"].data_ptr(),
+             g[f"l_{cn}"].data_ptr(), self.stream.cuda_stream)
 
 
 def sparse_engine_class(m, batch):
@@ -560,8 +554,11 @@ def __getattr__(name):
 
 class _PearceEngineBase(_BallMlpEngine):
     """BALL_experiment.py --elbo GPVAE_Pearce | VAE | NP: exact per-video GP regression on the recognition network's
-    outputs (build_pearce_elbo_graphs, GPVAE_Pearce_model.py:89-236).  The step is shared; a subclass says how long a
-    video it takes (_check_tmax), owns the GP matrices (_alloc_gp) and issues the GP-regression calls (_gp_fwd / _gp_bwd)."""
+    outputs (build_pearce_elbo_graphs, GPVAE_Pearce_model.py:89-236); the encoder head is not clamped.  A subclass says how
+    long a video it takes (_check_tmax), owns the GP matrices (_alloc_gp) and issues the GP-regression calls (_gp_fwd / _gp_bwd)."""
+
+    clip_qs = False
+    _FIELDS = dict(mu="y", var_raw="var_raw", var="s2", z="z", zbar="zbar", ybar="ybar", s2bar="s2bar")
 
     def __init__(self, type_elbo="GPVAE_Pearce", lt=5.0, context_ratio=0.5, GP_joint=False, GP_init=2.0, *, batch=35,
                  tmax=30, px=32, py=32, hidden=500, beta=1.0, lr=1e-3, clip_grad=False, device="cuda:0", params=None,
@@ -574,13 +571,14 @@ class _PearceEngineBase(_BallMlpEngine):
         init = dict(params or {})
         init.setdefault("l_x", torch.tensor([l0], dtype=_F64))
         init.setdefault("l_y", torch.tensor([l0], dtype=_F64))
-        self._init_common(dict(l_x=(1,), l_y=(1,)), init, batch=batch, tmax=tmax, px=px, py=py, hidden=hidden, beta=beta,
-                          lr=lr, clip_grad=clip_grad, device=device, seed=seed)
+        self._init_common(dict(l_x=(1,), l_y=(1,)), init, "an exact-GP", batch=batch, tmax=tmax, px=px, py=py, hidden=hidden,
+                          beta=beta, lr=lr, clip_grad=clip_grad, device=device, seed=seed)
         f64 = dict(dtype=_F64, device=self.dev)
         B, T = batch, tmax
         self.times = torch.arange(0, tmax, **f64)                       # GPVAE_Pearce_model.py:119-120 (0-based)
         self.buf = {k: torch.zeros(2, T, B, **f64) for k in ("y", "var_raw", "s2", "p_m", "p_v", "eps", "z", "zbar", "ybar",
                                                             "s2bar", "row_ce")}
+        self.fld = {k: [self.buf[n][0], self.buf[n][1]] for k, n in self._FIELDS.items()}
         self._alloc_gp()                                                # Ai, c_Ai (2,B,T,T) and what the GP calls need beyond
         self.alpha = torch.zeros(2, B, T, **f64)
         self.lh, self.ce, self.dl_part = torch.zeros(2, B, **f64), torch.zeros(2, B, **f64), torch.zeros(2, B, **f64)
@@ -617,67 +615,48 @@ class _PearceEngineBase(_BallMlpEngine):
 
     def step(self, vid_batch, epsilon=None, adam=True, backward=True, ran_ind=None, con_tf=None):
         """One step.  NP: `ran_ind` (batch,tmax) permutations and `con_tf` are drawn when not given."""
-        B, T, P = self.B, self.T, self.P
+        B, T = self.B, self.T
         assert tuple(vid_batch.shape) == (B, T, self.px, self.py)
-        p, g, s, b = self.params, self.grads, self.stream.cuda_stream, self.buf
-        st = self.state.data_ptr()
-        f64 = dict(dtype=_F64, device=self.dev)
-        R = B * T
-        is_np = self.type_elbo == "NP"
-        idx = tmask = None
-        if is_np:
+        self._split = None                                              # NP, on the host: (context indices, target mask, con_tf)
+        if self.type_elbo == "NP":
             if ran_ind is None:
                 ran_ind, con_tf = self.draw_context_split()
             ran_ind = np.asarray(ran_ind)
             idx = torch.as_tensor(ran_ind[:, :con_tf].astype(np.int32)).contiguous()
             tm = np.zeros((B, T))
             np.put_along_axis(tm, ran_ind[:, con_tf:], 1.0, axis=1)
-            tmask = torch.as_tensor(tm, dtype=_F64)
-        self.stream.wait_stream(torch.cuda.current_stream(self.dev))
-        with torch.cuda.stream(self.stream):
-            if is_np:
-                idx, tmask = idx.to(self.dev), tmask.to(self.dev)
-            X = vid_batch.to(self.dev, _F64).contiguous().view(R, P)
-            h1, h2 = self._encode(X)
-            call("svgp_ball_head_fwd", B, T, 0, p["encB2"].data_ptr(), h2.data_ptr(), b["y"][0].data_ptr(),
-                 b["var_raw"][0].data_ptr(), b["s2"][0].data_ptr(), b["y"][1].data_ptr(), b["var_raw"][1].data_ptr(),
-                 b["s2"][1].data_ptr(), s)
-            ex = ey = None
-            if epsilon is not None:
-                e = epsilon.to(self.dev, _F64)
-                ex, ey = e[:, :, 0].t().contiguous(), e[:, :, 1].t().contiguous()
-            full = self._bufs(tmask=tmask)
-            self._gp_fwd(full, ex, ey)
-            ctx = None
-            if is_np:
-                ctx = self._bufs(n=con_tf, idx=idx, context=True)
-                self._gp_fwd(ctx, None, None)
-            z = torch.empty(R, 2, **f64)
-            call("svgp_ball_pack_z", B, T, b["z"][0].data_ptr(), b["z"][1].data_ptr(), z.data_ptr(), s)
-            g1, pred, row_recon, dlog = self._decode_recon(z, X, backward, None if tmask is None else tmask.view(-1))
-            self.act = dict(pred=pred.view(B, T, self.px, self.py), z=z.view(B, T, 2))
-            if backward:
-                dz = self._decoder_backward(z, g1, dlog)
-                call("svgp_ball_unpack_zbar", B, T, dz.data_ptr(), b["zbar"][0].data_ptr(), b["zbar"][1].data_ptr(), s)
-                self._gp_bwd(full, 1.0, 0, g["l_x"], g["l_y"])
-                if is_np:
-                    self._gp_bwd(ctx, -1.0, 1, self.c_dl[0:], self.c_dl[1:])
-                if not self.GP_joint:
-                    g["l_x"].zero_(); g["l_y"].zero_()
-                dh2 = torch.empty(R, 4, **f64)
-                call("svgp_ball_head_bwd", B, T, 0, b["var_raw"][0].data_ptr(), b["ybar"][0].data_ptr(),
-                     b["s2bar"][0].data_ptr(), b["var_raw"][1].data_ptr(), b["ybar"][1].data_ptr(),
-                     b["s2bar"][1].data_ptr(), dh2.data_ptr(), s)
-                self._encoder_backward(X, h1, dh2)
-                self._clip_and_adam(adam)
-            call("svgp_pearce_elbo_assemble", B, T, self.lh.data_ptr(), self.ce.data_ptr(),
-                 self.c_lh.data_ptr() if is_np else None, row_recon.data_ptr(), b["row_ce"].data_ptr(),
-                 None if tmask is None else tmask.data_ptr(), st, self.out.data_ptr(), s)
-            call("svgp_ball_finalize", B, int(bool(adam and backward)), 1, self.out.data_ptr(), st, s)
-            self._keep = (idx, tmask, ex, ey)
-        return self
+            self._split = (idx, torch.as_tensor(tm, dtype=_F64), con_tf)
+        return super().step(vid_batch, epsilon, adam, backward)
 
     train_step = step
+
+    def _row_weights(self):
+        self._idx = self._tmask = None
+        if self._split is None:
+            return None
+        self._idx, self._tmask = self._split[0].to(self.dev), self._split[1].to(self.dev)
+        return self._tmask.view(-1)
+
+    def _gp_forward(self, eps_c):
+        self._q = [self._bufs(tmask=self._tmask)]
+        self._gp_fwd(self._q[0], *eps_c)
+        if self._split is not None:
+            self._q.append(self._bufs(n=self._split[2], idx=self._idx, context=True))
+            self._gp_fwd(self._q[1], None, None)
+
+    def _gp_reverse(self):
+        g = self.grads
+        self._gp_bwd(self._q[0], 1.0, 0, g["l_x"], g["l_y"])
+        if self._split is not None:
+            self._gp_bwd(self._q[1], -1.0, 1, self.c_dl[0:], self.c_dl[1:])
+        if not self.GP_joint:
+            g["l_x"].zero_(); g["l_y"].zero_()
+
+    def _assemble(self, row_recon):
+        call("svgp_pearce_elbo_assemble", self.B, self.T, self.lh.data_ptr(), self.ce.data_ptr(),
+             None if self._split is None else self.c_lh.data_ptr(), row_recon.data_ptr(), self.buf["row_ce"].data_ptr(),
+             None if self._tmask is None else self._tmask.data_ptr(), self.state.data_ptr(), self.out.data_ptr(),
+             self.stream.cuda_stream)
 
     def outputs(self):
         """build_pearce_elbo_graphs' return tuple (elbo, elbo_recon, elbo_prior_kl, full_p_mu, full_p_var, qnet_mu, qnet_var,

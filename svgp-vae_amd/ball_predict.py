@@ -91,37 +91,54 @@ def _split_theta(path, ck, got, want, what):
 
 
 class _Predictor(_BallMlpEngine):
-    """What the two predictors share: the flat parameter vector on the device and `predict` around the GP stage.  A subclass sets
-    `shapes` and `clip_qs` (the clamp of the encoder head) before _setup and provides _gp_stage."""
+    """What the two predictors share: the flat parameter vector on the device (_BallMlpEngine._init_params), loading a checkpoint,
+    `predict` around the GP stage, and the GP call itself.  A subclass sets `clip_qs` (the clamp of the encoder head), names its
+    family (_KIND, _SPARSE, and _REFUSAL for a checkpoint of the other one), its meta keys and shapes (_META_KEYS, _SHAPE_KEYS,
+    _shapes) and its two GP entries (_ENTRIES), and provides _gp_stage."""
 
-    def _setup(self, params, kind, *, tmax, hidden, px, py, device):
-        name = type(self).__name__
-        missing = [k for k in self.shapes if k not in params]
-        if missing:
-            raise ValueError(f"{name}: parameters {missing} are missing ({kind} ball model has {list(self.shapes)})")
-        flat = []
-        for k, s in self.shapes.items():
-            v = params[k]
-            v = torch.as_tensor(np.asarray(v) if not torch.is_tensor(v) else v.detach().cpu(), dtype=_F64).reshape(-1)
-            if v.numel() != int(np.prod(s)):
-                raise ValueError(f"{name}: {k} has {v.numel()} elements, the model's shape {s} needs {int(np.prod(s))}")
-            flat.append(v)
-        self.lib = _lib.load_library()
-        if not torch.cuda.is_available():
-            raise _lib.SvgpError(f"{name} needs a HIP device; there is no CPU execution path")
-        self.dev = torch.device(device)
-        self.tmax, self.px, self.py, self.P, self.H = int(tmax), int(px), int(py), int(px) * int(py), int(hidden)
-        self.stream = torch.cuda.Stream(device=self.dev)
-        with torch.cuda.stream(self.stream):
-            self.theta = torch.cat(flat).to(self.dev)
-        self.params, off = {}, 0
-        for k, s in self.shapes.items():
-            n = int(np.prod(s))
-            self.params[k] = self.theta[off:off + n].view(s)
-            off += n
-        self._gemm_scratch = torch.empty(0, dtype=_F64, device=self.dev)
+    def _setup(self, params, shapes, *, tmax, hidden, px, py, device):
+        self._init_params(shapes, params, self._KIND, px=px, py=py, hidden=hidden, device=device)
+        self.tmax = int(tmax)
         self._work = torch.empty(0, dtype=_F64, device=self.dev)
-        self.stream.synchronize()
+
+    # ------------------------------------------------------------------ checkpoints
+    @classmethod
+    def load(cls, path, **overrides):
+        """A predictor from the `model.pt` of `BALL_experiment --save_model`.  The model's shape comes from the checkpoint's "meta"
+        dict (of which the class reads its _META_KEYS only); keywords override it, and stand in for it where an older checkpoint
+        has none."""
+        ck, shapes = _read_checkpoint(path)
+        meta = dict(ck.get("meta") or {})
+        device = overrides.pop("device", "cuda:0")
+        meta.update(overrides)
+        # the family is told by the inducing points, and by the meta dict's elbo where it has one
+        if ("ip_x" in shapes) != cls._SPARSE or ("elbo" in meta and (meta["elbo"] not in _PEARCE_ELBOS) != cls._SPARSE):
+            raise ValueError(f"{path}: {cls._REFUSAL}")
+        missing = [k for k in cls._META_KEYS if k not in meta]
+        if missing:
+            raise ValueError(f"{path}: the checkpoint has no meta entry for {', '.join(missing)}; pass "
+                             f"{', '.join(k + '=...' for k in missing)} to {cls.__name__}.load")
+        want = cls._shapes(**{k: int(meta[k]) for k in cls._SHAPE_KEYS})
+        params = _split_theta(path, ck, shapes, want, " ".join(f"{k}={meta[k]}" for k in cls._SHAPE_KEYS))
+        return cls(params, device=device, **{k: meta[k] for k in cls._META_KEYS})
+
+    # ------------------------------------------------------------------ the GP call
+    @staticmethod
+    def _set_xy(q, **pairs):
+        """q.<name>_x, q.<name>_y = the device pointers of each pair (None stays NULL)."""
+        for k, pair in pairs.items():
+            for cn, t in zip("xy", pair):
+                setattr(q, f"{k}_{cn}", None if t is None else t.data_ptr())
+
+    def _run_gp(self, fused, cfg, q):
+        """The one-launch entry, or the workspace entry on `self._work` sized by its *_workspace_elems entry."""
+        one, many = self._ENTRIES
+        if fused:
+            return call(one, C.byref(cfg), C.byref(q), self.stream.cuda_stream)
+        need = int(getattr(self.lib, many + "_workspace_elems")(C.byref(cfg)))      # 0: a shape the entry refuses (it says why)
+        if self._work.numel() < need:
+            self._work = torch.empty(need, dtype=_F64, device=self.dev)              # grows once per shape
+        call(many, C.byref(cfg), C.byref(q), self._work.data_ptr() if need else None, self.stream.cuda_stream)
 
     # ------------------------------------------------------------------ frames
     def predict(self, videos, query_times, observed=None, frame_times=None, eps=None):
@@ -182,30 +199,16 @@ class _Predictor(_BallMlpEngine):
 class BallPredictor(_Predictor):
     """A trained moving-ball SVGP-VAE, forward only.  `params`: name -> array for every entry of param_shapes(m, px, py, hidden)."""
 
-    def __init__(self, params, *, tmax, m, hidden=500, px=32, py=32, jitter, clip_qs, device="cuda:0"):
-        self.shapes = param_shapes(int(m), int(px), int(py), int(hidden))
-        self.m, self.jitter, self.clip_qs = int(m), float(jitter), bool(clip_qs)
-        self._setup(params, "a sparse-GP", tmax=tmax, hidden=hidden, px=px, py=py, device=device)
+    _KIND, _SPARSE, _META_KEYS, _SHAPE_KEYS = "a sparse-GP", True, META_KEYS, ("m", "hidden", "px", "py")
+    _REFUSAL = ("a checkpoint of an exact-GP baseline (GPVAE_Pearce / NP / VAE: no inducing points); BallPredictor handles the "
+                "sparse-GP models SVGPVAE_Hensman / SVGPVAE_Titsias only, use PearcePredictor")
+    _ENTRIES = ("svgp_ball_predict", "svgp_ball_predict_large")
+    _shapes = staticmethod(param_shapes)
 
-    # ------------------------------------------------------------------ checkpoints
-    @classmethod
-    def load(cls, path, **overrides):
-        """A predictor from the `model.pt` of `BALL_experiment --save_model`.  The model's shape comes from the checkpoint's "meta"
-        dict; keywords override it, and stand in for it where an older checkpoint has none."""
-        ck, shapes = _read_checkpoint(path)
-        meta = dict(ck.get("meta") or {})
-        device = overrides.pop("device", "cuda:0")
-        meta.update(overrides)
-        if meta.get("elbo") in _PEARCE_ELBOS or "ip_x" not in shapes:
-            raise ValueError(f"{path}: a checkpoint of an exact-GP baseline (GPVAE_Pearce / NP / VAE: no inducing points); "
-                             f"BallPredictor handles the sparse-GP models SVGPVAE_Hensman / SVGPVAE_Titsias only, use PearcePredictor")
-        missing = [k for k in META_KEYS if k not in meta]
-        if missing:
-            raise ValueError(f"{path}: the checkpoint has no meta entry for {', '.join(missing)}; pass "
-                             f"{', '.join(k + '=...' for k in missing)} to BallPredictor.load")
-        want = param_shapes(int(meta["m"]), int(meta["px"]), int(meta["py"]), int(meta["hidden"]))
-        params = _split_theta(path, ck, shapes, want, f"m={meta['m']} hidden={meta['hidden']} px={meta['px']} py={meta['py']}")
-        return cls(params, device=device, **{k: meta[k] for k in META_KEYS})
+    def __init__(self, params, *, tmax, m, hidden=500, px=32, py=32, jitter, clip_qs, device="cuda:0"):
+        self.m, self.jitter, self.clip_qs = int(m), float(jitter), bool(clip_qs)
+        self._setup(params, param_shapes(int(m), int(px), int(py), int(hidden)), tmax=tmax, hidden=hidden, px=px, py=py,
+                    device=device)
 
     def route(self, B, T, Q):
         return route((B, T, self.m, Q))
@@ -214,25 +217,13 @@ class BallPredictor(_Predictor):
     def _gp(self, mu, var, times, tq, mask, eps_c):
         """mu, var: two (T, B) tensors each; mask (T, B) or None; eps_c: two (Q, B) tensors or None.  Returns p_m, p_v, z lists."""
         T, B = mu[0].shape
-        Q, p, s = tq.numel(), self.params, self.stream.cuda_stream
-        f64 = dict(dtype=_F64, device=self.dev)
-        out = {k: [torch.empty(Q, B, **f64) for _ in range(2)] for k in ("p_m", "p_v", "z")}
+        Q, p = tq.numel(), self.params
+        out = {k: [torch.empty(Q, B, dtype=_F64, device=self.dev) for _ in range(2)] for k in ("p_m", "p_v", "z")}
         cfg = BallPredictCfg(B=B, T=T, m=self.m, Q=Q, jitter=self.jitter, clip_lo=CLIP_PV[0], clip_hi=CLIP_PV[1])
         q = BallPredictBufs()
         q.times, q.tq, q.mask = times.data_ptr(), tq.data_ptr(), None if mask is None else mask.data_ptr()
-        for c, cn in enumerate("xy"):
-            setattr(q, f"ip_{cn}", p[f"ip_{cn}"].data_ptr()); setattr(q, f"ls_{cn}", p[f"l_{cn}"].data_ptr())
-            setattr(q, f"mu_{cn}", mu[c].data_ptr()); setattr(q, f"var_{cn}", var[c].data_ptr())
-            setattr(q, f"eps_{cn}", None if eps_c is None else eps_c[c].data_ptr())
-            setattr(q, f"p_m_{cn}", out["p_m"][c].data_ptr()); setattr(q, f"p_v_{cn}", out["p_v"][c].data_ptr())
-            setattr(q, f"z_{cn}", out["z"][c].data_ptr())
-        if self.m <= FUSED_M_MAX:
-            call("svgp_ball_predict", C.byref(cfg), C.byref(q), s)
-        else:
-            need = int(self.lib.svgp_ball_predict_large_workspace_elems(C.byref(cfg)))      # 0: a shape the entry refuses (it says why)
-            if self._work.numel() < need:
-                self._work = torch.empty(need, **f64)                                     # grows once per shape
-            call("svgp_ball_predict_large", C.byref(cfg), C.byref(q), self._work.data_ptr() if need else None, s)
+        self._set_xy(q, ip=(p["ip_x"], p["ip_y"]), ls=(p["l_x"], p["l_y"]), mu=mu, var=var, eps=eps_c or (None, None), **out)
+        self._run_gp(self.m <= FUSED_M_MAX, cfg, q)
         return out["p_m"], out["p_v"], out["z"]
 
     def _gp_stage(self, mu, var, times, tq, mask, eps_c):
@@ -251,29 +242,16 @@ class PearcePredictor(_Predictor):
     the prior N(0, 1), which is the point of that baseline."""
 
     clip_qs = False
+    # of the "meta" dict only tmax, hidden, px, py are needed
+    _KIND, _SPARSE, _META_KEYS, _SHAPE_KEYS = "an exact-GP", False, PEARCE_META_KEYS, ("hidden", "px", "py")
+    _REFUSAL = ("a checkpoint of a sparse-GP model (SVGPVAE_Hensman / SVGPVAE_Titsias: it has inducing points); PearcePredictor "
+                "handles the exact-GP baselines GPVAE_Pearce / NP / VAE only, use BallPredictor")
+    _ENTRIES = ("svgp_pearce_predict", "svgp_pearce_predict_long")
+    _shapes = staticmethod(pearce_param_shapes)
 
     def __init__(self, params, *, tmax, hidden=500, px=32, py=32, device="cuda:0"):
-        self.shapes = pearce_param_shapes(int(px), int(py), int(hidden))
-        self._setup(params, "an exact-GP", tmax=tmax, hidden=hidden, px=px, py=py, device=device)
-
-    @classmethod
-    def load(cls, path, **overrides):
-        """A predictor from the `model.pt` of `BALL_experiment --save_model` with --elbo GPVAE_Pearce | NP | VAE.  Of the "meta"
-        dict only tmax, hidden, px, py are needed; keywords override them, and stand in for them where a checkpoint has none."""
-        ck, shapes = _read_checkpoint(path)
-        meta = dict(ck.get("meta") or {})
-        device = overrides.pop("device", "cuda:0")
-        meta.update(overrides)
-        if "ip_x" in shapes or ("elbo" in meta and meta["elbo"] not in _PEARCE_ELBOS):
-            raise ValueError(f"{path}: a checkpoint of a sparse-GP model (SVGPVAE_Hensman / SVGPVAE_Titsias: it has inducing points); "
-                             f"PearcePredictor handles the exact-GP baselines GPVAE_Pearce / NP / VAE only, use BallPredictor")
-        missing = [k for k in PEARCE_META_KEYS if k not in meta]
-        if missing:
-            raise ValueError(f"{path}: the checkpoint has no meta entry for {', '.join(missing)}; pass "
-                             f"{', '.join(k + '=...' for k in missing)} to PearcePredictor.load")
-        want = pearce_param_shapes(int(meta["px"]), int(meta["py"]), int(meta["hidden"]))
-        params = _split_theta(path, ck, shapes, want, f"hidden={meta['hidden']} px={meta['px']} py={meta['py']}")
-        return cls(params, device=device, **{k: meta[k] for k in PEARCE_META_KEYS})
+        self._setup(params, pearce_param_shapes(int(px), int(py), int(hidden)), tmax=tmax, hidden=hidden, px=px, py=py,
+                    device=device)
 
     def route(self, B, T, Q):
         return pearce_route((B, T, Q))
@@ -283,26 +261,15 @@ class PearcePredictor(_Predictor):
         """mu, var: two (T, B) tensors each; mask (T, B) or None; eps_c: two (Q, B) tensors or None.  Returns the p_m, p_v, z lists
         and lh (2, B)."""
         T, B = mu[0].shape
-        Q, p, s = tq.numel(), self.params, self.stream.cuda_stream
+        Q, p = tq.numel(), self.params
         f64 = dict(dtype=_F64, device=self.dev)
         out = {k: [torch.empty(Q, B, **f64) for _ in range(2)] for k in ("p_m", "p_v", "z")}
         lh = torch.empty(2, B, **f64)
         cfg = PearcePredictCfg(B=B, T=T, Q=Q, q_slices=int(q_slices))
         q = PearcePredictBufs()
         q.times, q.tq, q.mask, q.lh = times.data_ptr(), tq.data_ptr(), None if mask is None else mask.data_ptr(), lh.data_ptr()
-        for c, cn in enumerate("xy"):
-            setattr(q, f"ls_{cn}", p[f"l_{cn}"].data_ptr())
-            setattr(q, f"mu_{cn}", mu[c].data_ptr()); setattr(q, f"var_{cn}", var[c].data_ptr())
-            setattr(q, f"eps_{cn}", None if eps_c is None else eps_c[c].data_ptr())
-            setattr(q, f"p_m_{cn}", out["p_m"][c].data_ptr()); setattr(q, f"p_v_{cn}", out["p_v"][c].data_ptr())
-            setattr(q, f"z_{cn}", out["z"][c].data_ptr())
-        if T <= PEARCE_FUSED_T_MAX:
-            call("svgp_pearce_predict", C.byref(cfg), C.byref(q), s)
-        else:
-            need = int(self.lib.svgp_pearce_predict_long_workspace_elems(C.byref(cfg)))     # 0: a shape the entry refuses (it says why)
-            if self._work.numel() < need:
-                self._work = torch.empty(need, **f64)                                     # grows once per shape
-            call("svgp_pearce_predict_long", C.byref(cfg), C.byref(q), self._work.data_ptr() if need else None, s)
+        self._set_xy(q, ls=(p["l_x"], p["l_y"]), mu=mu, var=var, eps=eps_c or (None, None), **out)
+        self._run_gp(T <= PEARCE_FUSED_T_MAX, cfg, q)
         return out["p_m"], out["p_v"], out["z"], lh
 
     def _gp_stage(self, mu, var, times, tq, mask, eps_c):
