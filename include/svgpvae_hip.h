@@ -417,6 +417,27 @@ int svgp_gp_factor_bwd_nofinal_wgrad(const svgp_mnist_cfg*, const double* images
 int svgp_gp_stats_factor_bwd_wgrad(const svgp_mnist_cfg*, const double* images, double* ws, const double* state,
                                    void* stream);
 int svgp_gp_posterior_bwd_with_final(const svgp_mnist_cfg*, double* ws, const double* state, void* stream);
+/* In-kernel phase timeline of the two longest launches of the config-2 step (tools/decoder_phase_probe.py): probe instances of
+ * svgp_mnist_decoder_fwd_bwd_data_pre_tail and of svgp_gp_stats_factor_bwd_wgrad (m = 32, five LDS matrices).  Same results as the
+ * product launches; thread 0 of workgroup w also writes wall_clock64() stamps (100 MHz, one time axis for all workgroups) to row w of
+ * `stamps`, a device buffer of n_stamps elements that nothing else reads.  Zero it first: a slot a workgroup does not reach stays 0.
+ * Not for a captured stream (the buffer's address is handed over by a blocking copy into one device variable that every workgroup
+ * reads at its entry): synchronise the stream between a probe launch and the next probe call -- a call with another buffer while
+ * workgroups of the previous launch still wait for a slot would redirect their rows.
+ *   _decoder_..._probe: 16 slots per workgroup -- 0 entry, 1 weights staged, 2 z, 3 dense, 4 / 5 / 6 UpC1 / UpC2 / UpC3 forward,
+ *     7 copy-outs + squared error, 8 UpC3 data-reverse, 9 d2 scaled and stored, 10 UpC2 data-reverse, 11 d1 scaled and stored,
+ *     12 UpC1 data-reverse, 13 z-bar, 14 exit (slots 2..13: the workgroup's last image); a rider workgroup writes 0, 14 and 15 only.
+ *   _gp_stats_..._probe: 8 slots -- 0 entry, then for a rider 1 staged, 2 UpC3, 3 UpC2, 4 UpC1 + dense (its last image), 5 partial
+ *     stored; 6 exit (every workgroup).
+ *   Last slot of a row: bits 0..31 HW_ID (bits 8..15: compute unit, shader array, shader engine), 32..35 XCC_ID, 56..59 a rider's
+ *     layer-group mask (1 UpC3, 2 UpC2, 4 UpC1 + dense), 60..63 role (decoder launch: 1 image, 2 rider; factor launch: 1 statistics,
+ *     2 channel, 3 rider).
+ * SVGP_ERR_INVALID when the buffer is NULL or holds fewer than (workgroups x slots) elements, SVGP_ERR_UNSUPPORTED for another form. */
+int svgp_mnist_decoder_fwd_bwd_data_pre_tail_probe(const svgp_mnist_cfg*, const double* theta, const double* images, double* ws,
+                                                   const double* state, unsigned long long* stamps, long long n_stamps,
+                                                   void* stream);
+int svgp_gp_stats_factor_bwd_wgrad_probe(const svgp_mnist_cfg*, const double* images, double* ws, const double* state,
+                                         unsigned long long* stamps, long long n_stamps, void* stream);
 /* tf.train.AdamOptimizer.apply_gradients, TF1 formula (MNIST_experiment.py:200,207-208) */
 int svgp_adam_tf1_step(int64_t n, double* theta, const double* grad, double* adam_m, double* adam_v,
                        const double* state, double beta1, double beta2, double epsilon, void* stream);

@@ -177,6 +177,8 @@ SIGNATURES = {
     "svgp_gp_factor_bwd_nofinal": [_CFG, _P, _P, _P],
     "svgp_gp_factor_bwd_nofinal_wgrad": [_CFG, _P, _P, _P, _P],
     "svgp_gp_stats_factor_bwd_wgrad": [_CFG, _P, _P, _P, _P],
+    "svgp_gp_stats_factor_bwd_wgrad_probe": [_CFG, _P, _P, _P, _P, C.c_longlong, _P],
+    "svgp_mnist_decoder_fwd_bwd_data_pre_tail_probe": [_CFG, _P, _P, _P, _P, _P, C.c_longlong, _P],
     "svgp_mnist_encoder_bwd_km": [_CFG, _P, _P, _P, _P, _P],
     "svgp_mnist_encoder_bwd_km_sum": [_CFG, _P, _P, _P, _P, _P, _P],
     "svgp_mnist_encoder_bwd_km_regs": [C.POINTER(C.c_int)],

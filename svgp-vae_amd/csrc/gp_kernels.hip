@@ -16,6 +16,9 @@
 #include "sweep32.hpp"
 
 namespace {
+// rows of the phase probes: read by the PROBE kernel instances only, set by their entry points ahead of the launch
+// (one variable for all probe launches: the caller synchronises between a probe launch and the next probe call, include/svgpvae_hip.h)
+__device__ unsigned long long* g_probe_rows;
 
 // =============================================================================================
 // LDS matrix helpers.  LDS matrices are m x m with leading dimension ld = m + 1 (odd-ish pad:
@@ -1050,10 +1053,17 @@ struct FactBwdArgs {
 // STAT: 0 = the reverse statistics were a launch of their own; 1 = they ride at the head of this launch and the channel workgroup
 // waits for them where Ki is last in LDS (before T1 A); 2 = ... a FIFTH LDS matrix keeps Ki for the whole workgroup (m * m <= 4 * 256
 // elements, no kl_form), the wait moves behind Kbar_l = Abar G^T and the hand-off loads fly during the next two products
-template <int MC, int STAT = 0>
+// PROBE (svgp_gp_stats_factor_bwd_wgrad_probe): the phase timeline of vae_dev.hpp, one row of SVGP_PROBE_FB_SLOTS stamps per workgroup
+// (roles: 1 statistics, 2 channel, 3 rider, with the rider's layer-group mask); the product instances hold no stamp.
+template <int MC, int STAT = 0, bool PROBE = false>
 __global__ __launch_bounds__(SVGP_BLOCK) void k_gp_factor_bwd(FactBwdArgs a) {
     extern __shared__ __align__(16) real smem[];
     int bid = (int)blockIdx.x;
+    unsigned long long* probe = nullptr;
+    if constexpr (PROBE) {
+        probe = g_probe_rows + (size_t)blockIdx.x * SVGP_PROBE_FB_SLOTS;
+        svgp_vae::probe_stamp<true>(probe, 0);
+    }
     if (STAT) {
         if (bid < a.n_stat) {                  // block l P + part: the P producers of a channel are neighbours, low channels first
             const int ls = bid / a.P, part = bid - ls * a.P;
@@ -1061,12 +1071,15 @@ __global__ __launch_bounds__(SVGP_BLOCK) void k_gp_factor_bwd(FactBwdArgs a) {
             __builtin_amdgcn_s_waitcnt(0);
             __syncthreads();
             if (threadIdx.x == 0) __hip_atomic_fetch_add(&a.flags[8 + ls], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            svgp_vae::probe_place<PROBE>(probe, 7, 1, 0);
+            svgp_vae::probe_stamp<PROBE>(probe, 6);
             return;
         }
         bid -= a.n_stat;
     }
     if (bid >= a.L) {
-        svgp_vae::decoder_wgrad_rider<SVGP_BLOCK>(a.wg, bid - a.L, smem);
+        svgp_vae::decoder_wgrad_rider<SVGP_BLOCK, PROBE, true>(a.wg, bid - a.L, smem, probe);      // n_types = 3 (factor_bwd_impl)
+        svgp_vae::probe_stamp<PROBE>(probe, 6);
         return;
     }
     const int m = MC ? MC : a.m, mp = pad16(m), ld = mp + 2, mm = mp * ld, l = bid;
@@ -1329,6 +1342,8 @@ __global__ __launch_bounds__(SVGP_BLOCK) void k_gp_factor_bwd(FactBwdArgs a) {
     __syncthreads();
     if (keep) mat_gemm_g_from<false, false>(Kb, RKb, R3, RKi, ld, m, real(-1));
     else mat_gemm_g<false, false>(Kb, R3, RKi, ld, m, real(-1), real(1));
+    svgp_vae::probe_place<PROBE>(probe, 7, 2, 0);
+    svgp_vae::probe_stamp<PROBE>(probe, 6);
 }
 
 // Kbar = sum_l Kbar_l + (L gK / 2) Ki ; one thread per element, channel loads batched.
@@ -1648,15 +1663,24 @@ __device__ __forceinline__ void factor_fwd_rider(const FactArgs& a, int l, real*
 // riders run everything of the stage that the chain up to this launch does not read -- G, A, the traces, M2, then that inverse and
 // KL (factor_fwd_tail) -- with SVGP_BLOCK live threads; its consumers (the reverse factor stage, the d form of the reverse row stage,
 // the closing scalars) all sit behind this launch.
-template <int RIDE>
+// PROBE (svgp_mnist_decoder_fwd_bwd_data_pre_tail_probe): the phase timeline of vae_dev.hpp, one row of SVGP_PROBE_DEC_SLOTS stamps
+// per workgroup (roles: 1 image workgroup, 2 rider: entry, exit of thread 0 and place only); the product instances hold no stamp.
+template <int RIDE, bool PROBE = false>
 __global__ __launch_bounds__(VAE_NT) void k_decoder_fwd_bwd_data(svgp_vae::DecFwdBwdArgs d, AjiArgs a, FactArgs f) {
     extern __shared__ __align__(16) real smem[];
     int l = blockIdx.x;
+    unsigned long long* probe = nullptr;
+    if constexpr (PROBE) {
+        probe = g_probe_rows + (size_t)blockIdx.x * SVGP_PROBE_DEC_SLOTS;
+        svgp_vae::probe_stamp<true>(probe, 0);
+        svgp_vae::probe_place<true>(probe, 15, RIDE && l < a.L ? 2 : 1, 0);
+    }
     if (RIDE) {
         if (l < a.L) {
             if (threadIdx.x >= SVGP_BLOCK) return;
             if (RIDE == 2) {
                 if (f.m == 32) factor_fwd_rider<32>(f, l, smem); else factor_fwd_rider<0>(f, l, smem);
+                svgp_vae::probe_stamp<PROBE>(probe, 14);
                 return;
             }
             const int m = a.m, ld = m + 1;
@@ -1673,7 +1697,7 @@ __global__ __launch_bounds__(VAE_NT) void k_decoder_fwd_bwd_data(svgp_vae::DecFw
         l -= a.L;
         __builtin_amdgcn_s_setprio(3);          // (the image waves before a rider's sweep wave on the same SIMD, as above)
     }
-    svgp_vae::decoder_fwd_bwd_data_images(d, l, (int)gridDim.x - (RIDE ? a.L : 0), smem);
+    svgp_vae::decoder_fwd_bwd_data_images<PROBE>(d, l, (int)gridDim.x - (RIDE ? a.L : 0), smem, probe);
 }
 
 // =============================================================================================
@@ -1907,8 +1931,17 @@ static const char NEED_SPLIT_TIT[] = "the split forward block (SVGP_FWD_SPLIT) d
     } while (0)
 static FactArgs make_fact_args(const svgp_mnist_cfg* c, const svgp_mnist_ws_layout& wl, double* ws, int defer_aji);
 // ride: 0 no riders, 1 the riders finish (A_hat + jI)^-1, 2 the riders run the whole tail of the forward factor stage
+// Sets g_probe_rows for a PROBE launch of `n_wg` workgroups with `slots` stamps each; `n_stamps` is the caller's capacity.
+static int probe_rows_set(unsigned long long* stamps, long long n_stamps, long long n_wg, int slots) {
+    SVGP_REQUIRE(stamps, SVGP_ERR_INVALID, "NULL stamp buffer");
+    SVGP_REQUIRE(n_stamps >= n_wg * slots, SVGP_ERR_INVALID, "stamp buffer of %lld elements, the launch writes %lld x %d", n_stamps,
+                 n_wg, slots);
+    SVGP_CHECK_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_probe_rows), &stamps, sizeof(stamps)));
+    return SVGP_OK;
+}
 static int decoder_fwd_bwd_data_impl(const svgp_mnist_cfg* c, const double* theta, const double* images, double* ws,
-                                     const double* state, int ride, void* stream) {
+                                     const double* state, int ride, void* stream, unsigned long long* stamps = nullptr,
+                                     long long n_stamps = 0) {
     GET_LAYOUTS();
     const bool aji = ride != 0;
     SVGP_REQUIRE(theta && images && ws && state, SVGP_ERR_INVALID, "NULL device pointer");
@@ -1934,10 +1967,19 @@ static int decoder_fwd_bwd_data_impl(const svgp_mnist_cfg* c, const double* thet
         if (lds_tail > lds) lds = lds_tail;
     }
     SVGP_REQUIRE(lds <= SVGP_LDS_MAX_BYTES, SVGP_ERR_UNSUPPORTED, "L = %d: %zu bytes of LDS", c->L, lds);
+    const dim3 grid((aji ? a.L : 0) + svgp_n_part(c));
+    if (stamps) {                           // the phase-timeline instance of the form the config-2 step runs
+        int rcp = probe_rows_set(stamps, n_stamps, grid.x, SVGP_PROBE_DEC_SLOTS);
+        if (rcp) return rcp;
+        rcp = set_dyn_lds(k_decoder_fwd_bwd_data<2, true>, lds);
+        if (rcp) return rcp;
+        hipLaunchKernelGGL((k_decoder_fwd_bwd_data<2, true>), grid, dim3(VAE_NT), lds, (hipStream_t)stream, d, a, f);
+        SVGP_LAUNCH_CHECK();
+        return SVGP_OK;
+    }
     int rc = ride == 2 ? set_dyn_lds(k_decoder_fwd_bwd_data<2>, lds)
              : aji     ? set_dyn_lds(k_decoder_fwd_bwd_data<1>, lds) : set_dyn_lds(k_decoder_fwd_bwd_data<0>, lds);
     if (rc) return rc;
-    const dim3 grid((aji ? a.L : 0) + svgp_n_part(c));
     if (ride == 2) hipLaunchKernelGGL(k_decoder_fwd_bwd_data<2>, grid, dim3(VAE_NT), lds, (hipStream_t)stream, d, a, f);
     else if (aji) hipLaunchKernelGGL(k_decoder_fwd_bwd_data<1>, grid, dim3(VAE_NT), lds, (hipStream_t)stream, d, a, f);
     else hipLaunchKernelGGL(k_decoder_fwd_bwd_data<0>, grid, dim3(VAE_NT), lds, (hipStream_t)stream, d, a, f);
@@ -1957,6 +1999,14 @@ extern "C" int svgp_mnist_decoder_fwd_bwd_data_pre_tail(const svgp_mnist_cfg* c,
                                                         const double* state, void* stream) {
     REQUIRE_FWD_SPLIT(c);
     return decoder_fwd_bwd_data_impl(c, theta, images, ws, state, 2, stream);
+}
+// ... its phase-timeline instance: same results, one row of SVGP_PROBE_DEC_SLOTS stamps per workgroup in `stamps`
+extern "C" int svgp_mnist_decoder_fwd_bwd_data_pre_tail_probe(const svgp_mnist_cfg* c, const double* theta, const double* images,
+                                                              double* ws, const double* state, unsigned long long* stamps,
+                                                              long long n_stamps, void* stream) {
+    REQUIRE_FWD_SPLIT(c);
+    SVGP_REQUIRE(stamps, SVGP_ERR_INVALID, "NULL stamp buffer");
+    return decoder_fwd_bwd_data_impl(c, theta, images, ws, state, 2, stream, stamps, n_stamps);
 }
 // out[0..2]: registers per lane, scratch bytes per lane, dynamic LDS bytes of that launch at latent size L (m <= 32)
 extern "C" int svgp_mnist_decoder_fused_tail_regs(int L, int* out) {
@@ -2248,7 +2298,8 @@ static FactBwdArgs make_fb(const svgp_mnist_cfg* c, const svgp_mnist_ws_layout& 
 }
 
 static int factor_bwd_impl(const svgp_mnist_cfg* c, double* ws, const double* state, bool with_final, void* stream,
-                           const double* images_for_wgrad = nullptr, bool with_stats = false, bool stat_four = false);
+                           const double* images_for_wgrad = nullptr, bool with_stats = false, bool stat_four = false,
+                           unsigned long long* stamps = nullptr, long long n_stamps = 0);
 extern "C" int svgp_gp_factor_bwd(const svgp_mnist_cfg* c, double* ws, const double* state, void* stream) {
     return factor_bwd_impl(c, ws, state, true, stream);
 }
@@ -2277,6 +2328,15 @@ int svgp_gp_stats_factor_bwd_wgrad_sched(const svgp_mnist_cfg* c, const double* 
 extern "C" int svgp_gp_stats_factor_bwd_wgrad(const svgp_mnist_cfg* c, const double* images, double* ws, const double* state,
                                               void* stream) {
     return svgp_gp_stats_factor_bwd_wgrad_sched(c, images, ws, state, stream, sched_read());
+}
+// ... its phase-timeline instance (m = 32, five LDS matrices: the config-2 form): same results, one row of SVGP_PROBE_FB_SLOTS
+// stamps per workgroup in `stamps`
+extern "C" int svgp_gp_stats_factor_bwd_wgrad_probe(const svgp_mnist_cfg* c, const double* images, double* ws, const double* state,
+                                                    unsigned long long* stamps, long long n_stamps, void* stream) {
+    SVGP_REQUIRE(c && c->m == 32, SVGP_ERR_UNSUPPORTED, "the phase probe is the m = 32 instance of the merged launch");
+    SVGP_REQUIRE(c->L <= 56, SVGP_ERR_UNSUPPORTED, "ws.flags holds 56 channel counters (L = %d)", c->L);
+    SVGP_REQUIRE(images && stamps, SVGP_ERR_INVALID, "NULL device pointer");
+    return factor_bwd_impl(c, ws, state, false, stream, images, true, false, stamps, n_stamps);
 }
 // m > 64: svgp_gp_factor_bwd piece by piece (the table in include/svgpvae_hip.h; what each piece needs: gp_large.hip svgp_big_factor_bwd)
 extern "C" int svgp_gp_factor_bwd_early(const svgp_mnist_cfg* c, double* ws, const double* state, void* stream) {
@@ -2307,7 +2367,8 @@ extern "C" int svgp_gp_factor_bwd_late_b_final(const svgp_mnist_cfg* c, double* 
     return big_factor(c, ws, state, false, stream, SVGP_BWD_FINAL, NEED_BIG_BWD);
 }
 static int factor_bwd_impl(const svgp_mnist_cfg* c, double* ws, const double* state, bool with_final, void* stream,
-                           const double* images_for_wgrad, bool with_stats, bool stat_four) {
+                           const double* images_for_wgrad, bool with_stats, bool stat_four, unsigned long long* stamps,
+                           long long n_stamps) {
     GET_LAYOUTS();
     SVGP_REQUIRE(ws && state, SVGP_ERR_INVALID, "NULL device pointer");
     if (c->m > SVGP_M_MAX) return svgp_big_factor_bwd(c, wl, ws, state, stream, 0, c->L, SVGP_BWD_ALL);
@@ -2337,6 +2398,17 @@ static int factor_bwd_impl(const svgp_mnist_cfg* c, double* ws, const double* st
     }
     const dim3 grid(a.n_stat + c->L + a.n_riders);
     int rc;
+    if (stamps) {                           // the phase-timeline instance of the form the config-2 step runs
+        SVGP_REQUIRE(with_stats && five && m == 32 && images_for_wgrad, SVGP_ERR_UNSUPPORTED,
+                     "the phase probe is the m = 32 five-matrix instance with riders (m = %d)", m);
+        rc = probe_rows_set(stamps, n_stamps, grid.x, SVGP_PROBE_FB_SLOTS);
+        if (rc) return rc;
+        rc = set_dyn_lds(k_gp_factor_bwd<32, 2, true>, lds);
+        if (rc) return rc;
+        hipLaunchKernelGGL((k_gp_factor_bwd<32, 2, true>), grid, dim3(SVGP_BLOCK), lds, (hipStream_t)stream, a);
+        SVGP_LAUNCH_CHECK();
+        return SVGP_OK;
+    }
     if (with_stats) {
         if (five) {
             rc = m == 32 ? set_dyn_lds(k_gp_factor_bwd<32, 2>, lds) : set_dyn_lds(k_gp_factor_bwd<0, 2>, lds);

@@ -74,6 +74,20 @@ __device__ __forceinline__ void gg_fwd(const real* in, int Hi, int Wi, int Hs, i
     }
 }
 
+// Operands of a boundary-tested tap in the rolled VALU forward below, the idiom of gg_fwd: the caller clamps the address (element 0
+// of the tile for a tap outside it), the N operands are loaded unconditionally -- contiguous, so they vectorise (ds_read_b128) -- and
+// the caller selects `valid ? v : 0` afterwards.  Written as `valid ? p[i] : 0` each element compiles to a ds_read_b64 in an
+// exec-masked block of its own (8 of them and 16 exec writes per tap trip).  The empty asm is for the compiler only: without it the
+// optimizer sinks the loads back under the test.  Only UpConv3::fwd_valu<true> uses it: the fused decoder launch is 1.3 - 1.5 us
+// shorter with it, the unrolled forward, bwd_data_valu and the two VALU weight-gradient forms measured slower.
+template <int N>
+__device__ __forceinline__ void tap_operands(real (&v)[N], const real* p) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) v[i] = p[i];
+#pragma unroll
+    for (int i = 0; i < N; ++i) asm volatile("" : "+v"(v[i]));
+}
+
 struct TapP { int oy, ox, woff, ooy, oox; };
 template <int NTAP, int CI, int CO, int NT, typename TapFn>
 __device__ __forceinline__ void gg_wgrad(const real* in, int Hi, int Wi, int Hs, int Ws, int sy, int sx, TapFn tapfn,
@@ -277,7 +291,8 @@ struct UpConv3 {
     // out = elu(conv(up(in)) + bias); item = (output pixel, group of COG channels)
     // ROLL: the two tap loops stay loops (one tap of CIN x COG FMAs per trip) instead of hoisting the 32 activation and 64 weight
     // LDS loads of an item: ~85 VGPRs fewer, same FMA order per output (bias, then ty, tx, ci), so the same bits.  For kernels that
-    // must stay within 168 VGPRs (decoder_fwd_bwd_data_images below).
+    // must stay within 168 VGPRs (decoder_fwd_bwd_data_images below).  Its activations come through tap_operands (unconditional
+    // vector loads, select afterwards); the unrolled form keeps the predicated reads, with which it is faster.
     template <bool ROLL = false>
     static __device__ void fwd_valu(const real* in, const real* We, const real* bias, real* out) {
         constexpr int TAP_UNROLL = ROLL ? 1 : 2;     // 1: no unrolling; 2 = the trip count: full
@@ -298,9 +313,13 @@ struct UpConv3 {
                     const bool valid = vy && ((unsigned)sx < (unsigned)HS);
                     const real* src = in + (valid ? (sy * HS + sx) * CIN : 0);
                     const real* wk = wc + (ty * 2 + tx) * CIN * COUT;
+                    real av[CIN];
+                    if constexpr (ROLL) tap_operands(av, src);
 #pragma unroll
                     for (int ci = 0; ci < CIN; ++ci) {
-                        const real a = valid ? src[ci] : real(0);
+                        real a;
+                        if constexpr (ROLL) a = valid ? av[ci] : real(0);
+                        else a = valid ? src[ci] : real(0);
 #pragma unroll
                         for (int g = 0; g < COG; ++g) acc[g] += a * wk[ci * COUT + g];
                     }
@@ -533,6 +552,30 @@ __device__ __forceinline__ void stage_copy(real* dst, const real* __restrict__ s
     for (int c0 = CH * NT; c0 < n; c0 += CH * NT) stage_chunk<NT, CH>(dst, src, n, c0);      // (uniform trip count: a scalar branch)
 }
 
+// In-kernel phase timeline (tools/decoder_phase_probe.py).  The PROBE instances of the two longest launches of the config-2 step
+// stamp wall_clock64() -- the constant 100 MHz counter, the same on every CU, so the rows of different workgroups share one time
+// axis -- at each phase; thread 0 of a workgroup writes slot k of the workgroup's row with an ordinary store, the last slot holds
+// where the workgroup ran and what it was.  The buffer is the caller's and nothing else reads it.  The product instances
+// (PROBE = false) contain none of this: a stamp compiles to nothing and the row pointer is never formed.
+#define SVGP_PROBE_DEC_SLOTS 16      // k_decoder_fwd_bwd_data: 0 entry .. 14 exit (include/svgpvae_hip.h has the list), 15 place
+#define SVGP_PROBE_FB_SLOTS 8        // k_gp_factor_bwd: 0 entry, 1 staged, 2 UpC3, 3 UpC2, 4 UpC1 + dense, 5 partial stored, 6 exit, 7 place
+template <bool PROBE>
+__device__ __forceinline__ void probe_stamp(unsigned long long* row, int k) {
+    if constexpr (PROBE) {
+        if (threadIdx.x == 0) row[k] = wall_clock64();
+    }
+}
+// bits 0..31 HW_ID (compute unit: bits 8..15), bits 32..35 XCC_ID, bits 56..59 `detail`, bits 60..63 `role`
+template <bool PROBE>
+__device__ __forceinline__ void probe_place(unsigned long long* row, int k, int role, int detail) {
+    if constexpr (PROBE) {
+        const unsigned hw = __builtin_amdgcn_s_getreg((31 << 11) | 4), xcc = __builtin_amdgcn_s_getreg((31 << 11) | 20);
+        if (threadIdx.x == 0)
+            row[k] = (unsigned long long)hw | ((unsigned long long)(xcc & 15u) << 32) | ((unsigned long long)(detail & 15) << 56) |
+                     ((unsigned long long)(role & 15) << 60);
+    }
+}
+
 struct EncOff { int c1w, c1b, c2w, c2b, c3w, c3b, dw, db, n; };
 struct DecOff { int dw, db, c1w, c1b, c2w, c2b, c3w, c3b, n; };
 
@@ -586,8 +629,8 @@ __host__ __device__ constexpr int dec_wgrad_lds(int nt, int L, int n_types) {
     return mx;
 }
 
-template <int NT>
-__device__ __forceinline__ void decoder_wgrad_rider(const DecWgradArgs& a, int rider, real* smem) {
+template <int NT, bool PROBE = false, bool EXCL = false>
+__device__ __forceinline__ void decoder_wgrad_rider(const DecWgradArgs& a, int rider, real* smem, unsigned long long* probe = nullptr) {
     static_assert(NT >= 256 && NT <= 512, "bias / chunk layouts are sized for 256..512 threads");
     const DecOff od = dec_off(a.L);
     // Riders are numbered TYPE-major, heaviest layer group first (UpC2: 113 K MACs per image, UpC3: 56 K, UpC1 + dense: 39 K): a launch that
@@ -607,6 +650,46 @@ __device__ __forceinline__ void decoder_wgrad_rider(const DecWgradArgs& a, int r
     if (mask & 4) { h0 = take(128); d1 = take(512); dh0 = take(128); z = take(64); gWe1 = take(1024); dacc = take(ndense + 128); }
     real* gb = take(32);             // c1b (8) | c2b (8) | c3b (1)
     real* scratch = p;
+    // One group of loads per image: every operand of the rider's layer groups is issued before the first wait (stage_issue: unconditional
+    // loads from indices kept inside the arrays) and stored to LDS afterwards, one round trip instead of one per pass of NT threads and
+    // array.  The first image's group flies while the accumulators are zeroed, a later image's during the products of the one before.
+    // The values wait in ONE register set rv.  EXCL (the reverse factor launch: always the three-type layout, a rider runs exactly one
+    // layer group): the groups share its first registers -- 15 doubles at NT = 256 instead of 29 with every group live, which is what
+    // keeps that kernel at three workgroups per CU.  Otherwise (n_types 1 or 2: a rider may run several groups) each group has its own.
+    const int t = threadIdx.x;
+    constexpr int C1568 = StageRegs<1568, NT>::C, C784 = StageRegs<784, NT>::C, C512 = StageRegs<512, NT>::C, C128 = StageRegs<128, NT>::C;
+    constexpr int N1 = C1568 + 2 * C784, N2 = C512 + C1568, N4 = 2 * C128 + C512 + 1;
+    constexpr int O1 = 0, O2 = EXCL ? 0 : N1, O4 = EXCL ? 0 : N1 + N2;
+    constexpr int NV = EXCL ? (N1 > N2 ? (N1 > N4 ? N1 : N4) : (N2 > N4 ? N2 : N4)) : N1 + N2 + N4;
+    real rv[NV];
+    auto put = [&](auto r, int off) {
+#pragma unroll
+        for (int k = 0; k < decltype(r)::C; ++k) rv[off + k] = r.v[k];
+    };
+    auto issue = [&](int n) {
+        if (mask & 1) {
+            put(stage_issue<1568, NT>(a.a2 + (size_t)n * 1568), O1);
+            put(stage_issue<784, NT>(a.recon + (size_t)n * 784), O1 + C1568);
+            put(stage_issue<784, NT>(a.images + (size_t)n * 784), O1 + C1568 + C784);
+        }
+        if (mask & 2) {
+            put(stage_issue<512, NT>(a.a1 + (size_t)n * 512), O2);
+            put(stage_issue<1568, NT>(a.d2 + (size_t)n * 1568), O2 + C512);
+        }
+        if (mask & 4) {
+            put(stage_issue<128, NT>(a.h0 + (size_t)n * 128), O4);
+            put(stage_issue<512, NT>(a.d1 + (size_t)n * 512), O4 + C128);
+            put(stage_issue<128, NT>(a.dh0 + (size_t)n * 128), O4 + C128 + C512);
+            rv[O4 + 2 * C128 + C512] = a.z[(size_t)n * a.L + (t < a.L ? t : a.L - 1)];
+        }
+    };
+    auto commit = [&](real* dst, auto tag, int off) {      // tag: an empty StageRegs type carrier
+        decltype(tag) r;
+#pragma unroll
+        for (int k = 0; k < decltype(tag)::C; ++k) r.v[k] = rv[off + k];
+        stage_commit(dst, r);
+    };
+    if (slot < a.b) issue(slot);
     if (mask & 1) for (int i = threadIdx.x; i < 128; i += NT) gWe3[i] = 0;
     if (mask & 2) for (int i = threadIdx.x; i < 1024; i += NT) gWe2[i] = 0;
     if (mask & 4) for (int i = threadIdx.x; i < 1024 + ndense + 128; i += NT) gWe1[i] = 0;     // gWe1 | dacc (contiguous)
@@ -615,29 +698,39 @@ __device__ __forceinline__ void decoder_wgrad_rider(const DecWgradArgs& a, int r
     for (int n = slot; n < a.b; n += a.n_slots) {
         __syncthreads();
         if (mask & 1) {
-            for (int i = threadIdx.x; i < 784; i += NT) {
-                const real o = a.recon[(size_t)n * 784 + i];
-                d3[i] = real(2) * gscale * (o - a.images[(size_t)n * 784 + i]) * elu_grad_from_out(o);
+#pragma unroll
+            for (int k = 0; k < C784; ++k) {
+                const int i = t + k * NT;
+                const real o = rv[O1 + C1568 + k];
+                if (i < 784) d3[i] = real(2) * gscale * (o - rv[O1 + C1568 + C784 + k]) * elu_grad_from_out(o);
             }
-            for (int i = threadIdx.x; i < 1568; i += NT) a2[i] = a.a2[(size_t)n * 1568 + i];
+            commit(a2, StageRegs<1568, NT>(), O1);
         }
         if (mask & 2) {
-            for (int i = threadIdx.x; i < 1568; i += NT) d2[i] = a.d2[(size_t)n * 1568 + i];
-            for (int i = threadIdx.x; i < 512; i += NT) a1[i] = a.a1[(size_t)n * 512 + i];
+            commit(d2, StageRegs<1568, NT>(), O2 + C512);
+            commit(a1, StageRegs<512, NT>(), O2);
         }
         if (mask & 4) {
-            for (int i = threadIdx.x; i < 512; i += NT) d1[i] = a.d1[(size_t)n * 512 + i];
-            if (threadIdx.x < 128) { h0[threadIdx.x] = a.h0[(size_t)n * 128 + threadIdx.x]; dh0[threadIdx.x] = a.dh0[(size_t)n * 128 + threadIdx.x]; }
-            if ((int)threadIdx.x < a.L) z[threadIdx.x] = a.z[(size_t)n * a.L + threadIdx.x];
+            commit(d1, StageRegs<512, NT>(), O4 + C128);
+            commit(h0, StageRegs<128, NT>(), O4);
+            commit(dh0, StageRegs<128, NT>(), O4 + C128 + C512);
+            if (t < a.L) z[t] = rv[O4 + 2 * C128 + C512];
         }
+        if (n + a.n_slots < a.b) issue(n + a.n_slots);      // the next image of this slot: one image ahead
         __syncthreads();
+        // (probe slots 1..4 are those of the rider's LAST image; the products end with a barrier)
+        probe_stamp<PROBE>(probe, 1);       // staged
         if (mask & 1) UpC3T<NT>::bwd_weight_mfma(a2, d3, gWe3, gb + 16, scratch);     // COUT = 1: chunked VALU form inside
+        probe_stamp<PROBE>(probe, 2);       // UpC3
         if (mask & 2) UpC2T<NT>::bwd_weight_valu(a1, d2, gWe2, gb + 8, scratch);
+        probe_stamp<PROBE>(probe, 3);       // UpC2
         if (mask & 4) {
             UpC1T<NT>::bwd_weight_mfma(h0, d1, gWe1, gb, scratch);
             for (int o = threadIdx.x; o < ndense; o += NT) dacc[o] += z[o >> 7] * dh0[o & 127];
             if (threadIdx.x < 128) dacc[ndense + threadIdx.x] += dh0[threadIdx.x];
         }
+        if constexpr (PROBE) __syncthreads();
+        probe_stamp<PROBE>(probe, 4);       // UpC1 + dense
     }
     __syncthreads();
     real* part = a.part + (size_t)slot * od.n;
@@ -655,6 +748,12 @@ __device__ __forceinline__ void decoder_wgrad_rider(const DecWgradArgs& a, int r
         for (int o = threadIdx.x; o < ndense; o += NT) part[od.dw + o] = dacc[o];
         if (threadIdx.x < 128) part[od.db + threadIdx.x] = dacc[ndense + threadIdx.x];
     }
+    if constexpr (PROBE) {                  // partial stored: every wave's stores have left
+        __builtin_amdgcn_s_waitcnt(0);
+        __syncthreads();
+        probe_place<PROBE>(probe, 7, 3, mask);
+    }
+    probe_stamp<PROBE>(probe, 5);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -771,7 +870,12 @@ __device__ __forceinline__ void decoder_bwd_data_images(const DecBwdDataArgs& a,
 // k_decoder_fwd_bwd_data in gp_kernels.hip, relies on that and on <= 168 VGPRs: the forward runs its rolled-tap form).
 // The z / pixel loads of an image are issued one image ahead (the first: before the weight staging).  The staging behind them is
 // still lds_copy_in: twelve dependent round trips.  Staged in groups (stage_issue / stage_copy above) the launch with its riders was
-// no faster stand-alone and the straight-line form cost six registers (170 > 168), so this kernel keeps the loops (NOTEBOOK 14.5c).
+// no faster stand-alone and the straight-line form cost six registers (170 > 168), so this kernel kept the loops (NOTEBOOK 14.5c).
+// The phase timeline (PROBE, NOTEBOOK 14.5d) puts entry -> weights staged at 3.0 us of the launch's 26, launch ramp included; with
+// the branch-free forward the kernel is at 160 - 162 VGPRs and the straight-line group fits (166 / 166 / 165): it shortens the launch
+// without riders by 0.4 us and the launch with riders, the form the step runs, by nothing (25.89 against 25.87 us), so the loops stay
+// (NOTEBOOK 14.5d).
+// PROBE: the phase-timeline instance (probe_stamp above); `probe` is the workgroup's row of stamps.
 // The squared-error partial of a workgroup goes to part_sums[4 * first + 2].
 // ------------------------------------------------------------------------------------------
 struct DecFwdBwdArgs {
@@ -784,7 +888,9 @@ struct DecFwdBwdArgs {
 __host__ __device__ constexpr int dec_fwd_bwd_lds(int L) {
     return L * 128 + 128 + 32 + DEC_NWE + 64 + 128 + 512 + 1568 + 784 + 1568 + 512 + 128 + 16;
 }
-__device__ __forceinline__ void decoder_fwd_bwd_data_images(const DecFwdBwdArgs& a, int first, int stride, real* smem) {
+template <bool PROBE = false>
+__device__ __forceinline__ void decoder_fwd_bwd_data_images(const DecFwdBwdArgs& a, int first, int stride, real* smem,
+                                                            unsigned long long* probe = nullptr) {
     const DecOff od = dec_off(a.L);
     real* w = smem;                  // dense weights L*128 | dense bias 128 (contiguous in theta)
     real* db = w + a.L * 128;
@@ -813,22 +919,29 @@ __device__ __forceinline__ void decoder_fwd_bwd_data_images(const DecFwdBwdArgs&
     lds_copy_in(We1, a.weff, DEC_NWE);
     const real gscale = (a.geco ? lag * a.inv_bglobal : real(1)) / real(784);
     real sq = 0;
+    // (probe slots 2..13 are those of the workgroup's LAST image)
     for (int n = first; n < a.b; n += stride) {
         __syncthreads();
+        if (n == first) probe_stamp<PROBE>(probe, 1);       // weight staging
         if (t < a.L) z[t] = zr;
         __syncthreads();
+        probe_stamp<PROBE>(probe, 2);       // z
         if (t < 128) {
             real acc = db[t];
             for (int i = 0; i < a.L; ++i) acc += z[i] * w[i * 128 + t];
             h0[t] = acc;
         }
         __syncthreads();
+        probe_stamp<PROBE>(probe, 3);       // dense
         UpC1::fwd_valu<true>(h0, We1, cb, a1);
         __syncthreads();
+        probe_stamp<PROBE>(probe, 4);       // UpC1 forward
         UpC2::fwd_valu<true>(a1, We2, cb + 8, a2);
         __syncthreads();
+        probe_stamp<PROBE>(probe, 5);       // UpC2 forward
         UpC3::fwd_valu<true>(a2, We3, cb + 16, d3);
         __syncthreads();
+        probe_stamp<PROBE>(probe, 6);       // UpC3 forward
         lds_copy_out(a.h0g + (size_t)n * 128, h0, 128);
         lds_copy_out(a.a1g + (size_t)n * 512, a1, 512);
         lds_copy_out(a.a2g + (size_t)n * 1568, a2, 1568);
@@ -855,24 +968,30 @@ __device__ __forceinline__ void decoder_fwd_bwd_data_images(const DecFwdBwdArgs&
             }
         }
         __syncthreads();
+        probe_stamp<PROBE>(probe, 7);       // copy-outs, squared error, d3, next image's loads issued
         UpC3::bwd_data_valu(d3, We3, d2);
         __syncthreads();
+        probe_stamp<PROBE>(probe, 8);       // UpC3 data-reverse
         for (int i = t; i < 1568; i += VAE_NT) {
             const real v = d2[i] * elu_grad_from_out(a2[i]);
             d2[i] = v;
             a.d2g[(size_t)n * 1568 + i] = v;
         }
         svgp_lds_barrier();             // (the stores to d2g / d1g / dh0g are for a later launch: no wave waits for them here)
+        probe_stamp<PROBE>(probe, 9);       // d2 = d2 * elu', stored
         UpC2::bwd_data_mfma(d2, We2, d1);
         svgp_lds_barrier();
+        probe_stamp<PROBE>(probe, 10);      // UpC2 data-reverse
         for (int i = t; i < 512; i += VAE_NT) {
             const real v = d1[i] * elu_grad_from_out(a1[i]);
             d1[i] = v;
             a.d1g[(size_t)n * 512 + i] = v;
         }
         svgp_lds_barrier();
+        probe_stamp<PROBE>(probe, 11);      // d1 = d1 * elu', stored
         UpC1::bwd_data_mfma(d1, We1, dh0);
         svgp_lds_barrier();
+        probe_stamp<PROBE>(probe, 12);      // UpC1 data-reverse
         if (t < 128) a.dh0g[(size_t)n * 128 + t] = dh0[t];
         // zbar[i] = sum_j dh0[j] w[i][j]: 8 lanes per latent channel, xor-shuffle combine
         {
@@ -885,9 +1004,12 @@ __device__ __forceinline__ void decoder_fwd_bwd_data_images(const DecFwdBwdArgs&
             acc += __shfl_xor(acc, 4, 64);
             if (i < a.L && part8 == 0) a.zbar[(size_t)n * a.L + i] = acc;
         }
+        if constexpr (PROBE) __syncthreads();
+        probe_stamp<PROBE>(probe, 13);      // z-bar
     }
     const real tot = block_sum(sq, red);
     if (t == 0) a.part_sums[first * 4 + 2] = tot;
+    probe_stamp<PROBE>(probe, 14);          // exit
 }
 
 // ------------------------------------------------------------------------------------------

@@ -265,10 +265,11 @@ __global__ __launch_bounds__(VAE_NT) void k_decoder_bwd_data(DecBwdDataArgs a) {
 
 // decoder reverse, WEIGHT half as a launch of its own (stand-alone entry point, probes; the training step runs the same device
 // function as riders of the reverse factor launch)
-template <int NT>
+// EXCL: the three-type layout (a rider runs one layer group: the staged operands of the groups share registers, vae_dev.hpp)
+template <int NT, bool EXCL>
 __global__ __launch_bounds__(NT) void k_decoder_bwd_weights(DecWgradArgs a) {
     extern __shared__ __align__(16) real smem[];
-    decoder_wgrad_rider<NT>(a, blockIdx.x, smem);
+    decoder_wgrad_rider<NT, false, EXCL>(a, blockIdx.x, smem);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -517,11 +518,16 @@ extern "C" int svgp_mnist_decoder_bwd_weights(const svgp_mnist_cfg* c, const dou
     SVGP_REQUIRE(n_types >= 1 && n_types <= 3, SVGP_ERR_INVALID, "n_types=%d (1, 2 or 3 workgroups per image)", n_types);
     const DecWgradArgs a = svgp_make_dec_wgrad_args(c, wl, images, ws, state, n_types);
     const size_t lds = (size_t)dec_wgrad_lds(threads, c->L, n_types) * sizeof(real);
-    int rc = threads == 256 ? set_dyn_lds(k_decoder_bwd_weights<256>, lds) : set_dyn_lds(k_decoder_bwd_weights<512>, lds);
-    if (rc) return rc;
     const dim3 grid(a.n_slots * a.n_types);
-    if (threads == 256) hipLaunchKernelGGL(k_decoder_bwd_weights<256>, grid, dim3(256), lds, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(k_decoder_bwd_weights<512>, grid, dim3(512), lds, (hipStream_t)stream, a);
+#define WGRAD_LAUNCH(NT_, EXCL_)                                                                                                  \
+    do {                                                                                                                          \
+        int rc = set_dyn_lds(k_decoder_bwd_weights<NT_, EXCL_>, lds);                                                             \
+        if (rc) return rc;                                                                                                        \
+        hipLaunchKernelGGL((k_decoder_bwd_weights<NT_, EXCL_>), grid, dim3(NT_), lds, (hipStream_t)stream, a);                    \
+    } while (0)
+    if (threads == 256) { if (n_types == 3) WGRAD_LAUNCH(256, true); else WGRAD_LAUNCH(256, false); }
+    else { if (n_types == 3) WGRAD_LAUNCH(512, true); else WGRAD_LAUNCH(512, false); }
+#undef WGRAD_LAUNCH
     SVGP_LAUNCH_CHECK();
     return SVGP_OK;
 }
