@@ -387,6 +387,13 @@ int svgp_mnist_decoder_fwd_bwd_data_pre(const svgp_mnist_cfg*, const double* the
 int svgp_mnist_decoder_fwd_bwd_data_pre_aji(const svgp_mnist_cfg*, const double* theta, const double* images, double* ws,
                                             const double* state, void* stream);
 int svgp_mnist_decoder_fused_regs(int L, int* out);
+/* The fused launches keep ws.dec_weff in LDS with the four parity classes of each up-convolution a padded stride apart (disjoint
+ * bank windows for the lanes of one 16-byte read; ws.dec_weff itself stays packed).  _weff_lds_offset: host arithmetic, no GPU --
+ * the offset in doubles, from the start of that image, of element `element` (packed index ((class * 4 + tap) * CIN + ci) * COUT + co)
+ * of layer 0..2 (UpC1, UpC2, UpC3: 1024, 1024, 128 elements); element == the layer's count returns the end of the layer's block;
+ * -1 outside.  _fused_lds_bytes: the dynamic LDS bytes of an image workgroup at latent size L (1..64; -1 outside), no GPU. */
+int svgp_mnist_decoder_weff_lds_offset(int layer, int element);
+int svgp_mnist_decoder_fused_lds_bytes(int L);
 /* m <= 32, no cfg.titsias: the forward block of the training step with ONLY what the decoder needs in front of it (schedule switch
  * SVGP_FWD_SPLIT; svgp_mnist_train_step and the unsharded svgp_mnist_train_step_dp run these four in the slots of
  * svgp_gp_factor_fwd_defer_aji, svgp_gp_posterior_fwd, svgp_mnist_decoder_fwd_bwd_data_pre_aji and svgp_gp_posterior_bwd_rows /

@@ -385,7 +385,9 @@ NON_STATUS = {"svgp_version": ([], C.c_int), "svgp_last_error": ([], C.c_char_p)
               "svgp_sprites_posterior_rows_workspace_elems": ([C.POINTER(PosteriorRowsCfg)], C.c_longlong),
               "svgp_ball_predict_large_workspace_elems": ([C.POINTER(BallPredictCfg)], C.c_longlong),
               "svgp_pearce_predict_long_workspace_elems": ([C.POINTER(PearcePredictCfg)], C.c_longlong),
-              "svgp_svigp_scale_offset": ([C.c_int, C.c_int, C.c_int], C.c_longlong)}
+              "svgp_svigp_scale_offset": ([C.c_int, C.c_int, C.c_int], C.c_longlong),
+              "svgp_mnist_decoder_weff_lds_offset": ([C.c_int, C.c_int], C.c_int),
+              "svgp_mnist_decoder_fused_lds_bytes": ([C.c_int], C.c_int)}
 
 _lib = None
 

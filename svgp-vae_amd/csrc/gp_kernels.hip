@@ -2045,6 +2045,18 @@ extern "C" int svgp_mnist_decoder_fused_regs(int L, int* out) {
     out[2] = out[5] = (int)(svgp_vae::dec_fwd_bwd_lds(L) * sizeof(real));
     return SVGP_OK;
 }
+// Where the fused launch keeps element `element` (packed index: class, tap, ci, co) of layer 0..2's effective weights in LDS, in
+// doubles from the start of the weight image; element == the layer's count gives the end of its block.  -1 outside.  Host arithmetic
+// only: the constexpr function the kernel stages with (vae_dev.hpp).
+extern "C" int svgp_mnist_decoder_weff_lds_offset(int layer, int element) {
+    const int nwe[3] = {svgp_vae::UpC1::NWE, svgp_vae::UpC2::NWE, svgp_vae::UpC3::NWE};
+    if (layer < 0 || layer > 2 || element < 0 || element > nwe[layer]) return -1;
+    return svgp_vae::dec_weff_lds_offset(layer, element);
+}
+// dynamic LDS bytes of an image workgroup of the fused launch at latent size L (what svgp_mnist_decoder_fused_regs reports in out[2])
+extern "C" int svgp_mnist_decoder_fused_lds_bytes(int L) {
+    return L >= 1 && L <= 64 ? (int)(svgp_vae::dec_fwd_bwd_lds(L) * sizeof(real)) : -1;
+}
 extern "C" int svgp_mnist_decoder_bwd_data_aji_regs(int* out) {
     SVGP_REQUIRE(out, SVGP_ERR_INVALID, "out is NULL");
     hipFuncAttributes fa;

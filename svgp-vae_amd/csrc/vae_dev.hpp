@@ -87,6 +87,37 @@ __device__ __forceinline__ void tap_operands(real (&v)[N], const real* p) {
 #pragma unroll
     for (int i = 0; i < N; ++i) asm volatile("" : "+v"(v[i]));
 }
+// ... with the tap's weights in the same group (UpConv3::fwd_valu<true, true>, the fused decoder launch only): N x COG values at
+// wk[ci * COUT + g], issued before the first wait, so a tap trip is ONE LDS round trip (with the weights read behind the pin it is
+// two: the activations' lgkmcnt(0), then the weights').  They are read as 16-byte vectors -- (ci, g = 0..1) for COG = 2, (ci, ci + 1)
+// for a single output channel -- because plain loads of two neighbouring doubles compile to ds_read2_b64, the 128 B/clk form.
+// `wk` MUST be 16-byte aligned: the vector type tells the compiler so, and a ds_read_b128 off 16 bytes is replayed at ~64 cycles.
+// UpConv3 asserts the strides; the caller asserts the base where it forms it (dec_fwd_bwd_we_offset).  A kernel whose We is only
+// 8-byte aligned (k_generate: an odd count of doubles in front of it) must not take this form.
+typedef double d2v_t __attribute__((ext_vector_type(2)));
+template <int N, int COG, int COUT>
+__device__ __forceinline__ void tap_operand_group(real (&v)[N], real (&wv)[N * COG], const real* p, const real* wk) {
+    static_assert(COG == 2 || (COG == 1 && COUT == 1 && N % 2 == 0), "weights of a tap as 16-byte vectors");
+#pragma unroll
+    for (int i = 0; i < N; ++i) v[i] = p[i];
+    if constexpr (COG == 2) {
+#pragma unroll
+        for (int ci = 0; ci < N; ++ci) {
+            const d2v_t w2 = *reinterpret_cast<const d2v_t*>(wk + ci * COUT);
+            wv[2 * ci] = w2.x; wv[2 * ci + 1] = w2.y;
+        }
+    } else {
+#pragma unroll
+        for (int ci = 0; ci < N; ci += 2) {
+            const d2v_t w2 = *reinterpret_cast<const d2v_t*>(wk + ci);
+            wv[ci] = w2.x; wv[ci + 1] = w2.y;
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < N; ++i) asm volatile("" : "+v"(v[i]));
+#pragma unroll
+    for (int i = 0; i < N * COG; ++i) asm volatile("" : "+v"(wv[i]));
+}
 
 struct TapP { int oy, ox, woff, ooy, oox; };
 template <int NTAP, int CI, int CO, int NT, typename TapFn>
@@ -246,11 +277,21 @@ struct Conv3 {
 // is accumulated on We (folded back to w once per workgroup).  Mathematically identical to the
 // reference's UpSampling2D + Conv2D (VAE_utils.py:132-140); summation order differs (1e-16 level).
 // ---------------------------------------------------------------------------------------------
-template <int HS, int PAD, int CIN, int COUT, int NT = VAE_NT>
+// WCS: distance in doubles between the four parity classes of the We image that fwd_valu, bwd_data_valu and bwd_data_mfma READ
+// (build_weff, fold_grad and the weight-gradient forms keep the packed layout, which is also that of ws.dec_weff).  Packed, the class
+// stride is 0 mod the 256-byte bank row, and the lanes of one ds_read_b128 group -- neighbouring output pixels, hence different
+// classes -- read different addresses on the same banks.  The fused decoder launch pads it (dec_weff_lds_index below).
+template <int HS, int PAD, int CIN, int COUT, int NT = VAE_NT, int WCS = 4 * CIN * COUT>
 struct UpConv3 {
     static constexpr int HOUT = 2 * HS - 2 + 2 * PAD;
     static constexpr int NPIX = HOUT * HOUT;
     static constexpr int NWE = 16 * CIN * COUT;          // effective weights
+    static constexpr int NWC = 4 * CIN * COUT;           // ... of one parity class
+    static constexpr int LWE = 3 * WCS + NWC;            // doubles of the LDS image with class stride WCS (= NWE when packed)
+    // every 16-byte weight read of fwd_valu<true, true> starts at an even count of doubles from We, which its caller keeps 16-byte aligned
+    static_assert(WCS >= NWC && WCS % 2 == 0 && (CIN * COUT) % 2 == 0, "class stride of the LDS weight image");
+    // packed index (class, tap, ci, co) -> index in the image with class stride WCS
+    static __host__ __device__ constexpr int lds_index(int e) { return (e / NWC) * WCS + e % NWC; }
     static constexpr int NW = 9 * CIN * COUT;            // raw weights
     static constexpr int COG = (COUT % 2 == 0) ? 2 : 1;
     static constexpr int NCG = COUT / COG;
@@ -260,6 +301,7 @@ struct UpConv3 {
 
     // We (LDS) from raw w (global or LDS)
     static __device__ void build_weff(const real* w, real* We) {
+        static_assert(WCS == NWC, "packed layout");
         for (int e = threadIdx.x; e < NWE; e += NT) {
             const int co = e % COUT, ci = (e / COUT) % CIN, tap = (e / (COUT * CIN)) % 4, cls = e / (COUT * CIN * 4);
             const int ty = tap >> 1, tx = tap & 1, py = cls >> 1, px = cls & 1;
@@ -274,6 +316,7 @@ struct UpConv3 {
     }
     // raw-weight gradient from the effective-weight gradient: gw[ky][kx] = sum_classes gWe[cls][T,T]
     static __device__ void fold_grad(const real* gWe, real* gw) {
+        static_assert(WCS == NWC, "packed layout");
         for (int e = threadIdx.x; e < NW; e += NT) {
             const int co = e % COUT, ci = (e / COUT) % CIN, kx = (e / (COUT * CIN)) % 3, ky = e / (COUT * CIN * 3);
             real s = 0;
@@ -293,8 +336,11 @@ struct UpConv3 {
     // LDS loads of an item: ~85 VGPRs fewer, same FMA order per output (bias, then ty, tx, ci), so the same bits.  For kernels that
     // must stay within 168 VGPRs (decoder_fwd_bwd_data_images below).  Its activations come through tap_operands (unconditional
     // vector loads, select afterwards); the unrolled form keeps the predicated reads, with which it is faster.
-    template <bool ROLL = false>
+    // WVEC (with ROLL): the tap's weights join the activations' group as 16-byte vector loads (tap_operand_group).  Only for a We that
+    // is 16-byte aligned -- the caller's static_assert, where it forms the pointer; the default is the form for any 8-byte aligned We.
+    template <bool ROLL = false, bool WVEC = false>
     static __device__ void fwd_valu(const real* in, const real* We, const real* bias, real* out) {
+        static_assert(ROLL || !WVEC, "the grouped weight reads exist in the rolled form only");
         constexpr int TAP_UNROLL = ROLL ? 1 : 2;     // 1: no unrolling; 2 = the trip count: full
         for (int it = threadIdx.x; it < NPIX * NCG; it += NT) {
             const int cg = it % NCG, p = it / NCG, x = p % HOUT, y = p / HOUT;
@@ -302,7 +348,7 @@ struct UpConv3 {
             real acc[COG];
 #pragma unroll
             for (int g = 0; g < COG; ++g) acc[g] = bias[cg * COG + g];
-            const real* wc = We + ((py * 2 + px) * 4) * CIN * COUT + cg * COG;
+            const real* wc = We + (py * 2 + px) * WCS + cg * COG;
 #pragma unroll TAP_UNROLL
             for (int ty = 0; ty < 2; ++ty) {
                 const int sy = Y + ty;
@@ -313,15 +359,26 @@ struct UpConv3 {
                     const bool valid = vy && ((unsigned)sx < (unsigned)HS);
                     const real* src = in + (valid ? (sy * HS + sx) * CIN : 0);
                     const real* wk = wc + (ty * 2 + tx) * CIN * COUT;
-                    real av[CIN];
-                    if constexpr (ROLL) tap_operands(av, src);
+                    if constexpr (WVEC) {
+                        real av[CIN], wv[CIN * COG];
+                        tap_operand_group<CIN, COG, COUT>(av, wv, src, wk);
 #pragma unroll
-                    for (int ci = 0; ci < CIN; ++ci) {
-                        real a;
-                        if constexpr (ROLL) a = valid ? av[ci] : real(0);
-                        else a = valid ? src[ci] : real(0);
+                        for (int ci = 0; ci < CIN; ++ci) {
+                            const real a = valid ? av[ci] : real(0);
 #pragma unroll
-                        for (int g = 0; g < COG; ++g) acc[g] += a * wk[ci * COUT + g];
+                            for (int g = 0; g < COG; ++g) acc[g] += a * wv[ci * COG + g];
+                        }
+                    } else {
+                        real av[CIN];
+                        if constexpr (ROLL) tap_operands(av, src);
+#pragma unroll
+                        for (int ci = 0; ci < CIN; ++ci) {
+                            real a;
+                            if constexpr (ROLL) a = valid ? av[ci] : real(0);
+                            else a = valid ? src[ci] : real(0);
+#pragma unroll
+                            for (int g = 0; g < COG; ++g) acc[g] += a * wk[ci * COUT + g];
+                        }
                     }
                 }
             }
@@ -348,7 +405,9 @@ struct UpConv3 {
                     const int x = 2 * (Xs - tx) + px + PAD;
                     const bool valid = vy && ((unsigned)x < (unsigned)HOUT);
                     const real* dp = dpre + (valid ? (y * HOUT + x) * COUT : 0);
-                    const real* wk = We + (((py * 2 + px) * 4 + ty * 2 + tx) * CIN + ig * CIG) * COUT;
+                    // (packed: the expression as it always stood -- written the other way the same sum compiles to other code)
+                    const real* wk = WCS == NWC ? We + (((py * 2 + px) * 4 + ty * 2 + tx) * CIN + ig * CIG) * COUT
+                                                : We + (py * 2 + px) * WCS + ((ty * 2 + tx) * CIN + ig * CIG) * COUT;
 #pragma unroll
                     for (int co = 0; co < COUT; ++co) {
                         const real d = valid ? dp[co] : real(0);
@@ -365,6 +424,7 @@ struct UpConv3 {
     // gWe += sum_pixels in * dpre ; gb += sum_pixels dpre.  item = (class, tap, ci, pixel chunk) -> COUT
     // outputs; chunks combined through `scratch` (>= VAE_SCRATCH reals) in fixed order.  Ends with a barrier.
     static __device__ void bwd_weight_valu(const real* in, const real* dpre, real* gWe, real* gb, real* scratch) {
+        static_assert(WCS == NWC, "packed layout");
         constexpr int NTC = 16 * CIN;
         constexpr int NCH0 = NT / NTC, NCH1 = VAE_SCRATCH / NWE;
         constexpr int NCH = NCH0 < NCH1 ? (NCH0 < 1 ? 1 : NCH0) : NCH1;
@@ -423,13 +483,14 @@ struct UpConv3 {
             const int py = (t >> 3) & 1, ty = (t >> 2) & 1, px = (t >> 1) & 1, tx = t & 1;
             oy[t] = py + PAD - 2 * ty;
             ox[t] = px + PAD - 2 * tx;
-            wo[t] = ((py * 2 + px) * 4 + ty * 2 + tx) * CIN * COUT;
+            wo[t] = (py * 2 + px) * WCS + (ty * 2 + tx) * CIN * COUT;
         }
         gg_fwd<16, true, false, COUT, CIN, NT>(dpre, HOUT, HOUT, HS, HS, 2, 2, oy, ox, wo, We, COUT, nullptr, din, HS, 1, 1, 0, 0);
     }
 
     // gWe += sum_pixels in * dpre ; gb += sum_pixels dpre.  Ends with a barrier.
     static __device__ void bwd_weight_mfma(const real* in, const real* dpre, real* gWe, real* gb, real* scratch) {
+        static_assert(WCS == NWC, "packed layout");
         if (COUT >= 2) {
             // 16 (class, tap) pairs = 16 "taps" of one gather-GEMM over the HOUT/2 x HOUT/2 class grid
             auto tapfn = [](int t) {
@@ -866,8 +927,13 @@ __device__ __forceinline__ void decoder_bwd_data_images(const DecBwdDataArgs& a,
 // second launch consumed only what workgroup n of the first produced: here a1, a2, recon and the weights stay in LDS between the
 // halves, the image pixels stay in registers (thread t owns pixels t and t + 512: squared error AND d3), d3 overwrites the
 // reconstruction in place.  Only the dense weights, the biases and ws.dec_weff are staged (the raw convolution weights are never
-// read in the `_pre` form): dec_fwd_bwd_lds(L) reals, 75.5 KB at L = 16, so two workgroups fit a CU (the rider form,
+// read in the `_pre` form): dec_fwd_bwd_lds(L) reals, 75.9 KB at L = 16, so two workgroups fit a CU (the rider form,
 // k_decoder_fwd_bwd_data in gp_kernels.hip, relies on that and on <= 168 VGPRs: the forward runs its rolled-tap form).
+// The LDS image of ws.dec_weff is NOT a copy: the staging loop places class c of a layer at c * WCS instead of c * 4 CIN COUT
+// (UpC1L / UpC2L / UpC3L and dec_weff_lds_index below; 54 doubles of padding in all), which is what the rolled forward's 16-byte
+// weight reads need to be conflict-free, and the three layers' forward, the VALU data reverse of UpC3 and the `wo` tables of the two
+// MFMA data reverses address it through the same WCS.  A tap trip of the forward is one group of LDS reads (tap_operand_group: 4
+// activation + 8 weight ds_read_b128 in UpC1 / UpC2, 4 + 4 in UpC3) with counted waits.  NOTEBOOK 14.5e.
 // The z / pixel loads of an image are issued one image ahead (the first: before the weight staging).  The staging behind them is
 // still lds_copy_in: twelve dependent round trips.  Staged in groups (stage_issue / stage_copy above) the launch with its riders was
 // no faster stand-alone and the straight-line form cost six registers (170 > 168), so this kernel kept the loops (NOTEBOOK 14.5c).
@@ -885,9 +951,38 @@ struct DecFwdBwdArgs {
     real* h0g; real* a1g; real* a2g; real* recon; real* part_sums;
     real* d2g; real* d1g; real* dh0g; real* zbar;
 };
-__host__ __device__ constexpr int dec_fwd_bwd_lds(int L) {
-    return L * 128 + 128 + 32 + DEC_NWE + 64 + 128 + 512 + 1568 + 784 + 1568 + 512 + 128 + 16;
+// The LDS image of the effective weights in this launch: ws.dec_weff with the class stride of each layer padded, so that the four
+// parity classes fall on disjoint windows of the 64-bank (256-byte) row of ds_read_b128.  In UpC1 / UpC2 the 16 lanes of a read
+// group are 4 output pixels x 4 channel pairs: a class needs 4 x 16 B = 64 B per (tap, ci), so the stride is 64 B past a multiple
+// of the row (256 + 8 doubles).  In UpC3 a lane is a pixel and a class needs 16 B per (tap, ci pair): 32 + 2 doubles.  Lanes of one
+// class read one address per channel pair (broadcast), lanes of different classes no common bank.  Only this launch uses the image;
+// ws.dec_weff itself, the riders and every other kernel keep the packed layout.
+using UpC1L = UpConv3<4, 1, 8, 8, VAE_NT, 256 + 8>;
+using UpC2L = UpConv3<8, 0, 8, 8, VAE_NT, 256 + 8>;
+using UpC3L = UpConv3<14, 1, 8, 1, VAE_NT, 32 + 2>;
+#define DEC_LWE (UpC1L::LWE + UpC2L::LWE + UpC3L::LWE)      // 1048 + 1048 + 134 = 2230
+static_assert(UpC1L::LWE % 2 == 0 && UpC2L::LWE % 2 == 0, "the three images start 16-byte aligned");
+// offset in the image (doubles from We1) of element e of layer 0..2, packed index (class, tap, ci, co); e = NWE gives the layer's end
+__host__ __device__ constexpr int dec_weff_lds_offset(int layer, int e) {
+    return layer == 0   ? (e < UpC1::NWE ? UpC1L::lds_index(e) : UpC1L::LWE)
+           : layer == 1 ? UpC1L::LWE + (e < UpC2::NWE ? UpC2L::lds_index(e) : UpC2L::LWE)
+                        : UpC1L::LWE + UpC2L::LWE + (e < UpC3::NWE ? UpC3L::lds_index(e) : UpC3L::LWE);
 }
+// ... of element i of ws.dec_weff (the three layers back to back)
+__host__ __device__ constexpr int dec_weff_lds_index(int i) {
+    return i < UpC1::NWE               ? dec_weff_lds_offset(0, i)
+           : i < UpC1::NWE + UpC2::NWE ? dec_weff_lds_offset(1, i - UpC1::NWE)
+                                       : dec_weff_lds_offset(2, i - UpC1::NWE - UpC2::NWE);
+}
+// doubles in front of the image in the launch's LDS block: dense weights L * 128 | dense bias 128 | convolution biases 32
+__host__ __device__ constexpr int dec_fwd_bwd_we_offset(int L) { return L * 128 + 128 + 32; }
+// even for every L (128 L is even whatever L is: checking two consecutive L covers the constant): with the block 16-byte aligned
+// (`extern __shared__ __align__(16)`) We1, and with the even LWE above We2 and We3, are 16-byte aligned, as fwd_valu<true, true> needs
+static_assert(dec_fwd_bwd_we_offset(1) % 2 == 0 && dec_fwd_bwd_we_offset(2) % 2 == 0 && 128 % 2 == 0, "We1 16-byte aligned");
+__host__ __device__ constexpr int dec_fwd_bwd_lds(int L) {
+    return dec_fwd_bwd_we_offset(L) + DEC_LWE + 64 + 128 + 512 + 1568 + 784 + 1568 + 512 + 128 + 16;
+}
+static_assert(dec_fwd_bwd_lds(16) * 8 <= 80 * 1024, "two workgroups per CU at L = 16");
 template <bool PROBE = false>
 __device__ __forceinline__ void decoder_fwd_bwd_data_images(const DecFwdBwdArgs& a, int first, int stride, real* smem,
                                                             unsigned long long* probe = nullptr) {
@@ -895,10 +990,10 @@ __device__ __forceinline__ void decoder_fwd_bwd_data_images(const DecFwdBwdArgs&
     real* w = smem;                  // dense weights L*128 | dense bias 128 (contiguous in theta)
     real* db = w + a.L * 128;
     real* cb = db + 128;             // c1b (8) | c2b (8) | c3b (1)
-    real* We1 = cb + 32;             // effective weights
-    real* We2 = We1 + UpC1::NWE;
-    real* We3 = We2 + UpC2::NWE;
-    real* z = We3 + UpC3::NWE;       // 64
+    real* We1 = smem + dec_fwd_bwd_we_offset(a.L);   // = cb + 32: effective weights, padded class strides (dec_weff_lds_index), 16-byte aligned
+    real* We2 = We1 + UpC1L::LWE;
+    real* We3 = We2 + UpC2L::LWE;
+    real* z = We3 + UpC3L::LWE;      // 64
     real* h0 = z + 64;               // 128
     real* a1 = h0 + 128;             // 512
     real* a2 = a1 + 512;             // 1568
@@ -916,7 +1011,7 @@ __device__ __forceinline__ void decoder_fwd_bwd_data_images(const DecFwdBwdArgs&
     lds_copy_in(w, a.th_dec + od.dw, a.L * 128 + 128);
     if (t < 8) { cb[t] = a.th_dec[od.c1b + t]; cb[8 + t] = a.th_dec[od.c2b + t]; }
     if (t == 0) cb[16] = a.th_dec[od.c3b];
-    lds_copy_in(We1, a.weff, DEC_NWE);
+    for (int i = t; i < DEC_NWE; i += blockDim.x) We1[dec_weff_lds_index(i)] = a.weff[i];     // lds_copy_in with the index remap
     const real gscale = (a.geco ? lag * a.inv_bglobal : real(1)) / real(784);
     real sq = 0;
     // (probe slots 2..13 are those of the workgroup's LAST image)
@@ -933,13 +1028,13 @@ __device__ __forceinline__ void decoder_fwd_bwd_data_images(const DecFwdBwdArgs&
         }
         __syncthreads();
         probe_stamp<PROBE>(probe, 3);       // dense
-        UpC1::fwd_valu<true>(h0, We1, cb, a1);
+        UpC1L::fwd_valu<true, true>(h0, We1, cb, a1);
         __syncthreads();
         probe_stamp<PROBE>(probe, 4);       // UpC1 forward
-        UpC2::fwd_valu<true>(a1, We2, cb + 8, a2);
+        UpC2L::fwd_valu<true, true>(a1, We2, cb + 8, a2);
         __syncthreads();
         probe_stamp<PROBE>(probe, 5);       // UpC2 forward
-        UpC3::fwd_valu<true>(a2, We3, cb + 16, d3);
+        UpC3L::fwd_valu<true, true>(a2, We3, cb + 16, d3);
         __syncthreads();
         probe_stamp<PROBE>(probe, 6);       // UpC3 forward
         lds_copy_out(a.h0g + (size_t)n * 128, h0, 128);
@@ -969,7 +1064,7 @@ __device__ __forceinline__ void decoder_fwd_bwd_data_images(const DecFwdBwdArgs&
         }
         __syncthreads();
         probe_stamp<PROBE>(probe, 7);       // copy-outs, squared error, d3, next image's loads issued
-        UpC3::bwd_data_valu(d3, We3, d2);
+        UpC3L::bwd_data_valu(d3, We3, d2);
         __syncthreads();
         probe_stamp<PROBE>(probe, 8);       // UpC3 data-reverse
         for (int i = t; i < 1568; i += VAE_NT) {
@@ -979,7 +1074,7 @@ __device__ __forceinline__ void decoder_fwd_bwd_data_images(const DecFwdBwdArgs&
         }
         svgp_lds_barrier();             // (the stores to d2g / d1g / dh0g are for a later launch: no wave waits for them here)
         probe_stamp<PROBE>(probe, 9);       // d2 = d2 * elu', stored
-        UpC2::bwd_data_mfma(d2, We2, d1);
+        UpC2L::bwd_data_mfma(d2, We2, d1);
         svgp_lds_barrier();
         probe_stamp<PROBE>(probe, 10);      // UpC2 data-reverse
         for (int i = t; i < 512; i += VAE_NT) {
@@ -989,7 +1084,7 @@ __device__ __forceinline__ void decoder_fwd_bwd_data_images(const DecFwdBwdArgs&
         }
         svgp_lds_barrier();
         probe_stamp<PROBE>(probe, 11);      // d1 = d1 * elu', stored
-        UpC1::bwd_data_mfma(d1, We1, dh0);
+        UpC1L::bwd_data_mfma(d1, We1, dh0);
         svgp_lds_barrier();
         probe_stamp<PROBE>(probe, 12);      // UpC1 data-reverse
         if (t < 128) a.dh0g[(size_t)n * 128 + t] = dh0[t];
