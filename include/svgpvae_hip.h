@@ -1027,6 +1027,50 @@ int svgp_casale_predict_var(int T, int N, int H, const double* K_tn, const doubl
                             const double* alpha, double* var, void* stream);
 int svgp_scale_f64(long long n, double f, double* x, void* stream);
 
+/* ---- Casale GP-VAE: posterior cache and conditional generation (casale_generate.hip) ----------------
+ * predict_test_set_Casale (GPVAE_Casale_model.py:158-203) without the train set.  The posterior at a query row
+ * x* = [id, angle, o*] depends on the train rows only through P = (alpha I + V^T V)^-1 (H,H) and U = P V^T Z (H,L) of the
+ * block above, plus L_W (Q,Q).  With kappa_r = k_W(angle*, angle_r), lambda = L_W^-1 kappa (forward substitution) and
+ * v*[k Q + r] = on*_k lambda_r (on* = o*, row-normalised with cfg.normalize_obj):  K_*n = v*^T V^T exactly, and
+ *   mean* = v*^T U (L)      var* = k** - |v*|^2 + alpha v*^T P v*  (ONE scalar per row)      k** = amplitude^2 |on*|^2
+ * which are K_*n K_inv Z and k** - k*^T K_inv k* of the reference.  z[i,l] = mean[i,l] + eps[i,l] sqrt(var[i]): row i's own
+ * variance for all its channels -- NOT the reference's tiling var[(i L + l) mod T] (:194, sic), which is no function of the
+ * query row; svgp_casale_predict_var's caller keeps that tiling.
+ * The cache is ONE float64 array [angles (Q) | L_W (Q,Q) | U (H,L) | P (H,H)], each field on a 16-element boundary
+ * (svgp_casale_cache_layout_get); P is stored as (P + P^T) / 2, symmetric bit for bit.
+ *   svgp_casale_cache_build : from the latent rows Z (N,L) of the sorted train set: the front half of svgp_casale_gp_fwd
+ *                        (svgp_casale_v_fwd, G, P, W, U on `ws`, the svgp_casale_layout workspace; no batch range, no row
+ *                        kernel), then one kernel that writes the cache.  gp, angles, obj_idx, ang_idx as above.
+ *   svgp_casale_generate : b query rows aux (b, 2+M) = [id, angle, o_1..o_M] -> images_out (b,28,28,1) = decode(z).  theta is
+ *                        the flat parameter vector [encoder | decoder | l_GP, amplitude, alpha | object_vectors] (decoder at
+ *                        n_enc, GP suffix at n_vae of svgp_casale_layout).  gather != 0: the object vector of a row is table row
+ *                        (int)row[0] (a row whose id is outside [0, n_obj) gets NaN images and moments instead of a read
+ *                        outside the table); gather == 0: the row's own columns 2:.  eps (b,L) may be NULL: z = mean.
+ *                        mean_out (b,L) and var_out (b) may each be NULL.  H <= 256: exactly ONE launch for any b (kappa,
+ *                        lambda, v*, both moments, the sample and the decoder per image in a workgroup that strides over the
+ *                        images; decoder weights and L_W staged in LDS once).  256 < H <= 2048: per pass of 256 rows a row
+ *                        kernel (v*, k**), svgp_dgemm_batched for v* P and v* U, a row-sum kernel, the decode launch.  Every
+ *                        sum has a fixed order: a row gives the same bits wherever it stands in a batch of any size.
+ *                        work: svgp_casale_generate_workspace_elems(cfg, b) doubles; 0 for H <= 256 (work may be NULL).
+ *   svgp_casale_generate_route : the launches of one pass as text, one name per line in launch order, from the plan the call
+ *                        itself walks; needs no device.
+ * cfg: N, n_obj, Q, M, L, normalize_obj as for the block above (b_cap >= 1; train_gp / train_ov are not read).
+ * Refused before any launch: svgp_casale_layout_get's refusals (Q > 32, H > 2048, M > 128, L > 64: SVGP_ERR_UNSUPPORTED);
+ * NULL theta / cache / aux / images_out, b < 0, NULL work where the size is non-zero, gather with n_obj < 1
+ * (SVGP_ERR_INVALID).  b = 0 returns SVGP_OK without a launch.  Plain launches on `stream`, no allocation, no
+ * synchronisation. */
+typedef struct {
+    int64_t angles, L_W, U, P, total;
+} svgp_casale_cache_layout;
+int svgp_casale_cache_layout_get(const svgp_casale_cfg*, svgp_casale_cache_layout* out);
+int svgp_casale_cache_build(const svgp_casale_cfg*, const double* gp, const double* angles, const int32_t* obj_idx,
+                            const int32_t* ang_idx, const double* Z, double* ws, double* cache, void* stream);
+long long svgp_casale_generate_workspace_elems(const svgp_casale_cfg*, long long b);
+int svgp_casale_generate(const svgp_casale_cfg*, long long b, const double* theta, const double* cache, const double* aux,
+                         int gather, const double* eps, double* images_out, double* mean_out, double* var_out, double* work,
+                         void* stream);
+int svgp_casale_generate_route(const svgp_casale_cfg*, char* buf, int cap);
+
 /* ---- bias analysis of the inducing mean vector (bias.hip): MNIST_experiment.py --bias_analysis, supplement C.4 ----------
  * The mean vector of channel l, c K_mm (Sigma_l + jI)^-1 K_mb (y_l / noise_l) with c = N_train / b (SVGPVAE_model.py:345-370),
  * is ws[mu_hat] (L, m) of every step.  The reference appends it to a host list every step and averages the list at the end

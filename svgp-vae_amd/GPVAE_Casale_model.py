@@ -596,6 +596,20 @@ class CasaleStepEngine:
             return self.stage.named("qvar_b", b)
         raise KeyError(name)
 
+    def posterior_cache(self, latent="sample", eps_full=None):
+        """generate.CasalePosteriorCache of the engine's live parameters: the encoder pass over the N train images on the
+        engine's own workspace, Z as `encode` forms it (latent="mean": qnet_mu), then the cache on the engine's GP stage.
+        No parameter leaves the device.  The stage's workspace is rewritten: ws_view of the last step is void afterwards."""
+        from .generate import CasalePosteriorCache
+        self.stream.wait_stream(torch.cuda.current_stream(self.dev))
+        with torch.cuda.stream(self.stream):
+            call("svgp_mnist_encoder_fwd", C.byref(self._cfgN), self.theta.data_ptr(), self.images.data_ptr(), self.wsN.data_ptr(),
+                 self.stream.cuda_stream)
+            take = lambda n: self.wsN[getattr(self.wlN, n):getattr(self.wlN, n) + self.N * self.L].view(self.N, self.L)
+            Z = CasalePosteriorCache._latents(take("qnet_mu"), take("qnet_var_raw"), bool(self.clip), latent, eps_full)
+        self.stream.synchronize()
+        return CasalePosteriorCache._from_stage(self.theta, self.stage, self.GP.ov_joint, Z)
+
     def predict(self, test_images, test_aux, take_mean=False, eps_full=None, epsilon=None):
         """predict_test_set_Casale with the engine's current parameters: a fresh latent sample of the train set, then the
         GP predictive posterior at the test rows."""

@@ -99,6 +99,11 @@ class CasaleLayout(C.Structure):
     _fields_ = [(n, C.c_int64) for n in CASALE_FIELDS]
 
 
+class CasaleCacheLayout(C.Structure):
+    """svgp_casale_cache_layout (include/svgpvae_hip.h): offsets into the Casale posterior cache, in float64 elements."""
+    _fields_ = [(n, C.c_int64) for n in ("angles", "L_W", "U", "P", "total")]
+
+
 class CacheLayout(C.Structure):
     """svgp_mnist_cache_layout (include/svgpvae_hip.h): offsets into the posterior cache, in float64 elements."""
     _fields_ = [(n, C.c_int64) for n in ("acc_S", "acc_v", "acc_rows", "w", "X", "total")]
@@ -329,6 +334,10 @@ SIGNATURES = {
     "svgp_casale_predict_var": [C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P],
     "svgp_casale_v_fwd": [C.POINTER(CasaleCfg), _P, _P, _P, _P, _P, _P],
     "svgp_scale_f64": [C.c_longlong, C.c_double, _P, _P],
+    "svgp_casale_cache_layout_get": [C.POINTER(CasaleCfg), C.POINTER(CasaleCacheLayout)],
+    "svgp_casale_cache_build": [C.POINTER(CasaleCfg), _P, _P, _P, _P, _P, _P, _P, _P],
+    "svgp_casale_generate": [C.POINTER(CasaleCfg), C.c_longlong, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P],
+    "svgp_casale_generate_route": [C.POINTER(CasaleCfg), C.c_char_p, C.c_int],
     "svgp_mean_vectors_accumulate": [C.c_int, C.c_int, _P, _P, _P],
     "svgp_mean_vectors_bias": [C.c_int, C.c_int, _P, _P, _P, _P],
     "svgp_rotate_cubic_f64": [C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P],
@@ -382,6 +391,7 @@ NON_STATUS = {"svgp_version": ([], C.c_int), "svgp_last_error": ([], C.c_char_p)
               "svgp_svigp_workspace_elems": ([C.c_int, C.c_int, C.c_int], C.c_longlong),
               "svgp_mnist_cache_workspace_elems": ([_CFG], C.c_longlong),
               "svgp_mnist_generate_workspace_elems": ([_CFG], C.c_longlong),
+              "svgp_casale_generate_workspace_elems": ([C.POINTER(CasaleCfg), C.c_longlong], C.c_longlong),
               "svgp_sprites_posterior_rows_workspace_elems": ([C.POINTER(PosteriorRowsCfg)], C.c_longlong),
               "svgp_ball_predict_large_workspace_elems": ([C.POINTER(BallPredictCfg)], C.c_longlong),
               "svgp_pearce_predict_long_workspace_elems": ([C.POINTER(PearcePredictCfg)], C.c_longlong),
@@ -417,7 +427,8 @@ def load_library(path=None):
     # the ctypes mirrors must have the layout the library was compiled with (svgp_struct_sizeof)
     mirrors = dict(enumerate((MnistCfg, ParamLayout, WsLayout, StreamKdesc, ConvDesc, SpritesKcfg, PearceBufs, SumJob,
                               CasaleCfg, CasaleLayout, BallLargeCfg, CacheLayout)))
-    mirrors.update({13: BallPredictCfg, 14: BallPredictBufs, 15: PearcePredictCfg, 16: PearcePredictBufs})     # code 12 is not assigned
+    mirrors.update({13: BallPredictCfg, 14: BallPredictBufs, 15: PearcePredictCfg, 16: PearcePredictBufs,
+                    18: CasaleCacheLayout})                                              # codes 12 and 17 are not assigned
     for which, cls in mirrors.items():
         if lib.svgp_struct_sizeof(which) != C.sizeof(cls):
             raise SvgpError(f"{p}: sizeof({cls.__name__}) is {lib.svgp_struct_sizeof(which)} in the library but "

@@ -38,6 +38,7 @@ extern "C" int svgp_struct_sizeof(int which) {
     case 14: return (int)sizeof(svgp_ball_predict_bufs);
     case 15: return (int)sizeof(svgp_pearce_predict_cfg);
     case 16: return (int)sizeof(svgp_pearce_predict_bufs);
+    case 18: return (int)sizeof(svgp_casale_cache_layout);    // (17 stays unassigned: tests/test_pearce_predict_cpu.py pins it to -1)
     default: return -1;
     }
 }

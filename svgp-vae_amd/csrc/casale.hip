@@ -524,6 +524,28 @@ extern "C" int svgp_casale_v_fwd(const svgp_casale_cfg* c, const double* gp, con
     return SVGP_OK;
 }
 
+// The front half of svgp_casale_gp_fwd, which is all the posterior cache needs (casale_generate.hip): K_W, L_W, V, G, P, W, U
+// from the latent rows Z; no batch range, no row kernel.  The caller has validated cfg and pointers.
+int svgp_casale_hspace_fwd(const svgp_casale_cfg* c, const svgp_casale_layout& wl, const double* gp, const double* angles,
+                           const int32_t* obj_idx, const int32_t* ang_idx, const double* Z, double* ws, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    const int N = c->N, L = c->L, H = c->M * c->Q;
+    const real* alpha = gp + 2;
+    real *V = ws + wl.V, *P = ws + wl.P, *U = ws + wl.U;
+    int rc = svgp_casale_v_fwd(c, gp, angles, obj_idx, ang_idx, ws, stream);
+    if (rc) return rc;
+    rc = svgp_dgemm_splitk(1, 0, H, H, N, 1.0, V, H, V, H, 0.0, ws + wl.G, H, ws + wl.scr_splitk, wl.scr_splitk_len, stream);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_p_init, dim3(nblk((long long)H * H)), dim3(SVGP_BLOCK), 0, s, H, ws + wl.G, alpha, P);
+    SVGP_LAUNCH_CHECK();
+    rc = svgp_spd_inverse_batched(H, 1, P, ws + wl.logdet, ws + wl.scr_inv, stream);
+    if (rc) return rc;
+    rc = svgp_dgemm_splitk(1, 0, H, L, N, 1.0, V, H, Z, L, 0.0, ws + wl.W, L, ws + wl.scr_splitk, wl.scr_splitk_len, stream);
+    if (rc) return rc;
+    CAS_GEMM(0, 0, H, L, H, 1.0, P, H, 0, ws + wl.W, L, 0, 0.0, U, L, 0, 1, stream);
+    return SVGP_OK;
+}
+
 extern "C" int svgp_casale_gp_fwd(const svgp_casale_cfg* c, const double* gp, const double* angles, const int32_t* obj_idx,
                                   const int32_t* ang_idx, const double* Z, const double* zb, int lo, int hi, double* ws,
                                   void* stream) {
@@ -535,17 +557,8 @@ extern "C" int svgp_casale_gp_fwd(const svgp_casale_cfg* c, const double* gp, co
     const int N = c->N, L = c->L, H = c->M * c->Q, b = hi - lo;
     const real* alpha = gp + 2;
     real *V = ws + wl.V, *P = ws + wl.P, *U = ws + wl.U;
-    rc = svgp_casale_v_fwd(c, gp, angles, obj_idx, ang_idx, ws, stream);
+    rc = svgp_casale_hspace_fwd(c, wl, gp, angles, obj_idx, ang_idx, Z, ws, stream);
     if (rc) return rc;
-    rc = svgp_dgemm_splitk(1, 0, H, H, N, 1.0, V, H, V, H, 0.0, ws + wl.G, H, ws + wl.scr_splitk, wl.scr_splitk_len, stream);
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_p_init, dim3(nblk((long long)H * H)), dim3(SVGP_BLOCK), 0, s, H, ws + wl.G, alpha, P);
-    SVGP_LAUNCH_CHECK();
-    rc = svgp_spd_inverse_batched(H, 1, P, ws + wl.logdet, ws + wl.scr_inv, stream);
-    if (rc) return rc;
-    rc = svgp_dgemm_splitk(1, 0, H, L, N, 1.0, V, H, Z, L, 0.0, ws + wl.W, L, ws + wl.scr_splitk, wl.scr_splitk_len, stream);
-    if (rc) return rc;
-    CAS_GEMM(0, 0, H, L, H, 1.0, P, H, 0, ws + wl.W, L, 0, 0.0, U, L, 0, 1, stream);
     CAS_GEMM(0, 0, b, H, H, 1.0, V + (size_t)lo * H, H, 0, P, H, 0, 0.0, ws + wl.VPb, H, 0, 1, stream);
     hipLaunchKernelGGL(k_rows_fwd, dim3((N + 3) / 4), dim3(SVGP_BLOCK), 0, s, N, H, L, lo, hi, V, U, Z, zb, ws + wl.VPb, alpha,
                        ws + wl.VU, ws + wl.A, ws + wl.part);

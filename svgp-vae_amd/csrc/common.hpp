@@ -52,6 +52,9 @@ int svgp_dgemm_splitk_rows2(int ta, int tb, int M, int N, int K, double alpha, d
 // gp_kernels.hip: the m <= 64 form of svgp_mnist_cache_build (generate.hip), where the LDS sweep of the factor stage lives
 int svgp_cache_build_small(const svgp_mnist_cfg* c, const svgp_mnist_param_layout& pl, const double* theta, const double* accS,
                            const double* accv, const double* rows, double* w, double* X, void* stream);
+// casale.hip: the front half of svgp_casale_gp_fwd (K_W, L_W, V, G, P, W, U) for svgp_casale_cache_build (casale_generate.hip)
+int svgp_casale_hspace_fwd(const svgp_casale_cfg* c, const svgp_casale_layout& wl, const double* gp, const double* angles,
+                           const int32_t* obj_idx, const int32_t* ang_idx, const double* Z, double* ws, void* stream);
 // gp_kernels.hip: a piece set (SVGP_FWD_*, below) of the large-m forward factor stage on all channels, with the entry points' checks
 int svgp_gp_factor_fwd_pieces(const svgp_mnist_cfg* c, double* ws, void* stream, unsigned pieces);
 // gp_kernels.hip: svgp_gp_posterior_bwd_with_final whose pass 1 also forms d and the L3 partials (the d form of SVGP_FWD_SPLIT, m <= 32)
