@@ -190,8 +190,8 @@ const char* svgp_last_error(void);
  * time (a stale mirror shifts every later field silently): which = 0 svgp_mnist_cfg, 1 svgp_mnist_param_layout,
  * 2 svgp_mnist_ws_layout, 3 svgp_stream_kdesc, 4 svgp_conv_desc, 5 svgp_sprites_kcfg, 6 svgp_pearce_bufs,
  * 7 svgp_sum_job, 8 svgp_casale_cfg, 9 svgp_casale_layout, 10 svgp_ball_large_cfg, 11 svgp_mnist_cache_layout,
- * 13 svgp_ball_predict_cfg, 14 svgp_ball_predict_bufs, 15 svgp_pearce_predict_cfg, 16 svgp_pearce_predict_bufs; -1 otherwise
- * (12 is not assigned). */
+ * 13 svgp_ball_predict_cfg, 14 svgp_ball_predict_bufs, 15 svgp_pearce_predict_cfg, 16 svgp_pearce_predict_bufs,
+ * 18 svgp_casale_cache_layout, 19 svgp_cvae_cfg, 20 svgp_cvae_ws_layout; -1 otherwise (12 and 17 are not assigned). */
 int         svgp_struct_sizeof(int which);
 
 int svgp_mnist_param_layout_get(const svgp_mnist_cfg* cfg, svgp_mnist_param_layout* out);
@@ -1284,6 +1284,64 @@ int svgp_event_create(void** event_out);
 int svgp_event_record(void* event, void* stream);
 int svgp_event_elapsed_ms(void* start, void* stop, float* ms_out); /* synchronises on `stop`      */
 int svgp_event_destroy(void* event);
+
+/* ---- plain VAE / conditional VAE on rotated MNIST (csrc/cvae.hip) ---------------------------------------------------------
+ * forward_pass_standard_VAE_rotated_mnist (SVGPVAE_model.py:718-782) on mnistVAE (cvae = 0) or mnistCVAE (cvae = 1,
+ * VAE_utils.py:165-258), float64.  aux is (b, 2) rows [id, angle]; only cvae = 1 reads it (it may be NULL otherwise).
+ *   encoder   cvae: input channels [image, sin a, cos a]; three stride-2 valid 3 x 3 ELU convolutions, flatten to 32, cvae: concatenate
+ *             [sin a, cos a] (34); dense to 2 L.  mu = enc[:, :L], var = exp(enc[:, L:]), with clip_qs clipped to [1e-3, 10] (the clip mask
+ *             enters the reverse pass).  z = mu + eps sqrt(var); eps (b, L) given, or NULL: Philox on state[SVGP_ST_RNG_CTR], index n L + l,
+ *             and the counter advances by one per call.
+ *   decoder   cvae: [z, sin a, cos a] (L + 2); dense 128 -> (4, 4, 8), cvae: two constant planes -> (4, 4, 10); up 2x, conv same, ELU;
+ *             up 2x, conv valid, ELU; up 2x, conv 8 -> 1 same, ELU.
+ *   scalars   sq = sum (x - xhat)^2, KL = 0.5 (-b L - sum log var + sum var + sum mu^2), elbo = -(0.5 / sigma^2) sq - KL; they go to
+ *             state[SVGP_ST_ELBO], [SVGP_ST_RECON_LOSS] = sq / 784, [SVGP_ST_KL_TERM] = KL.  The step minimises -elbo.
+ * Parameters: the reference's variable-creation order under the names of svgp_mnist_param_layout (cvae = 1: enc_c1_w (3,3,3,8),
+ * enc_d_w (34, 2L), dec_d_w (L+2, 128), dec_c1_w (3,3,10,8); 6 329 parameters at L = 16, 5 721 for cvae = 0, whose layout is the first
+ * n_vae entries of svgp_mnist_param_layout); ip .. ov = n_total.
+ * svgp_cvae_train_step: TWO launches (svgp_cvae_step_route prints them).  k_cvae_step_images: min(b, 256) workgroups, workgroup g walks
+ *   the images g, g + grid, ... through forward and reverse with every activation in LDS (svgp_cvae_lds_bytes(cvae, L): the dynamic
+ *   LDS of that launch, the same for every 1 <= L <= 64; -1 for other arguments); k_cvae_reduce_adam: grad (n_total) as fixed-order
+ *   sums -- no float atomics, the same input gives the same bits --, TF1 Adam on state[SVGP_ST_LR] as svgp_adam_tf1_step computes it
+ *   (adam = 0: theta and the moments stay untouched, adam_m / adam_v may be NULL), the scalars, SVGP_ST_ADAM_T += 1 with adam.
+ *   cfg.store = 1 also writes ws.recon (b,28,28,1), ws.qnet_mu, ws.qnet_var, ws.z (b, L).
+ * svgp_cvae_forward: the same forward with the stored fields and the scalars, no reverse pass.
+ * svgp_cvae_encode: b rows -> mu, var (b, L) (clipped when cfg.clip_qs).  svgp_cvae_decode: z (b, L) and the angles of aux -> (b,28,28,1).
+ * svgp_cvae_predict (predict_CVAE, SVGPVAE_model.py:785-820; cvae = 1 only, cfg.b = test rows): encodes the n_train train rows WITHOUT
+ *   clipping, z_n = mu_n + eps_n sqrt(var_n) (eps (n_train, L) or NULL: Philox); test row t gets the mean of z_n over the train rows with
+ *   aux_train[n, 0] == aux_test[t, 0] (a comparison of doubles, rows summed in ascending n; no such row: NaN, nothing read out of range),
+ *   decoded at aux_test[t, 1]; *loss_out = mean over all test pixels of (x - xhat)^2.  Two launches (svgp_cvae_predict_route): the encoder
+ *   over the train rows, then one in which a workgroup forms its test rows' means and decodes them.  work: svgp_cvae_predict_workspace_elems.
+ * Refused before any launch: NULL cfg / pointers, b < 0, b > b_cap, cvae or store outside {0, 1}, sigma <= 0 (SVGP_ERR_INVALID);
+ * L < 1 or L > 64 (SVGP_ERR_UNSUPPORTED).  b = 0 returns SVGP_OK without a launch.  Workspace offsets depend on b_cap, not on b. */
+typedef struct {
+    int32_t b, b_cap, L;
+    int32_t cvae;       /* 0 = mnistVAE, 1 = mnistCVAE */
+    int32_t clip_qs, store;
+    double  sigma;      /* sigma_gaussian_decoder */
+} svgp_cvae_cfg;
+typedef struct {        /* offsets into ws, in float64 elements */
+    int64_t part, sums;              /* (256, part_stride) convolution weight-gradient partials; (256, 2) [sq, KL] */
+    int64_t a3, dpre, zx, dh0;       /* operand rows of the dense layers' weight gradients: (b, 32|34), (b, 2L), (b, L|L+2), (b, 128) */
+    int64_t recon, qnet_mu, qnet_var, z;
+    int64_t part_stride, total;
+} svgp_cvae_ws_layout;
+int svgp_cvae_param_layout_get(const svgp_cvae_cfg*, svgp_mnist_param_layout* out);
+int svgp_cvae_ws_layout_get(const svgp_cvae_cfg*, svgp_cvae_ws_layout* out);
+int svgp_cvae_lds_bytes(int cvae, int L);
+int svgp_cvae_step_route(const svgp_cvae_cfg*, char* buf, int cap);
+int svgp_cvae_predict_route(const svgp_cvae_cfg*, char* buf, int cap);
+int svgp_cvae_train_step(const svgp_cvae_cfg*, double* theta, const double* images, const double* aux, const double* eps, double* ws,
+                         double* grad, double* adam_m, double* adam_v, double* state, int adam, void* stream);
+int svgp_cvae_forward(const svgp_cvae_cfg*, const double* theta, const double* images, const double* aux, const double* eps, double* ws,
+                      double* state, void* stream);
+int svgp_cvae_encode(const svgp_cvae_cfg*, const double* theta, const double* images, const double* aux, double* mu, double* var,
+                     void* stream);
+int svgp_cvae_decode(const svgp_cvae_cfg*, const double* theta, const double* z, const double* aux, double* images_out, void* stream);
+long long svgp_cvae_predict_workspace_elems(const svgp_cvae_cfg*, long long n_train);
+int svgp_cvae_predict(const svgp_cvae_cfg*, long long n_train, const double* theta, const double* images_train, const double* aux_train,
+                      const double* eps, const double* images_test, const double* aux_test, double* work, double* recon_out,
+                      double* loss_out, double* state, void* stream);
 
 #ifdef __cplusplus
 }

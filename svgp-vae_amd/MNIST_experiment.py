@@ -22,7 +22,8 @@ write), `--show_pics` (no plots) and `--ram` (the reference's TensorFlow memory 
 parameters, same loaders / inducing-point init, per-epoch train MSE and the conditional-generation MSE on the test set.
 `--elbo GPVAE_Casale` mirrors run_experiment_rotated_mnist_Casale (:786-1110): Casale's GP-VAE with the three optimisation
 regimes of `--opt_regime` (joint / GP / VAE), one Adam state, conditional generation on the test set every 5 epochs.
-Other --elbo values (VAE, CVAE, GPVAE_Casale_batch) are baselines outside this build.
+`--elbo VAE | CVAE` run under `python -m svgp_vae_amd.VAE_experiment` (same flags); this module keeps refusing them and names that
+command.  `--elbo GPVAE_Casale_batch` is outside this build.
 """
 import argparse
 import json
@@ -492,6 +493,9 @@ def main(argv=None):
         return run_experiment_rotated_mnist_SVIGP_Hensman(args, vars(args))
     if args.elbo == "GPVAE_Casale":
         return run_experiment_rotated_mnist_Casale(args, vars(args))
+    if args.elbo in ("VAE", "CVAE"):
+        raise NotImplementedError(f"--elbo {args.elbo} runs under its own driver: python -m svgp_vae_amd.VAE_experiment --elbo {args.elbo} ... "
+                                  f"(same flags; DESIGN.md section 9k)")
     raise NotImplementedError(f"--elbo {args.elbo}: only SVGPVAE_Hensman / SVGPVAE_Titsias / SVIGP_Hensman / GPVAE_Casale are built "
                               f"(see DESIGN.md section 9)")
 

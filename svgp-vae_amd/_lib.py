@@ -104,6 +104,19 @@ class CasaleCacheLayout(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("angles", "L_W", "U", "P", "total")]
 
 
+class CvaeCfg(C.Structure):
+    """svgp_cvae_cfg (include/svgpvae_hip.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("b", "b_cap", "L", "cvae", "clip_qs", "store")] + [("sigma", C.c_double)]
+
+
+CVAE_WS_FIELDS = ("part", "sums", "a3", "dpre", "zx", "dh0", "recon", "qnet_mu", "qnet_var", "z", "part_stride", "total")
+
+
+class CvaeWsLayout(C.Structure):
+    """svgp_cvae_ws_layout (include/svgpvae_hip.h)."""
+    _fields_ = [(n, C.c_int64) for n in CVAE_WS_FIELDS]
+
+
 class CacheLayout(C.Structure):
     """svgp_mnist_cache_layout (include/svgpvae_hip.h): offsets into the posterior cache, in float64 elements."""
     _fields_ = [(n, C.c_int64) for n in ("acc_S", "acc_v", "acc_rows", "w", "X", "total")]
@@ -354,6 +367,15 @@ SIGNATURES = {
     "svgp_pearce_predict": [C.POINTER(PearcePredictCfg), C.POINTER(PearcePredictBufs), _P],
     "svgp_pearce_predict_long": [C.POINTER(PearcePredictCfg), C.POINTER(PearcePredictBufs), _P, _P],
     "svgp_pearce_predict_route": [C.POINTER(PearcePredictCfg), C.c_int, C.c_char_p, C.c_int],
+    "svgp_cvae_param_layout_get": [C.POINTER(CvaeCfg), C.POINTER(ParamLayout)],
+    "svgp_cvae_ws_layout_get": [C.POINTER(CvaeCfg), C.POINTER(CvaeWsLayout)],
+    "svgp_cvae_step_route": [C.POINTER(CvaeCfg), C.c_char_p, C.c_int],
+    "svgp_cvae_predict_route": [C.POINTER(CvaeCfg), C.c_char_p, C.c_int],
+    "svgp_cvae_train_step": [C.POINTER(CvaeCfg), _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int, _P],
+    "svgp_cvae_forward": [C.POINTER(CvaeCfg), _P, _P, _P, _P, _P, _P, _P],
+    "svgp_cvae_encode": [C.POINTER(CvaeCfg), _P, _P, _P, _P, _P, _P],
+    "svgp_cvae_decode": [C.POINTER(CvaeCfg), _P, _P, _P, _P, _P],
+    "svgp_cvae_predict": [C.POINTER(CvaeCfg), C.c_longlong] + [_P] * 11,
     "svgp_stream_create": [C.POINTER(_P)],
     "svgp_stream_destroy": [_P],
     "svgp_stream_sync": [_P],
@@ -397,7 +419,9 @@ NON_STATUS = {"svgp_version": ([], C.c_int), "svgp_last_error": ([], C.c_char_p)
               "svgp_pearce_predict_long_workspace_elems": ([C.POINTER(PearcePredictCfg)], C.c_longlong),
               "svgp_svigp_scale_offset": ([C.c_int, C.c_int, C.c_int], C.c_longlong),
               "svgp_mnist_decoder_weff_lds_offset": ([C.c_int, C.c_int], C.c_int),
-              "svgp_mnist_decoder_fused_lds_bytes": ([C.c_int], C.c_int)}
+              "svgp_mnist_decoder_fused_lds_bytes": ([C.c_int], C.c_int),
+              "svgp_cvae_lds_bytes": ([C.c_int, C.c_int], C.c_int),
+              "svgp_cvae_predict_workspace_elems": ([C.POINTER(CvaeCfg), C.c_longlong], C.c_longlong)}
 
 _lib = None
 
@@ -428,7 +452,7 @@ def load_library(path=None):
     mirrors = dict(enumerate((MnistCfg, ParamLayout, WsLayout, StreamKdesc, ConvDesc, SpritesKcfg, PearceBufs, SumJob,
                               CasaleCfg, CasaleLayout, BallLargeCfg, CacheLayout)))
     mirrors.update({13: BallPredictCfg, 14: BallPredictBufs, 15: PearcePredictCfg, 16: PearcePredictBufs,
-                    18: CasaleCacheLayout})                                              # codes 12 and 17 are not assigned
+                    18: CasaleCacheLayout, 19: CvaeCfg, 20: CvaeWsLayout})             # codes 12 and 17 are not assigned
     for which, cls in mirrors.items():
         if lib.svgp_struct_sizeof(which) != C.sizeof(cls):
             raise SvgpError(f"{p}: sizeof({cls.__name__}) is {lib.svgp_struct_sizeof(which)} in the library but "

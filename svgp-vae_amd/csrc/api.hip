@@ -39,6 +39,8 @@ extern "C" int svgp_struct_sizeof(int which) {
     case 15: return (int)sizeof(svgp_pearce_predict_cfg);
     case 16: return (int)sizeof(svgp_pearce_predict_bufs);
     case 18: return (int)sizeof(svgp_casale_cache_layout);    // (17 stays unassigned: tests/test_pearce_predict_cpu.py pins it to -1)
+    case 19: return (int)sizeof(svgp_cvae_cfg);
+    case 20: return (int)sizeof(svgp_cvae_ws_layout);
     default: return -1;
     }
 }
