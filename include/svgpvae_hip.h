@@ -394,6 +394,17 @@ int svgp_mnist_decoder_fused_regs(int L, int* out);
  * -1 outside.  _fused_lds_bytes: the dynamic LDS bytes of an image workgroup at latent size L (1..64; -1 outside), no GPU. */
 int svgp_mnist_decoder_weff_lds_offset(int layer, int element);
 int svgp_mnist_decoder_fused_lds_bytes(int L);
+/* The same launches keep three 8-channel activation arrays at a padded PIXEL stride in LDS (d2 and d1 for the stride-2 gathers of the
+ * two MFMA data reverses, a2 for the 16-byte gathers of the UpC3 forward; a2g, d2g, d1g stay packed) and pay for it, inside the
+ * unchanged footprint, by two aliases of arrays that are never live together (d1 in the d3 block, dh0 on h0).  Host arithmetic, no GPU:
+ * _fused_lds_array: array `which` (0 dense weights and biases, 1 effective-weight image, 2 z, 3 h0, 4 a1, 5 a2, 6 d3, 7 d2, 8 d1,
+ *   9 dh0, 10 reduction scratch) at latent size L (1..64): returns its extent in doubles and writes (where the pointer is not NULL) its
+ *   offset in doubles in the block, its pixel stride in doubles (0: no pixel structure) and the first and last phase-probe stamp
+ *   (1..14, svgp_mnist_decoder_fwd_bwd_data_pre_tail_probe) of its live interval.  -1 outside.
+ * _fused_lds_index: where packed element `packed_element` (pixel * channels + channel; for array 1 the index in ws.dec_weff) of array
+ *   1..10 lies in its block, in doubles; -1 outside. */
+int svgp_mnist_decoder_fused_lds_array(int L, int which, int* offset, int* pixel_stride, int* first_stamp, int* last_stamp);
+int svgp_mnist_decoder_fused_lds_index(int which, int packed_element);
 /* m <= 32, no cfg.titsias: the forward block of the training step with ONLY what the decoder needs in front of it (schedule switch
  * SVGP_FWD_SPLIT; svgp_mnist_train_step and the unsharded svgp_mnist_train_step_dp run these four in the slots of
  * svgp_gp_factor_fwd_defer_aji, svgp_gp_posterior_fwd, svgp_mnist_decoder_fwd_bwd_data_pre_aji and svgp_gp_posterior_bwd_rows /

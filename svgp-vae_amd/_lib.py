@@ -420,6 +420,8 @@ NON_STATUS = {"svgp_version": ([], C.c_int), "svgp_last_error": ([], C.c_char_p)
               "svgp_svigp_scale_offset": ([C.c_int, C.c_int, C.c_int], C.c_longlong),
               "svgp_mnist_decoder_weff_lds_offset": ([C.c_int, C.c_int], C.c_int),
               "svgp_mnist_decoder_fused_lds_bytes": ([C.c_int], C.c_int),
+              "svgp_mnist_decoder_fused_lds_array": ([C.c_int, C.c_int] + [C.POINTER(C.c_int)] * 4, C.c_int),
+              "svgp_mnist_decoder_fused_lds_index": ([C.c_int, C.c_int], C.c_int),
               "svgp_cvae_lds_bytes": ([C.c_int, C.c_int], C.c_int),
               "svgp_cvae_predict_workspace_elems": ([C.POINTER(CvaeCfg), C.c_longlong], C.c_longlong)}
 

@@ -2057,6 +2057,29 @@ extern "C" int svgp_mnist_decoder_weff_lds_offset(int layer, int element) {
 extern "C" int svgp_mnist_decoder_fused_lds_bytes(int L) {
     return L >= 1 && L <= 64 ? (int)(svgp_vae::dec_fwd_bwd_lds(L) * sizeof(real)) : -1;
 }
+// Array `which` (0 dense weights + biases, 1 effective-weight image, 2 z, 3 h0, 4 a1, 5 a2, 6 d3, 7 d2, 8 d1, 9 dh0, 10 reduction
+// scratch) of an image workgroup's LDS block at latent size L: returns its extent in doubles and writes its offset in doubles, its
+// pixel stride in doubles (0: no pixel structure) and the first and last probe stamp (1..14) of the phases in which it is live.
+// -1 outside.  _lds_index: where packed element (pixel * channels + channel) of that array lies in its block; -1 outside.
+// Host arithmetic only: the constexpr functions the kernel takes its pointers and index maps from (vae_dev.hpp).
+extern "C" int svgp_mnist_decoder_fused_lds_array(int L, int which, int* offset, int* pixel_stride, int* first_stamp, int* last_stamp) {
+    if (L < 1 || L > 64 || which < 0 || which >= svgp_vae::DEC_LDS_NARRAYS) return -1;
+    const svgp_vae::DecLdsArray a = svgp_vae::dec_fwd_bwd_lds_array(L, which);
+    if (offset) *offset = a.offset;
+    if (pixel_stride) *pixel_stride = a.stride;
+    if (first_stamp) *first_stamp = a.first;
+    if (last_stamp) *last_stamp = a.last;
+    return a.extent;
+}
+extern "C" int svgp_mnist_decoder_fused_lds_index(int which, int packed_element) {
+    if (which < 0 || which >= svgp_vae::DEC_LDS_NARRAYS || packed_element < 0) return -1;
+    const svgp_vae::DecLdsArray a = svgp_vae::dec_fwd_bwd_lds_array(16, which);       // extent and stride do not depend on L ...
+    if (which == svgp_vae::DEC_LDS_DENSE) return -1;                                  // ... but for the dense weights: no map
+    const int packed = which == svgp_vae::DEC_LDS_WEFF ? DEC_NWE : a.stride > 8 ? a.extent / a.stride * 8 : a.extent;
+    if (packed_element >= packed) return -1;
+    return which == svgp_vae::DEC_LDS_WEFF ? svgp_vae::dec_weff_lds_index(packed_element)
+                                           : svgp_vae::dec_fwd_bwd_lds_index(which, packed_element);
+}
 extern "C" int svgp_mnist_decoder_bwd_data_aji_regs(int* out) {
     SVGP_REQUIRE(out, SVGP_ERR_INVALID, "out is NULL");
     hipFuncAttributes fa;

@@ -19,10 +19,14 @@ typedef double d4v_t __attribute__((ext_vector_type(4)));
 //             TW: weights stored [co][ci] are read transposed (data gradient).
 //   gg_wgrad: gW_t[ci][co] += sum_pixels in_t[pixel][ci] * dout[pixel][co]; A[i = ci][k = pixel], B[k = pixel][j = co];
 //             a wave owns whole taps, so the LDS accumulators need no atomics.
-// LDS bank conflicts of the 16-pixel gathers (stride Ci doubles) cost a few cycles per fetch and hide under the
-// 64-cycle issue of the f64 MFMA.
+// SI / SO: doubles between consecutive pixels of `in` / `out` (packed: CI / CO).  A gather is one ds_read_b64 per lane, serviced as
+// two half waves of 16 pixels x 2 channels.  With input stride 2 and 8 packed doubles per pixel, neighbouring pixels of a half wave are
+// 128 bytes apart and the sixteen fall on two 16-byte windows of the 256-byte bank row: 7 distinct addresses on the busiest bank in
+// the mean (tools/lds_bank_model.py).  Every gather of a group is issued before the first MFMA, so the group's MFMA chain waits for
+// all of them: these conflicts do NOT hide under the 64-cycle issue of the f64 MFMA -- the stride-2 data reverses of the fused decoder
+// launch are 3.9 and 2.3 us of its phase timeline (NOTEBOOK 14.5d) -- and that launch pads the pixel stride (SI = 9: 2 in the mean).
 // ---------------------------------------------------------------------------------------------
-template <int NTAP, bool TW, bool ELU_BIAS, int CI, int CO, int NT = VAE_NT>
+template <int NTAP, bool TW, bool ELU_BIAS, int CI, int CO, int NT = VAE_NT, int SI = CI, int SO = CO>
 __device__ __forceinline__ void gg_fwd(const real* in, int Hi, int Wi, int Hs, int Ws, int sy, int sx,
                                        const int (&oy)[NTAP], const int (&ox)[NTAP], const int (&woff)[NTAP],
                                        const real* W, int ldw, const real* bias, real* out, int Wo, int osy, int osx,
@@ -44,13 +48,19 @@ __device__ __forceinline__ void gg_fwd(const real* in, int Hi, int Wi, int Hs, i
         const int pa = grp * 16 + r;
         const bool pv = pa < NP;
         const int ya = pv ? pa / Ws : 0, xa = pv ? pa % Ws : 0;
+        // Padded input stride: the tap addresses are formed from this one value, which the empty asm makes the compiler form per group.
+        // Without it the sixteen `pixel * SI` of a one-group layer are hoisted out of the caller's image loop and live through its
+        // MFMA phases (174 VGPRs in the fused decoder launch, 160 with it); the validity masks stay hoisted -- they are scalar.
+        // Pinning `pa` itself un-hoists those too: 218.  Packed, `pb` is dead and the address expression is the one that always stood.
+        int pb = ya * sy * Wi + xa * sx;
+        if constexpr (SI != CI) asm volatile("" : "+v"(pb));
         // A operands of the whole group first (independent LDS reads in flight together), then the MFMA chain
         real areg[NTAP * KQ];
 #pragma unroll
         for (int t = 0; t < NTAP; ++t) {
             const int iy = ya * sy + oy[t], ix = xa * sx + ox[t];
             const bool valid = pv && ((unsigned)iy < (unsigned)Hi) && ((unsigned)ix < (unsigned)Wi);
-            const real* ap = in + (valid ? (iy * Wi + ix) * CI : 0);
+            const real* ap = in + (valid ? (SI != CI ? pb + oy[t] * Wi + ox[t] : iy * Wi + ix) * SI : 0);
 #pragma unroll
             for (int kq = 0; kq < KQ; ++kq) {
                 const int c = kq * 4 + q, cc = c < CI ? c : CI - 1;
@@ -68,7 +78,7 @@ __device__ __forceinline__ void gg_fwd(const real* in, int Hi, int Wi, int Hs, i
                 const int y = po / Ws, x = po % Ws;
                 real v = acc[e];
                 if (ELU_BIAS) v = elu_f(v + bias[r]);
-                out[((y * osy + ooy) * Wo + x * osx + oox) * CO + r] = v;
+                out[((y * osy + ooy) * Wo + x * osx + oox) * SO + r] = v;
             }
         }
     }
@@ -281,8 +291,12 @@ struct Conv3 {
 // (build_weff, fold_grad and the weight-gradient forms keep the packed layout, which is also that of ws.dec_weff).  Packed, the class
 // stride is 0 mod the 256-byte bank row, and the lanes of one ds_read_b128 group -- neighbouring output pixels, hence different
 // classes -- read different addresses on the same banks.  The fused decoder launch pads it (dec_weff_lds_index below).
-template <int HS, int PAD, int CIN, int COUT, int NT = VAE_NT, int WCS = 4 * CIN * COUT>
+// Pixel strides, in doubles, of the LDS activations (packed by default; the fused decoder launch pads three, dec_act_* below):
+// FIS / FOS: of `in` / `out` of fwd_valu;  RIS: of `dpre` of bwd_data_mfma;  ROS: of `din` of bwd_data_mfma and bwd_data_valu.
+template <int HS, int PAD, int CIN, int COUT, int NT = VAE_NT, int WCS = 4 * CIN * COUT, int FIS = CIN, int FOS = COUT,
+          int RIS = COUT, int ROS = CIN>
 struct UpConv3 {
+    static_assert(FIS >= CIN && FOS >= COUT && RIS >= COUT && ROS >= CIN, "pixel strides of the LDS activations");
     static constexpr int HOUT = 2 * HS - 2 + 2 * PAD;
     static constexpr int NPIX = HOUT * HOUT;
     static constexpr int NWE = 16 * CIN * COUT;          // effective weights
@@ -341,6 +355,7 @@ struct UpConv3 {
     template <bool ROLL = false, bool WVEC = false>
     static __device__ void fwd_valu(const real* in, const real* We, const real* bias, real* out) {
         static_assert(ROLL || !WVEC, "the grouped weight reads exist in the rolled form only");
+        static_assert(!ROLL || FIS % 2 == 0, "the 16-byte activation reads of the rolled form start at even counts of doubles");
         constexpr int TAP_UNROLL = ROLL ? 1 : 2;     // 1: no unrolling; 2 = the trip count: full
         for (int it = threadIdx.x; it < NPIX * NCG; it += NT) {
             const int cg = it % NCG, p = it / NCG, x = p % HOUT, y = p / HOUT;
@@ -357,7 +372,7 @@ struct UpConv3 {
                 for (int tx = 0; tx < 2; ++tx) {
                     const int sx = X + tx;
                     const bool valid = vy && ((unsigned)sx < (unsigned)HS);
-                    const real* src = in + (valid ? (sy * HS + sx) * CIN : 0);
+                    const real* src = in + (valid ? (sy * HS + sx) * FIS : 0);
                     const real* wk = wc + (ty * 2 + tx) * CIN * COUT;
                     if constexpr (WVEC) {
                         real av[CIN], wv[CIN * COG];
@@ -383,7 +398,7 @@ struct UpConv3 {
                 }
             }
 #pragma unroll
-            for (int g = 0; g < COG; ++g) out[p * COUT + cg * COG + g] = elu_f(acc[g]);
+            for (int g = 0; g < COG; ++g) out[p * FOS + cg * COG + g] = elu_f(acc[g]);
         }
     }
 
@@ -417,7 +432,7 @@ struct UpConv3 {
                 }
             }
 #pragma unroll
-            for (int g = 0; g < CIG; ++g) din[ps * CIN + ig * CIG + g] = acc[g];
+            for (int g = 0; g < CIG; ++g) din[ps * ROS + ig * CIG + g] = acc[g];
         }
     }
 
@@ -485,7 +500,8 @@ struct UpConv3 {
             ox[t] = px + PAD - 2 * tx;
             wo[t] = (py * 2 + px) * WCS + (ty * 2 + tx) * CIN * COUT;
         }
-        gg_fwd<16, true, false, COUT, CIN, NT>(dpre, HOUT, HOUT, HS, HS, 2, 2, oy, ox, wo, We, COUT, nullptr, din, HS, 1, 1, 0, 0);
+        gg_fwd<16, true, false, COUT, CIN, NT, RIS, ROS>(dpre, HOUT, HOUT, HS, HS, 2, 2, oy, ox, wo, We, COUT, nullptr, din, HS, 1, 1, 0,
+                                                         0);
     }
 
     // gWe += sum_pixels in * dpre ; gb += sum_pixels dpre.  Ends with a barrier.
@@ -551,6 +567,11 @@ __device__ __forceinline__ void lds_copy_in(real* dst, const real* __restrict__ 
 }
 __device__ __forceinline__ void lds_copy_out(real* __restrict__ dst, const real* src, int n) {
     for (int i = threadIdx.x; i < n; i += blockDim.x) dst[i] = src[i];
+}
+// ... from an 8-channel array kept at pixel stride S in LDS (dec_act_index below) to its packed global copy
+template <int S>
+__device__ __forceinline__ void lds_copy_out_px(real* __restrict__ dst, const real* src, int n) {
+    for (int i = threadIdx.x; i < n; i += blockDim.x) dst[i] = src[S == 8 ? i : (i >> 3) * S + (i & 7)];
 }
 __device__ __forceinline__ void lds_zero(real* dst, int n) {
     for (int i = threadIdx.x; i < n; i += blockDim.x) dst[i] = 0;
@@ -957,9 +978,32 @@ struct DecFwdBwdArgs {
 // of the row (256 + 8 doubles).  In UpC3 a lane is a pixel and a class needs 16 B per (tap, ci pair): 32 + 2 doubles.  Lanes of one
 // class read one address per channel pair (broadcast), lanes of different classes no common bank.  Only this launch uses the image;
 // ws.dec_weff itself, the riders and every other kernel keep the packed layout.
-using UpC1L = UpConv3<4, 1, 8, 8, VAE_NT, 256 + 8>;
-using UpC2L = UpConv3<8, 0, 8, 8, VAE_NT, 256 + 8>;
-using UpC3L = UpConv3<14, 1, 8, 1, VAE_NT, 32 + 2>;
+// The same launch pads the PIXEL stride of three of its 8-channel activation arrays (packed: 8 doubles), for the reads that gather
+// pixels a fixed distance apart (tools/lds_bank_model.py has the conflict degrees, NOTEBOOK 14.5f the measurements):
+//   d2 (14 x 14), read by the UpC2 data reverse: ds_read_b64 of 16 pixels x 2 channels, input stride 2.  Packed, two neighbours are
+//      128 bytes apart: 7.2 distinct addresses on the busiest bank in the mean; at 9 doubles 2.2.
+//   d1 (8 x 8), read by the UpC1 data reverse, the same gather: 7.1 -> 2.1.
+//   a2 (14 x 14), read by the UpC3 forward: ds_read_b128 of 16 output pixels = 8 to 9 source pixels 64 bytes apart, so pixels sx and
+//      sx + 4 share banks: 3.0 -> 1.3 at 10 doubles (even: the 16-byte reads stay aligned).
+// Only the LDS side moves: a2g, d2g and d1g keep the packed layout (dec_act_index in the copy-outs and the two elu' passes), and the
+// arithmetic is untouched.  DEC_ACT_STRIDE_*: overridable on the compiler's command line to measure a piece alone (8 = packed).
+#ifndef DEC_ACT_STRIDE_D2
+#define DEC_ACT_STRIDE_D2 9
+#endif
+#ifndef DEC_ACT_STRIDE_D1
+#define DEC_ACT_STRIDE_D1 9
+#endif
+#ifndef DEC_ACT_STRIDE_A2
+#define DEC_ACT_STRIDE_A2 10
+#endif
+constexpr int DEC_S_D2 = DEC_ACT_STRIDE_D2, DEC_S_D1 = DEC_ACT_STRIDE_D1, DEC_S_A2 = DEC_ACT_STRIDE_A2;
+static_assert(DEC_S_D2 >= 8 && DEC_S_D1 >= 8 && DEC_S_A2 >= 8 && DEC_S_A2 % 2 == 0, "pixel strides of d2, d1, a2 in the fused launch");
+// packed index i = pixel * 8 + channel of an 8-channel activation array -> index at pixel stride S
+template <int S>
+__host__ __device__ constexpr int dec_act_index(int i) { return S == 8 ? i : (i >> 3) * S + (i & 7); }
+using UpC1L = UpConv3<4, 1, 8, 8, VAE_NT, 256 + 8, 8, 8, DEC_S_D1, 8>;                 // h0 -> a1;  d1 -> dh0
+using UpC2L = UpConv3<8, 0, 8, 8, VAE_NT, 256 + 8, 8, DEC_S_A2, DEC_S_D2, DEC_S_D1>;   // a1 -> a2;  d2 -> d1
+using UpC3L = UpConv3<14, 1, 8, 1, VAE_NT, 32 + 2, DEC_S_A2, 1, 1, DEC_S_D2>;          // a2 -> recon;  d3 -> d2
 #define DEC_LWE (UpC1L::LWE + UpC2L::LWE + UpC3L::LWE)      // 1048 + 1048 + 134 = 2230
 static_assert(UpC1L::LWE % 2 == 0 && UpC2L::LWE % 2 == 0, "the three images start 16-byte aligned");
 // offset in the image (doubles from We1) of element e of layer 0..2, packed index (class, tap, ci, co); e = NWE gives the layer's end
@@ -983,6 +1027,45 @@ __host__ __device__ constexpr int dec_fwd_bwd_lds(int L) {
     return dec_fwd_bwd_we_offset(L) + DEC_LWE + 64 + 128 + 512 + 1568 + 784 + 1568 + 512 + 128 + 16;
 }
 static_assert(dec_fwd_bwd_lds(16) * 8 <= 80 * 1024, "two workgroups per CU at L = 16");
+// The arrays of the block: offset and extent in doubles, pixel stride (0: no pixel structure), and the live interval in terms of the
+// probe stamps 1..14 of the image loop below -- stamp k closes phase k, every phase ends in a barrier, and an array is live from the
+// phase of its first write to the phase of its last read of an image.  The sum above is the PACKED map's and stays the footprint
+// (77 744 bytes at L = 16: two workgroups per CU); the padding of a2 and d2 (392 + 196 doubles at strides 10 and 9) is paid for by two
+// aliases of arrays that are never live together, and what remains (52 doubles behind `red`) is unused:
+//   d1 lies in the d3 block: d3 is last read by the UpC3 data reverse (phase 8), d1 first written by the UpC2 data reverse (10);
+//   dh0 lies on h0: h0 is last read by its copy-out (phase 7), dh0 first written by the UpC1 data reverse (12).
+// Each interval lies inside one trip of the image loop (first <= last, written before read in every trip), so a workgroup that walks
+// several images meets the aliased blocks in the same order every time: d3 (6..8) | d1 (10..12) | d3 of the next image, ...
+enum { DEC_LDS_DENSE = 0, DEC_LDS_WEFF, DEC_LDS_Z, DEC_LDS_H0, DEC_LDS_A1, DEC_LDS_A2, DEC_LDS_D3, DEC_LDS_D2, DEC_LDS_D1, DEC_LDS_DH0,
+       DEC_LDS_RED, DEC_LDS_NARRAYS };
+struct DecLdsArray { int offset, extent, stride, first, last; };
+__host__ __device__ constexpr DecLdsArray dec_fwd_bwd_lds_array(int L, int which) {
+    const int z = dec_fwd_bwd_we_offset(L) + DEC_LWE, a2 = z + 64 + 128 + 512, d3 = a2 + 196 * DEC_S_A2, d2 = d3 + 784;
+    switch (which) {
+    case DEC_LDS_DENSE: return {0, dec_fwd_bwd_we_offset(L), 0, 1, 13};   // dense weights | dense bias | convolution biases: staged once
+    case DEC_LDS_WEFF: return {dec_fwd_bwd_we_offset(L), DEC_LWE, 0, 1, 12};   // effective weights: staged once, last the UpC1 data reverse
+    case DEC_LDS_Z: return {z, 64, 0, 2, 3};                              // z (2) -> dense (3)
+    case DEC_LDS_H0: return {z + 64, 128, 8, 3, 7};                       // dense (3) -> UpC1 forward (4), copy-out (7)
+    case DEC_LDS_A1: return {z + 64 + 128, 512, 8, 4, 11};                // UpC1 forward (4) -> UpC2 forward (5), copy-out (7), d1 elu' (11)
+    case DEC_LDS_A2: return {a2, 196 * DEC_S_A2, DEC_S_A2, 5, 9};         // UpC2 forward (5) -> UpC3 forward (6), copy-out (7), d2 elu' (9)
+    case DEC_LDS_D3: return {d3, 784, 1, 6, 8};                           // reconstruction (6), d3 in place (7) -> UpC3 data reverse (8)
+    case DEC_LDS_D2: return {d2, 196 * DEC_S_D2, DEC_S_D2, 8, 10};        // UpC3 data reverse (8), elu' (9) -> UpC2 data reverse (10)
+    case DEC_LDS_D1: return {d3, 64 * DEC_S_D1, DEC_S_D1, 10, 12};        // UpC2 data reverse (10), elu' (11) -> UpC1 data reverse (12)
+    case DEC_LDS_DH0: return {z + 64, 128, 8, 12, 13};                    // UpC1 data reverse (12) -> store, z-bar (13)
+    case DEC_LDS_RED: return {d2 + 196 * DEC_S_D2, 16, 0, 14, 14};        // the squared-error sum, after the loop
+    default: return {-1, -1, -1, -1, -1};
+    }
+}
+static_assert(64 * DEC_S_D1 <= 784, "d1 inside the d3 block");
+static_assert(dec_fwd_bwd_lds_array(1, DEC_LDS_RED).offset + 16 <= dec_fwd_bwd_lds(1) &&
+              dec_fwd_bwd_lds_array(2, DEC_LDS_RED).offset + 16 <= dec_fwd_bwd_lds(2), "the padded map inside the packed footprint");
+static_assert(dec_fwd_bwd_lds_array(1, DEC_LDS_A2).offset % 2 == 0 && dec_fwd_bwd_lds_array(2, DEC_LDS_A2).offset % 2 == 0,
+              "a2 16-byte aligned (the activation reads of UpC3L::fwd_valu<true, true>)");
+// index in its block of packed element i (pixel * channels + channel) of array `which`; only a2, d2 and d1 are not the identity
+__host__ __device__ constexpr int dec_fwd_bwd_lds_index(int which, int i) {
+    return which == DEC_LDS_A2 ? dec_act_index<DEC_S_A2>(i) : which == DEC_LDS_D2 ? dec_act_index<DEC_S_D2>(i)
+           : which == DEC_LDS_D1 ? dec_act_index<DEC_S_D1>(i) : i;
+}
 template <bool PROBE = false>
 __device__ __forceinline__ void decoder_fwd_bwd_data_images(const DecFwdBwdArgs& a, int first, int stride, real* smem,
                                                             unsigned long long* probe = nullptr) {
@@ -993,15 +1076,16 @@ __device__ __forceinline__ void decoder_fwd_bwd_data_images(const DecFwdBwdArgs&
     real* We1 = smem + dec_fwd_bwd_we_offset(a.L);   // = cb + 32: effective weights, padded class strides (dec_weff_lds_index), 16-byte aligned
     real* We2 = We1 + UpC1L::LWE;
     real* We3 = We2 + UpC2L::LWE;
-    real* z = We3 + UpC3L::LWE;      // 64
-    real* h0 = z + 64;               // 128
-    real* a1 = h0 + 128;             // 512
-    real* a2 = a1 + 512;             // 1568
-    real* d3 = a2 + 1568;            // 784: the reconstruction, then d3 in place
-    real* d2 = d3 + 784;             // 1568
-    real* d1 = d2 + 1568;            // 512
-    real* dh0 = d1 + 512;            // 128
-    real* red = dh0 + 128;           // 16
+    // (dec_fwd_bwd_lds_array above: the map the host entries report, with each array's live interval in probe stamps)
+    real* z = smem + dec_fwd_bwd_lds_array(a.L, DEC_LDS_Z).offset;       // 64                                     live  2 ..  3
+    real* h0 = smem + dec_fwd_bwd_lds_array(a.L, DEC_LDS_H0).offset;     // 128                                          3 ..  7
+    real* a1 = smem + dec_fwd_bwd_lds_array(a.L, DEC_LDS_A1).offset;     // 512                                          4 .. 11
+    real* a2 = smem + dec_fwd_bwd_lds_array(a.L, DEC_LDS_A2).offset;     // 196 pixels x DEC_S_A2                        5 ..  9
+    real* d3 = smem + dec_fwd_bwd_lds_array(a.L, DEC_LDS_D3).offset;     // 784: the reconstruction, then d3 in place    6 ..  8
+    real* d2 = smem + dec_fwd_bwd_lds_array(a.L, DEC_LDS_D2).offset;     // 196 pixels x DEC_S_D2                        8 .. 10
+    real* d1 = smem + dec_fwd_bwd_lds_array(a.L, DEC_LDS_D1).offset;     // 64 pixels x DEC_S_D1, IN THE d3 BLOCK       10 .. 12
+    real* dh0 = smem + dec_fwd_bwd_lds_array(a.L, DEC_LDS_DH0).offset;   // 128, ON h0                                  12 .. 13
+    real* red = smem + dec_fwd_bwd_lds_array(a.L, DEC_LDS_RED).offset;   // 16                                          14
     const int t = threadIdx.x;
     const real lag = a.geco ? a.state[SVGP_ST_LAGRANGE] : real(0);
     // image `first` exists for every workgroup (the grid has min(b, 256) image workgroups)
@@ -1039,7 +1123,7 @@ __device__ __forceinline__ void decoder_fwd_bwd_data_images(const DecFwdBwdArgs&
         probe_stamp<PROBE>(probe, 6);       // UpC3 forward
         lds_copy_out(a.h0g + (size_t)n * 128, h0, 128);
         lds_copy_out(a.a1g + (size_t)n * 512, a1, 512);
-        lds_copy_out(a.a2g + (size_t)n * 1568, a2, 1568);
+        lds_copy_out_px<DEC_S_A2>(a.a2g + (size_t)n * 1568, a2, 1568);
         {   // pixels t and t + 512: reconstruction out, squared error, d3 in place (each element read and written by its one owner)
             const real o = d3[t];
             a.recon[(size_t)n * 784 + t] = o;
@@ -1067,9 +1151,12 @@ __device__ __forceinline__ void decoder_fwd_bwd_data_images(const DecFwdBwdArgs&
         UpC3L::bwd_data_valu(d3, We3, d2);
         __syncthreads();
         probe_stamp<PROBE>(probe, 8);       // UpC3 data-reverse
-        for (int i = t; i < 1568; i += VAE_NT) {
-            const real v = d2[i] * elu_grad_from_out(a2[i]);
-            d2[i] = v;
+        int tl = t;
+        if constexpr (DEC_S_D2 != 8 || DEC_S_A2 != 8 || DEC_S_D1 != 8) asm volatile("" : "+v"(tl));
+        for (int i = t, il = tl; i < 1568; i += VAE_NT, il += VAE_NT) {
+            const int j = dec_act_index<DEC_S_D2>(il);
+            const real v = d2[j] * elu_grad_from_out(a2[dec_act_index<DEC_S_A2>(il)]);
+            d2[j] = v;
             a.d2g[(size_t)n * 1568 + i] = v;
         }
         svgp_lds_barrier();             // (the stores to d2g / d1g / dh0g are for a later launch: no wave waits for them here)
@@ -1077,9 +1164,11 @@ __device__ __forceinline__ void decoder_fwd_bwd_data_images(const DecFwdBwdArgs&
         UpC2L::bwd_data_mfma(d2, We2, d1);
         svgp_lds_barrier();
         probe_stamp<PROBE>(probe, 10);      // UpC2 data-reverse
+        if constexpr (DEC_S_D1 != 8) asm volatile("" : "+v"(tl));
         for (int i = t; i < 512; i += VAE_NT) {
-            const real v = d1[i] * elu_grad_from_out(a1[i]);
-            d1[i] = v;
+            const int j = dec_act_index<DEC_S_D1>(tl);
+            const real v = d1[j] * elu_grad_from_out(a1[i]);
+            d1[j] = v;
             a.d1g[(size_t)n * 512 + i] = v;
         }
         svgp_lds_barrier();
