@@ -16,7 +16,6 @@
 
 namespace {
 
-inline int nb256(long long n) { return (int)((n + 255) / 256); }
 
 // ---------------------------------------------------------------------------------------------------------
 // SE kernel matrices on scalar inputs: K (m,m), Kn (T,m), knn (T) = 1
@@ -502,7 +501,7 @@ extern "C" int svgp_se1d_kernel_matrix_fwd(int T, int m, const double* x, const 
                                            double* Kn, double* knn, void* stream) {
     SVGP_REQUIRE(T >= 1 && m >= 1, SVGP_ERR_INVALID, "need T >= 1, m >= 1 (T=%d m=%d)", T, m);
     REQ_PTRS(x, z, ls, K, Kn, knn);
-    hipLaunchKernelGGL(k_se1d_fwd, dim3(nb256((long long)T * m + (long long)m * m + T)), dim3(256), 0,
+    hipLaunchKernelGGL(k_se1d_fwd, dim3(svgp_blocks((long long)T * m + (long long)m * m + T)), dim3(256), 0,
                        (hipStream_t)stream, T, m, x, z, ls, K, Kn, knn);
     SVGP_LAUNCH_CHECK();
     return SVGP_OK;
@@ -521,7 +520,7 @@ extern "C" int svgp_se1d_kernel_matrix_bwd(int T, int m, const double* x, const 
 extern "C" int svgp_bias_act_fwd(long long rows, int C, int act, const double* bias, double* x, void* stream) {
     SVGP_REQUIRE(rows >= 1 && C >= 1 && (act == 0 || act == 1), SVGP_ERR_INVALID, "bad argument");
     REQ_PTRS(bias, x);
-    hipLaunchKernelGGL(k_bias_act, dim3(nb256(rows * C)), dim3(256), 0, (hipStream_t)stream, rows * C, C, act, bias, x);
+    hipLaunchKernelGGL(k_bias_act, dim3(svgp_blocks(rows * C)), dim3(256), 0, (hipStream_t)stream, rows * C, C, act, bias, x);
     SVGP_LAUNCH_CHECK();
     return SVGP_OK;
 }
@@ -545,7 +544,7 @@ extern "C" int svgp_ball_head_fwd(int B, int T, int clip, const double* bias, co
     REQ_PTRS(bias, h, mu_x, var_raw_x, var_x, mu_y, var_raw_y, var_y);
     HeadPtrs o;
     o.mu[0] = mu_x; o.mu[1] = mu_y; o.var_raw[0] = var_raw_x; o.var_raw[1] = var_raw_y; o.var[0] = var_x; o.var[1] = var_y;
-    hipLaunchKernelGGL(k_ball_head_fwd, dim3(nb256((long long)B * T * 2)), dim3(256), 0, (hipStream_t)stream, B, T, clip,
+    hipLaunchKernelGGL(k_ball_head_fwd, dim3(svgp_blocks((long long)B * T * 2)), dim3(256), 0, (hipStream_t)stream, B, T, clip,
                        bias, h, o);
     SVGP_LAUNCH_CHECK();
     return SVGP_OK;
@@ -559,7 +558,7 @@ extern "C" int svgp_ball_head_bwd(int B, int T, int clip, const double* var_raw_
     HeadBwdPtrs p;
     p.var_raw[0] = var_raw_x; p.var_raw[1] = var_raw_y; p.ybar[0] = ybar_x; p.ybar[1] = ybar_y;
     p.s2bar[0] = s2bar_x; p.s2bar[1] = s2bar_y;
-    hipLaunchKernelGGL(k_ball_head_bwd, dim3(nb256((long long)B * T * 2)), dim3(256), 0, (hipStream_t)stream, B, T, clip,
+    hipLaunchKernelGGL(k_ball_head_bwd, dim3(svgp_blocks((long long)B * T * 2)), dim3(256), 0, (hipStream_t)stream, B, T, clip,
                        p, dh);
     SVGP_LAUNCH_CHECK();
     return SVGP_OK;
@@ -568,14 +567,14 @@ extern "C" int svgp_ball_head_bwd(int B, int T, int clip, const double* var_raw_
 extern "C" int svgp_ball_pack_z(int B, int T, const double* zx, const double* zy, double* z, void* stream) {
     SVGP_REQUIRE(B >= 1 && T >= 1, SVGP_ERR_INVALID, "bad shape");
     REQ_PTRS(zx, zy, z);
-    hipLaunchKernelGGL(k_ball_pack_z, dim3(nb256((long long)B * T * 2)), dim3(256), 0, (hipStream_t)stream, B, T, zx, zy, z);
+    hipLaunchKernelGGL(k_ball_pack_z, dim3(svgp_blocks((long long)B * T * 2)), dim3(256), 0, (hipStream_t)stream, B, T, zx, zy, z);
     SVGP_LAUNCH_CHECK();
     return SVGP_OK;
 }
 extern "C" int svgp_ball_unpack_zbar(int B, int T, const double* dz, double* zbar_x, double* zbar_y, void* stream) {
     SVGP_REQUIRE(B >= 1 && T >= 1, SVGP_ERR_INVALID, "bad shape");
     REQ_PTRS(dz, zbar_x, zbar_y);
-    hipLaunchKernelGGL(k_ball_unpack_zbar, dim3(nb256((long long)B * T * 2)), dim3(256), 0, (hipStream_t)stream, B, T, dz,
+    hipLaunchKernelGGL(k_ball_unpack_zbar, dim3(svgp_blocks((long long)B * T * 2)), dim3(256), 0, (hipStream_t)stream, B, T, dz,
                        zbar_x, zbar_y);
     SVGP_LAUNCH_CHECK();
     return SVGP_OK;
@@ -640,7 +639,7 @@ extern "C" int svgp_ball_rasterize(long long frames, int px, int py, double r, c
     SVGP_REQUIRE(frames >= 1 && px >= 1 && py >= 1, SVGP_ERR_INVALID, "bad shape");
     REQ_PTRS(paths, vid);
     const long long tot = frames * px * py;
-    hipLaunchKernelGGL(k_ball_rasterize, dim3(nb256(tot)), dim3(256), 0, (hipStream_t)stream, tot, px, py, r * r, paths, vid);
+    hipLaunchKernelGGL(k_ball_rasterize, dim3(svgp_blocks(tot)), dim3(256), 0, (hipStream_t)stream, tot, px, py, r * r, paths, vid);
     SVGP_LAUNCH_CHECK();
     return SVGP_OK;
 }
@@ -668,10 +667,6 @@ static int pearce_args(const svgp_pearce_bufs* q, PearceArgs* a) {
     a->Ai = q->Ai; a->alpha = q->alpha; a->lh = q->lh; a->ce = q->ce; a->row_ce = q->row_ce; a->dl_part = q->dl_part;
     return SVGP_OK;
 }
-static int set_lds(const void* fn, size_t bytes) {
-    SVGP_CHECK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    return SVGP_OK;
-}
 
 extern "C" int svgp_pearce_gp_fwd(const svgp_pearce_bufs* q, const double* eps_x, const double* eps_y, const double* state,
                                   void* stream) {
@@ -685,11 +680,11 @@ extern "C" int svgp_pearce_gp_fwd(const svgp_pearce_bufs* q, const double* eps_x
     a.eps_in[0] = eps_x; a.eps_in[1] = eps_y; a.use_rng = eps_x == nullptr; a.state = state;
     const size_t lds = ((size_t)3 * a.n * (a.n + 1) + 3 * a.n + 16) * sizeof(real);
     if (a.n <= 32) {
-        rc = set_lds((const void*)k_pearce_fwd<32>, lds);
+        rc = set_dyn_lds(k_pearce_fwd<32>, lds);
         if (rc) return rc;
         hipLaunchKernelGGL(k_pearce_fwd<32>, dim3(a.B, 2), dim3(256), lds, (hipStream_t)stream, a);
     } else {
-        rc = set_lds((const void*)k_pearce_fwd<64>, lds);
+        rc = set_dyn_lds(k_pearce_fwd<64>, lds);
         if (rc) return rc;
         hipLaunchKernelGGL(k_pearce_fwd<64>, dim3(a.B, 2), dim3(256), lds, (hipStream_t)stream, a);
     }
@@ -709,11 +704,11 @@ extern "C" int svgp_pearce_gp_bwd(const svgp_pearce_bufs* q, double seed_lh_scal
     a.state = state; a.seed_lh_scale = seed_lh_scale; a.accumulate = accumulate;
     const size_t lds = ((size_t)4 * a.n * (a.n + 1) + 5 * a.n + 16) * sizeof(real);
     if (a.n <= 32) {
-        rc = set_lds((const void*)k_pearce_bwd<32>, lds);
+        rc = set_dyn_lds(k_pearce_bwd<32>, lds);
         if (rc) return rc;
         hipLaunchKernelGGL(k_pearce_bwd<32>, dim3(a.B, 2), dim3(256), lds, (hipStream_t)stream, a);
     } else {
-        rc = set_lds((const void*)k_pearce_bwd<64>, lds);
+        rc = set_dyn_lds(k_pearce_bwd<64>, lds);
         if (rc) return rc;
         hipLaunchKernelGGL(k_pearce_bwd<64>, dim3(a.B, 2), dim3(256), lds, (hipStream_t)stream, a);
     }
@@ -730,7 +725,7 @@ extern "C" int svgp_pearce_elbo_assemble(int B, int T, const double* lh, const d
     SVGP_REQUIRE(B >= 1 && T >= 1, SVGP_ERR_INVALID, "bad shape");
     REQ_PTRS(lh, ce, row_recon, state, out);
     SVGP_REQUIRE(tmask == nullptr || row_ce != nullptr, SVGP_ERR_INVALID, "a target mask needs the per-frame CE terms");
-    hipLaunchKernelGGL(k_pearce_assemble, dim3(nb256(B)), dim3(256), 0, (hipStream_t)stream, B, T, lh, ce, con_lh, row_recon,
+    hipLaunchKernelGGL(k_pearce_assemble, dim3(svgp_blocks(B)), dim3(256), 0, (hipStream_t)stream, B, T, lh, ce, con_lh, row_recon,
                        row_ce, tmask, state, out);
     SVGP_LAUNCH_CHECK();
     return SVGP_OK;
@@ -744,7 +739,7 @@ __global__ void k_scale_rows(long long tot, int C, const real* __restrict__ w, r
 extern "C" int svgp_scale_rows(long long rows, int C, const double* w, double* x, void* stream) {
     SVGP_REQUIRE(rows >= 1 && C >= 1, SVGP_ERR_INVALID, "bad shape");
     REQ_PTRS(w, x);
-    hipLaunchKernelGGL(k_scale_rows, dim3(nb256(rows * C)), dim3(256), 0, (hipStream_t)stream, rows * C, C, w, x);
+    hipLaunchKernelGGL(k_scale_rows, dim3(svgp_blocks(rows * C)), dim3(256), 0, (hipStream_t)stream, rows * C, C, w, x);
     SVGP_LAUNCH_CHECK();
     return SVGP_OK;
 }

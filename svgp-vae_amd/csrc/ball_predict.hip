@@ -261,23 +261,19 @@ int bp_args(const svgp_ball_predict_cfg* g, const svgp_ball_predict_bufs* q, BpA
     return SVGP_OK;
 }
 
-inline int64_t bp_al16(int64_t n) { return (n + 15) / 16 * 16; }
 struct BpWork { int64_t K, Kn, knn, K2, Kq, kbb, KnP, PY, Mats, V, W, logdet, inv, tpm, tpv, rows, total; };
 BpWork bp_work(const svgp_ball_predict_cfg* g) {
     const int64_t m = g->m, T = g->T, nb = g->B < BPL_NB ? g->B : BPL_NB, nq = g->Q < BPL_QC ? g->Q : BPL_QC;
-    int64_t p = 0;
-    auto take = [&](int64_t n) { int64_t r = p; p += bp_al16(n); return r; };
+    SvgpTake16 c16;
     BpWork o;
-    o.K = take(m * m); o.Kn = take(T * m); o.knn = take(T); o.K2 = take(m * m); o.Kq = take(nq * m); o.kbb = take(nq);
-    o.KnP = take(nb * T * m); o.PY = take(T * nb); o.Mats = take((nb + 1) * m * m); o.V = take(m * nb); o.W = take(nb * m);
-    o.logdet = take(nb + 1); o.inv = take((int64_t)svgp_spd_inverse_workspace_elems((int)m, (int)nb + 1));
-    o.tpm = take(nq * nb); o.tpv = take(nq * nb);
-    o.rows = take(m > 256 ? 16 * nq * nb : 0);      // svgp_sprites_posterior_rows_workspace_elems: at most 16 b L, 0 up to m = 256
-    o.total = p;
+    o.K = c16.take(m * m); o.Kn = c16.take(T * m); o.knn = c16.take(T); o.K2 = c16.take(m * m); o.Kq = c16.take(nq * m); o.kbb = c16.take(nq);
+    o.KnP = c16.take(nb * T * m); o.PY = c16.take(T * nb); o.Mats = c16.take((nb + 1) * m * m); o.V = c16.take(m * nb); o.W = c16.take(nb * m);
+    o.logdet = c16.take(nb + 1); o.inv = c16.take((int64_t)svgp_spd_inverse_workspace_elems((int)m, (int)nb + 1));
+    o.tpm = c16.take(nq * nb); o.tpv = c16.take(nq * nb);
+    o.rows = c16.take(m > 256 ? 16 * nq * nb : 0);      // svgp_sprites_posterior_rows_workspace_elems: at most 16 b L, 0 up to m = 256
+    o.total = c16.p;
     return o;
 }
-
-inline unsigned bp_blocks(long long n) { return (unsigned)((n + SVGP_BLOCK - 1) / SVGP_BLOCK); }
 
 }  // namespace
 
@@ -293,12 +289,9 @@ extern "C" int svgp_ball_predict_route(const svgp_ball_predict_cfg* g, int large
             char sub[128];
             int r = svgp_sprites_posterior_rows_route(&rc_, sub, (int)sizeof(sub));
             if (r) return r;
-            pos += snprintf(buf + pos, cap - pos, "%s", sub);
-        } else {
-            pos += snprintf(buf + pos, cap - pos, "%s\n", BP_NAME[s.op]);
+            return svgp_route_append(buf, cap, &pos, "%s", sub);
         }
-        SVGP_REQUIRE(pos < cap, SVGP_ERR_INVALID, "route text needs more than %d bytes", cap);
-        return (int)SVGP_OK;
+        return svgp_route_append(buf, cap, &pos, "%s\n", BP_NAME[s.op]);
     });
 }
 
@@ -312,11 +305,13 @@ extern "C" int svgp_ball_predict(const svgp_ball_predict_cfg* g, const svgp_ball
         const dim3 grid((unsigned)a.B, 2);
         if (a.m <= 32) {
             const size_t lds = bp_lds_bytes(a.m, 32);
-            SVGP_CHECK_HIP(hipFuncSetAttribute((const void*)k_ball_predict<32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            rc = set_dyn_lds(k_ball_predict<32>, lds);
+            if (rc) return rc;
             hipLaunchKernelGGL(k_ball_predict<32>, grid, dim3(256), lds, (hipStream_t)stream, a);
         } else {
             const size_t lds = bp_lds_bytes(a.m, 64);
-            SVGP_CHECK_HIP(hipFuncSetAttribute((const void*)k_ball_predict<64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            rc = set_dyn_lds(k_ball_predict<64>, lds);
+            if (rc) return rc;
             hipLaunchKernelGGL(k_ball_predict<64>, grid, dim3(256), lds, (hipStream_t)stream, a);
         }
         SVGP_LAUNCH_CHECK();
@@ -348,7 +343,7 @@ extern "C" int svgp_ball_predict_large(const svgp_ball_predict_cfg* g, const svg
         case BP_KMAT:
             return svgp_se1d_kernel_matrix_fwd(T, m, a.times, a.ip[c], a.ls[c], work + w.K, work + w.Kn, work + w.knn, stream);
         case BP_SCALE:
-            hipLaunchKernelGGL(k_bp_scale_rows, dim3(bp_blocks((long long)nb * T * m)), dim3(SVGP_BLOCK), 0, st, a, c, s.b0, nb, work + w.Kn,
+            hipLaunchKernelGGL(k_bp_scale_rows, dim3(svgp_blocks((long long)nb * T * m)), dim3(SVGP_BLOCK), 0, st, a, c, s.b0, nb, work + w.Kn,
                                work + w.KnP, work + w.PY);
             SVGP_LAUNCH_CHECK();
             break;
@@ -356,7 +351,7 @@ extern "C" int svgp_ball_predict_large(const svgp_ball_predict_cfg* g, const svg
             return svgp_dgemm_batched(1, 0, m, m, T, 1.0, work + w.Kn, m, 0, work + w.KnP, m, (long long)T * m, 0.0, work + w.Mats, m, mm, nb,
                                       stream);
         case BP_PRIOR:
-            hipLaunchKernelGGL(k_bp_add_prior, dim3(bp_blocks((nb + 1) * mm)), dim3(SVGP_BLOCK), 0, st, m, nb, a.jitter, work + w.K,
+            hipLaunchKernelGGL(k_bp_add_prior, dim3(svgp_blocks((nb + 1) * mm)), dim3(SVGP_BLOCK), 0, st, m, nb, a.jitter, work + w.K,
                                work + w.Mats);
             SVGP_LAUNCH_CHECK();
             break;
@@ -367,7 +362,7 @@ extern "C" int svgp_ball_predict_large(const svgp_ball_predict_cfg* g, const svg
         case BP_W:          // w_l = Si_l V[:, l]
             return svgp_dgemm_batched(0, 0, m, 1, m, 1.0, work + w.Mats, m, mm, work + w.V, nb, 1, 0.0, work + w.W, 1, m, nb, stream);
         case BP_SUB:
-            hipLaunchKernelGGL(k_bp_subtract, dim3(bp_blocks(nb * mm)), dim3(SVGP_BLOCK), 0, st, m, nb, work + w.Mats);
+            hipLaunchKernelGGL(k_bp_subtract, dim3(svgp_blocks(nb * mm)), dim3(SVGP_BLOCK), 0, st, m, nb, work + w.Mats);
             SVGP_LAUNCH_CHECK();
             break;
         case BP_KQ:
@@ -378,7 +373,7 @@ extern "C" int svgp_ball_predict_large(const svgp_ball_predict_cfg* g, const svg
                                                nullptr, work + w.rows, stream);
         }
         case BP_FINISH:
-            hipLaunchKernelGGL(k_bp_finish, dim3(bp_blocks((long long)s.nq * nb)), dim3(SVGP_BLOCK), 0, st, a, c, s.b0, nb, s.q0, s.nq,
+            hipLaunchKernelGGL(k_bp_finish, dim3(svgp_blocks((long long)s.nq * nb)), dim3(SVGP_BLOCK), 0, st, a, c, s.b0, nb, s.q0, s.nq,
                                work + w.tpm, work + w.tpv);
             SVGP_LAUNCH_CHECK();
             break;

@@ -437,7 +437,6 @@ __global__ __launch_bounds__(SVGP_BLOCK) void k_scale(long long n, real f, real*
     if (idx < n) x[idx] *= f;
 }
 
-inline unsigned nblk(long long n) { return (unsigned)((n + SVGP_BLOCK - 1) / SVGP_BLOCK); }
 
 int check_cfg(const svgp_casale_cfg* c) {
     SVGP_REQUIRE(c != nullptr, SVGP_ERR_INVALID, "casale cfg is NULL");
@@ -518,7 +517,7 @@ extern "C" int svgp_casale_v_fwd(const svgp_casale_cfg* c, const double* gp, con
     const int N = c->N, Q = c->Q, M = c->M, H = M * Q;
     hipLaunchKernelGGL(k_kw_chol, dim3(1), dim3(SVGP_BLOCK), 0, s, Q, angles, gp, ws + wl.K_W, ws + wl.L_W);
     SVGP_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_v_build, dim3(nblk((long long)N * H)), dim3(SVGP_BLOCK), 0, s, N, Q, M, c->normalize_obj, gp + 3,
+    hipLaunchKernelGGL(k_v_build, dim3(svgp_blocks((long long)N * H)), dim3(SVGP_BLOCK), 0, s, N, Q, M, c->normalize_obj, gp + 3,
                        ws + wl.L_W, obj_idx, ang_idx, ws + wl.V);
     SVGP_LAUNCH_CHECK();
     return SVGP_OK;
@@ -536,7 +535,7 @@ int svgp_casale_hspace_fwd(const svgp_casale_cfg* c, const svgp_casale_layout& w
     if (rc) return rc;
     rc = svgp_dgemm_splitk(1, 0, H, H, N, 1.0, V, H, V, H, 0.0, ws + wl.G, H, ws + wl.scr_splitk, wl.scr_splitk_len, stream);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_p_init, dim3(nblk((long long)H * H)), dim3(SVGP_BLOCK), 0, s, H, ws + wl.G, alpha, P);
+    hipLaunchKernelGGL(k_p_init, dim3(svgp_blocks((long long)H * H)), dim3(SVGP_BLOCK), 0, s, H, ws + wl.G, alpha, P);
     SVGP_LAUNCH_CHECK();
     rc = svgp_spd_inverse_batched(H, 1, P, ws + wl.logdet, ws + wl.scr_inv, stream);
     if (rc) return rc;
@@ -589,13 +588,13 @@ extern "C" int svgp_casale_gp_bwd(const svgp_casale_cfg* c, const double* gp, co
     const real* Vb = V + (size_t)lo * H;
     CAS_GEMM(1, 0, H, H, b, seed * L, Vb, H, 0, Vb, H, 0, 0.0, Pbar, H, 0, 1, stream);
     CAS_GEMM(0, 1, H, H, L, 1.0, Ubar, L, 0, W, L, 0, 1.0, Pbar, H, 0, 1, stream);
-    hipLaunchKernelGGL(k_add_diag, dim3(nblk(H)), dim3(SVGP_BLOCK), 0, s, H, seed * L * 0.5, alpha, Pbar);
+    hipLaunchKernelGGL(k_add_diag, dim3(svgp_blocks(H)), dim3(SVGP_BLOCK), 0, s, H, seed * L * 0.5, alpha, Pbar);
     SVGP_LAUNCH_CHECK();
     // Wbar = P Ubar;  Mbar = -P Pbar P, kept as Mbar + Mbar^T
     CAS_GEMM(0, 0, H, L, H, 1.0, P, H, 0, Ubar, L, 0, 0.0, Wbar, L, 0, 1, stream);
     CAS_GEMM(0, 0, H, H, H, 1.0, Pbar, H, 0, P, H, 0, 0.0, T, H, 0, 1, stream);
     CAS_GEMM(0, 0, H, H, H, -1.0, P, H, 0, T, H, 0, 0.0, Mb, H, 0, 1, stream);
-    hipLaunchKernelGGL(k_msym, dim3(nblk((long long)H * H)), dim3(SVGP_BLOCK), 0, s, H, Mb);
+    hipLaunchKernelGGL(k_msym, dim3(svgp_blocks((long long)H * H)), dim3(SVGP_BLOCK), 0, s, H, Mb);
     SVGP_LAUNCH_CHECK();
     // Vbar += V (Mbar + Mbar^T) + Z Wbar^T;  Zbar += V Wbar
     CAS_GEMM(0, 0, N, H, H, 1.0, V, H, 0, Mb, H, 0, 1.0, Vbar, H, 0, 1, stream);
@@ -646,7 +645,7 @@ extern "C" int svgp_casale_vae_sample(const svgp_casale_cfg* c, int b, const dou
     SVGP_REQUIRE(b >= 1 && b <= c->b_cap, SVGP_ERR_INVALID, "batch of %d rows outside [1, b_cap = %d]", b, c->b_cap);
     SVGP_REQUIRE(mu && var_raw && eps && z_dec && ws, SVGP_ERR_INVALID, "NULL device pointer");
     const long long n = (long long)b * c->L;
-    hipLaunchKernelGGL(k_vae_sample, dim3(nblk(n)), dim3(SVGP_BLOCK), 0, (hipStream_t)stream, n, mu, var_raw, eps, z_dec,
+    hipLaunchKernelGGL(k_vae_sample, dim3(svgp_blocks(n)), dim3(SVGP_BLOCK), 0, (hipStream_t)stream, n, mu, var_raw, eps, z_dec,
                        ws + wl.lv_part);
     SVGP_LAUNCH_CHECK();
     return SVGP_OK;
@@ -659,7 +658,7 @@ extern "C" int svgp_casale_vae_seeds(const svgp_casale_cfg* c, int b, double sca
     SVGP_REQUIRE(b >= 1 && b <= c->b_cap, SVGP_ERR_INVALID, "batch of %d rows outside [1, b_cap = %d]", b, c->b_cap);
     SVGP_REQUIRE(mu && var_raw && eps && dec_zbar && ybar && s2bar, SVGP_ERR_INVALID, "NULL device pointer");
     const long long n = (long long)b * c->L;
-    hipLaunchKernelGGL(k_vae_seeds, dim3(nblk(n)), dim3(SVGP_BLOCK), 0, (hipStream_t)stream, n, scale, mu, var_raw, eps, dec_zbar,
+    hipLaunchKernelGGL(k_vae_seeds, dim3(svgp_blocks(n)), dim3(SVGP_BLOCK), 0, (hipStream_t)stream, n, scale, mu, var_raw, eps, dec_zbar,
                        ybar, s2bar);
     SVGP_LAUNCH_CHECK();
     return SVGP_OK;
@@ -673,7 +672,7 @@ extern "C" int svgp_casale_finalize(const svgp_casale_cfg* c, int mode, int b, d
     SVGP_REQUIRE(b >= 1 && b <= c->b_cap, SVGP_ERR_INVALID, "batch of %d rows outside [1, b_cap = %d]", b, c->b_cap);
     SVGP_REQUIRE(mode == 0 || sigma_vae > 0, SVGP_ERR_INVALID, "sigma_vae = %g (> 0)", sigma_vae);
     SVGP_REQUIRE(dec_sums && ws && out && state, SVGP_ERR_INVALID, "NULL device pointer");
-    const int n_lv = mode == 0 ? (int)wl.n_lv : (int)nblk((long long)b * c->L);
+    const int n_lv = mode == 0 ? (int)wl.n_lv : (int)svgp_blocks((long long)b * c->L);
     hipLaunchKernelGGL(k_cas_finalize, dim3(1), dim3(64), 0, (hipStream_t)stream, mode, c->L, n_lv, beta, sigma_vae, did_adam,
                        dec_sums,
                        ws + wl.terms, ws + wl.lv_part, out, state);
@@ -694,7 +693,7 @@ extern "C" int svgp_casale_predict_var(int T, int N, int H, const double* K_tn, 
 extern "C" int svgp_scale_f64(long long n, double f, double* x, void* stream) {
     SVGP_REQUIRE(n >= 0 && x, SVGP_ERR_INVALID, "NULL device pointer");
     if (n == 0) return SVGP_OK;
-    hipLaunchKernelGGL(k_scale, dim3(nblk(n)), dim3(SVGP_BLOCK), 0, (hipStream_t)stream, n, f, x);
+    hipLaunchKernelGGL(k_scale, dim3(svgp_blocks(n)), dim3(SVGP_BLOCK), 0, (hipStream_t)stream, n, f, x);
     SVGP_LAUNCH_CHECK();
     return SVGP_OK;
 }

@@ -24,14 +24,11 @@ using namespace svgp_vae;
 #define CG_ROWS 256            // H beyond: query rows per pass of the five launches (the workspace holds 2 x CG_ROWS x H)
 #define CG_MMAX 128
 
-inline int64_t al16(int64_t n) { return (n + 15) / 16 * 16; }
-
 void cache_layout_fill(const svgp_casale_cfg* c, svgp_casale_cache_layout* o) {
     const int64_t Q = c->Q, H = (int64_t)c->M * c->Q, L = c->L;
-    int64_t p = 0;
-    auto take = [&](int64_t n) { int64_t r = p; p += al16(n); return r; };      // 16-element boundaries, as the workspace's
-    o->angles = take(Q); o->L_W = take(Q * Q); o->U = take(H * L); o->P = take(H * H);
-    o->total = p;
+    SvgpTake16 c16;      // 16-element boundaries, as the workspace's
+    o->angles = c16.take(Q); o->L_W = c16.take(Q * Q); o->U = c16.take(H * L); o->P = c16.take(H * H);
+    o->total = c16.p;
 }
 
 // cache = [angles | L_W | U | P], P written as (P + P^T) / 2: symmetric bit for bit (the sum of two doubles commutes)
@@ -70,12 +67,9 @@ struct CGenArgs {
     real* mean; real* var; // (b, L), (b) or NULL
 };
 
-// object vector of query row n, or nullptr when the row's id is outside the table (gen_obj_row of generate.hip)
+// object vector of query row n, or nullptr when the row's id is outside the table
 __device__ __forceinline__ const real* cgen_obj_row(const CGenArgs& a, int n) {
-    const real* row = a.aux + (size_t)n * (2 + a.M);
-    if (!a.gather) return row + 2;
-    const long long id = (long long)row[0];
-    return (id >= 0 && id < a.n_obj) ? a.gp + 3 + (size_t)id * a.M : nullptr;
+    return svgp_query_obj_row(a.aux, a.M, a.gather, a.gp + 3, a.n_obj, n);
 }
 
 // lambda = L_W^-1 kappa in the first wave: lane r holds x_r = kappa_r - sum_{j < r} L_W[r][j] lambda_j (j ascending), lane j
@@ -92,109 +86,86 @@ __device__ __forceinline__ real cgen_forward_subst(int Q, const real* lw, int ld
     return lam;
 }
 
-// One workgroup of VAE_NT threads walks images blockIdx.x, + gridDim.x, ... (k_generate's pattern: decoder weights, the effective
-// up-convolution weights and here L_W staged in LDS once).  GP, per image: thread r < Q forms kappa_r, the first wave lambda, thread
-// i < H v*_i; thread i < H then (sum_j P[j][i] v_j) v_i, j ascending (P is symmetric: the column walk is coalesced over i), thread
+// One workgroup of VAE_NT threads walks images blockIdx.x, + gridDim.x, ... on the decoder forward piece of vae_dev.hpp (decoder weights,
+// the effective up-convolution weights and here L_W staged in LDS once).  GP, per image: thread r < Q forms kappa_r, the first wave
+// lambda, thread i < H v*_i; thread i < H then (sum_j P[j][i] v_j) v_i, j ascending (P is symmetric: the column walk is coalesced over i), thread
 // 256 + l meanwhile sum_j v_j U[j][l], j ascending; thread l < L adds the H terms and the H squares in index order (every l the same
 // sums from the same LDS words) and forms z.  Fixed order everywhere: a row gives the same bits wherever it stands in a batch of any
 // size.  Rolled up-convolutions (fwd_valu<true>), as k_generate<true>: the unrolled ones exceed 256 VGPRs there and spill.
+// !GP (H > 256): decode of the samples a.z only.
 template <bool GP>
 __global__ __launch_bounds__(VAE_NT) void k_casale_generate(CGenArgs a) {
     extern __shared__ __align__(16) real smem[];
+    if constexpr (!GP) {
+        decoder_fwd_rows(a.b, a.L, a.th_dec, a.z, a.images, blockIdx.x, gridDim.x, smem);
+        return;
+    }
     const DecOff od = dec_off(a.L);
-    real* w = smem;                  // od.n
-    real* z = w + od.n;              // 64
-    real* h0 = z + 64;               // 128
-    real* a1 = h0 + 128;             // 512
-    real* a2 = a1 + 512;             // 1568
-    real* out = a2 + 1568;           // 784
-    real* We1 = out + 784;           // effective weights of the three up-convolutions
-    real* We2 = We1 + UpC1::NWE;
-    real* We3 = We2 + UpC2::NWE;
-    real* lw = We1 + DEC_NWE;        // GP: CG_QMAX x CG_LWS
+    const DecFwdLds d = dec_fwd_carve<false>(smem, od.n);
+    real* lw = d.We1 + DEC_NWE;      // CG_QMAX x CG_LWS
     real* lam = lw + CG_QMAX * CG_LWS;   // CG_QMAX
     real* on = lam + CG_QMAX;        // CG_MMAX: the normalised object vector
     real* vs = on + CG_MMAX;         // CG_HFUSED: v*
     real* qt = vs + CG_HFUSED;       // CG_HFUSED: terms of the quadratic form
     real* mn = qt + CG_HFUSED;       // 64: mean*
     real* sc = mn + 64;              // 2: k**
-    lds_copy_in(w, a.th_dec, od.n);
     const int Q = a.Q, M = a.M, H = a.H, L = a.L, st = 2 + a.M;
-    if (GP)
-        for (int e = threadIdx.x; e < Q * Q; e += VAE_NT) lw[(e / Q) * CG_LWS + e % Q] = a.LW[e];
-    __syncthreads();
-    UpC1::build_weff(w + od.c1w, We1);
-    UpC2::build_weff(w + od.c2w, We2);
-    UpC3::build_weff(w + od.c3w, We3);
+    for (int e = threadIdx.x; e < Q * Q; e += VAE_NT) lw[(e / Q) * CG_LWS + e % Q] = a.LW[e];
+    decoder_fwd_stage(d, od, a.th_dec);
     for (int n = blockIdx.x; n < a.b; n += gridDim.x) {
         __syncthreads();
-        if (GP) {
-            const real* orow = cgen_obj_row(a, n);
-            const real amp = a.gp[1], ls = a.gp[0], a2_ = amp * amp, inv_l2 = real(1) / (ls * ls), alpha = a.gp[2];
-            const int t = threadIdx.x;
-            if (t < 64) {            // (Q <= 32: one wave)
-                const real kap = t < Q ? svgp_view_k(a.aux[(size_t)n * st + 1] - a.ang[t], a2_, inv_l2) : real(0);
-                const real l = cgen_forward_subst(Q, lw, CG_LWS, kap);
-                if (t < Q) lam[t] = l;
-            } else if (t >= 128 && t < 128 + M) {
-                const int k = t - 128;
-                real v = __builtin_nan("");
-                if (orow) v = orow[k] * (a.normalize ? real(1) / sqrt(svgp_dotM(orow, orow, M)) : real(1));
-                on[k] = v;
-            } else if (t == 256) {
-                sc[0] = !orow ? __builtin_nan("") : (a.normalize ? a2_ : a2_ * svgp_dotM(orow, orow, M));
-            }
-            __syncthreads();
-            if (t < H) vs[t] = on[t / Q] * lam[t % Q];
-            __syncthreads();
-            if (t < H) {
-                const real* Pc = a.P + t;
-                real r = 0;
+        const real* orow = cgen_obj_row(a, n);
+        const real amp = a.gp[1], ls = a.gp[0], a2_ = amp * amp, inv_l2 = real(1) / (ls * ls), alpha = a.gp[2];
+        const int t = threadIdx.x;
+        if (t < 64) {            // (Q <= 32: one wave)
+            const real kap = t < Q ? svgp_view_k(a.aux[(size_t)n * st + 1] - a.ang[t], a2_, inv_l2) : real(0);
+            const real l = cgen_forward_subst(Q, lw, CG_LWS, kap);
+            if (t < Q) lam[t] = l;
+        } else if (t >= 128 && t < 128 + M) {
+            const int k = t - 128;
+            real v = __builtin_nan("");
+            if (orow) v = orow[k] * (a.normalize ? real(1) / sqrt(svgp_dotM(orow, orow, M)) : real(1));
+            on[k] = v;
+        } else if (t == 256) {
+            sc[0] = svgp_query_kxx(orow, M, a.normalize, a2_);
+        }
+        __syncthreads();
+        if (t < H) vs[t] = on[t / Q] * lam[t % Q];
+        __syncthreads();
+        if (t < H) {
+            const real* Pc = a.P + t;
+            real r = 0;
 #pragma unroll 4
-                for (int j = 0; j < H; ++j) r += Pc[(size_t)j * H] * vs[j];
-                qt[t] = r * vs[t];
-            } else if (t >= CG_HFUSED && t < CG_HFUSED + L) {
-                const int l = t - CG_HFUSED;
-                real m_ = 0;
+            for (int j = 0; j < H; ++j) r += Pc[(size_t)j * H] * vs[j];
+            qt[t] = r * vs[t];
+        } else if (t >= CG_HFUSED && t < CG_HFUSED + L) {
+            const int l = t - CG_HFUSED;
+            real m_ = 0;
 #pragma unroll 4
-                for (int j = 0; j < H; ++j) m_ += vs[j] * a.U[(size_t)j * L + l];
-                mn[l] = m_;
-            }
-            __syncthreads();
-            if (t < L) {
-                real qs = 0, vv = 0;
+            for (int j = 0; j < H; ++j) m_ += vs[j] * a.U[(size_t)j * L + l];
+            mn[l] = m_;
+        }
+        __syncthreads();
+        if (t < L) {
+            real qs = 0, vv = 0;
 #pragma unroll 1
-                for (int i = 0; i < H; ++i) { qs += qt[i]; vv += vs[i] * vs[i]; }
-                const real var = sc[0] - vv + alpha * qs, m_ = mn[t];
-                const size_t e = (size_t)n * L + t;
-                if (a.mean) a.mean[e] = m_;
-                if (a.var && t == 0) a.var[n] = var;
-                z[t] = a.eps ? m_ + a.eps[e] * sqrt(var) : m_;
-            }
-        } else {
-            if ((int)threadIdx.x < L) z[threadIdx.x] = a.z[(size_t)n * L + threadIdx.x];
+            for (int i = 0; i < H; ++i) { qs += qt[i]; vv += vs[i] * vs[i]; }
+            const real var = sc[0] - vv + alpha * qs, m_ = mn[t];
+            const size_t e = (size_t)n * L + t;
+            if (a.mean) a.mean[e] = m_;
+            if (a.var && t == 0) a.var[n] = var;
+            d.z[t] = a.eps ? m_ + a.eps[e] * sqrt(var) : m_;
         }
         __syncthreads();
-        if (threadIdx.x < 128) {
-            real acc = w[od.db + threadIdx.x];
-            for (int i = 0; i < L; ++i) acc += z[i] * w[od.dw + i * 128 + threadIdx.x];
-            h0[threadIdx.x] = acc;
-        }
-        __syncthreads();
-        UpC1::fwd_valu<GP>(h0, We1, w + od.c1b, a1);
-        __syncthreads();
-        UpC2::fwd_valu<GP>(a1, We2, w + od.c2b, a2);
-        __syncthreads();
-        UpC3::fwd_valu<GP>(a2, We3, w + od.c3b, out);
-        __syncthreads();
-        lds_copy_out(a.images + (size_t)n * 784, out, 784);
+        decoder_fwd_layers<true>(d, od, L);
+        lds_copy_out(a.images + (size_t)n * 784, d.out, 784);
     }
 }
 
 // LDS doubles of k_casale_generate<true> behind the decoder's part
 #define CG_LDS_GP (CG_QMAX * CG_LWS + CG_QMAX + CG_MMAX + 2 * CG_HFUSED + 64 + 2)
-static_assert((size_t)(64 * 128 + 128 + 576 + 8 + 576 + 8 + 72 + 1 + 64 + 128 + 512 + 1568 + 784 + DEC_NWE + CG_LDS_GP) * sizeof(real) <=
-                  SVGP_LDS_MAX_BYTES, "LDS of k_casale_generate<true> at L = 64, Q = 32, H = 256");
+static_assert((size_t)(dec_fwd_lds(dec_off(64).n, false) + CG_LDS_GP) * sizeof(real) <= SVGP_LDS_MAX_BYTES,
+              "LDS of k_casale_generate<true> at L = 64, Q = 32, H = 256");
 
 // H > 256: one wave per query row n of the pass: v* (H) and k**; a row whose id is outside the table gives a NaN row
 __global__ __launch_bounds__(64) void k_casale_generate_rows(CGenArgs a, real* __restrict__ Vq, real* __restrict__ kss) {
@@ -208,7 +179,7 @@ __global__ __launch_bounds__(64) void k_casale_generate_rows(CGenArgs a, real* _
     __syncthreads();
     const real inv = (orow && a.normalize) ? real(1) / sqrt(svgp_dotM(orow, orow, M)) : real(1);
     for (int h = t; h < H; h += 64) Vq[(size_t)n * H + h] = orow ? orow[h / Q] * inv * lam[h % Q] : __builtin_nan("");
-    if (t == 0) kss[n] = !orow ? __builtin_nan("") : (a.normalize ? a2_ : a2_ * svgp_dotM(orow, orow, M));
+    if (t == 0) kss[n] = svgp_query_kxx(orow, M, a.normalize, a2_);
 }
 
 // H > 256: thread (n, l): var = k** - sum_j v_j^2 + alpha sum_j (v* P)[j] v_j, j ascending; mean from the product v* U; z
@@ -228,12 +199,6 @@ __global__ __launch_bounds__(SVGP_BLOCK) void k_casale_generate_rowsum(CGenArgs 
     z[e] = a.eps ? m_ + a.eps[e] * sqrt(var) : m_;
 }
 
-template <typename F>
-int set_dyn_lds(F kernel, size_t bytes) {
-    SVGP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    return SVGP_OK;
-}
-
 // The launches of one pass of svgp_casale_generate, in order: the call walks this list, svgp_casale_generate_route prints it.
 enum CGenOp { CGEN_FUSED, CGEN_ROWS, CGEN_PROD_P, CGEN_PROD_U, CGEN_ROWSUM, CGEN_DECODE };
 const char* const CGEN_NAME[] = {"k_casale_generate", "k_casale_generate_rows", "svgp_dgemm_batched", "svgp_dgemm_batched",
@@ -249,10 +214,9 @@ CGenWork cgen_work(const svgp_casale_cfg* c, long long b) {
     const int64_t H = (int64_t)c->M * c->Q, L = c->L;
     if (H <= CG_HFUSED || b < 1) return o;
     const int64_t rows = b < CG_ROWS ? b : CG_ROWS;
-    int64_t p = 0;
-    auto take = [&](int64_t n) { int64_t r = p; p += al16(n); return r; };
-    o.Vq = take(rows * H); o.VP = take(rows * H); o.kss = take(rows); o.mean = take(rows * L); o.z = take(rows * L);
-    o.total = p;
+    SvgpTake16 c16;
+    o.Vq = c16.take(rows * H); o.VP = c16.take(rows * H); o.kss = c16.take(rows); o.mean = c16.take(rows * L); o.z = c16.take(rows * L);
+    o.total = c16.p;
     return o;
 }
 
@@ -279,7 +243,7 @@ extern "C" int svgp_casale_cache_build(const svgp_casale_cfg* c, const double* g
     cache_layout_fill(c, &cl);
     const int Q = c->Q, H = c->M * c->Q, L = c->L;
     const long long tot = (long long)Q + (long long)Q * Q + (long long)H * L + (long long)H * H;
-    hipLaunchKernelGGL(k_casale_cache_pack, dim3((unsigned)((tot + SVGP_BLOCK - 1) / SVGP_BLOCK)), dim3(SVGP_BLOCK), 0,
+    hipLaunchKernelGGL(k_casale_cache_pack, dim3(svgp_blocks(tot)), dim3(SVGP_BLOCK), 0,
                        (hipStream_t)stream, Q, H, L, angles, ws + wl.L_W, ws + wl.U, ws + wl.P, cache + cl.angles, cache + cl.L_W,
                        cache + cl.U, cache + cl.P);
     SVGP_LAUNCH_CHECK();
@@ -301,11 +265,8 @@ extern "C" int svgp_casale_generate_route(const svgp_casale_cfg* c, char* buf, i
     const int n = cgen_plan(c, ops);
     int pos = 0;
     buf[0] = 0;
-    for (int i = 0; i < n; ++i) {
-        pos += snprintf(buf + pos, cap - pos, "%s\n", CGEN_NAME[ops[i]]);
-        SVGP_REQUIRE(pos < cap, SVGP_ERR_INVALID, "route text needs more than %d bytes", cap);
-    }
-    return SVGP_OK;
+    for (int i = 0; i < n && !rc; ++i) rc = svgp_route_append(buf, cap, &pos, "%s\n", CGEN_NAME[ops[i]]);
+    return rc;
 }
 
 extern "C" int svgp_casale_generate(const svgp_casale_cfg* c, long long b, const double* theta, const double* cache, const double* aux,
@@ -329,7 +290,7 @@ extern "C" int svgp_casale_generate(const svgp_casale_cfg* c, long long b, const
     a.ang = cache + cl.angles; a.LW = cache + cl.L_W; a.U = cache + cl.U; a.P = cache + cl.P;
     a.z = work ? work + gw.z : nullptr;
     const int64_t n_dec = wl.n_vae - wl.n_enc;
-    const size_t lds_dec = (size_t)(n_dec + 64 + 128 + 512 + 1568 + 784 + DEC_NWE) * sizeof(real);
+    const size_t lds_dec = (size_t)dec_fwd_lds((int)n_dec, false) * sizeof(real);
     const size_t lds_gp = lds_dec + (size_t)CG_LDS_GP * sizeof(real);       // (L = 64: 16 587 doubles = 132 696 bytes, asserted above)
     hipStream_t st = (hipStream_t)stream;
     CGenOp ops[8];
@@ -365,7 +326,7 @@ extern "C" int svgp_casale_generate(const svgp_casale_cfg* c, long long b, const
                 if (rc) return rc;
                 break;
             case CGEN_ROWSUM:
-                hipLaunchKernelGGL(k_casale_generate_rowsum, dim3((unsigned)(((long long)bb * L + SVGP_BLOCK - 1) / SVGP_BLOCK)),
+                hipLaunchKernelGGL(k_casale_generate_rowsum, dim3(svgp_blocks((long long)bb * L)),
                                    dim3(SVGP_BLOCK), 0, st, a, work + gw.Vq, work + gw.VP, work + gw.kss, work + gw.mean, work + gw.z);
                 SVGP_LAUNCH_CHECK();
                 break;

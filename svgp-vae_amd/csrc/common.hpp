@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstdarg>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -168,6 +169,29 @@ static inline int svgp_n_post_actual(const svgp_mnist_cfg* c) {
     return c->m > SVGP_M_MAX ? (c->b * c->L + SVGP_BLOCK - 1) / SVGP_BLOCK : c->L * svgp_n_postblk(c);
 }
 
+// ---- host glue of the launch code
+// blocks of SVGP_BLOCK threads over n elements
+static inline unsigned svgp_blocks(long long n) { return (unsigned)((n + SVGP_BLOCK - 1) / SVGP_BLOCK); }
+// layout cursor: take(n) returns the offset of a field of n elements and advances to the next 16-element (128-byte) boundary; p: the total
+struct SvgpTake16 {
+    int64_t p = 0;
+    int64_t take(int64_t n) { const int64_t r = p; p += (n + 15) / 16 * 16; return r; }
+};
+template <typename F>
+int set_dyn_lds(F kernel, size_t bytes) {
+    SVGP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    return SVGP_OK;
+}
+// route texts: appends one formatted piece at *pos of buf (cap bytes)
+__attribute__((format(printf, 4, 5))) static inline int svgp_route_append(char* buf, int cap, int* pos, const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    *pos += vsnprintf(buf + *pos, cap - *pos, fmt, ap);
+    va_end(ap);
+    SVGP_REQUIRE(*pos < cap, SVGP_ERR_INVALID, "route text needs more than %d bytes", cap);
+    return SVGP_OK;
+}
+
 // linalg.hip: fused one-launch-per-block-step inverse of nmain + nextra matrices (m < SVGP_CHOL_INVERSE_MIN_M)
 int svgp_spd_inverse_fused(int m, int nmain, double* A, double* logdet, int nextra, double* Ae, double* logdet_e,
                            double* work, void* stream);
@@ -321,6 +345,28 @@ __device__ __forceinline__ real svgp_dotM(const real* x, const real* y, int M) {
     real s = 0;
     for (int k = 0; k < M; ++k) s += x[k] * y[k];
     return s;
+}
+// Query rows of the generation entries (generate.hip, casale_generate.hip): aux (b, 2+M) rows [id, angle, o_1..o_M].
+// The object vector of row n: the row's own columns, or (gather) row `id` of table (n_obj, M); nullptr when that id is outside the table
+__device__ __forceinline__ const real* svgp_query_obj_row(const real* aux, int M, int gather, const real* table, int n_obj, int n) {
+    const real* row = aux + (size_t)n * (2 + M);
+    if (!gather) return row + 2;
+    const long long id = (long long)row[0];
+    return (id >= 0 && id < n_obj) ? table + (size_t)id * M : nullptr;
+}
+// k_xx of a query row with object vector on (a2 = amplitude^2); NaN for a row without a vector
+__device__ __forceinline__ real svgp_query_kxx(const real* on, int M, int normalize, real a2) {
+    return !on ? __builtin_nan("") : (normalize ? a2 : a2 * svgp_dotM(on, on, M));
+}
+// element j of the MNIST kernel row of query row n against the inducing points ip (m, 2+M), with the expressions of
+// svgp_km_fwd_element below; on: the row's object vector, not nullptr
+__device__ __forceinline__ real svgp_query_kx(const real* on, const real* aux, int n, const real* ip, int j, int M, int normalize,
+                                              real a2, real inv_l2) {
+    const int st = 2 + M;
+    const real* oj = ip + (size_t)j * st + 2;
+    real D = svgp_dotM(on, oj, M);
+    if (normalize) D /= sqrt(svgp_dotM(on, on, M)) * sqrt(svgp_dotM(oj, oj, M));
+    return svgp_view_k(aux[(size_t)n * st + 1] - ip[(size_t)j * st + 1], a2, inv_l2) * D;
 }
 // element idx of [K_nm (b m) | K_mm (m m) | k_nn (b)]; idx beyond: nothing
 __device__ __forceinline__ void svgp_km_fwd_element(const SvgpKernArgs& a, long long idx, real* __restrict__ K,

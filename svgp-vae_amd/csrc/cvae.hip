@@ -562,12 +562,6 @@ __global__ __launch_bounds__(VAE_NT) void k_cvae_fwd(CvaeArgs a) {
     }
 }
 
-template <typename F>
-int set_dyn_lds(F kernel, size_t bytes) {
-    SVGP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    return SVGP_OK;
-}
-
 int check_cfg(const svgp_cvae_cfg* c) {
     SVGP_REQUIRE(c != nullptr, SVGP_ERR_INVALID, "cfg is NULL");
     SVGP_REQUIRE(c->b >= 0 && c->b <= c->b_cap, SVGP_ERR_INVALID, "need 0 <= b <= b_cap (b=%d b_cap=%d)", c->b, c->b_cap);
@@ -581,13 +575,12 @@ int check_cfg(const svgp_cvae_cfg* c) {
 void ws_fill(const svgp_cvae_cfg* c, svgp_cvae_ws_layout* w) {
     const CvaeOff o = cvae_off(c->cvae, c->L);
     const int64_t cap = c->b_cap, L = c->L;
-    int64_t p = 0;
-    auto take = [&](int64_t n) { int64_t r = p; p += (n + 15) / 16 * 16; return r; };      // fields start on 128-byte boundaries
-    w->part = take((int64_t)SVGP_MAX_PART * o.npc); w->sums = take(SVGP_MAX_PART * 2);
-    w->a3 = take(cap * o.NI); w->dpre = take(cap * 2 * L); w->zx = take(cap * o.ZW); w->dh0 = take(cap * 128);
-    w->recon = take(cap * 784); w->qnet_mu = take(cap * L); w->qnet_var = take(cap * L); w->z = take(cap * L);
+    SvgpTake16 c16;      // fields start on 128-byte boundaries
+    w->part = c16.take((int64_t)SVGP_MAX_PART * o.npc); w->sums = c16.take(SVGP_MAX_PART * 2);
+    w->a3 = c16.take(cap * o.NI); w->dpre = c16.take(cap * 2 * L); w->zx = c16.take(cap * o.ZW); w->dh0 = c16.take(cap * 128);
+    w->recon = c16.take(cap * 784); w->qnet_mu = c16.take(cap * L); w->qnet_var = c16.take(cap * L); w->z = c16.take(cap * L);
     w->part_stride = o.npc;
-    w->total = p;
+    w->total = c16.p;
 }
 
 CvaeArgs make_args(const svgp_cvae_cfg* c, const double* theta, const double* images, const double* aux, const double* eps, double* ws,
@@ -618,13 +611,10 @@ int launch_fwd(const CvaeArgs& a, int rows, hipStream_t st) {
 
 int route_text(const char* const* names, int n, char* buf, int cap) {
     SVGP_REQUIRE(buf && cap >= 1, SVGP_ERR_INVALID, "bad argument");
-    int pos = 0;
+    int pos = 0, rc = SVGP_OK;
     buf[0] = 0;
-    for (int i = 0; i < n; ++i) {
-        pos += snprintf(buf + pos, cap - pos, "%s\n", names[i]);
-        SVGP_REQUIRE(pos < cap, SVGP_ERR_INVALID, "route text needs more than %d bytes", cap);
-    }
-    return SVGP_OK;
+    for (int i = 0; i < n && !rc; ++i) rc = svgp_route_append(buf, cap, &pos, "%s\n", names[i]);
+    return rc;
 }
 
 }  // namespace

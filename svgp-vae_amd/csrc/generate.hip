@@ -22,15 +22,12 @@ namespace {
 
 using namespace svgp_vae;
 
-inline int64_t al16(int64_t n) { return (n + 15) / 16 * 16; }
-
 void cache_layout_fill(const svgp_mnist_cfg* c, svgp_mnist_cache_layout* o) {
     const int64_t m = c->m, L = c->L;
-    int64_t p = 0;
-    auto take = [&](int64_t n) { int64_t r = p; p += al16(n); return r; };      // 16-element boundaries, as the workspace's
-    o->acc_S = take(L * m * m); o->acc_v = take(L * m); o->acc_rows = take(1);
-    o->w = take(L * m); o->X = take(L * m * m);
-    o->total = p;
+    SvgpTake16 c16;      // 16-element boundaries, as the workspace's
+    o->acc_S = c16.take(L * m * m); o->acc_v = c16.take(L * m); o->acc_rows = c16.take(1);
+    o->w = c16.take(L * m); o->X = c16.take(L * m * m);
+    o->total = c16.p;
 }
 
 // ---- accumulation: element i of [S (L m m) | v (L m) | rows]; the P row partials of an element are added in index order first
@@ -104,99 +101,69 @@ struct GenArgs {
 
 // object vector of query row n, or nullptr when the row's id is outside the table
 __device__ __forceinline__ const real* gen_obj_row(const GenArgs& a, int n) {
-    const real* row = a.aux + (size_t)n * (2 + a.M);
-    if (!a.gather) return row + 2;
-    const long long id = (long long)row[0];
-    return (id >= 0 && id < a.n_obj) ? a.ov + (size_t)id * a.M : nullptr;
+    return svgp_query_obj_row(a.aux, a.M, a.gather, a.ov, a.n_obj, n);
 }
 
-// One workgroup of VAE_NT threads walks images blockIdx.x, + gridDim.x, ... (k_decoder_fwd's pattern: decoder weights and the effective
-// up-convolution weights staged in LDS once).  GP: per image, thread j < m forms k_x[j] with the expressions of svgp_km_fwd_element;
-// thread (l, i) forms k_i sum_j X_l[j][i] k_j, j ascending (X is symmetric: the column walk is coalesced over i); thread l adds the
+// One workgroup of VAE_NT threads walks images blockIdx.x, + gridDim.x, ... on the decoder forward piece of vae_dev.hpp (decoder weights
+// and the effective up-convolution weights staged in LDS once).  GP: per image, thread j < m forms k_x[j] (svgp_query_kx); thread
+// (l, i) forms k_i sum_j X_l[j][i] k_j, j ascending (X is symmetric: the column walk is coalesced over i); thread l adds the
 // m terms of channel l in index order, p_m = sum_j k_j w_l[j] in index order, z = p_m + eps sqrt(p_v).  Fixed order everywhere: a row
 // gives the same bits wherever it stands in the batch.  The GP form runs the rolled up-convolutions (fwd_valu<true>: same FMA order, ~85
-// VGPRs fewer): with the fully unrolled ones it needs more than 256 VGPRs and spills.
+// VGPRs fewer): with the fully unrolled ones it needs more than 256 VGPRs and spills.  !GP (m > 64): decode of the samples a.z only.
 template <bool GP>
 __global__ __launch_bounds__(VAE_NT) void k_generate(GenArgs a) {
     extern __shared__ __align__(16) real smem[];
+    if constexpr (!GP) {
+        decoder_fwd_rows(a.b, a.L, a.th_dec, a.z, a.images, blockIdx.x, gridDim.x, smem);
+        return;
+    }
     const DecOff od = dec_off(a.L);
-    real* w = smem;                  // od.n
-    real* z = w + od.n;              // 64
-    real* h0 = z + 64;               // 128
-    real* a1 = h0 + 128;             // 512
-    real* a2 = a1 + 512;             // 1568
-    real* out = a2 + 1568;           // 784
-    real* We1 = out + 784;           // effective weights of the three up-convolutions
-    real* We2 = We1 + UpC1::NWE;
-    real* We3 = We2 + UpC2::NWE;
-    real* kx = We1 + DEC_NWE;        // GP: m (+ k_xx at kx[m])
-    real* qt = kx + a.m + 1;         // GP: L m terms of the quadratic forms
-    lds_copy_in(w, a.th_dec, od.n);
-    __syncthreads();
-    UpC1::build_weff(w + od.c1w, We1);
-    UpC2::build_weff(w + od.c2w, We2);
-    UpC3::build_weff(w + od.c3w, We3);
-    const int m = a.m, L = a.L, st = 2 + a.M;
+    const DecFwdLds d = dec_fwd_carve<false>(smem, od.n);
+    real* kx = d.We1 + DEC_NWE;      // m (+ k_xx at kx[m])
+    real* qt = kx + a.m + 1;         // L m terms of the quadratic forms
+    decoder_fwd_stage(d, od, a.th_dec);
+    const int m = a.m, L = a.L;
     for (int n = blockIdx.x; n < a.b; n += gridDim.x) {
         __syncthreads();
-        if (GP) {
-            const real* on = gen_obj_row(a, n);
-            if ((int)threadIdx.x <= m) {
-                const real amp = *a.amp, ls = *a.ls, a2_ = amp * amp, inv_l2 = real(1) / (ls * ls);
-                real val;
-                if (!on) {
-                    val = __builtin_nan("");
-                } else if ((int)threadIdx.x < m) {
-                    const int j = threadIdx.x;
-                    const real* oj = a.ip + (size_t)j * st + 2;
-                    real D = svgp_dotM(on, oj, a.M);
-                    if (a.normalize) D /= sqrt(svgp_dotM(on, on, a.M)) * sqrt(svgp_dotM(oj, oj, a.M));
-                    val = svgp_view_k(a.aux[(size_t)n * st + 1] - a.ip[(size_t)j * st + 1], a2_, inv_l2) * D;
-                } else {
-                    val = a.normalize ? a2_ : a2_ * svgp_dotM(on, on, a.M);
-                }
-                kx[threadIdx.x] = val;
+        const real* on = gen_obj_row(a, n);
+        if ((int)threadIdx.x <= m) {
+            const real amp = *a.amp, ls = *a.ls, a2_ = amp * amp, inv_l2 = real(1) / (ls * ls);
+            real val;
+            if (!on) {
+                val = __builtin_nan("");
+            } else if ((int)threadIdx.x < m) {
+                val = svgp_query_kx(on, a.aux, n, a.ip, threadIdx.x, a.M, a.normalize, a2_, inv_l2);
+            } else {
+                val = svgp_query_kxx(on, a.M, a.normalize, a2_);
             }
-            __syncthreads();
-            for (int p = threadIdx.x; p < L * m; p += VAE_NT) {
-                const int l = p / m, i = p % m;
-                const real* Xl = a.X + (size_t)l * m * m + i;
-                real r = 0;
+            kx[threadIdx.x] = val;
+        }
+        __syncthreads();
+        for (int p = threadIdx.x; p < L * m; p += VAE_NT) {
+            const int l = p / m, i = p % m;
+            const real* Xl = a.X + (size_t)l * m * m + i;
+            real r = 0;
 #pragma unroll 4
-                for (int j = 0; j < m; ++j) r += Xl[(size_t)j * m] * kx[j];
-                qt[p] = r * kx[i];
-            }
-            __syncthreads();
-            if ((int)threadIdx.x < L) {
-                const int l = threadIdx.x;
-                real qs = 0, pm = 0;
-#pragma unroll 1
-                for (int i = 0; i < m; ++i) qs += qt[l * m + i];
-#pragma unroll 1
-                for (int j = 0; j < m; ++j) pm += kx[j] * a.w[(size_t)l * m + j];
-                const real pv = kx[m] + qs;
-                const size_t e = (size_t)n * L + l;
-                if (a.p_m) a.p_m[e] = pm;
-                if (a.p_v) a.p_v[e] = pv;
-                z[l] = a.eps ? pm + a.eps[e] * sqrt(pv) : pm;
-            }
-        } else {
-            if ((int)threadIdx.x < L) z[threadIdx.x] = a.z[(size_t)n * L + threadIdx.x];
+            for (int j = 0; j < m; ++j) r += Xl[(size_t)j * m] * kx[j];
+            qt[p] = r * kx[i];
         }
         __syncthreads();
-        if (threadIdx.x < 128) {
-            real acc = w[od.db + threadIdx.x];
-            for (int i = 0; i < L; ++i) acc += z[i] * w[od.dw + i * 128 + threadIdx.x];
-            h0[threadIdx.x] = acc;
+        if ((int)threadIdx.x < L) {
+            const int l = threadIdx.x;
+            real qs = 0, pm = 0;
+#pragma unroll 1
+            for (int i = 0; i < m; ++i) qs += qt[l * m + i];
+#pragma unroll 1
+            for (int j = 0; j < m; ++j) pm += kx[j] * a.w[(size_t)l * m + j];
+            const real pv = kx[m] + qs;
+            const size_t e = (size_t)n * L + l;
+            if (a.p_m) a.p_m[e] = pm;
+            if (a.p_v) a.p_v[e] = pv;
+            d.z[l] = a.eps ? pm + a.eps[e] * sqrt(pv) : pm;
         }
         __syncthreads();
-        UpC1::fwd_valu<GP>(h0, We1, w + od.c1b, a1);
-        __syncthreads();
-        UpC2::fwd_valu<GP>(a1, We2, w + od.c2b, a2);
-        __syncthreads();
-        UpC3::fwd_valu<GP>(a2, We3, w + od.c3b, out);
-        __syncthreads();
-        lds_copy_out(a.images + (size_t)n * 784, out, 784);
+        decoder_fwd_layers<true>(d, od, L);
+        lds_copy_out(a.images + (size_t)n * 784, d.out, 784);
     }
 }
 
@@ -205,14 +172,11 @@ __global__ __launch_bounds__(VAE_NT) void k_generate(GenArgs a) {
 __global__ __launch_bounds__(SVGP_BLOCK) void k_generate_kx(GenArgs a, real* __restrict__ Kx) {
     const long long idx = (long long)blockIdx.x * SVGP_BLOCK + threadIdx.x;
     if (idx >= (long long)a.b * a.m) return;
-    const int n = (int)(idx / a.m), j = (int)(idx % a.m), st = 2 + a.M;
+    const int n = (int)(idx / a.m), j = (int)(idx % a.m);
     const real* on = gen_obj_row(a, n);
     if (!on) { Kx[idx] = __builtin_nan(""); return; }
-    const real* oj = a.ip + (size_t)j * st + 2;
     const real amp = *a.amp, ls = *a.ls;
-    real D = svgp_dotM(on, oj, a.M);
-    if (a.normalize) D /= sqrt(svgp_dotM(on, on, a.M)) * sqrt(svgp_dotM(oj, oj, a.M));
-    Kx[idx] = svgp_view_k(a.aux[(size_t)n * st + 1] - a.ip[(size_t)j * st + 1], amp * amp, real(1) / (ls * ls)) * D;
+    Kx[idx] = svgp_query_kx(on, a.aux, n, a.ip, j, a.M, a.normalize, amp * amp, real(1) / (ls * ls));
 }
 
 // m > 64: thread (n, l): p_v = k_xx + sum_j P_l[n][j] Kx[n][j], j ascending; p_m from the product K_x w^T; z
@@ -222,8 +186,7 @@ __global__ __launch_bounds__(SVGP_BLOCK) void k_generate_rowsum(GenArgs a, const
     if (e >= (long long)a.b * a.L) return;
     const int n = (int)(e / a.L), l = (int)(e % a.L), m = a.m;
     const real* on = gen_obj_row(a, n);
-    const real amp = *a.amp, a2_ = amp * amp;
-    const real kxx = !on ? __builtin_nan("") : (a.normalize ? a2_ : a2_ * svgp_dotM(on, on, a.M));
+    const real amp = *a.amp, kxx = svgp_query_kxx(on, a.M, a.normalize, amp * amp);
     const real* pr = P + ((size_t)l * a.b + n) * m;
     const real* kr = Kx + (size_t)n * m;
     real qs = 0;
@@ -234,14 +197,8 @@ __global__ __launch_bounds__(SVGP_BLOCK) void k_generate_rowsum(GenArgs a, const
     z[e] = a.eps ? pm + a.eps[e] * sqrt(pv) : pm;
 }
 
-template <typename F>
-int set_dyn_lds(F kernel, size_t bytes) {
-    SVGP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    return SVGP_OK;
-}
-
-static_assert((size_t)(64 * 128 + 128 + 576 + 8 + 576 + 8 + 72 + 1 + 64 + 128 + 512 + 1568 + 784 + DEC_NWE + SVGP_M_MAX + 1 + 64 * SVGP_M_MAX) *
-                      sizeof(real) <= SVGP_LDS_MAX_BYTES, "LDS of k_generate<true> at L = 64, m = SVGP_M_MAX");
+static_assert((size_t)(dec_fwd_lds(dec_off(64).n, false) + SVGP_M_MAX + 1 + 64 * SVGP_M_MAX) * sizeof(real) <= SVGP_LDS_MAX_BYTES,
+              "LDS of k_generate<true> at L = 64, m = SVGP_M_MAX");
 
 // The launches of one svgp_mnist_generate call, in order: svgp_mnist_generate walks this list, svgp_mnist_generate_route prints it.
 enum GenOp { GEN_FUSED, GEN_KX, GEN_PROD_X, GEN_PROD_W, GEN_ROWSUM, GEN_DECODE };
@@ -258,10 +215,9 @@ GenWork gen_work(const svgp_mnist_cfg* c) {
     GenWork o = {0, 0, 0, 0, 0};
     if (c->m <= SVGP_M_MAX) return o;
     const int64_t b = gen_rows_cap(c), m = c->m, L = c->L;
-    int64_t p = 0;
-    auto take = [&](int64_t n) { int64_t r = p; p += al16(n); return r; };
-    o.Kx = take(b * m); o.P = take(L * b * m); o.pm = take(b * L); o.z = take(b * L);
-    o.total = p;
+    SvgpTake16 c16;
+    o.Kx = c16.take(b * m); o.P = c16.take(L * b * m); o.pm = c16.take(b * L); o.z = c16.take(b * L);
+    o.total = c16.p;
     return o;
 }
 struct CacheWork { int64_t K, B, logdet, inv, total; };
@@ -269,11 +225,10 @@ CacheWork cache_work(const svgp_mnist_cfg* c) {
     CacheWork o = {0, 0, 0, 0, 0};
     if (c->m <= SVGP_M_MAX) return o;
     const int64_t m = c->m, L = c->L;
-    int64_t p = 0;
-    auto take = [&](int64_t n) { int64_t r = p; p += al16(n); return r; };
-    o.K = take(m * m); o.B = take((L + 1) * m * m); o.logdet = take(L + 1);
-    o.inv = take((int64_t)svgp_spd_inverse_workspace_elems((int)m, (int)L + 1));
-    o.total = p;
+    SvgpTake16 c16;
+    o.K = c16.take(m * m); o.B = c16.take((L + 1) * m * m); o.logdet = c16.take(L + 1);
+    o.inv = c16.take((int64_t)svgp_spd_inverse_workspace_elems((int)m, (int)L + 1));
+    o.total = c16.p;
     return o;
 }
 
@@ -297,8 +252,7 @@ extern "C" int svgp_gp_stats_accumulate(const svgp_mnist_cfg* c, const double* w
     svgp_mnist_cache_layout cl;
     cache_layout_fill(c, &cl);
     const long long nS = (long long)c->L * c->m * c->m, nv = (long long)c->L * c->m;
-    const unsigned nblk = (unsigned)((nS + nv + 1 + SVGP_BLOCK - 1) / SVGP_BLOCK);
-    hipLaunchKernelGGL(k_stats_accumulate, dim3(nblk), dim3(SVGP_BLOCK), 0, (hipStream_t)stream, nS, nv, (int)wl.stat_parts,
+    hipLaunchKernelGGL(k_stats_accumulate, dim3(svgp_blocks(nS + nv + 1)), dim3(SVGP_BLOCK), 0, (hipStream_t)stream, nS, nv, (int)wl.stat_parts,
                        first != 0, (real)c->b, ws + wl.S, ws + wl.v, cache + cl.acc_S, cache + cl.acc_v, cache + cl.acc_rows);
     SVGP_LAUNCH_CHECK();
     return SVGP_OK;
@@ -327,7 +281,7 @@ extern "C" int svgp_mnist_cache_build(const svgp_mnist_cfg* c, const double* the
     rc = svgp_kernel_matrix_xy(c->M, c->normalize_obj, m, ip, 0, m, ip, 0, nullptr, theta + pl.l_GP, theta + pl.amplitude, 0, work + cw.K, stream);
     if (rc) return rc;
     const long long tot = (long long)(L + 1) * m * m;
-    hipLaunchKernelGGL(k_cache_sigma, dim3((unsigned)((tot + SVGP_BLOCK - 1) / SVGP_BLOCK)), dim3(SVGP_BLOCK), 0, (hipStream_t)stream, m, L,
+    hipLaunchKernelGGL(k_cache_sigma, dim3(svgp_blocks(tot)), dim3(SVGP_BLOCK), 0, (hipStream_t)stream, m, L,
                        (real)c->N_train, (real)c->jitter, work + cw.K, cache + cl.acc_S, cache + cl.acc_rows, work + cw.B);
     SVGP_LAUNCH_CHECK();
     rc = svgp_spd_inverse_batched(m, L + 1, work + cw.B, work + cw.logdet, work + cw.inv, stream);
@@ -351,11 +305,8 @@ extern "C" int svgp_mnist_generate_route(const svgp_mnist_cfg* c, char* buf, int
     const int n = gen_plan(c, ops);
     int pos = 0;
     buf[0] = 0;
-    for (int i = 0; i < n; ++i) {
-        pos += snprintf(buf + pos, cap - pos, "%s\n", GEN_NAME[ops[i]]);
-        SVGP_REQUIRE(pos < cap, SVGP_ERR_INVALID, "route text needs more than %d bytes", cap);
-    }
-    return SVGP_OK;
+    for (int i = 0; i < n && !rc; ++i) rc = svgp_route_append(buf, cap, &pos, "%s\n", GEN_NAME[ops[i]]);
+    return rc;
 }
 
 extern "C" int svgp_mnist_generate(const svgp_mnist_cfg* c, const double* theta, const double* cache, const double* aux, int gather,
@@ -378,8 +329,8 @@ extern "C" int svgp_mnist_generate(const svgp_mnist_cfg* c, const double* theta,
     a.w = cache + cl.w; a.X = cache + cl.X; a.eps = eps; a.z = work ? work + gw.z : nullptr;
     a.images = images_out; a.p_m = p_m_out; a.p_v = p_v_out;
     const int64_t n_dec = pl.n_vae - pl.n_enc;
-    const size_t lds_dec = (size_t)(n_dec + 64 + 128 + 512 + 1568 + 784 + DEC_NWE) * sizeof(real);
-    // (the fused form runs for m <= 64 and svgp_check_cfg holds L <= 64: at most 18 954 doubles = 151 632 bytes, asserted below)
+    const size_t lds_dec = (size_t)dec_fwd_lds((int)n_dec, false) * sizeof(real);
+    // (the fused form runs for m <= 64 and svgp_check_cfg holds L <= 64: at most 18 954 doubles = 151 632 bytes, asserted above)
     const size_t lds_gp = lds_dec + (size_t)(m + 1 + (int64_t)L * m) * sizeof(real);
     const dim3 grid(svgp_n_part(c));
     hipStream_t st = (hipStream_t)stream;
@@ -394,7 +345,7 @@ extern "C" int svgp_mnist_generate(const svgp_mnist_cfg* c, const double* theta,
             SVGP_LAUNCH_CHECK();
             break;
         case GEN_KX:
-            hipLaunchKernelGGL(k_generate_kx, dim3((unsigned)(((long long)b * m + SVGP_BLOCK - 1) / SVGP_BLOCK)), dim3(SVGP_BLOCK), 0, st, a,
+            hipLaunchKernelGGL(k_generate_kx, dim3(svgp_blocks((long long)b * m)), dim3(SVGP_BLOCK), 0, st, a,
                                work + gw.Kx);
             SVGP_LAUNCH_CHECK();
             break;
@@ -407,7 +358,7 @@ extern "C" int svgp_mnist_generate(const svgp_mnist_cfg* c, const double* theta,
             if (rc) return rc;
             break;
         case GEN_ROWSUM:
-            hipLaunchKernelGGL(k_generate_rowsum, dim3((unsigned)(((long long)b * L + SVGP_BLOCK - 1) / SVGP_BLOCK)), dim3(SVGP_BLOCK), 0, st, a,
+            hipLaunchKernelGGL(k_generate_rowsum, dim3(svgp_blocks((long long)b * L)), dim3(SVGP_BLOCK), 0, st, a,
                                work + gw.Kx, work + gw.P, work + gw.pm, work + gw.z);
             SVGP_LAUNCH_CHECK();
             break;

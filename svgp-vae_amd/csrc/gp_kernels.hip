@@ -1743,12 +1743,6 @@ __global__ __launch_bounds__(SVGP_BLOCK) void k_cache_build(CacheArgs a) {
     }
 }
 
-template <typename F>
-int set_dyn_lds(F kernel, size_t bytes) {
-    SVGP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    return SVGP_OK;
-}
 // launch of a kernel template <int MC> (compile-time m): the m = 32 instance for config 2, the run-time-m instance otherwise
 #define LAUNCH_MC(kern, m_, grid_, lds_, stream_, args_)                                                              \
     do {                                                                                                              \

@@ -553,7 +553,6 @@ __global__ void k_ball_asum(int mm, int L, real Btot, const real* __restrict__ A
     out[o] = s;
 }
 
-inline unsigned nblk(long long n) { return (unsigned)((n + 255) / 256); }
 
 }  // namespace
 
@@ -623,7 +622,7 @@ int svgp_big_stats(const svgp_mnist_cfg* c, const svgp_mnist_ws_layout& wl, doub
     // scr_bl (free until the row-form SW weights / the reverse row stage), results in the contiguous [ud | td] of statB, the factor c
     // applied to td's rows by the reduction pass: the same partial sums per element as two contractions, two launches less
     const bool stacked = mode == 1 && wl.td == wl.ud + (int64_t)L * m;
-    hipLaunchKernelGGL(k_big_weights, dim3(nblk((long long)b * L)), dim3(256), 0, st, b * L, L, mode, SVGP_LOSS_FLAGS(c), c->clip_pv, cc, state,
+    hipLaunchKernelGGL(k_big_weights, dim3(svgp_blocks((long long)b * L)), dim3(256), 0, st, b * L, L, mode, SVGP_LOSS_FLAGS(c), c->clip_pv, cc, state,
                        ws + wl.qnet_mu, ws + wl.qnet_var, ws + wl.p_m, ws + wl.p_v, ws + wl.e, ws + wl.eps,
                        ws + wl.zbar, wbuf, abuf, bbuf, stacked ? s.bl0 : (real*)nullptr);
     SVGP_LAUNCH_CHECK();
@@ -653,7 +652,7 @@ int svgp_big_stats(const svgp_mnist_cfg* c, const svgp_mnist_ws_layout& wl, doub
         // the rank-local row sums of the reverse pass (they enter Kbar linearly: no exchange, see the file header):
         // [Qs; Pbar^T] (2 m, m) = X^T Kn, split over the rows when that leaves few output tiles (config 3: 23.6 + 25.9 us for the two
         // products as single launches with a contraction of 1024, round 4)
-        hipLaunchKernelGGL(k_big_rowlocal, dim3(nblk((long long)b * m)), dim3(256), 0, st, b, m, L, SVGP_LOSS_FLAGS(c), state,
+        hipLaunchKernelGGL(k_big_rowlocal, dim3(svgp_blocks((long long)b * m)), dim3(256), 0, st, b, m, L, SVGP_LOSS_FLAGS(c), state,
                            ws + wl.qnet_var, wbuf, Kn, s.KS + (size_t)b * m, s.sKS, s.X, s.qbar);
         SVGP_LAUNCH_CHECK();
         RUNC(svgp_dgemm_splitk(1, 0, 2 * m, m, b, 1.0, s.X, 2 * m, Kn, m, 0.0, s.Qs, m, s.sk2, s.sk2_elems, stream));   // Qs | Pbar^T (contiguous)
@@ -668,7 +667,7 @@ int svgp_big_stats(const svgp_mnist_cfg* c, const svgp_mnist_ws_layout& wl, doub
         // k_big_recip, read by the epilogue.  (tried: plain SW + the pass; removed)
         if (!c->titsias && c->b == c->b_global && c->b < 3 * m) {
             real* mhalf_g3 = s.ldtmp + c->L + 8;       // (slots L + 1 .. L + 15 of the log-det scratch are free)
-            hipLaunchKernelGGL(k_big_recip, dim3(nblk((long long)b * L)), dim3(256), 0, st, b * L, ws + wl.qnet_var, s.wst,
+            hipLaunchKernelGGL(k_big_recip, dim3(svgp_blocks((long long)b * L)), dim3(256), 0, st, b * L, ws + wl.qnet_var, s.wst,
                                SVGP_LOSS_FLAGS(c), L, state, mhalf_g3);
             SVGP_LAUNCH_CHECK();
             svgp_gemm_epi ep;
@@ -720,12 +719,12 @@ int svgp_big_factor_fwd(const svgp_mnist_cfg* c, const svgp_mnist_ws_layout& wl,
                  SVGP_CHOL_INVERSE_MIN_M);
     const bool do_k = pieces & SVGP_FWD_K, do_sig = pieces & SVGP_FWD_SIG;
     if (do_sig) {
-        hipLaunchKernelGGL(k_big_add_diag, dim3(nblk(mm * L)), dim3(256), 0, st, m, L, cc, c->jitter, K, ws + wl.S + om, 0LL, Si);
+        hipLaunchKernelGGL(k_big_add_diag, dim3(svgp_blocks(mm * L)), dim3(256), 0, st, m, L, cc, c->jitter, K, ws + wl.S + om, 0LL, Si);
         SVGP_LAUNCH_CHECK();
     }
     if (do_k) {
         // K_mm inverse + log det (SVGPVAE_model.py:239,270,273) next to the channel matrices (:331)
-        hipLaunchKernelGGL(k_big_add_diag, dim3(nblk(mm)), dim3(256), 0, st, m, 1, real(0), c->jitter, K, (const real*)nullptr,
+        hipLaunchKernelGGL(k_big_add_diag, dim3(svgp_blocks(mm)), dim3(256), 0, st, m, 1, real(0), c->jitter, K, (const real*)nullptr,
                            0LL, Ki);
         SVGP_LAUNCH_CHECK();
     }
@@ -772,7 +771,7 @@ int svgp_big_factor_fwd(const svgp_mnist_cfg* c, const svgp_mnist_ws_layout& wl,
     if (do_k) {
         // q_n = k_n^T Ki k_n;  W = (Kn Ki) K behind the rows of Kn;  P^T = K Ki
         GEMM(0, 1, b, m, m, 1.0, Kn, m, 0, Ki, m, 0, 0.0, s.KnKi, m, 0, 1);           // kept: the reverse pass reads Kn Ki again
-        hipLaunchKernelGGL(k_big_rowdot, dim3(nblk((long long)b * 64)), dim3(256), 0, st, b, m, 1, real(1), s.KnKi, 0LL, Kn,
+        hipLaunchKernelGGL(k_big_rowdot, dim3(svgp_blocks((long long)b * 64)), dim3(256), 0, st, b, m, 1, real(1), s.KnKi, 0LL, Kn,
                            ws + wl.q, 1, 0);
         SVGP_LAUNCH_CHECK();
         GEMM(0, 1, b, m, m, 1.0, s.KnKi, m, 0, K, m, 0, 0.0, s.W, m, 0, 1);
@@ -782,9 +781,9 @@ int svgp_big_factor_fwd(const svgp_mnist_cfg* c, const svgp_mnist_ws_layout& wl,
         // (Aji holds A_hat + jI: written by the product A = K G above; the tail inverts it in place)
         RUNC(svgp_spd_inverse_batched(m, L, Aji, s.ldtmp, s.inv, stream));
         if (ball_kl)
-            hipLaunchKernelGGL(k_ball_kl, dim3(nblk(L)), dim3(256), 0, st, m, L, (real)c->L, ws + wl.ldK, s.ldtmp, klp, klq, ws + wl.KL);
+            hipLaunchKernelGGL(k_ball_kl, dim3(svgp_blocks(L)), dim3(256), 0, st, m, L, (real)c->L, ws + wl.ldK, s.ldtmp, klp, klq, ws + wl.KL);
         else
-            hipLaunchKernelGGL(k_big_kl, dim3(nblk(L)), dim3(256), 0, st, m, L, ws + wl.ldK, s.ldtmp, klp, ws + wl.KL + l0);
+            hipLaunchKernelGGL(k_big_kl, dim3(svgp_blocks(L)), dim3(256), 0, st, m, L, ws + wl.ldK, s.ldtmp, klp, ws + wl.KL + l0);
         SVGP_LAUNCH_CHECK();
     }
     return SVGP_OK;
@@ -801,7 +800,7 @@ int svgp_big_posterior_fwd(const svgp_mnist_cfg* c, const svgp_mnist_ws_layout& 
     // [Kn; W] Si_l in one product over the 2 b stacked rows; kept for svgp_big_posterior_bwd / svgp_big_stats (mode 1)
     GEMM(0, 1, 2 * b, m, m, 1.0, Kn, m, 0, ws + wl.Si, m, mm, 0.0, s.KS, m, s.sKS, L);
     // r = k^T Si k -> p_v slot and s = w^T Si w (= k^T Ki A Ki k) -> d slot: one launch, two jobs
-    hipLaunchKernelGGL(k_big_rowdot2, dim3(nblk((long long)b * L * 64), 2), dim3(256), 0, st, b, m, L, real(1), s.KS, s.KS + bm, s.sKS,
+    hipLaunchKernelGGL(k_big_rowdot2, dim3(svgp_blocks((long long)b * L * 64), 2), dim3(256), 0, st, b, m, L, real(1), s.KS, s.KS + bm, s.sKS,
                        Kn, (const real*)s.W, ws + wl.p_v, ws + wl.d, L);
     SVGP_LAUNCH_CHECK();
     GEMM(0, 1, b, L, m, cc, Kn, m, 0, ws + wl.t, m, 0, 0.0, ws + wl.p_m, L, 0, 1);               // p_m = c Kn t^T
@@ -811,7 +810,7 @@ int svgp_big_posterior_fwd(const svgp_mnist_cfg* c, const svgp_mnist_ws_layout& 
     a.knn = ws + wl.knn; a.q = ws + wl.q; a.y = ws + wl.qnet_mu; a.s2 = ws + wl.qnet_var; a.eps_in = eps; a.state = state;
     a.p_m = ws + wl.p_m; a.p_v = ws + wl.p_v; a.e = ws + wl.e; a.d = ws + wl.d; a.eps = ws + wl.eps; a.z = ws + wl.z;
     a.part = ws + wl.part_sums + (size_t)svgp_n_part(c) * 4;
-    const unsigned nb = nblk((long long)b * L);
+    const unsigned nb = svgp_blocks((long long)b * L);
     SVGP_REQUIRE((long long)nb <= wl.n_post, SVGP_ERR_INVALID, "partial-sum layout too small");
     hipLaunchKernelGGL(k_big_post_final, dim3(nb), dim3(256), 0, st, a);
     SVGP_LAUNCH_CHECK();
@@ -850,7 +849,7 @@ int svgp_big_factor_bwd(const svgp_mnist_cfg* c, const svgp_mnist_ws_layout& wl,
     a.A2 = ws + wl.A2 + om; a.mu = ws + wl.mu_hat + ov; a.u = ws + wl.u + ov; a.ud = ws + wl.ud + ov; a.td = ws + wl.td + ov;
     a.v = ws + wl.v + ov;
     a.ubar = s.vec0; a.mubar = s.vec1; a.tbar = s.vec2; a.Sibar = s.mm1; a.Sg = s.mm1; a.HG = s.mm3; a.Ssym = ws + wl.Ssym + om;
-    const unsigned gmm = nblk(mm * L), ntp = (unsigned)((m + TP - 1) / TP);
+    const unsigned gmm = svgp_blocks(mm * L), ntp = (unsigned)((m + TP - 1) / TP);
     // SW_l = W^T diag(p_l) W = P^T S_l P -- forward quantities only.  Over the rows (a statistics product with contraction b) when ALL
     // rows of the batch are local (b == b_global) and that is the cheaper form (m^2 b against 3 m^3 per channel): at the end of the
     // reverse statistics (svgp_big_stats, mode 1).  From S_l otherwise -- under data parallelism S_l is the all-reduced statistic, so SW needs no exchange of
@@ -879,13 +878,13 @@ int svgp_big_factor_bwd(const svgp_mnist_cfg* c, const svgp_mnist_ws_layout& wl,
                            (const real*)s.mm0, Db);
         SVGP_LAUNCH_CHECK();
         GEMM(0, 1, m, m, m, 1.0, A, m, mm, A, m, mm, 0.0, s.mm3, m, mm, L);                         // A A               (mm3)
-        hipLaunchKernelGGL(k_ball_asum, dim3(nblk(mm)), dim3(256), 0, st, (int)mm, L, Btot, (const real*)A, (const real*)s.mm3, s.Asum);
+        hipLaunchKernelGGL(k_ball_asum, dim3(svgp_blocks(mm)), dim3(256), 0, st, (int)mm, L, Btot, (const real*)A, (const real*)s.mm3, s.Asum);
         SVGP_LAUNCH_CHECK();
         GEMM(0, 1, m, m, m, 1.0, G, m, mm, Db, m, mm, 0.0, s.mm0, m, mm, L);                        // H = G D           (mm0: M is consumed)
         GEMM_SYM(0, 1, m, m, 1.0, s.mm0, m, mm, G, m, mm, 0.0, s.mm3, m, mm, L);                    // HG = H G^T        (mm3: A A is consumed)
-        hipLaunchKernelGGL(k_big_sum_channels, dim3(nblk(mm)), dim3(256), 0, st, (int)mm, L, real(1), s.mm0, s.Zs);
+        hipLaunchKernelGGL(k_big_sum_channels, dim3(svgp_blocks(mm)), dim3(256), 0, st, (int)mm, L, real(1), s.mm0, s.Zs);
         SVGP_LAUNCH_CHECK();
-        hipLaunchKernelGGL(k_big_sum_channels, dim3(nblk(mm)), dim3(256), 0, st, (int)mm, L, real(1), s.mm3, s.HGs);
+        hipLaunchKernelGGL(k_big_sum_channels, dim3(svgp_blocks(mm)), dim3(256), 0, st, (int)mm, L, real(1), s.mm3, s.HGs);
         SVGP_LAUNCH_CHECK();
     } else if (pieces & SVGP_BWD_EARLY_B) {
         real* G = ws + wl.G + om;
@@ -901,7 +900,7 @@ int svgp_big_factor_bwd(const svgp_mnist_cfg* c, const svgp_mnist_ws_layout& wl,
             GEMM(0, 1, m, m, m, 1.0, G, m, mm, Db, m, mm, 0.0, s.mm0, m, mm, L);
         }
         GEMM_SYM(0, 1, m, m, 1.0, s.mm0, m, mm, G, m, mm, 0.0, s.mm3, m, mm, L);         // HG = H G^T = Si K D K Si  (mm3)
-        hipLaunchKernelGGL(k_big_sum_channels3, dim3(nblk(mm), 3), dim3(256), 0, st, (int)mm, L, real(1), (const real*)s.mm0, s.Zs,
+        hipLaunchKernelGGL(k_big_sum_channels3, dim3(svgp_blocks(mm), 3), dim3(256), 0, st, (int)mm, L, real(1), (const real*)s.mm0, s.Zs,
                            (const real*)s.mm3, s.HGs, (const real*)A, s.Asum);
         SVGP_LAUNCH_CHECK();
     }
@@ -942,7 +941,7 @@ int svgp_big_factor_bwd(const svgp_mnist_cfg* c, const svgp_mnist_ws_layout& wl,
         if (!x_early) RUNC(x_block());
         hipLaunchKernelGGL(k_big_fb_ssym, dim3(ntp, ntp, L), dim3(256), 0, st, a);
         SVGP_LAUNCH_CHECK();
-        hipLaunchKernelGGL(k_big_sum_channels, dim3(nblk(mm)), dim3(256), 0, st, (int)mm, L, real(1), s.mm1, s.Sgs);
+        hipLaunchKernelGGL(k_big_sum_channels, dim3(svgp_blocks(mm)), dim3(256), 0, st, (int)mm, L, real(1), s.mm1, s.Sgs);
         SVGP_LAUNCH_CHECK();
     }
     // The gradient of Ki is needed for the channel sum only (Ki is shared): Kib = rep_weight (gK/2 sum A + sum ubar mu^T) + Qs + Pbar K,
@@ -955,14 +954,14 @@ int svgp_big_factor_bwd(const svgp_mnist_cfg* c, const svgp_mnist_ws_layout& wl,
     f.rank1_late = a.rank1_late; f.vbar = a.vbar;      // (KiPbar: KBAR's last product, read by FINAL only)
     if (pieces & SVGP_BWD_KBAR) {
         GEMM(0, 0, m, m, m, 1.0, K, m, 0, s.Pbar, m, 0, 0.0, s.tA, m, 0, 1);                // K Pbar^T = (Pbar K)^T   (s.Pbar holds Pbar^T)
-        hipLaunchKernelGGL(k_big_fb_kib, dim3(nblk(mm)), dim3(256), 0, st, f);             // Kib (tB)
+        hipLaunchKernelGGL(k_big_fb_kib, dim3(svgp_blocks(mm)), dim3(256), 0, st, f);             // Kib (tB)
         SVGP_LAUNCH_CHECK();
         GEMM(0, 0, m, m, m, 1.0, Ki, m, 0, s.tB, m, 0, 0.0, s.tC, m, 0, 1);                 // Ki Kib             (tC)
         GEMM(0, 1, m, m, m, 1.0, s.tC, m, 0, Ki, m, 0, 0.0, s.tA, m, 0, 1);                 // Ki Kib Ki          (tA)
         GEMM(0, 1, m, m, m, 1.0, s.Pbar, m, 0, Ki, m, 0, 0.0, s.tB, m, 0, 1);               // Pbar^T Ki = (Ki Pbar)^T   (tB)
     }
     if (pieces & SVGP_BWD_FINAL) {
-        hipLaunchKernelGGL(k_big_fb_final, dim3(nblk(mm)), dim3(256), 0, st, f);
+        hipLaunchKernelGGL(k_big_fb_final, dim3(svgp_blocks(mm)), dim3(256), 0, st, f);
         SVGP_LAUNCH_CHECK();
     }
     return SVGP_OK;
@@ -987,11 +986,11 @@ int svgp_big_posterior_bwd(const svgp_mnist_cfg* c, const svgp_mnist_ws_layout& 
     // one (b, m, m, L) product: Kn Si_l comes from the forward pass (svgp_big_posterior_fwd on this workspace), Kn Ki from
     // svgp_big_factor_fwd; the d-term's share arrives through Wbar P^T below
     GEMM(0, 1, b, m, m, 1.0, Kn, m, 0, ws + wl.Ssym, m, mm, 0.0, s.bm, m, bm, L);
-    hipLaunchKernelGGL(k_big_rowdot, dim3(nblk((long long)b * L * 64)), dim3(256), 0, st, b, m, L, real(0.5), s.bm, bm, Kn,
+    hipLaunchKernelGGL(k_big_rowdot, dim3(svgp_blocks((long long)b * L * 64)), dim3(256), 0, st, b, m, L, real(0.5), s.bm, bm, Kn,
                        s.bl0, L, 0);
     SVGP_LAUNCH_CHECK();
     GEMM(0, 1, b, L, m, 1.0, Kn, m, 0, ws + wl.vbar, m, 0, 0.0, s.bl1, L, 0, 1);   // kv = Kn vbar^T
-    hipLaunchKernelGGL(k_big_pb_elem, dim3(nblk((long long)b * L)), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_big_pb_elem, dim3(svgp_blocks((long long)b * L)), dim3(256), 0, st, a);
     SVGP_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_big_pb_knbar, dim3(b), dim3(256), 5 * (size_t)L * sizeof(real), st, a);
     SVGP_LAUNCH_CHECK();

@@ -521,7 +521,6 @@ __global__ void k_clip(long long tot, real thr, real* __restrict__ g) {
     if (i < tot) g[i] = clip_keep_nan(g[i], -thr, thr);
 }
 
-inline unsigned nb256(long long n) { return (unsigned)((n + 255) / 256); }
 
 int make_spk(const svgp_sprites_kcfg* c, const double* aux, const double* ip, const double* table, const double* se,
              SpK& a) {
@@ -544,7 +543,7 @@ extern "C" int svgp_sprites_kernel_matrix_fwd(const svgp_sprites_kcfg* c, const 
     if (rc) return rc;
     SVGP_REQUIRE(K && Kn && knn, SVGP_ERR_INVALID, "NULL pointer");
     const int nbt = (a.b + 15) / 16, nmt = (a.m + 15) / 16;
-    hipLaunchKernelGGL(k_sprites_kernel_fwd_tiles, dim3((unsigned)(nbt * nmt + nmt * nmt) + nb256(a.b)), dim3(256), 0,
+    hipLaunchKernelGGL(k_sprites_kernel_fwd_tiles, dim3((unsigned)(nbt * nmt + nmt * nmt) + svgp_blocks(a.b)), dim3(256), 0,
                        (hipStream_t)stream, a, nbt, nmt, K, Kn, knn);
     SVGP_LAUNCH_CHECK();
     return SVGP_OK;
@@ -608,7 +607,7 @@ extern "C" int svgp_sprites_kernel_matrix_bwd(const svgp_sprites_kcfg* c, const 
         real* part0 = part_se + (size_t)(a.m + a.b) * 4 + 16;
         real* part1 = part0 + (size_t)s0 * a.m * NV;
         const int t0 = (a.m + KB_TT - 1) / KB_TT, t1 = (a.b + KB_TT - 1) / KB_TT;
-        const dim3 grid(t0 > t1 ? t0 : t1, s0 > s1 ? s0 : s1, 2), gridf(nb256((long long)(a.m + a.b) * NV));
+        const dim3 grid(t0 > t1 ? t0 : t1, s0 > s1 ? s0 : s1, 2), gridf(svgp_blocks((long long)(a.m + a.b) * NV));
         if (bk == 1) {
             hipLaunchKernelGGL((k_sprites_kernel_bwd_tiles<8, 16>), grid, dim3(256), 0, st, a, s0, s1, Kbar, Knbar, part0, part1);
             SVGP_LAUNCH_CHECK();
@@ -641,35 +640,35 @@ extern "C" int svgp_sprites_aux_fwd(int b, int seg_len, int Lc, const double* re
                                     void* stream) {
     SVGP_REQUIRE(b >= 1 && seg_len >= 1 && b % seg_len == 0 && repr && action_ids && aux, SVGP_ERR_INVALID,
                  "batch must be a multiple of the frames-per-character count (SPRITES_experiment.py:40-41)");
-    hipLaunchKernelGGL(k_sprites_aux_fwd, dim3(nb256((long long)b * (1 + Lc))), dim3(256), 0, (hipStream_t)stream, b, seg_len,
+    hipLaunchKernelGGL(k_sprites_aux_fwd, dim3(svgp_blocks((long long)b * (1 + Lc))), dim3(256), 0, (hipStream_t)stream, b, seg_len,
                        Lc, repr, action_ids, aux);
     SVGP_LAUNCH_CHECK();
     return SVGP_OK;
 }
 extern "C" int svgp_sprites_aux_bwd(int b, int seg_len, int Lc, const double* d_char, double* d_repr, void* stream) {
     SVGP_REQUIRE(b >= 1 && seg_len >= 1 && b % seg_len == 0 && d_char && d_repr, SVGP_ERR_INVALID, "bad argument");
-    hipLaunchKernelGGL(k_sprites_aux_bwd, dim3(nb256((long long)b * Lc)), dim3(256), 0, (hipStream_t)stream, b, seg_len, Lc,
+    hipLaunchKernelGGL(k_sprites_aux_bwd, dim3(svgp_blocks((long long)b * Lc)), dim3(256), 0, (hipStream_t)stream, b, seg_len, Lc,
                        d_char, d_repr);
     SVGP_LAUNCH_CHECK();
     return SVGP_OK;
 }
 extern "C" int svgp_avgpool_fwd(int n, int HW, int Cc, const double* x, double* y, void* stream) {
     SVGP_REQUIRE(n >= 1 && HW >= 1 && Cc >= 1 && x && y, SVGP_ERR_INVALID, "bad argument");
-    hipLaunchKernelGGL(k_avgpool_fwd<double>, dim3(nb256((long long)n * Cc)), dim3(256), 0, (hipStream_t)stream, n, HW, Cc, x, y);
+    hipLaunchKernelGGL(k_avgpool_fwd<double>, dim3(svgp_blocks((long long)n * Cc)), dim3(256), 0, (hipStream_t)stream, n, HW, Cc, x, y);
     SVGP_LAUNCH_CHECK();
     return SVGP_OK;
 }
 extern "C" int svgp_avgpool_bwd(int n, int HW, int Cc, const double* dy, double* dx, void* stream) {
     SVGP_REQUIRE(n >= 1 && HW >= 1 && Cc >= 1 && dy && dx, SVGP_ERR_INVALID, "bad argument");
     const long long tot = (long long)n * HW * Cc;
-    hipLaunchKernelGGL(k_avgpool_bwd<double>, dim3(nb256(tot)), dim3(256), 0, (hipStream_t)stream, tot, HW, Cc, dy, dx);
+    hipLaunchKernelGGL(k_avgpool_bwd<double>, dim3(svgp_blocks(tot)), dim3(256), 0, (hipStream_t)stream, tot, HW, Cc, dy, dx);
     SVGP_LAUNCH_CHECK();
     return SVGP_OK;
 }
 extern "C" int svgp_enc_head_fwd(int b, int L, int clip, const double* bias, double* enc, double* mu, double* var_raw,
                                  double* var, void* stream) {
     SVGP_REQUIRE(b >= 1 && L >= 1 && bias && enc && mu && var_raw && var, SVGP_ERR_INVALID, "bad argument");
-    hipLaunchKernelGGL(k_enc_head_fwd, dim3(nb256((long long)b * 2 * L)), dim3(256), 0, (hipStream_t)stream, b, L, clip, bias,
+    hipLaunchKernelGGL(k_enc_head_fwd, dim3(svgp_blocks((long long)b * 2 * L)), dim3(256), 0, (hipStream_t)stream, b, L, clip, bias,
                        enc, mu, var_raw, var);
     SVGP_LAUNCH_CHECK();
     return SVGP_OK;
@@ -677,7 +676,7 @@ extern "C" int svgp_enc_head_fwd(int b, int L, int clip, const double* bias, dou
 extern "C" int svgp_enc_head_bwd(int b, int L, int clip, const double* var_raw, const double* ybar, const double* s2bar,
                                  double* d_enc, void* stream) {
     SVGP_REQUIRE(b >= 1 && L >= 1 && var_raw && ybar && s2bar && d_enc, SVGP_ERR_INVALID, "bad argument");
-    hipLaunchKernelGGL(k_enc_head_bwd, dim3(nb256((long long)b * 2 * L)), dim3(256), 0, (hipStream_t)stream, b, L, clip,
+    hipLaunchKernelGGL(k_enc_head_bwd, dim3(svgp_blocks((long long)b * 2 * L)), dim3(256), 0, (hipStream_t)stream, b, L, clip,
                        var_raw, ybar, s2bar, d_enc);
     SVGP_LAUNCH_CHECK();
     return SVGP_OK;
@@ -695,13 +694,13 @@ __global__ void k_gauss_cross_entropy(long long n, const double* __restrict__ mu
 extern "C" int svgp_gauss_cross_entropy(long long n, const double* mu1, const double* var1, const double* mu2,
                                         const double* var2, double* out, void* stream) {
     SVGP_REQUIRE(n >= 1 && mu1 && var1 && mu2 && var2 && out, SVGP_ERR_INVALID, "bad argument");
-    hipLaunchKernelGGL(k_gauss_cross_entropy, dim3(nb256(n)), dim3(256), 0, (hipStream_t)stream, n, mu1, var1, mu2, var2, out);
+    hipLaunchKernelGGL(k_gauss_cross_entropy, dim3(svgp_blocks(n)), dim3(256), 0, (hipStream_t)stream, n, mu1, var1, mu2, var2, out);
     SVGP_LAUNCH_CHECK();
     return SVGP_OK;
 }
 extern "C" int svgp_bias_add(long long rows, int Cc, const double* bias, double* x, void* stream) {
     SVGP_REQUIRE(rows >= 1 && Cc >= 1 && bias && x, SVGP_ERR_INVALID, "bad argument");
-    hipLaunchKernelGGL(k_bias_add<double>, dim3(nb256(rows * Cc)), dim3(256), 0, (hipStream_t)stream, rows * Cc, Cc, bias, x);
+    hipLaunchKernelGGL(k_bias_add<double>, dim3(svgp_blocks(rows * Cc)), dim3(256), 0, (hipStream_t)stream, rows * Cc, Cc, bias, x);
     SVGP_LAUNCH_CHECK();
     return SVGP_OK;
 }
@@ -716,7 +715,7 @@ extern "C" int svgp_sqerr_fwd(long long tot, int n_part, const double* x, const 
 extern "C" int svgp_sqerr_bwd(long long tot, int geco, int b_global, int n_pix, const double* state, const double* x,
                               const double* xhat, double* dxhat, void* stream) {
     SVGP_REQUIRE(tot >= 1 && b_global >= 1 && n_pix >= 1 && state && x && xhat && dxhat, SVGP_ERR_INVALID, "bad argument");
-    hipLaunchKernelGGL(k_sqerr_bwd<double>, dim3(nb256(tot)), dim3(256), 0, (hipStream_t)stream, tot, geco, 1.0 / b_global,
+    hipLaunchKernelGGL(k_sqerr_bwd<double>, dim3(svgp_blocks(tot)), dim3(256), 0, (hipStream_t)stream, tot, geco, 1.0 / b_global,
                        1.0 / n_pix, state, x, xhat, dxhat);
     SVGP_LAUNCH_CHECK();
     return SVGP_OK;
@@ -725,20 +724,20 @@ extern "C" int svgp_sqerr_bwd(long long tot, int geco, int b_global, int n_pix, 
 // the partial sums of the reconstruction error and the device state stay float64
 extern "C" int svgp_avgpool_fwd_f32(int n, int HW, int Cc, const float* x, float* y, void* stream) {
     SVGP_REQUIRE(n >= 1 && HW >= 1 && Cc >= 1 && x && y, SVGP_ERR_INVALID, "bad argument");
-    hipLaunchKernelGGL(k_avgpool_fwd<float>, dim3(nb256((long long)n * Cc)), dim3(256), 0, (hipStream_t)stream, n, HW, Cc, x, y);
+    hipLaunchKernelGGL(k_avgpool_fwd<float>, dim3(svgp_blocks((long long)n * Cc)), dim3(256), 0, (hipStream_t)stream, n, HW, Cc, x, y);
     SVGP_LAUNCH_CHECK();
     return SVGP_OK;
 }
 extern "C" int svgp_avgpool_bwd_f32(int n, int HW, int Cc, const float* dy, float* dx, void* stream) {
     SVGP_REQUIRE(n >= 1 && HW >= 1 && Cc >= 1 && dy && dx, SVGP_ERR_INVALID, "bad argument");
     const long long tot = (long long)n * HW * Cc;
-    hipLaunchKernelGGL(k_avgpool_bwd<float>, dim3(nb256(tot)), dim3(256), 0, (hipStream_t)stream, tot, HW, Cc, dy, dx);
+    hipLaunchKernelGGL(k_avgpool_bwd<float>, dim3(svgp_blocks(tot)), dim3(256), 0, (hipStream_t)stream, tot, HW, Cc, dy, dx);
     SVGP_LAUNCH_CHECK();
     return SVGP_OK;
 }
 extern "C" int svgp_bias_add_f32(long long rows, int Cc, const float* bias, float* x, void* stream) {
     SVGP_REQUIRE(rows >= 1 && Cc >= 1 && bias && x, SVGP_ERR_INVALID, "bad argument");
-    hipLaunchKernelGGL(k_bias_add<float>, dim3(nb256(rows * Cc)), dim3(256), 0, (hipStream_t)stream, rows * Cc, Cc, bias, x);
+    hipLaunchKernelGGL(k_bias_add<float>, dim3(svgp_blocks(rows * Cc)), dim3(256), 0, (hipStream_t)stream, rows * Cc, Cc, bias, x);
     SVGP_LAUNCH_CHECK();
     return SVGP_OK;
 }
@@ -752,7 +751,7 @@ extern "C" int svgp_sqerr_fwd_f32(long long tot, int n_part, const float* x, con
 extern "C" int svgp_sqerr_bwd_f32(long long tot, int geco, int b_global, int n_pix, const double* state, const float* x,
                                   const float* xhat, float* dxhat, void* stream) {
     SVGP_REQUIRE(tot >= 1 && b_global >= 1 && n_pix >= 1 && state && x && xhat && dxhat, SVGP_ERR_INVALID, "bad argument");
-    hipLaunchKernelGGL(k_sqerr_bwd<float>, dim3(nb256(tot)), dim3(256), 0, (hipStream_t)stream, tot, geco, 1.0 / b_global,
+    hipLaunchKernelGGL(k_sqerr_bwd<float>, dim3(svgp_blocks(tot)), dim3(256), 0, (hipStream_t)stream, tot, geco, 1.0 / b_global,
                        1.0 / n_pix, state, x, xhat, dxhat);
     SVGP_LAUNCH_CHECK();
     return SVGP_OK;
@@ -809,7 +808,7 @@ extern "C" int svgp_softmax_xent(int n, int C, const double* logits, const doubl
 extern "C" int svgp_clip_by_value(long long tot, double thr, double* g, void* stream) {
     SVGP_REQUIRE(tot >= 0 && thr > 0 && (g || tot == 0), SVGP_ERR_INVALID, "bad argument");
     if (tot == 0) return SVGP_OK;
-    hipLaunchKernelGGL(k_clip, dim3(nb256(tot)), dim3(256), 0, (hipStream_t)stream, tot, thr, g);
+    hipLaunchKernelGGL(k_clip, dim3(svgp_blocks(tot)), dim3(256), 0, (hipStream_t)stream, tot, thr, g);
     SVGP_LAUNCH_CHECK();
     return SVGP_OK;
 }

@@ -512,13 +512,6 @@ StatsPlan stats_plan(long long n, int m, int L) {
     return p;
 }
 
-template <typename F>
-int set_lds(F kernel, size_t bytes) {
-    SVGP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    return SVGP_OK;
-}
-
 int check_kdesc(const svgp_stream_kdesc* kd) {
     SVGP_REQUIRE(kd != nullptr, SVGP_ERR_INVALID, "kernel descriptor is NULL");
     SVGP_REQUIRE(kd->kind >= 0 && kd->kind <= 2, SVGP_ERR_INVALID, "kernel kind %d", kd->kind);
@@ -631,9 +624,9 @@ extern "C" int svgp_stream_stats_f32(int64_t n, int m, int L, const float* K_nm,
     // 32-row chunks: 128 MFMAs per wave between barriers (16-row chunks measured 6 % slower)
     constexpr int KC = 32;
     const size_t lds = (size_t)4 * KC * ST_LD * sizeof(float);
-    int rc = set_lds(k_stats_mfma_f32<KC, false>, lds);
+    int rc = set_dyn_lds(k_stats_mfma_f32<KC, false>, lds);
     if (rc) return rc;
-    rc = set_lds(k_stats_mfma_f32<KC, true>, lds);
+    rc = set_dyn_lds(k_stats_mfma_f32<KC, true>, lds);
     if (rc) return rc;
     // the full tile pairs first, then the (5 / 8 as expensive) diagonal tiles fill the tail
     if (p.npair > p.ntile)

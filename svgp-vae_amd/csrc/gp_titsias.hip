@@ -25,7 +25,6 @@
 
 namespace {
 
-inline unsigned nblk(long long n) { return (unsigned)((n + 255) / 256); }
 
 // P2[n][l] = 1 / (var + j);  PY[n][l] = y / (var + j);  KnP[l][n][i] = Kn[n][i] / (var_nl + j)
 __global__ __launch_bounds__(256) void k_tit_weights(int b, int L, real jitter, const real* __restrict__ y,
@@ -180,10 +179,10 @@ int svgp_titsias_stats_wl(const svgp_mnist_cfg* c, const svgp_mnist_ws_layout& w
     real* P2 = ws + wl.scr_bl;               // (b, L)
     real* PY = P2 + (size_t)b * L;           // (b, L)
     real* KnP = ws + wl.scr_bm;              // (L, b, m)
-    hipLaunchKernelGGL(k_tit_weights, dim3(nblk((long long)b * L)), dim3(256), 0, st, b, L, c->jitter, ws + wl.qnet_mu,
+    hipLaunchKernelGGL(k_tit_weights, dim3(svgp_blocks((long long)b * L)), dim3(256), 0, st, b, L, c->jitter, ws + wl.qnet_mu,
                        ws + wl.qnet_var, P2, PY);
     SVGP_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_tit_scale_rows, dim3(nblk((long long)L * b * m)), dim3(256), 0, st, b, m, L, P2, ws + wl.Kn, KnP);
+    hipLaunchKernelGGL(k_tit_scale_rows, dim3(svgp_blocks((long long)L * b * m)), dim3(256), 0, st, b, m, L, P2, ws + wl.Kn, KnP);
     SVGP_LAUNCH_CHECK();
     // S2_l = Kn^T (Kn / d_l)        v2 = PY^T Kn
     RUNC(svgp_dgemm_batched(1, 0, m, m, b, 1.0, ws + wl.Kn, m, 0, KnP, m, (long long)b * m, 0.0, ws + wl.tit_S2, m,
@@ -203,7 +202,7 @@ int svgp_titsias_fwd_wl(const svgp_mnist_cfg* c, const svgp_mnist_ws_layout& wl,
     hipStream_t st = (hipStream_t)stream;
     real* Si2 = ws + wl.tit_Si;
     real* scal = ws + wl.tit_scal;           // [log det Sigma2 (L) | v2.t2 (L) | row sum (1)]
-    hipLaunchKernelGGL(k_tit_sigma, dim3(nblk((long long)L * m * m)), dim3(256), 0, st, m, L, c->jitter, ws + wl.tit_S2,
+    hipLaunchKernelGGL(k_tit_sigma, dim3(svgp_blocks((long long)L * m * m)), dim3(256), 0, st, m, L, c->jitter, ws + wl.tit_S2,
                        ws + wl.K, Si2);
     SVGP_LAUNCH_CHECK();
     RUNC(svgp_spd_inverse_batched(m, L, Si2, scal, ws + wl.scr_inv, stream));
@@ -240,29 +239,29 @@ int svgp_titsias_bwd_wl(const svgp_mnist_cfg* c, const svgp_mnist_ws_layout& wl,
     SVGP_REQUIRE(wl.scr_bm - wl.Knbar_part >= (long long)b * m + 2LL * b * L, SVGP_ERR_INVALID,
                  "ws.Knbar_part holds %lld elements, the Titsias reverse stage keeps b m + 2 b L there (b=%d m=%d L=%d)",
                  (long long)(wl.scr_bm - wl.Knbar_part), b, m, L);
-    hipLaunchKernelGGL(k_tit_sb, dim3(nblk((long long)L * mm)), dim3(256), 0, st, m, L, flags, state, ws + wl.tit_Si,
+    hipLaunchKernelGGL(k_tit_sb, dim3(svgp_blocks((long long)L * mm)), dim3(256), 0, st, m, L, flags, state, ws + wl.tit_Si,
                        ws + wl.tit_t, Sb);
     SVGP_LAUNCH_CHECK();
     // U_l = Kn Sb_l;  Cb = Kn t2^T;  W = Kn Ki
     RUNC(svgp_dgemm_batched(0, 0, b, m, m, 1.0, ws + wl.Kn, m, 0, Sb, m, mm, 0.0, U, m, (long long)b * m, L, stream));
     RUNC(svgp_dgemm_batched(0, 1, b, L, m, 1.0, ws + wl.Kn, m, 0, ws + wl.tit_t, m, 0, 0.0, Cb, L, 0, 1, stream));
     RUNC(svgp_dgemm_batched(0, 0, b, m, m, 1.0, ws + wl.Kn, m, 0, ws + wl.Ki, m, 0, 0.0, W, m, 0, 1, stream));
-    hipLaunchKernelGGL(k_tit_rows_nl, dim3(nblk((long long)b * L)), dim3(256), 0, st, b, m, L, flags, c->jitter, state,
+    hipLaunchKernelGGL(k_tit_rows_nl, dim3(svgp_blocks((long long)b * L)), dim3(256), 0, st, b, m, L, flags, c->jitter, state,
                        ws + wl.qnet_mu, ws + wl.qnet_var, ws + wl.knn, ws + wl.q, ws + wl.Kn, U, Cb, ws + wl.ybar,
                        ws + wl.s2bar, cA, cB);
     SVGP_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_tit_rows_ni, dim3(nblk((long long)b * m)), dim3(256), 0, st, b, m, L, flags, state,
+    hipLaunchKernelGGL(k_tit_rows_ni, dim3(svgp_blocks((long long)b * m)), dim3(256), 0, st, b, m, L, flags, state,
                        ws + wl.qnet_var, U, ws + wl.tit_t, W, cA, cB, ws + wl.Knbar, ws + wl.knnbar);
     SVGP_LAUNCH_CHECK();
     // Kbar += sum_l Sb_l + g2/2 (L Ki - Ki (sum_l S_l) Ki)
-    hipLaunchKernelGGL(k_tit_sum_l, dim3(nblk(mm)), dim3(256), 0, st, (int)mm, L * svgp_stat_parts(c), ws + wl.S, Ssum);   // sum over channels and row partials
+    hipLaunchKernelGGL(k_tit_sum_l, dim3(svgp_blocks(mm)), dim3(256), 0, st, (int)mm, L * svgp_stat_parts(c), ws + wl.S, Ssum);   // sum over channels and row partials
     SVGP_LAUNCH_CHECK();
     RUNC(svgp_dgemm_batched(0, 0, m, m, m, 1.0, ws + wl.Ki, m, 0, Ssum, m, 0, 0.0, T1, m, 0, 1, stream));
     RUNC(svgp_dgemm_batched(0, 0, m, m, m, 1.0, T1, m, 0, ws + wl.Ki, m, 0, 0.0, T2, m, 0, 1, stream));
     // m <= 64: the kernel-matrix reverse pass multiplies the whole of Kbar by cfg.rep_weight.  m > 64: it takes Kbar as it is, with
     // rank-local row sums in it unweighted (gp_large.hip header), so the replicated part added here carries the weight itself
     const real w_rep = m > SVGP_M_MAX ? (real)c->rep_weight : real(1);
-    hipLaunchKernelGGL(k_tit_kbar, dim3(nblk(mm)), dim3(256), 0, st, (int)mm, L, flags, w_rep, state, Sb, ws + wl.Ki, T2,
+    hipLaunchKernelGGL(k_tit_kbar, dim3(svgp_blocks(mm)), dim3(256), 0, st, (int)mm, L, flags, w_rep, state, Sb, ws + wl.Ki, T2,
                        ws + wl.Kbar);
     SVGP_LAUNCH_CHECK();
     return SVGP_OK;

@@ -261,21 +261,17 @@ int pp_args(const svgp_pearce_predict_cfg* g, const svgp_pearce_predict_bufs* q,
     return SVGP_OK;
 }
 
-inline int64_t pp_al16(int64_t n) { return (n + 15) / 16 * 16; }
 struct PlWork { int64_t Am, yv, alpha, logdet, inv, Kq, R, total; };
 PlWork pp_work(const svgp_pearce_predict_cfg* g) {
     const int64_t T = g->T, nm = 2 * (g->B < PPL_NB ? g->B : PPL_NB), nq = g->Q < PPL_QC ? g->Q : PPL_QC;
-    int64_t p = 0;
-    auto take = [&](int64_t n) { int64_t r = p; p += pp_al16(n); return r; };
+    SvgpTake16 c16;
     PlWork o;
-    o.Am = take(nm * T * T); o.yv = take(nm * T); o.alpha = take(nm * T); o.logdet = take(nm);
-    o.inv = take((int64_t)svgp_spd_inverse_workspace_elems((int)T, (int)nm));
-    o.Kq = take(nm * nq * T); o.R = take(nm * nq * T);
-    o.total = p;
+    o.Am = c16.take(nm * T * T); o.yv = c16.take(nm * T); o.alpha = c16.take(nm * T); o.logdet = c16.take(nm);
+    o.inv = c16.take((int64_t)svgp_spd_inverse_workspace_elems((int)T, (int)nm));
+    o.Kq = c16.take(nm * nq * T); o.R = c16.take(nm * nq * T);
+    o.total = c16.p;
     return o;
 }
-
-inline unsigned pp_blocks(long long n) { return (unsigned)((n + SVGP_BLOCK - 1) / SVGP_BLOCK); }
 
 }  // namespace
 
@@ -286,9 +282,7 @@ extern "C" int svgp_pearce_predict_route(const svgp_pearce_predict_cfg* g, int l
     int pos = 0;
     buf[0] = 0;
     return pp_walk(g, long_form != 0, [&](const PpStep& s) -> int {
-        pos += snprintf(buf + pos, cap - pos, "%s\n", PP_NAME[s.op]);
-        SVGP_REQUIRE(pos < cap, SVGP_ERR_INVALID, "route text needs more than %d bytes", cap);
-        return (int)SVGP_OK;
+        return svgp_route_append(buf, cap, &pos, "%s\n", PP_NAME[s.op]);
     });
 }
 
@@ -331,7 +325,7 @@ extern "C" int svgp_pearce_predict_long(const svgp_pearce_predict_cfg* g, const 
         switch (s.op) {
         case PP_FUSED: break;
         case PP_BUILD:
-            hipLaunchKernelGGL(k_pp_build, dim3(pp_blocks(tt), nm), dim3(SVGP_BLOCK), 0, st, a, h);
+            hipLaunchKernelGGL(k_pp_build, dim3(svgp_blocks(tt), nm), dim3(SVGP_BLOCK), 0, st, a, h);
             SVGP_LAUNCH_CHECK();
             break;
         case PP_INVERSE:
@@ -346,7 +340,7 @@ extern "C" int svgp_pearce_predict_long(const svgp_pearce_predict_cfg* g, const 
             SVGP_LAUNCH_CHECK();
             break;
         case PP_KQ:
-            hipLaunchKernelGGL(k_pp_kq, dim3(pp_blocks((long long)s.nq * T), nm), dim3(SVGP_BLOCK), 0, st, a, h);
+            hipLaunchKernelGGL(k_pp_kq, dim3(svgp_blocks((long long)s.nq * T), nm), dim3(SVGP_BLOCK), 0, st, a, h);
             SVGP_LAUNCH_CHECK();
             break;
         case PP_GEMM:       // R_l (nq, T) = Kq_l (nq, T) Ai_l (T, T)

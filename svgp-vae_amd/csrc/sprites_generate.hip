@@ -216,9 +216,8 @@ extern "C" int svgp_sprites_posterior_rows_route(const svgp_posterior_rows_cfg* 
     SVGP_REQUIRE(buf && cap >= 1, SVGP_ERR_INVALID, "bad argument");
     int rc = rows_check(c);
     if (rc) return rc;
-    const int pos = snprintf(buf, cap, rows_split(c) > 1 ? "%s\nk_sprites_posterior_finish\n" : "%s\n", "k_sprites_posterior_rows");
-    SVGP_REQUIRE(pos < cap, SVGP_ERR_INVALID, "route text needs more than %d bytes", cap);
-    return SVGP_OK;
+    int pos = 0;
+    return svgp_route_append(buf, cap, &pos, rows_split(c) > 1 ? "%s\nk_sprites_posterior_finish\n" : "%s\n", "k_sprites_posterior_rows");
 }
 
 extern "C" int svgp_sprites_posterior_rows(const svgp_posterior_rows_cfg* c, const double* Kb, const double* kbb, const double* w,
@@ -238,7 +237,7 @@ extern "C" int svgp_sprites_posterior_rows(const svgp_posterior_rows_cfg* c, con
     SVGP_LAUNCH_CHECK();
     if (S > 1) {
         const size_t n = (size_t)c->b * c->L;
-        hipLaunchKernelGGL(k_sprites_posterior_finish, dim3((unsigned)((n + SVGP_BLOCK - 1) / SVGP_BLOCK)), dim3(SVGP_BLOCK), 0,
+        hipLaunchKernelGGL(k_sprites_posterior_finish, dim3(svgp_blocks((long long)n)), dim3(SVGP_BLOCK), 0,
                            (hipStream_t)stream, a);
         SVGP_LAUNCH_CHECK();
     }

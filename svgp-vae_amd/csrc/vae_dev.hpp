@@ -667,11 +667,72 @@ __device__ __host__ inline EncOff enc_off(int L) {
     o.c3w = p; p += 576; o.c3b = p; p += 8; o.dw = p; p += 32 * 2 * L; o.db = p; p += 2 * L; o.n = p;
     return o;
 }
-__device__ __host__ inline DecOff dec_off(int L) {
-    DecOff o; int p = 0;
+__device__ __host__ constexpr DecOff dec_off(int L) {
+    DecOff o = {}; int p = 0;
     o.dw = p; p += L * 128; o.db = p; p += 128; o.c1w = p; p += 576; o.c1b = p; p += 8;
     o.c2w = p; p += 576; o.c2b = p; p += 8; o.c3w = p; p += 72; o.c3b = p; p += 1; o.n = p;
     return o;
+}
+
+// ------------------------------------------------------------------------------------------
+// Decoder forward z -> dense -> UpC1 -> UpC2 -> UpC3 -> out of ONE image in LDS: the map and the pieces of k_decoder_fwd
+// (vae_mnist.hip), k_generate (generate.hip) and k_casale_generate (casale_generate.hip).
+// LDS: w n_dec | z 64 | h0 128 | a1 512 | a2 1568 | out 784 | [red 16] | We1 We2 We3; a kernel's own arrays start at We1 + DEC_NWE.
+// red (the scratch of block_sum) exists in k_decoder_fwd only.
+// ------------------------------------------------------------------------------------------
+struct DecFwdLds { real *w, *z, *h0, *a1, *a2, *out, *red, *We1, *We2, *We3; };
+__host__ __device__ constexpr int dec_fwd_lds(int n_dec, bool red) {
+    return n_dec + 64 + 128 + 512 + 1568 + 784 + (red ? 16 : 0) + DEC_NWE;
+}
+static_assert(dec_fwd_lds(dec_off(64).n, false) == 14793 && dec_fwd_lds(dec_off(64).n, true) == 14809, "decoder forward map at L = 64");
+template <bool RED>
+__device__ __forceinline__ DecFwdLds dec_fwd_carve(real* smem, int n_dec) {
+    DecFwdLds l;
+    l.w = smem; l.z = l.w + n_dec; l.h0 = l.z + 64; l.a1 = l.h0 + 128; l.a2 = l.a1 + 512; l.out = l.a2 + 1568;
+    l.red = RED ? l.out + 784 : nullptr;
+    l.We1 = l.out + 784 + (RED ? 16 : 0); l.We2 = l.We1 + UpC1::NWE; l.We3 = l.We2 + UpC2::NWE;
+    return l;
+}
+// theta's decoder part into l.w, then the effective weights of the three up-convolutions from the LDS copy (one coalesced read of
+// the raw weights).  k_decoder_fwd stages in its own, measured load order instead.
+__device__ __forceinline__ void decoder_fwd_stage(const DecFwdLds& l, const DecOff& od, const real* th_dec) {
+    lds_copy_in(l.w, th_dec, od.n);
+    __syncthreads();
+    UpC1::build_weff(l.w + od.c1w, l.We1);
+    UpC2::build_weff(l.w + od.c2w, l.We2);
+    UpC3::build_weff(l.w + od.c3w, l.We3);
+}
+// l.z -> l.out, a barrier behind each of the four layers (the caller's barrier stands between its writes of l.z and this).
+// ROLLED: fwd_valu<ROLLED>, the same FMA order in ~85 VGPRs fewer
+template <bool ROLLED>
+__device__ __forceinline__ void decoder_fwd_layers(const DecFwdLds& l, const DecOff& od, int L) {
+    if (threadIdx.x < 128) {
+        real acc = l.w[od.db + threadIdx.x];
+        for (int i = 0; i < L; ++i) acc += l.z[i] * l.w[od.dw + i * 128 + threadIdx.x];
+        l.h0[threadIdx.x] = acc;
+    }
+    __syncthreads();
+    UpC1::fwd_valu<ROLLED>(l.h0, l.We1, l.w + od.c1b, l.a1);
+    __syncthreads();
+    UpC2::fwd_valu<ROLLED>(l.a1, l.We2, l.w + od.c2b, l.a2);
+    __syncthreads();
+    UpC3::fwd_valu<ROLLED>(l.a2, l.We3, l.w + od.c3b, l.out);
+    __syncthreads();
+}
+// decode only: one workgroup of VAE_NT threads turns rows first, first + stride, ... of z (b, L) in global memory into images (b, 784).
+// LDS: dec_fwd_lds(n_dec, false) reals
+__device__ __forceinline__ void decoder_fwd_rows(int b, int L, const real* th_dec, const real* zg, real* images, int first, int stride,
+                                                 real* smem) {
+    const DecOff od = dec_off(L);
+    const DecFwdLds l = dec_fwd_carve<false>(smem, od.n);
+    decoder_fwd_stage(l, od, th_dec);
+    for (int n = first; n < b; n += stride) {
+        __syncthreads();
+        if ((int)threadIdx.x < L) l.z[threadIdx.x] = zg[(size_t)n * L + threadIdx.x];
+        __syncthreads();
+        decoder_fwd_layers<false>(l, od, L);
+        lds_copy_out(images + (size_t)n * 784, l.out, 784);
+    }
 }
 
 

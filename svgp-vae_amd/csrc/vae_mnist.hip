@@ -104,65 +104,45 @@ __global__ __launch_bounds__(VAE_NT) void k_decoder_fwd(int b, int L, const real
                                                             const real* __restrict__ weff) {
     extern __shared__ __align__(16) real smem[];
     const DecOff od = dec_off(L);
-    real* w = smem;                  // od.n
-    real* z = w + od.n;              // 64
-    real* h0 = z + 64;               // 128
-    real* a1 = h0 + 128;             // 512
-    real* a2 = a1 + 512;             // 1568
-    real* out = a2 + 1568;           // 784
-    real* red = out + 784;           // 16
-    real* We1 = red + 16;            // effective weights of the three up-convolutions
-    real* We2 = We1 + UpC1::NWE;
-    real* We3 = We2 + UpC2::NWE;
+    const DecFwdLds l = dec_fwd_carve<true>(smem, od.n);
     // one group of loads (stage_issue, vae_dev.hpp): the first image's z, the effective weights, then theta in chunks
     const int t = threadIdx.x, lz = t < L ? t : L - 1;
     real zr = zg[(size_t)min((int)blockIdx.x, b - 1) * L + lz];
     if (PRE) {
         const auto rwe = stage_issue<DEC_NWE, VAE_NT>(weff);
-        stage_copy<VAE_NT>(w, th_dec, od.n);
-        stage_commit<DEC_NWE, VAE_NT>(We1, rwe);
+        stage_copy<VAE_NT>(l.w, th_dec, od.n);
+        stage_commit<DEC_NWE, VAE_NT>(l.We1, rwe);
     } else {
-        stage_copy<VAE_NT>(w, th_dec, od.n);
+        stage_copy<VAE_NT>(l.w, th_dec, od.n);
         __syncthreads();
-        UpC1::build_weff(w + od.c1w, We1);       // from the LDS copy (one coalesced read of the raw weights)
-        UpC2::build_weff(w + od.c2w, We2);
-        UpC3::build_weff(w + od.c3w, We3);
+        UpC1::build_weff(l.w + od.c1w, l.We1);       // from the LDS copy (one coalesced read of the raw weights)
+        UpC2::build_weff(l.w + od.c2w, l.We2);
+        UpC3::build_weff(l.w + od.c3w, l.We3);
     }
     real sq = 0;
     for (int n = blockIdx.x; n < b; n += gridDim.x) {
         __syncthreads();
-        if (t < L) z[t] = zr;
+        if (t < L) l.z[t] = zr;
         // this image's pixels (read at the end of the iteration) and the next image's z: in flight during the layers
         const auto px = stage_issue<784, VAE_NT>(images + (size_t)n * 784);
         if (n + (int)gridDim.x < b) zr = zg[(size_t)(n + gridDim.x) * L + lz];
         __syncthreads();
-        if (threadIdx.x < 128) {
-            real acc = w[od.db + threadIdx.x];
-            for (int i = 0; i < L; ++i) acc += z[i] * w[od.dw + i * 128 + threadIdx.x];
-            h0[threadIdx.x] = acc;
-        }
-        __syncthreads();
-        UpC1::fwd_valu(h0, We1, w + od.c1b, a1);
-        __syncthreads();
-        UpC2::fwd_valu(a1, We2, w + od.c2b, a2);
-        __syncthreads();
-        UpC3::fwd_valu(a2, We3, w + od.c3b, out);
-        __syncthreads();
-        lds_copy_out(h0g + (size_t)n * 128, h0, 128);
-        lds_copy_out(a1g + (size_t)n * 512, a1, 512);
-        lds_copy_out(a2g + (size_t)n * 1568, a2, 1568);
+        decoder_fwd_layers<false>(l, od, L);
+        lds_copy_out(h0g + (size_t)n * 128, l.h0, 128);
+        lds_copy_out(a1g + (size_t)n * 512, l.a1, 512);
+        lds_copy_out(a2g + (size_t)n * 1568, l.a2, 1568);
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
             const int i = t + k * VAE_NT;
             if (i < 784) {
-                const real o = out[i];
+                const real o = l.out[i];
                 recon[(size_t)n * 784 + i] = o;
                 const real df = px.v[k] - o;
                 sq += df * df;
             }
         }
     }
-    const real tot = block_sum(sq, red);
+    const real tot = block_sum(sq, l.red);
     if (threadIdx.x == 0) part_sums[blockIdx.x * 4 + 2] = tot;
 }
 
@@ -335,13 +315,6 @@ __global__ __launch_bounds__(SVGP_BLOCK) void k_grad_reduce(int n_part, int n_en
     }
 }
 
-template <typename F>
-int set_dyn_lds(F kernel, size_t bytes) {
-    SVGP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    return SVGP_OK;
-}
-
 }  // namespace
 
 #define GET_LAYOUTS()                                          \
@@ -408,7 +381,7 @@ static int decoder_fwd_impl(const svgp_mnist_cfg* c, const double* theta, const 
     GET_LAYOUTS();
     SVGP_REQUIRE(theta && images && ws, SVGP_ERR_INVALID, "NULL device pointer");
     const int64_t n_dec = pl.n_vae - pl.n_enc;
-    const size_t lds = (size_t)(n_dec + 64 + 128 + 512 + 1568 + 784 + 16 + DEC_NWE) * sizeof(real);
+    const size_t lds = (size_t)dec_fwd_lds((int)n_dec, true) * sizeof(real);
     int rc = pre ? set_dyn_lds(k_decoder_fwd<true>, lds) : set_dyn_lds(k_decoder_fwd<false>, lds);
     if (rc) return rc;
 #define DEC_FWD_ARGS c->b, c->L, theta + pl.n_enc, images, ws + wl.z, ws + wl.dec_h0, ws + wl.dec_a1, ws + wl.dec_a2, ws + wl.recon, \

@@ -41,31 +41,58 @@ def _cfg(shape, b, b_cap):
                     normalize_obj=shape["normalize_obj"], N_train=shape["N_train"], jitter=shape["jitter"], rep_weight=1.0)
 
 
-class PosteriorCache:
-    """[acc_S | acc_v | acc_rows | w | X] of svgp_mnist_cache_layout (`data`, one float64 device tensor) with the flat parameter
-    vector `theta` it was built for and the shape fields: the whole deployed model."""
+class _Cache:
+    """What the two posterior caches share: the parameter vector `theta` and the cache `data` as float64 device tensors of the
+    lengths the shape asks for, a stream, and the file {_KEY: data, "theta", "shape"}.  A subclass's _layouts(shape) sets
+    self.shape and its layout structs and returns those two lengths."""
+    _KEY = _WHAT = None
 
     def __init__(self, shape, theta, data, device="cuda:0"):
         _lib.load_library()
         if not torch.cuda.is_available():
-            raise _lib.SvgpError("PosteriorCache needs a HIP device; there is no CPU execution path")
-        self.shape = {k: (float(shape[k]) if k in ("N_train", "jitter") else int(shape[k])) for k in _SHAPE_KEYS}
+            raise _lib.SvgpError(f"{type(self).__name__} needs a HIP device; there is no CPU execution path")
         self.device = torch.device(device)
+        n_theta, n_data = self._layouts(shape)
+        self.theta = torch.as_tensor(theta, dtype=_F64).reshape(-1).to(self.device).contiguous()
+        if self.theta.numel() != n_theta:
+            raise ValueError(f"theta has {self.theta.numel()} elements, the shape {self.shape} needs {n_theta}")
+        self.data = (torch.zeros(n_data, dtype=_F64, device=self.device) if data is None
+                     else torch.as_tensor(data, dtype=_F64).reshape(-1).to(self.device).contiguous())
+        if self.data.numel() != n_data:
+            raise ValueError(f"cache has {self.data.numel()} elements, the shape {self.shape} needs {n_data}")
+        self.stream = torch.cuda.Stream(device=self.device)
+        self.stream.wait_stream(torch.cuda.current_stream(self.device))
+
+    def save(self, path):
+        """One tensor (the cache), the parameter vector and the shape fields."""
+        torch.cuda.synchronize(self.device)
+        torch.save({self._KEY: self.data.cpu(), "theta": self.theta.cpu(), "shape": dict(self.shape)}, path)
+
+    @classmethod
+    def load(cls, path, device="cuda:0"):
+        ck = torch.load(path, map_location="cpu")
+        if not isinstance(ck, dict) or any(k not in ck for k in (cls._KEY, "theta", "shape")):
+            raise ValueError(f"{path}: not a {cls._WHAT} file")
+        return cls(ck["shape"], ck["theta"], ck[cls._KEY], device=device)
+
+
+class PosteriorCache(_Cache):
+    """[acc_S | acc_v | acc_rows | w | X] of svgp_mnist_cache_layout (`data`, one float64 device tensor) with the flat parameter
+    vector `theta` it was built for and the shape fields: the whole deployed model."""
+    _KEY, _WHAT = "cache", "posterior cache"
+
+    def __init__(self, shape, theta, data, device="cuda:0"):
+        super().__init__(shape, theta, data, device)
+        n_work = int(self.lib_elems("svgp_mnist_generate_workspace_elems", _cfg(self.shape, GEN_ROWS, GEN_ROWS)))
+        self.work = torch.empty(n_work, dtype=_F64, device=self.device) if n_work else None
+
+    def _layouts(self, shape):
+        self.shape = {k: (float(shape[k]) if k in ("N_train", "jitter") else int(shape[k])) for k in _SHAPE_KEYS}
         self.cl, self.pl = CacheLayout(), ParamLayout()
         cfg = _cfg(self.shape, 1, GEN_ROWS)
         call("svgp_mnist_cache_layout_get", C.byref(cfg), C.byref(self.cl))
         call("svgp_mnist_param_layout_get", C.byref(cfg), C.byref(self.pl))
-        self.theta = torch.as_tensor(theta, dtype=_F64).reshape(-1).to(self.device).contiguous()
-        if self.theta.numel() != self.pl.n_total:
-            raise ValueError(f"theta has {self.theta.numel()} elements, the shape {self.shape} needs {self.pl.n_total}")
-        self.data = (torch.zeros(self.cl.total, dtype=_F64, device=self.device) if data is None
-                     else torch.as_tensor(data, dtype=_F64).reshape(-1).to(self.device).contiguous())
-        if self.data.numel() != self.cl.total:
-            raise ValueError(f"cache has {self.data.numel()} elements, the shape {self.shape} needs {self.cl.total}")
-        self.stream = torch.cuda.Stream(device=self.device)
-        self.stream.wait_stream(torch.cuda.current_stream(self.device))
-        n_work = int(self.lib_elems("svgp_mnist_generate_workspace_elems", _cfg(self.shape, GEN_ROWS, GEN_ROWS)))
-        self.work = torch.empty(n_work, dtype=_F64, device=self.device) if n_work else None
+        return self.pl.n_total, self.cl.total
 
     @staticmethod
     def lib_elems(name, cfg):
@@ -120,19 +147,6 @@ class PosteriorCache:
         eng.synchronize()
         return self
 
-    # ------------------------------------------------------------------ files
-    def save(self, path):
-        """One tensor (the cache), the parameter vector and the shape fields."""
-        torch.cuda.synchronize(self.device)
-        torch.save({"cache": self.data.cpu(), "theta": self.theta.cpu(), "shape": dict(self.shape)}, path)
-
-    @classmethod
-    def load(cls, path, device="cuda:0"):
-        ck = torch.load(path, map_location="cpu")
-        if not isinstance(ck, dict) or any(k not in ck for k in ("cache", "theta", "shape")):
-            raise ValueError(f"{path}: not a posterior cache file")
-        return cls(ck["shape"], ck["theta"], ck["cache"], device=device)
-
 
 _CASALE_KEYS = ("N", "n_obj", "Q", "M", "L", "normalize_obj", "ov_joint")
 
@@ -142,7 +156,7 @@ def _casale_cfg(shape):
                      normalize_obj=shape["normalize_obj"], train_gp=0, train_ov=shape["ov_joint"])
 
 
-class CasalePosteriorCache:
+class CasalePosteriorCache(_Cache):
     """The Casale GP-VAE after training, without the train set: `data` = [angles | L_W | U | P] of
     svgp_casale_cache_layout (one float64 device tensor), `theta` = [encoder | decoder | l_GP, amplitude, alpha | object_vectors]
     and the shape fields (N, n_obj, Q, M, L, normalize_obj, ov_joint).  P = (alpha I + V^T V)^-1 and U = P V^T Z are all the
@@ -151,27 +165,16 @@ class CasalePosteriorCache:
         cache = CasalePosteriorCache.build(vae, GP, train_images, train_aux)      # or eng.posterior_cache()
         images = generate(cache, aux)                                             # decode of the posterior mean
         images, mean, var = generate(cache, aux, eps=eps, return_moments=True)    # mean (b, L), var (b,)"""
+    _KEY, _WHAT = "casale_cache", "Casale posterior cache"
+    work = None                          # H > 256: svgp_casale_generate_workspace_elems(cfg, b) doubles, allocated by generate
 
-    def __init__(self, shape, theta, data, device="cuda:0"):
-        _lib.load_library()
-        if not torch.cuda.is_available():
-            raise _lib.SvgpError("CasalePosteriorCache needs a HIP device; there is no CPU execution path")
+    def _layouts(self, shape):
         self.shape = {k: int(shape[k]) for k in _CASALE_KEYS}
-        self.device = torch.device(device)
         self.cfg = _casale_cfg(self.shape)
         self.cl, self.wl = CasaleCacheLayout(), CasaleLayout()
         call("svgp_casale_cache_layout_get", C.byref(self.cfg), C.byref(self.cl))       # refuses Q > 32, H > 2048, M > 128, L > 64
         call("svgp_casale_layout_get", C.byref(self.cfg), C.byref(self.wl))
-        self.theta = torch.as_tensor(theta, dtype=_F64).reshape(-1).to(self.device).contiguous()
-        if self.theta.numel() != self.wl.n_total:
-            raise ValueError(f"theta has {self.theta.numel()} elements, the shape {self.shape} needs {self.wl.n_total}")
-        self.data = (torch.zeros(self.cl.total, dtype=_F64, device=self.device) if data is None
-                     else torch.as_tensor(data, dtype=_F64).reshape(-1).to(self.device).contiguous())
-        if self.data.numel() != self.cl.total:
-            raise ValueError(f"cache has {self.data.numel()} elements, the shape {self.shape} needs {self.cl.total}")
-        self.stream = torch.cuda.Stream(device=self.device)
-        self.stream.wait_stream(torch.cuda.current_stream(self.device))
-        self.work = None                 # H > 256: svgp_casale_generate_workspace_elems(cfg, b) doubles, allocated by generate
+        return self.wl.n_total, self.cl.total
 
     def field(self, name):
         """View of a cache field (angles, L_W, U, P)."""
@@ -260,29 +263,18 @@ class CasalePosteriorCache:
         self.Z = Z
         return self
 
-    # ------------------------------------------------------------------ files
-    def save(self, path):
-        """One tensor (the cache), the parameter vector and the shape fields."""
-        torch.cuda.synchronize(self.device)
-        torch.save({"casale_cache": self.data.cpu(), "theta": self.theta.cpu(), "shape": dict(self.shape)}, path)
 
-    @classmethod
-    def load(cls, path, device="cuda:0"):
-        ck = torch.load(path, map_location="cpu")
-        if not isinstance(ck, dict) or any(k not in ck for k in ("casale_cache", "theta", "shape")):
-            raise ValueError(f"{path}: not a Casale posterior cache file")
-        return cls(ck["shape"], ck["theta"], ck["casale_cache"], device=device)
-
-
-def _generate_casale(cache, aux, eps, gather, return_moments):
+def _query(cache, aux, eps, gather, return_moments, var_shape):
+    """The checks of a generate call and its device tensors: (b, aux, eps or None, images, first moment (b, L) or None, second
+    moment (b,) + var_shape or None)."""
     sh = cache.shape
-    if gather is None:
-        gather = bool(sh["ov_joint"])
     aux = torch.as_tensor(aux, dtype=_F64)
     if aux.dim() != 2 or aux.shape[1] != 2 + sh["M"]:
         raise ValueError(f"aux must be (b, {2 + sh['M']}) rows [id, angle, object vector], got {tuple(aux.shape)}")
     b = int(aux.shape[0])
     if gather:
+        if sh["n_obj"] < 1:
+            raise ValueError("gather=True needs a model with an object-vector table; pass gather=False and the vectors in aux")
         ids = aux[:, 0]
         if b and not bool(((ids >= 0) & (ids < sh["n_obj"]) & (ids == ids.floor())).all()):
             raise ValueError(f"ids in aux[:, 0] must be integers in [0, {sh['n_obj']})")
@@ -290,12 +282,16 @@ def _generate_casale(cache, aux, eps, gather, return_moments):
         eps = torch.as_tensor(eps, dtype=_F64)
         if tuple(eps.shape) != (b, sh["L"]):
             raise ValueError(f"eps must be ({b}, {sh['L']}), got {tuple(eps.shape)}")
+    dev = cache.device                   # (the checks above need no device)
+    out = lambda *shape: torch.empty(*shape, dtype=_F64, device=dev)
+    return (b, aux.to(dev).contiguous(), None if eps is None else eps.to(dev).contiguous(), out(b, 28, 28, 1), out(b, sh["L"]) if return_moments else None,
+            out(b, *var_shape) if return_moments else None)
+
+
+def _generate_casale(cache, aux, eps, gather, return_moments):
+    gather = bool(cache.shape["ov_joint"]) if gather is None else gather
+    b, d_aux, d_eps, images, mean, var = _query(cache, aux, eps, gather, return_moments, ())
     dev = cache.device
-    d_aux = aux.to(dev).contiguous()
-    d_eps = None if eps is None else eps.to(dev).contiguous()
-    images = torch.empty(b, 28, 28, 1, dtype=_F64, device=dev)
-    mean = torch.empty(b, sh["L"], dtype=_F64, device=dev) if return_moments else None
-    var = torch.empty(b, dtype=_F64, device=dev) if return_moments else None
     ptr = lambda t: None if t is None else t.data_ptr()
     n_work = int(_lib.load_library().svgp_casale_generate_workspace_elems(C.byref(cache.cfg), b))      # 0 for H <= 256
     if n_work and (cache.work is None or cache.work.numel() < n_work):
@@ -323,25 +319,7 @@ def generate(cache, aux, eps=None, gather=None, return_moments=False):
         return _generate_casale(cache, aux, eps, gather, return_moments)
     gather = True if gather is None else gather
     sh, dev = cache.shape, cache.device
-    aux = torch.as_tensor(aux, dtype=_F64)
-    if aux.dim() != 2 or aux.shape[1] != 2 + sh["M"]:
-        raise ValueError(f"aux must be (b, {2 + sh['M']}) rows [id, angle, object vector], got {tuple(aux.shape)}")
-    b = int(aux.shape[0])
-    if gather:
-        if sh["n_obj"] < 1:
-            raise ValueError("gather=True needs a model with an object-vector table; pass gather=False and the vectors in aux")
-        ids = aux[:, 0]
-        if b and not bool(((ids >= 0) & (ids < sh["n_obj"]) & (ids == ids.floor())).all()):
-            raise ValueError(f"ids in aux[:, 0] must be integers in [0, {sh['n_obj']})")
-    d_aux = aux.to(dev).contiguous()
-    d_eps = None
-    if eps is not None:
-        d_eps = torch.as_tensor(eps, dtype=_F64).to(dev).contiguous()
-        if d_eps.shape != (b, sh["L"]):
-            raise ValueError(f"eps must be ({b}, {sh['L']}), got {tuple(d_eps.shape)}")
-    images = torch.empty(b, 28, 28, 1, dtype=_F64, device=dev)
-    p_m = torch.empty(b, sh["L"], dtype=_F64, device=dev) if return_moments else None
-    p_v = torch.empty(b, sh["L"], dtype=_F64, device=dev) if return_moments else None
+    b, d_aux, d_eps, images, p_m, p_v = _query(cache, aux, eps, gather, return_moments, (sh["L"],))
     cache.stream.wait_stream(torch.cuda.current_stream(dev))
     ptr = lambda t, lo: None if t is None else t[lo:].data_ptr()
     step = GEN_ROWS if cache.work is not None else max(b, 1)

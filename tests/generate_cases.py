@@ -23,7 +23,8 @@ TOL, PATH_TOL = 1e-8, 1e-10
 JITTER = 1e-6
 
 # name -> m, L, M, n_obj, train rows, query rows, table.  E is the first shape on the GEMM path; A and B have m neither a
-# multiple of 4 nor of 16; F has no object-vector table (gather = 0: the object vector is the query row's own columns).
+# multiple of 4 nor of 16; F has no object-vector table (gather = 0: the object vector is the query row's own columns); G asks
+# for the largest LDS of the fused launch (m = 64, L = 64: 151 632 bytes).
 CASES = {
     "A": dict(m=5, L=1, M=2, n_obj=6, rows=37, q=3, table=True),
     "B": dict(m=12, L=3, M=4, n_obj=20, rows=37, q=5, table=True),
@@ -31,8 +32,9 @@ CASES = {
     "D": dict(m=64, L=4, M=16, n_obj=40, rows=150, q=7, table=True),
     "E": dict(m=65, L=4, M=16, n_obj=40, rows=150, q=7, table=True),
     "F": dict(m=12, L=3, M=4, n_obj=0, rows=37, q=5, table=False),
+    "G": dict(m=64, L=64, M=16, n_obj=40, rows=150, q=7, table=True),
 }
-SEED = dict(A=1, B=2, C=3, D=4, E=5, F=6)
+SEED = dict(A=1, B=2, C=3, D=4, E=5, F=6, G=7)
 
 
 @functools.lru_cache(maxsize=None)
