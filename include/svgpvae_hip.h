@@ -191,7 +191,8 @@ const char* svgp_last_error(void);
  * 2 svgp_mnist_ws_layout, 3 svgp_stream_kdesc, 4 svgp_conv_desc, 5 svgp_sprites_kcfg, 6 svgp_pearce_bufs,
  * 7 svgp_sum_job, 8 svgp_casale_cfg, 9 svgp_casale_layout, 10 svgp_ball_large_cfg, 11 svgp_mnist_cache_layout,
  * 13 svgp_ball_predict_cfg, 14 svgp_ball_predict_bufs, 15 svgp_pearce_predict_cfg, 16 svgp_pearce_predict_bufs,
- * 18 svgp_casale_cache_layout, 19 svgp_cvae_cfg, 20 svgp_cvae_ws_layout; -1 otherwise (12 and 17 are not assigned). */
+ * 18 svgp_casale_cache_layout, 19 svgp_cvae_cfg, 20 svgp_cvae_ws_layout, 22 svgp_ball_predict_joint_cfg,
+ * 23 svgp_ball_predict_joint_bufs; -1 otherwise (12, 17 and 21 are not assigned). */
 int         svgp_struct_sizeof(int which);
 
 int svgp_mnist_param_layout_get(const svgp_mnist_cfg* cfg, svgp_mnist_param_layout* out);
@@ -1275,6 +1276,54 @@ int svgp_pearce_predict(const svgp_pearce_predict_cfg* cfg, const svgp_pearce_pr
 long long svgp_pearce_predict_long_workspace_elems(const svgp_pearce_predict_cfg* cfg);
 int svgp_pearce_predict_long(const svgp_pearce_predict_cfg* cfg, const svgp_pearce_predict_bufs* bufs, double* work, void* stream);
 int svgp_pearce_predict_route(const svgp_pearce_predict_cfg* cfg, int long_form, char* buf, int cap);
+
+/* ---- moving ball: joint posterior over the query times, coherent sample paths (ball_predict_joint.hip) --
+ * The full covariance of SVGP.approximate_posterior_params (SVGPVAE_model.py:141-171; the (batch, tmax, tmax) matrix B) at
+ * arbitrary query times, and sample paths drawn with it.  With p, K, Kn, Sig, Si, Ki, w, X and k = SE(tq, ip) exactly those of
+ * svgp_ball_predict above, per video b and latent coordinate:
+ *   C   = SE(tq, tq) + k X k^T                 (Q x Q; diag C is svgp_ball_predict's p_v; nothing is clamped)
+ *   Lc  = chol(C + path_jitter I)  lower       p_m = k w       z = p_m + Lc eps   (eps NULL: z = p_m)
+ * Inputs as svgp_ball_predict's.  eps, p_m and z are (Q, B) per coordinate; cov and chol are (B, Q, Q) per coordinate, cov
+ * symmetric bit for bit (one triangle is formed and mirrored), chol with its strict upper triangle zero.  eps, cov, chol and z may
+ * each be NULL (not read / not written; without chol and without a draw no factor is taken).  A video with every frame dropped has
+ * p_m = 0 exactly and cov = SE(tq, tq): paths from the prior.  A non-positive pivot gives NaN in that (video, coordinate)'s chol
+ * and z only, the convention of svgp_potrf_batched: no error code, no host synchronisation.
+ * svgp_ball_predict_joint: 1 <= m <= 64, 1 <= Q <= 64, 1 <= T <= 16384.  ONE launch, a workgroup per (video, coordinate), the
+ *   Cholesky in LDS; no workspace, no atomics, fixed summation order: the same inputs give the same bits, and permuting tq
+ *   permutes the rows and columns of cov bit for bit.
+ * svgp_ball_predict_joint_large: m, T, Q <= 2048 (every shape of the fused entry included): per chunk of
+ *   min(64, B, max(1, 2^22 / Q^2)) videos the steps of svgp_ball_predict_large up to X and w, svgp_se1d_kernel_matrix_fwd for k,
+ *   svgp_dgemm_batched twice (k X, then (k X) k^T), a kernel that adds SE(tq, tq), mirrors the lower triangle, writes cov and adds
+ *   path_jitter, svgp_potrf_batched (run with one step of iterative refinement on every panel solve, so that Lc Lc^T meets C +
+ *   path_jitter I at the level of an unblocked factorisation for Q > 64 too), and a closing kernel (p_m, z, the copy of chol).  work holds
+ *   svgp_ball_predict_joint_large_workspace_elems(cfg) doubles (0 for a refused cfg), which grows with neither B beyond a chunk nor
+ *   its covariance block beyond 2^22 doubles.
+ * svgp_ball_predict_joint_route: the kernels (library entry points for the shared pieces) of one call as text, one name per line
+ *   in launch order, from the same plan as the launch code; needs no device.  SVGP_ERR_INVALID when cap bytes do not hold the text.
+ * Refused with a message before any launch: a NULL cfg / bufs / pointer (mask, eps, cov, chol and z excepted), B, T, m or Q < 1,
+ *   path_jitter < 0, NULL work (SVGP_ERR_INVALID); m, T or Q beyond the entry's range (SVGP_ERR_UNSUPPORTED).
+ * Explicit stream, no allocation, no synchronisation.                                                                          */
+typedef struct {
+    int32_t B, T, m, Q;
+    double jitter, path_jitter;
+} svgp_ball_predict_joint_cfg;
+typedef struct {
+    const double *times, *tq;                 /* (T), (Q) */
+    const double *ip_x, *ip_y;                /* (m) */
+    const double *ls_x, *ls_y;                /* scalars */
+    const double *mu_x, *mu_y, *var_x, *var_y;/* (T, B) */
+    const double *mask;                       /* (T, B) or NULL */
+    const double *eps_x, *eps_y;              /* (Q, B) or NULL */
+    double *p_m_x, *p_m_y;                    /* (Q, B) */
+    double *cov_x, *cov_y;                    /* (B, Q, Q) or NULL */
+    double *chol_x, *chol_y;                  /* (B, Q, Q) or NULL */
+    double *z_x, *z_y;                        /* (Q, B) or NULL */
+} svgp_ball_predict_joint_bufs;
+int svgp_ball_predict_joint(const svgp_ball_predict_joint_cfg* cfg, const svgp_ball_predict_joint_bufs* bufs, void* stream);
+long long svgp_ball_predict_joint_large_workspace_elems(const svgp_ball_predict_joint_cfg* cfg);
+int svgp_ball_predict_joint_large(const svgp_ball_predict_joint_cfg* cfg, const svgp_ball_predict_joint_bufs* bufs, double* work,
+                                  void* stream);
+int svgp_ball_predict_joint_route(const svgp_ball_predict_joint_cfg* cfg, int large, char* buf, int cap);
 
 /* ---- runtime helpers: HIP graphs and events without going through torch ---------------------*/
 int svgp_stream_create(void** stream_out);

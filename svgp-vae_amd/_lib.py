@@ -138,6 +138,17 @@ class BallPredictBufs(C.Structure):
                                           "eps_x", "eps_y", "p_m_x", "p_m_y", "p_v_x", "p_v_y", "z_x", "z_y")]
 
 
+class BallPredictJointCfg(C.Structure):
+    """svgp_ball_predict_joint_cfg (include/svgpvae_hip.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("B", "T", "m", "Q")] + [(n, C.c_double) for n in ("jitter", "path_jitter")]
+
+
+class BallPredictJointBufs(C.Structure):
+    """svgp_ball_predict_joint_bufs (include/svgpvae_hip.h)."""
+    _fields_ = [(n, C.c_void_p) for n in ("times", "tq", "ip_x", "ip_y", "ls_x", "ls_y", "mu_x", "mu_y", "var_x", "var_y", "mask",
+                                          "eps_x", "eps_y", "p_m_x", "p_m_y", "cov_x", "cov_y", "chol_x", "chol_y", "z_x", "z_y")]
+
+
 class PearcePredictCfg(C.Structure):
     """svgp_pearce_predict_cfg (include/svgpvae_hip.h)."""
     _fields_ = [(n, C.c_int32) for n in ("B", "T", "Q", "q_slices")]
@@ -364,6 +375,9 @@ SIGNATURES = {
     "svgp_ball_predict": [C.POINTER(BallPredictCfg), C.POINTER(BallPredictBufs), _P],
     "svgp_ball_predict_large": [C.POINTER(BallPredictCfg), C.POINTER(BallPredictBufs), _P, _P],
     "svgp_ball_predict_route": [C.POINTER(BallPredictCfg), C.c_int, C.c_char_p, C.c_int],
+    "svgp_ball_predict_joint": [C.POINTER(BallPredictJointCfg), C.POINTER(BallPredictJointBufs), _P],
+    "svgp_ball_predict_joint_large": [C.POINTER(BallPredictJointCfg), C.POINTER(BallPredictJointBufs), _P, _P],
+    "svgp_ball_predict_joint_route": [C.POINTER(BallPredictJointCfg), C.c_int, C.c_char_p, C.c_int],
     "svgp_pearce_predict": [C.POINTER(PearcePredictCfg), C.POINTER(PearcePredictBufs), _P],
     "svgp_pearce_predict_long": [C.POINTER(PearcePredictCfg), C.POINTER(PearcePredictBufs), _P, _P],
     "svgp_pearce_predict_route": [C.POINTER(PearcePredictCfg), C.c_int, C.c_char_p, C.c_int],
@@ -416,6 +430,7 @@ NON_STATUS = {"svgp_version": ([], C.c_int), "svgp_last_error": ([], C.c_char_p)
               "svgp_casale_generate_workspace_elems": ([C.POINTER(CasaleCfg), C.c_longlong], C.c_longlong),
               "svgp_sprites_posterior_rows_workspace_elems": ([C.POINTER(PosteriorRowsCfg)], C.c_longlong),
               "svgp_ball_predict_large_workspace_elems": ([C.POINTER(BallPredictCfg)], C.c_longlong),
+              "svgp_ball_predict_joint_large_workspace_elems": ([C.POINTER(BallPredictJointCfg)], C.c_longlong),
               "svgp_pearce_predict_long_workspace_elems": ([C.POINTER(PearcePredictCfg)], C.c_longlong),
               "svgp_svigp_scale_offset": ([C.c_int, C.c_int, C.c_int], C.c_longlong),
               "svgp_mnist_decoder_weff_lds_offset": ([C.c_int, C.c_int], C.c_int),
@@ -454,7 +469,8 @@ def load_library(path=None):
     mirrors = dict(enumerate((MnistCfg, ParamLayout, WsLayout, StreamKdesc, ConvDesc, SpritesKcfg, PearceBufs, SumJob,
                               CasaleCfg, CasaleLayout, BallLargeCfg, CacheLayout)))
     mirrors.update({13: BallPredictCfg, 14: BallPredictBufs, 15: PearcePredictCfg, 16: PearcePredictBufs,
-                    18: CasaleCacheLayout, 19: CvaeCfg, 20: CvaeWsLayout})             # codes 12 and 17 are not assigned
+                    18: CasaleCacheLayout, 19: CvaeCfg, 20: CvaeWsLayout, 22: BallPredictJointCfg,
+                    23: BallPredictJointBufs})                                         # codes 12, 17 and 21 are not assigned
     for which, cls in mirrors.items():
         if lib.svgp_struct_sizeof(which) != C.sizeof(cls):
             raise SvgpError(f"{p}: sizeof({cls.__name__}) is {lib.svgp_struct_sizeof(which)} in the library but "

@@ -2,11 +2,15 @@
 extrapolate a few frames -- from a `BALL_experiment --save_model` checkpoint.
 
     python -m svgp_vae_amd.ball_predict --checkpoint RUN/model.pt (--videos F.npy | --test_batch K --base_dir D)
-        [--drop 0.5 --drop_seed S | --observed mask.npy] [--upsample R | --query_times t1 t2 ..] [--sample --seed S] --out frames.npy
+        [--drop 0.5 --drop_seed S | --observed mask.npy] [--upsample R | --query_times t1 t2 ..]
+        [--sample | --sample_paths [--path_jitter J]] [--seed S] [--save_cov cov.npy] --out frames.npy
 
 BallPredictor (SVGPVAE_Hensman / SVGPVAE_Titsias): the GP posterior of SVGP.approximate_posterior_params (SVGPVAE_model.py:142-171)
 is evaluated at arbitrary query times from the frames that are observed (a dropped frame is a frame of precision 0):
 svgp_ball_predict, ONE launch per batch for m <= 64 whatever the number of videos and query times, svgp_ball_predict_large beyond.
+`predict(paths=True)` draws one coherent path per video, z = p_m + chol(C + path_jitter I) eps with the full posterior covariance C
+over the query times, and `return_cov=True` returns C: svgp_ball_predict_joint, ONE launch for m <= 64 and
+Q <= 64, svgp_ball_predict_joint_large beyond.
 PearcePredictor (the exact-GP baselines GPVAE_Pearce / NP / VAE): build_1d_gp (GPVAE_Pearce_model.py:8-86) with a general X_test on
 the observed frames of each video: svgp_pearce_predict, ONE launch, up to 64 frames, svgp_pearce_predict_long beyond.
 load_predictor picks the class from the checkpoint, so the command line serves all five --elbo values.  Encoder and decoder are
@@ -18,23 +22,33 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import BallPredictBufs, BallPredictCfg, PearcePredictBufs, PearcePredictCfg, call
+from ._lib import (BallPredictBufs, BallPredictCfg, BallPredictJointBufs, BallPredictJointCfg, PearcePredictBufs, PearcePredictCfg,
+                   SvgpError, call)
 from .ball import _BallMlpEngine, mlp_param_shapes
 
 _F64 = torch.float64
 CLIP_PV = (1e-4, 1000.0)                                  # SVGPVAE_model.py:701: only the sample clamps
 FUSED_M_MAX = 64
+JOINT_FUSED_Q_MAX = 64
 PEARCE_FUSED_T_MAX = 64
 META_KEYS = ("tmax", "m", "hidden", "px", "py", "jitter", "clip_qs")
 PEARCE_META_KEYS = ("tmax", "hidden", "px", "py")          # all an exact-GP model's shape needs; m, jitter, clip_qs are ignored
 _PEARCE_ELBOS = ("GPVAE_Pearce", "NP", "VAE")
 
 
-def route(shape):
+def joint_is_fused(m, Q):
+    return m <= FUSED_M_MAX and Q <= JOINT_FUSED_Q_MAX
+
+
+def route(shape, joint=False):
     """The kernels of the GP stage of one `predict` call of shape (B, T, m, Q), in launch order (svgp_ball_predict_route); needs
-    no device."""
+    no device.  joint: those of the joint entry a call with paths / return_cov adds (svgp_ball_predict_joint_route)."""
     B, T, m, Q = shape
     buf = C.create_string_buffer(1 << 16)
+    if joint:
+        cfg = BallPredictJointCfg(B=int(B), T=int(T), m=int(m), Q=int(Q), jitter=0.0, path_jitter=0.0)
+        call("svgp_ball_predict_joint_route", C.byref(cfg), int(not joint_is_fused(m, Q)), buf, len(buf))
+        return buf.value.decode().split()
     cfg = BallPredictCfg(B=int(B), T=int(T), m=int(m), Q=int(Q), jitter=0.0, clip_lo=CLIP_PV[0], clip_hi=CLIP_PV[1])
     call("svgp_ball_predict_route", C.byref(cfg), int(m > FUSED_M_MAX), buf, len(buf))
     return buf.value.decode().split()
@@ -130,9 +144,9 @@ class _Predictor(_BallMlpEngine):
             for cn, t in zip("xy", pair):
                 setattr(q, f"{k}_{cn}", None if t is None else t.data_ptr())
 
-    def _run_gp(self, fused, cfg, q):
+    def _run_gp(self, fused, cfg, q, entries=None):
         """The one-launch entry, or the workspace entry on `self._work` sized by its *_workspace_elems entry."""
-        one, many = self._ENTRIES
+        one, many = entries or self._ENTRIES
         if fused:
             return call(one, C.byref(cfg), C.byref(q), self.stream.cuda_stream)
         need = int(getattr(self.lib, many + "_workspace_elems")(C.byref(cfg)))      # 0: a shape the entry refuses (it says why)
@@ -141,10 +155,24 @@ class _Predictor(_BallMlpEngine):
         call(many, C.byref(cfg), C.byref(q), self._work.data_ptr() if need else None, self.stream.cuda_stream)
 
     # ------------------------------------------------------------------ frames
-    def predict(self, videos, query_times, observed=None, frame_times=None, eps=None):
+    def predict(self, videos, query_times, observed=None, frame_times=None, eps=None, paths=False, return_cov=False, path_jitter=None):
         """videos (B, T, px, py); query_times (Q) arbitrary reals; observed (B, T) bool, default all; frame_times (T), default 1..T;
         eps (B, Q, 2) or None (decode the posterior mean).  Returns dict(frames (B, Q, px, py) in [0, 1], p_m, p_v, z (B, Q, 2));
-        PearcePredictor adds lh (B, 2)."""
+        PearcePredictor adds lh (B, 2).
+        BallPredictor only: paths=True (needs eps) makes z, and with it frames, ONE coherent sample path per video, z = p_m +
+        chol(C + path_jitter I) eps with C the posterior covariance over the query times (path_jitter defaults to the model's
+        jitter) instead of an independent draw per query time; return_cov=True adds p_cov (B, 2, Q, Q) = C."""
+        if paths or return_cov:
+            if not self._SPARSE:
+                raise NotImplementedError(f"{type(self).__name__}: the joint posterior over the query times (paths / return_cov) is "
+                                          "implemented for the sparse-GP models only, by BallPredictor")
+            if paths and eps is None:
+                raise ValueError("paths=True needs eps (B, Q, 2)")
+            path_jitter = self.jitter if path_jitter is None else float(path_jitter)
+            if not (path_jitter >= 0.0 and np.isfinite(path_jitter)):
+                raise ValueError(f"path_jitter must be finite and >= 0, got {path_jitter}")
+        elif path_jitter is not None:
+            raise ValueError("path_jitter applies to paths=True / return_cov=True only")
         videos = torch.as_tensor(np.asarray(videos) if not torch.is_tensor(videos) else videos)
         if videos.dim() != 4 or tuple(videos.shape[2:]) != (self.px, self.py):
             raise ValueError(f"videos must be (B, T, {self.px}, {self.py}), got {tuple(videos.shape)}")
@@ -182,7 +210,10 @@ class _Predictor(_BallMlpEngine):
             mu, var_raw, var = ([torch.empty(T, B, **f64) for _ in range(2)] for _ in range(3))
             call("svgp_ball_head_fwd", B, T, int(self.clip_qs), p["encB2"].data_ptr(), h2.data_ptr(), mu[0].data_ptr(),
                  var_raw[0].data_ptr(), var[0].data_ptr(), mu[1].data_ptr(), var_raw[1].data_ptr(), var[1].data_ptr(), s)
-            p_m, p_v, zc, extra = self._gp_stage(mu, var, times, tq, mask, eps_c)
+            if paths or return_cov:
+                p_m, p_v, zc, extra = self._gp_stage_joint(mu, var, times, tq, mask, eps_c, paths, return_cov, path_jitter)
+            else:
+                p_m, p_v, zc, extra = self._gp_stage(mu, var, times, tq, mask, eps_c)
             z = torch.empty(B * Q, 2, **f64)
             call("svgp_ball_pack_z", B, Q, zc[0].data_ptr(), zc[1].data_ptr(), z.data_ptr(), s)
             _, logits = self._decode_logits(z)
@@ -193,6 +224,12 @@ class _Predictor(_BallMlpEngine):
             st2 = lambda v: torch.stack([v[0].t(), v[1].t()], 2).contiguous()
             out = dict(frames=frames.view(B, Q, self.px, self.py), p_m=st2(p_m), p_v=st2(p_v), z=z.view(B, Q, 2), **extra)
         self.stream.synchronize()
+        if paths:
+            bad = (~torch.isfinite(out["z"])).any(2).any(1).nonzero().reshape(-1).tolist()
+            if bad:
+                raise SvgpError(f"sample paths of video{'s' if len(bad) != 1 else ''} {', '.join(str(b) for b in bad)} are not finite: "
+                                f"C + path_jitter I has no Cholesky factor in float64 at path_jitter = {path_jitter:g} (or the inputs "
+                                "are not finite); raise path_jitter")
         return out
 
 
@@ -210,12 +247,13 @@ class BallPredictor(_Predictor):
         self._setup(params, param_shapes(int(m), int(px), int(py), int(hidden)), tmax=tmax, hidden=hidden, px=px, py=py,
                     device=device)
 
-    def route(self, B, T, Q):
-        return route((B, T, self.m, Q))
+    def route(self, B, T, Q, joint=False):
+        return route((B, T, self.m, Q), joint)
 
     # ------------------------------------------------------------------ the GP stage alone
-    def _gp(self, mu, var, times, tq, mask, eps_c):
-        """mu, var: two (T, B) tensors each; mask (T, B) or None; eps_c: two (Q, B) tensors or None.  Returns p_m, p_v, z lists."""
+    def _gp(self, mu, var, times, tq, mask, eps_c, force_large=False):
+        """mu, var: two (T, B) tensors each; mask (T, B) or None; eps_c: two (Q, B) tensors or None.  Returns p_m, p_v, z lists.
+        force_large: the workspace entry also where the one-launch entry takes the shape (timings)."""
         T, B = mu[0].shape
         Q, p = tq.numel(), self.params
         out = {k: [torch.empty(Q, B, dtype=_F64, device=self.dev) for _ in range(2)] for k in ("p_m", "p_v", "z")}
@@ -223,11 +261,36 @@ class BallPredictor(_Predictor):
         q = BallPredictBufs()
         q.times, q.tq, q.mask = times.data_ptr(), tq.data_ptr(), None if mask is None else mask.data_ptr()
         self._set_xy(q, ip=(p["ip_x"], p["ip_y"]), ls=(p["l_x"], p["l_y"]), mu=mu, var=var, eps=eps_c or (None, None), **out)
-        self._run_gp(self.m <= FUSED_M_MAX, cfg, q)
+        self._run_gp(self.m <= FUSED_M_MAX and not force_large, cfg, q)
         return out["p_m"], out["p_v"], out["z"]
 
     def _gp_stage(self, mu, var, times, tq, mask, eps_c):
         return self._gp(mu, var, times, tq, mask, eps_c) + ({},)
+
+    def _gp_joint(self, mu, var, times, tq, mask, eps_c, path_jitter, want_cov=True, want_chol=False, want_z=True,
+                  force_large=False):
+        """The joint entry alone.  Returns dict(p_m, z: two (Q, B) tensors each; cov, chol: two (B, Q, Q) tensors each); an output
+        that was not asked for is None.  force_large: as in _gp."""
+        T, B = mu[0].shape
+        Q, p = tq.numel(), self.params
+        new = lambda *shape: [torch.empty(*shape, dtype=_F64, device=self.dev) for _ in range(2)]
+        out = dict(p_m=new(Q, B), cov=new(B, Q, Q) if want_cov else None, chol=new(B, Q, Q) if want_chol else None,
+                   z=new(Q, B) if want_z else None)
+        cfg = BallPredictJointCfg(B=B, T=T, m=self.m, Q=Q, jitter=self.jitter, path_jitter=path_jitter)
+        q = BallPredictJointBufs()
+        q.times, q.tq, q.mask = times.data_ptr(), tq.data_ptr(), None if mask is None else mask.data_ptr()
+        self._set_xy(q, ip=(p["ip_x"], p["ip_y"]), ls=(p["l_x"], p["l_y"]), mu=mu, var=var, eps=eps_c or (None, None),
+                     **{k: v or (None, None) for k, v in out.items()})
+        self._run_gp(joint_is_fused(self.m, Q) and not force_large, cfg, q, ("svgp_ball_predict_joint", "svgp_ball_predict_joint_large"))
+        return out
+
+    def _gp_stage_joint(self, mu, var, times, tq, mask, eps_c, paths, return_cov, path_jitter):
+        """p_v (and, without paths, p_m and the independent draw z) from the marginal entry, whose keys keep their bits; the path
+        and the covariance from the joint one, whose p_m the path is built on."""
+        p_m, p_v, z = self._gp(mu, var, times, tq, mask, None if paths else eps_c)
+        j = self._gp_joint(mu, var, times, tq, mask, eps_c if paths else None, path_jitter, want_cov=return_cov, want_z=paths)
+        extra = dict(p_cov=torch.stack(j["cov"], 1)) if return_cov else {}
+        return (j["p_m"], p_v, j["z"], extra) if paths else (p_m, p_v, z, extra)
 
 
 class PearcePredictor(_Predictor):
@@ -299,11 +362,25 @@ def build_parser():
     qt = p.add_mutually_exclusive_group()
     qt.add_argument("--upsample", type=int, default=None, help="R: the frame times with R - 1 new times between neighbours")
     qt.add_argument("--query_times", type=float, nargs="+", default=None)
-    p.add_argument("--sample", action="store_true", help="z = p_m + eps sqrt(p_v) with eps from --seed; default: the posterior mean")
+    draw = p.add_mutually_exclusive_group()
+    draw.add_argument("--sample", action="store_true", help="z = p_m + eps sqrt(p_v) with eps from --seed, an independent draw per query "
+                      "time; default: the posterior mean")
+    # the joint arguments are absent from the namespace unless given (argparse.SUPPRESS), so that a command line without them
+    # parses to the namespace it always did: read them with joint_args
+    draw.add_argument("--sample_paths", action="store_true", default=argparse.SUPPRESS,
+                      help="one coherent sample path per video, z = p_m + chol(C + J I) eps with eps from --seed (sparse-GP checkpoints)")
+    p.add_argument("--path_jitter", type=float, default=argparse.SUPPRESS, help="J of --sample_paths; default: the model's jitter")
+    p.add_argument("--save_cov", type=str, default=argparse.SUPPRESS,
+                   help=".npy for the posterior covariance over the query times (B, 2, Q, Q)")
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--device", type=str, default="cuda:0")
     p.add_argument("--out", required=True)
     return p
+
+
+def joint_args(args):
+    """(sample_paths, path_jitter or None, save_cov or None) of a parsed command line."""
+    return getattr(args, "sample_paths", False), getattr(args, "path_jitter", None), getattr(args, "save_cov", None)
 
 
 def parse_args(argv=None):
@@ -317,6 +394,11 @@ def parse_args(argv=None):
         p.error("--drop must be in [0, 1)")
     if args.upsample is not None and args.upsample < 1:
         p.error("--upsample must be at least 1")
+    sample_paths, path_jitter, save_cov = joint_args(args)
+    if path_jitter is not None and not path_jitter >= 0.0:
+        p.error("--path_jitter must be >= 0")
+    if path_jitter is not None and not (sample_paths or save_cov):
+        p.error("--path_jitter needs --sample_paths or --save_cov")
     return args
 
 
@@ -331,6 +413,11 @@ def query_grid(T, upsample=None, query_times=None):
 def main(argv=None):
     args = parse_args(argv)
     pred = load_predictor(args.checkpoint, device=args.device)
+    sample_paths, path_jitter, save_cov = joint_args(args)
+    joint = sample_paths or save_cov is not None
+    if joint and not isinstance(pred, BallPredictor):
+        raise SystemExit(f"{args.checkpoint}: --sample_paths, --path_jitter and --save_cov need a sparse-GP checkpoint (SVGPVAE_Hensman / "
+                         "SVGPVAE_Titsias, served by BallPredictor); the exact-GP baselines' joint posterior is not implemented")
     if args.videos is not None:
         videos = np.load(args.videos)
     else:
@@ -347,13 +434,19 @@ def main(argv=None):
     elif args.drop is not None:
         observed = np.random.RandomState(args.drop_seed).rand(B, T) >= args.drop
     tq, at_frames = query_grid(T, args.upsample, args.query_times)
-    eps = np.random.RandomState(args.seed).randn(B, tq.size, 2) if args.sample else None
-    out = pred.predict(videos, tq, observed=observed, eps=eps)
+    eps = np.random.RandomState(args.seed).randn(B, tq.size, 2) if args.sample or sample_paths else None
+    kw = dict(paths=sample_paths, return_cov=save_cov is not None, path_jitter=path_jitter) if joint else {}
+    out = pred.predict(videos, tq, observed=observed, eps=eps, **kw)
     frames = out["frames"].cpu().numpy()
     np.save(args.out, frames)
+    if save_cov is not None:
+        np.save(save_cov, out["p_cov"].cpu().numpy())
     names = pred.route(B, T, tq.size)
     print(f"{B} videos x {tq.size} query times -> {args.out}   route ({len(names)} GP launch{'es' if len(names) != 1 else ''}): "
           f"{' '.join(names)}")
+    if joint:
+        names = pred.route(B, T, tq.size, joint=True)
+        print(f"joint route ({len(names)} GP launch{'es' if len(names) != 1 else ''}): {' '.join(names)}")
     if args.test_batch is not None and observed is not None and at_frames is not None and not observed.all():
         err = (frames[:, at_frames] - videos)[~observed]
         print(f"MSE of the {int((~observed).sum())} filled-in frames against the held-back ones: {float((err ** 2).mean()):.6g}")

@@ -41,6 +41,8 @@ extern "C" int svgp_struct_sizeof(int which) {
     case 18: return (int)sizeof(svgp_casale_cache_layout);    // (17 stays unassigned: tests/test_pearce_predict_cpu.py pins it to -1)
     case 19: return (int)sizeof(svgp_cvae_cfg);
     case 20: return (int)sizeof(svgp_cvae_ws_layout);
+    case 22: return (int)sizeof(svgp_ball_predict_joint_cfg); // (21 stays unassigned: pinned to -1 by the tests)
+    case 23: return (int)sizeof(svgp_ball_predict_joint_bufs);
     default: return -1;
     }
 }

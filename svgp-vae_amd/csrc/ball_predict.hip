@@ -15,6 +15,7 @@
 // X = 0 and w = 0 exactly.  The query times are walked in chunks of 16: 16 lanes share a query, each takes the rows i = lane,
 // lane + 16, ... of k^T X k and of k . w, and an xor-shuffle adds the 16 partials; a query's bits do not depend on where it stands.
 // LDS at m = 64: two 64 x 65 matrices, the 16 x 65 chunk and 4 x 64 + 32 values = 77 184 bytes (two workgroups per CU).
+// The kernel's way to X and w is bp_factors of ball_predict_shared.hpp, which the joint predictor (ball_predict_joint.hip) inlines too.
 //
 // svgp_ball_predict_large (m <= 2048, T <= 2048): the same quantities from the library's global-memory pieces, walked in chunks of
 // BPL_NB videos and BPL_QC query rows so that the workspace grows with neither B nor Q (bp_walk below is the one plan both the
@@ -22,117 +23,35 @@
 // (kbb = 1), an unbounded clip range and no draw: the clamp applies to the sample only and is taken in k_bp_finish.
 #include "common.hpp"
 #include "lds_spd_inverse.hpp"
+#include "ball_predict_shared.hpp"
 
 #include <cmath>
 
 namespace {
 
-constexpr int BP_TC = 16;            // frames (and query times) of a chunk of the fused kernel
-constexpr int BP_M_MAX = 64, BP_T_MAX = 16384;
-constexpr int BPL_T_MAX = 2048;
-constexpr int BPL_NB = 64;           // videos of a chunk of the large form = channels of one svgp_sprites_posterior_rows call
 constexpr int BPL_QC = 4096;         // query rows of a chunk of the large form
 
-struct BpArgs {
-    int B, T, m, Q;
-    real jitter, lo, hi;
-    const real* times; const real* tq; const real* mask;
-    const real* ip[2]; const real* ls[2]; const real* mu[2]; const real* var[2]; const real* eps[2];
+struct BpArgs : BpIn {
+    real lo, hi;
+    const real* eps[2];
     real* p_m[2]; real* p_v[2]; real* z[2];
 };
-
-__device__ __forceinline__ void bp_precision(const BpArgs& a, int c, size_t e, real& p, real& py) {
-    p = recip_no_nan(a.var[c][e]);
-    if (a.mask) p *= a.mask[e];
-    py = p == real(0) ? real(0) : p * a.mu[c][e];
-}
 
 // Thread layout as in lds_spd_inverse: column j = tid & (CW - 1), row lane i0 = tid / CW; a thread owns (i0 + RL r, j).
 template <int CW>
 __global__ __launch_bounds__(256) void k_ball_predict(BpArgs a) {
     extern __shared__ __align__(16) real smem[];
-    constexpr int RL = 256 / CW, RMAX = CW / RL, KS = CW + 1;
+    constexpr int RL = 256 / CW, KS = CW + 1;
     const int tid = threadIdx.x, j = tid & (CW - 1), i0 = tid / CW;
-    const int b = blockIdx.x, c = blockIdx.y, m = a.m, ld = m + 1, B = a.B, T = a.T, Q = a.Q;
-    real* Km = smem;                 // m x ld : K, K + j I, its inverse
-    real* Sg = Km + m * ld;          // m x ld : Sig + j I, its inverse, X
-    real* kt = Sg + m * ld;          // BP_TC x KS : kernel rows of a chunk of frames / of query times, columns >= m zero
-    real* zv = kt + BP_TC * KS;      // CW : inducing points
-    real* vv = zv + CW;              // CW : Kn^T (p y)
-    real* wv = vv + CW;              // CW : w
-    real* piv = wv + CW;             // CW : pivots of the sweep
-    real* pc = piv + CW;             // BP_TC : p of the chunk
-    real* pyc = pc + BP_TC;          // BP_TC : p y of the chunk
-    const real* __restrict__ times = a.times;
+    const int b = blockIdx.x, c = blockIdx.y, m = a.m, ld = m + 1, B = a.B, Q = a.Q;
+    const BpLds s = bp_lds_map<CW>(smem, m * ld, m * ld);
+    real* Sg = s.Sg; real* kt = s.kt; real* zv = s.zv; real* wv = s.wv;
     const real* __restrict__ tq = a.tq;
     const real* __restrict__ eps = a.eps[c];
     real* __restrict__ o_pm = a.p_m[c];
     real* __restrict__ o_pv = a.p_v[c];
     real* __restrict__ o_z = a.z[c];
-    const real l = *a.ls[c], il2 = real(-0.5) / (l * l);
-    if (tid < CW) zv[tid] = tid < m ? a.ip[c][tid] : real(0);
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < RMAX; ++r) {
-        const int i = i0 + RL * r;
-        if (i < m && j < m) { const real d = zv[i] - zv[j]; Km[i * ld + j] = exp(d * d * il2); }
-    }
-    // ---- the frames, in order
-    real acc[RMAX], vacc = 0;
-#pragma unroll
-    for (int r = 0; r < RMAX; ++r) acc[r] = 0;
-    for (int t0 = 0; t0 < T; t0 += BP_TC) {
-        const int cnt = T - t0 < BP_TC ? T - t0 : BP_TC;
-        __syncthreads();             // the previous chunk is consumed
-        if (tid < BP_TC) {
-            real p = 0, py = 0;
-            if (tid < cnt) bp_precision(a, c, (size_t)(t0 + tid) * B + b, p, py);
-            pc[tid] = p; pyc[tid] = py;
-        }
-#pragma unroll
-        for (int r = 0; r < BP_TC / RL; ++r) {
-            const int tc = i0 + RL * r;
-            real k = 0;
-            if (tc < cnt && j < m) { const real d = times[t0 + tc] - zv[j]; k = exp(d * d * il2); }
-            kt[tc * KS + j] = k;
-        }
-        __syncthreads();
-#pragma unroll 2
-        for (int tc = 0; tc < cnt; ++tc) {
-            const real* kr = kt + tc * KS;
-            const real kj = kr[j], pk = pc[tc] * kj;
-#pragma unroll
-            for (int r = 0; r < RMAX; ++r) acc[r] += pk * kr[i0 + RL * r];
-            if (i0 == 0) vacc += pyc[tc] * kj;
-        }
-    }
-    // Sig + j I beside K + j I: equal bit for bit where every p was 0
-#pragma unroll
-    for (int r = 0; r < RMAX; ++r) {
-        const int i = i0 + RL * r;
-        if (i < m && j < m) {
-            const real k = Km[i * ld + j], jit = i == j ? a.jitter : real(0);
-            Sg[i * ld + j] = (k + acc[r]) + jit;
-            Km[i * ld + j] = k + jit;
-        }
-    }
-    if (i0 == 0) vv[j] = vacc;
-#pragma unroll 1
-    for (int which = 0; which < 2; ++which) lds_spd_inverse<CW>(which ? Sg : Km, ld, m, piv);      // one copy of the sweep's code
-    if (tid < CW) {
-        real s = 0;
-        if (tid < m) {
-#pragma unroll 4
-            for (int k = 0; k < m; ++k) s += Sg[tid * ld + k] * vv[k];
-        }
-        wv[tid] = s;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < RMAX; ++r) {
-        const int i = i0 + RL * r;
-        if (i < m && j < m) Sg[i * ld + j] -= Km[i * ld + j];
-    }
+    const real il2 = bp_factors<CW>(a, b, c, s);          // X in Sg, w in wv
     // ---- the query times: 16 per chunk, 16 lanes per query
     const int qc = tid >> 4, l16 = tid & 15;
     for (int q0 = 0; q0 < Q; q0 += BP_TC) {
@@ -166,14 +85,14 @@ __global__ __launch_bounds__(256) void k_ball_predict(BpArgs a) {
     }
 }
 
-inline size_t bp_lds_bytes(int m, int CW) { return ((size_t)2 * m * (m + 1) + BP_TC * (CW + 1) + 4 * CW + 2 * BP_TC) * sizeof(real); }
+inline size_t bp_lds_bytes(int m, int CW) { return ((size_t)2 * m * (m + 1) + bp_lds_tail_elems(CW)) * sizeof(real); }
 static_assert(((size_t)2 * 64 * 65 + BP_TC * 65 + 4 * 64 + 2 * BP_TC) * sizeof(real) <= SVGP_LDS_MAX_BYTES / 2, "two workgroups per CU at m = 64");
 
 // ---------------------------------------------------------------------------------------------------------
 // the large form's own kernels
 // ---------------------------------------------------------------------------------------------------------
 // KnP (nb, T, m) = diag(p_l) Kn per video l = b0 + .. of the chunk, PY (T, nb) = p y
-__global__ __launch_bounds__(SVGP_BLOCK) void k_bp_scale_rows(BpArgs a, int c, int b0, int nb, const real* __restrict__ Kn,
+__global__ __launch_bounds__(SVGP_BLOCK) void k_bp_scale_rows(BpIn a, int c, int b0, int nb, const real* __restrict__ Kn,
                                                               real* __restrict__ KnP, real* __restrict__ PY) {
     const long long tot = (long long)nb * a.T * a.m, e = (long long)blockIdx.x * SVGP_BLOCK + threadIdx.x;
     if (e >= tot) return;
@@ -210,12 +129,6 @@ __global__ __launch_bounds__(SVGP_BLOCK) void k_bp_finish(BpArgs a, int c, int b
 // ---------------------------------------------------------------------------------------------------------
 // one plan for the launch code and the route text
 // ---------------------------------------------------------------------------------------------------------
-enum BpOp { BP_FUSED, BP_KMAT, BP_SCALE, BP_SIGMA, BP_PRIOR, BP_V, BP_INVERSE, BP_W, BP_SUB, BP_KQ, BP_ROWS, BP_FINISH };
-const char* const BP_NAME[] = {"k_ball_predict", "svgp_se1d_kernel_matrix_fwd", "k_bp_scale_rows", "svgp_dgemm_batched", "k_bp_add_prior",
-                               "svgp_dgemm_batched", "svgp_spd_inverse_batched", "svgp_dgemm_batched", "k_bp_subtract",
-                               "svgp_se1d_kernel_matrix_fwd", "svgp_sprites_posterior_rows", "k_bp_finish"};
-struct BpStep { BpOp op; int c, b0, nb, q0, nq; };
-
 // calls f(step) for every launch group of one call, in order; stops at the first non-zero return
 template <class F>
 int bp_walk(const svgp_ball_predict_cfg* g, bool large, F f) {
@@ -225,8 +138,7 @@ int bp_walk(const svgp_ball_predict_cfg* g, bool large, F f) {
         if ((rc = f(BpStep{BP_KMAT, c, 0, 0, 0, 0}))) return rc;
         for (int b0 = 0; b0 < g->B; b0 += BPL_NB) {
             const int nb = g->B - b0 < BPL_NB ? g->B - b0 : BPL_NB;
-            for (BpOp op : {BP_SCALE, BP_SIGMA, BP_PRIOR, BP_V, BP_INVERSE, BP_W, BP_SUB})
-                if ((rc = f(BpStep{op, c, b0, nb, 0, 0}))) return rc;
+            if ((rc = bp_walk_factors(c, b0, nb, f))) return rc;
             for (int q0 = 0; q0 < g->Q; q0 += BPL_QC) {
                 const int nq = g->Q - q0 < BPL_QC ? g->Q - q0 : BPL_QC;
                 for (BpOp op : {BP_KQ, BP_ROWS, BP_FINISH})
@@ -261,14 +173,13 @@ int bp_args(const svgp_ball_predict_cfg* g, const svgp_ball_predict_bufs* q, BpA
     return SVGP_OK;
 }
 
-struct BpWork { int64_t K, Kn, knn, K2, Kq, kbb, KnP, PY, Mats, V, W, logdet, inv, tpm, tpv, rows, total; };
+struct BpWork { BpFactorWork f; int64_t K2, Kq, kbb, tpm, tpv, rows, total; };
 BpWork bp_work(const svgp_ball_predict_cfg* g) {
     const int64_t m = g->m, T = g->T, nb = g->B < BPL_NB ? g->B : BPL_NB, nq = g->Q < BPL_QC ? g->Q : BPL_QC;
     SvgpTake16 c16;
     BpWork o;
-    o.K = c16.take(m * m); o.Kn = c16.take(T * m); o.knn = c16.take(T); o.K2 = c16.take(m * m); o.Kq = c16.take(nq * m); o.kbb = c16.take(nq);
-    o.KnP = c16.take(nb * T * m); o.PY = c16.take(T * nb); o.Mats = c16.take((nb + 1) * m * m); o.V = c16.take(m * nb); o.W = c16.take(nb * m);
-    o.logdet = c16.take(nb + 1); o.inv = c16.take((int64_t)svgp_spd_inverse_workspace_elems((int)m, (int)nb + 1));
+    o.f = bp_factor_work(c16, m, T, nb);
+    o.K2 = c16.take(m * m); o.Kq = c16.take(nq * m); o.kbb = c16.take(nq);
     o.tpm = c16.take(nq * nb); o.tpv = c16.take(nq * nb);
     o.rows = c16.take(m > 256 ? 16 * nq * nb : 0);      // svgp_sprites_posterior_rows_workspace_elems: at most 16 b L, 0 up to m = 256
     o.total = c16.p;
@@ -276,6 +187,56 @@ BpWork bp_work(const svgp_ball_predict_cfg* g) {
 }
 
 }  // namespace
+
+const char* const BP_NAME[] = {"k_ball_predict", "svgp_se1d_kernel_matrix_fwd", "k_bp_scale_rows", "svgp_dgemm_batched", "k_bp_add_prior",
+                               "svgp_dgemm_batched", "svgp_spd_inverse_batched", "svgp_dgemm_batched", "k_bp_subtract",
+                               "svgp_se1d_kernel_matrix_fwd", "svgp_sprites_posterior_rows", "k_bp_finish",
+                               "k_ball_predict_joint", "svgp_se1d_kernel_matrix_fwd", "svgp_dgemm_batched", "svgp_dgemm_batched", "k_bpj_cov",
+                               "svgp_potrf_batched", "k_bpj_finish"};
+
+BpFactorWork bp_factor_work(SvgpTake16& c16, int64_t m, int64_t T, int64_t nb) {
+    BpFactorWork o;
+    o.K = c16.take(m * m); o.Kn = c16.take(T * m); o.knn = c16.take(T);
+    o.KnP = c16.take(nb * T * m); o.PY = c16.take(T * nb); o.Mats = c16.take((nb + 1) * m * m); o.V = c16.take(m * nb); o.W = c16.take(nb * m);
+    o.logdet = c16.take(nb + 1); o.inv = c16.take((int64_t)svgp_spd_inverse_workspace_elems((int)m, (int)nb + 1));
+    return o;
+}
+
+int bp_factor_launch(const BpIn& a, const BpStep& s, const BpFactorWork& w, double* work, void* stream) {
+    const int c = s.c, nb = s.nb, m = a.m, T = a.T;
+    const long long mm = (long long)m * m;
+    hipStream_t st = (hipStream_t)stream;
+    switch (s.op) {
+    case BP_KMAT:
+        return svgp_se1d_kernel_matrix_fwd(T, m, a.times, a.ip[c], a.ls[c], work + w.K, work + w.Kn, work + w.knn, stream);
+    case BP_SCALE:
+        hipLaunchKernelGGL(k_bp_scale_rows, dim3(svgp_blocks((long long)nb * T * m)), dim3(SVGP_BLOCK), 0, st, a, c, s.b0, nb, work + w.Kn,
+                           work + w.KnP, work + w.PY);
+        SVGP_LAUNCH_CHECK();
+        break;
+    case BP_SIGMA:      // Kn^T diag(p_l) Kn: the shared Kn has stride 0
+        return svgp_dgemm_batched(1, 0, m, m, T, 1.0, work + w.Kn, m, 0, work + w.KnP, m, (long long)T * m, 0.0, work + w.Mats, m, mm, nb,
+                                  stream);
+    case BP_PRIOR:
+        hipLaunchKernelGGL(k_bp_add_prior, dim3(svgp_blocks((nb + 1) * mm)), dim3(SVGP_BLOCK), 0, st, m, nb, a.jitter, work + w.K,
+                           work + w.Mats);
+        SVGP_LAUNCH_CHECK();
+        break;
+    case BP_V:          // V (m, nb) = Kn^T PY
+        return svgp_dgemm_batched(1, 0, m, nb, T, 1.0, work + w.Kn, m, 0, work + w.PY, nb, 0, 0.0, work + w.V, nb, 0, 1, stream);
+    case BP_INVERSE:
+        return svgp_spd_inverse_batched(m, nb + 1, work + w.Mats, work + w.logdet, work + w.inv, stream);
+    case BP_W:          // w_l = Si_l V[:, l]
+        return svgp_dgemm_batched(0, 0, m, 1, m, 1.0, work + w.Mats, m, mm, work + w.V, nb, 1, 0.0, work + w.W, 1, m, nb, stream);
+    case BP_SUB:
+        hipLaunchKernelGGL(k_bp_subtract, dim3(svgp_blocks(nb * mm)), dim3(SVGP_BLOCK), 0, st, m, nb, work + w.Mats);
+        SVGP_LAUNCH_CHECK();
+        break;
+    default:
+        SVGP_REQUIRE(false, SVGP_ERR_INVALID, "bp_factor_launch: op %d is not a factor step", (int)s.op);
+    }
+    return SVGP_OK;
+}
 
 extern "C" int svgp_ball_predict_route(const svgp_ball_predict_cfg* g, int large, char* buf, int cap) {
     SVGP_REQUIRE(buf && cap >= 1, SVGP_ERR_INVALID, "bad argument");
@@ -333,43 +294,17 @@ extern "C" int svgp_ball_predict_large(const svgp_ball_predict_cfg* g, const svg
     const BpWork w = bp_work(g);
     SVGP_REQUIRE(work != nullptr, SVGP_ERR_INVALID, "work is NULL (B = %d, T = %d, m = %d, Q = %d needs %lld doubles)", g->B, g->T, g->m,
                  g->Q, (long long)w.total);
-    const int m = a.m, T = a.T;
-    const long long mm = (long long)m * m;
+    const int m = a.m;
     hipStream_t st = (hipStream_t)stream;
     return bp_walk(g, true, [&](const BpStep& s) -> int {
         const int c = s.c, nb = s.nb;
         switch (s.op) {
         case BP_FUSED: break;
-        case BP_KMAT:
-            return svgp_se1d_kernel_matrix_fwd(T, m, a.times, a.ip[c], a.ls[c], work + w.K, work + w.Kn, work + w.knn, stream);
-        case BP_SCALE:
-            hipLaunchKernelGGL(k_bp_scale_rows, dim3(svgp_blocks((long long)nb * T * m)), dim3(SVGP_BLOCK), 0, st, a, c, s.b0, nb, work + w.Kn,
-                               work + w.KnP, work + w.PY);
-            SVGP_LAUNCH_CHECK();
-            break;
-        case BP_SIGMA:      // Kn^T diag(p_l) Kn: the shared Kn has stride 0
-            return svgp_dgemm_batched(1, 0, m, m, T, 1.0, work + w.Kn, m, 0, work + w.KnP, m, (long long)T * m, 0.0, work + w.Mats, m, mm, nb,
-                                      stream);
-        case BP_PRIOR:
-            hipLaunchKernelGGL(k_bp_add_prior, dim3(svgp_blocks((nb + 1) * mm)), dim3(SVGP_BLOCK), 0, st, m, nb, a.jitter, work + w.K,
-                               work + w.Mats);
-            SVGP_LAUNCH_CHECK();
-            break;
-        case BP_V:          // V (m, nb) = Kn^T PY
-            return svgp_dgemm_batched(1, 0, m, nb, T, 1.0, work + w.Kn, m, 0, work + w.PY, nb, 0, 0.0, work + w.V, nb, 0, 1, stream);
-        case BP_INVERSE:
-            return svgp_spd_inverse_batched(m, nb + 1, work + w.Mats, work + w.logdet, work + w.inv, stream);
-        case BP_W:          // w_l = Si_l V[:, l]
-            return svgp_dgemm_batched(0, 0, m, 1, m, 1.0, work + w.Mats, m, mm, work + w.V, nb, 1, 0.0, work + w.W, 1, m, nb, stream);
-        case BP_SUB:
-            hipLaunchKernelGGL(k_bp_subtract, dim3(svgp_blocks(nb * mm)), dim3(SVGP_BLOCK), 0, st, m, nb, work + w.Mats);
-            SVGP_LAUNCH_CHECK();
-            break;
         case BP_KQ:
             return svgp_se1d_kernel_matrix_fwd(s.nq, m, a.tq + s.q0, a.ip[c], a.ls[c], work + w.K2, work + w.Kq, work + w.kbb, stream);
         case BP_ROWS: {
             const svgp_posterior_rows_cfg rc_ = {s.nq, m, nb, -INFINITY, INFINITY};
-            return svgp_sprites_posterior_rows(&rc_, work + w.Kq, work + w.kbb, work + w.W, work + w.Mats, nullptr, work + w.tpm, work + w.tpv,
+            return svgp_sprites_posterior_rows(&rc_, work + w.Kq, work + w.kbb, work + w.f.W, work + w.f.Mats, nullptr, work + w.tpm, work + w.tpv,
                                                nullptr, work + w.rows, stream);
         }
         case BP_FINISH:
@@ -377,6 +312,8 @@ extern "C" int svgp_ball_predict_large(const svgp_ball_predict_cfg* g, const svg
                                work + w.tpm, work + w.tpv);
             SVGP_LAUNCH_CHECK();
             break;
+        default:
+            return bp_factor_launch(a, s, w.f, work, stream);
         }
         return (int)SVGP_OK;
     });

@@ -470,7 +470,14 @@ extern "C" size_t svgp_potri_workspace_elems(int m, int batch) {
 // zeroed -- what a tile of at most ZBAND x ZBAND that touches the diagonal can read of it.
 #define ZBAND 128
 static bool potrf_wide_steps(int m) { return m >= 512; }
-static int potrf_impl(int m, int batch, double* A, int lda, long long strideA, double* logdet, double* work, void* stream, int band) {
+// refine != 0 (svgp_potrf_batched_refined, for callers that need the factor's residual |A - L L^T| at the level of an unblocked
+// factorisation): the panel solve L_ik = A_ik L_kk^-T multiplies by the EXPLICIT inverse of the diagonal block's factor, which leaves
+// a residual of order u cond(L_kk) |A_ik| where a substitution leaves u |L_ik| |L_kk^T|.  One step of iterative refinement in working
+// precision removes it: R = A_ik - L_ik L_kk^T (in place on the panel, which the copy-back overwrites anyway), L_ik += R L_kk^-T --
+// two more products per block step.  The block steps are then always 64 wide: the 128-wide diagonal kernel solves its inner panel
+// by the same explicit inverse.  With refine == 0 nothing changes.
+static int potrf_impl(int m, int batch, double* A, int lda, long long strideA, double* logdet, double* work, void* stream, int band,
+                      int refine = 0) {
     SVGP_REQUIRE(m >= 1 && batch >= 0 && lda >= m, SVGP_ERR_INVALID, "bad m / batch / lda (m=%d batch=%d lda=%d)", m, batch, lda);
     if (batch == 0) return SVGP_OK;
     SVGP_REQUIRE(A && logdet && work, SVGP_ERR_INVALID, "NULL device pointer");
@@ -490,7 +497,7 @@ static int potrf_impl(int m, int batch, double* A, int lda, long long strideA, d
     d2.nblk2 = nblk2; d2.logdet = logdet;
     // Block steps of W = 128 rows from m >= 512 (k_chol_diag2: half the dependent launches, K = 128 products; the triangular inverse
     // of svgp_spd_inverse_batched then starts from 128-blocks: 512 x 16 inverse 557 -> 522 us), 64 below
-    const int W = potrf_wide_steps(m) ? 2 * CB : CB, nstep = (m + W - 1) / W;   // (256 x 17: 243 -> 255 us, 512 x 16: 553 -> 561 with the wide steps)
+    const int W = potrf_wide_steps(m) && !refine ? 2 * CB : CB, nstep = (m + W - 1) / W;   // (256 x 17: 243 -> 255 us, 512 x 16: 553 -> 561 with the wide steps)
     // Look-ahead (right-looking with the trailing update split): after panel k is solved, ONLY block column k + 1 is updated on
     // the caller's stream -- that is all the next diagonal block and the next panel solve need -- and the rest of the trailing
     // update (columns k + 2 ..) runs on a side branch beside them: a block step costs max(trailing update, column update +
@@ -528,6 +535,13 @@ static int potrf_impl(int m, int batch, double* A, int lda, long long strideA, d
         // tile columns span the panel and one would overwrite operand columns the other is still reading.)
         RUNC(svgp_dgemm_tri_batched(0, 0, 1, rem, nbk, nbk, 1.0, panel, lda, strideA, Lk, ldk, sLk, 0.0, Pn, W, (long long)m * W,
                                     batch, stream));
+        if (refine) {
+            const real* Lkk = A + (size_t)r0 * lda + r0;         // the factor of the diagonal block, its strict upper part zero
+            RUNC(svgp_dgemm_tri_batched(0, 0, 1, rem, nbk, nbk, -1.0, Pn, W, (long long)m * W, Lkk, lda, strideA, 1.0, panel, lda, strideA,
+                                        batch, stream));
+            RUNC(svgp_dgemm_tri_batched(0, 0, 1, rem, nbk, nbk, 1.0, panel, lda, strideA, Lk, ldk, sLk, 1.0, Pn, W, (long long)m * W,
+                                        batch, stream));
+        }
         hipLaunchKernelGGL(k_copy_block, dim3(nblk256((long long)rem * nbk), batch), dim3(256), 0, s, rem, nbk, Pn, W,
                            (long long)m * W, panel, lda, strideA);
         SVGP_LAUNCH_CHECK();
@@ -563,6 +577,9 @@ extern "C" int svgp_potrf_batched(int m, int batch, double* A, int lda, long lon
 }
 int svgp_potrf_batched_band(int m, int batch, double* A, int lda, long long strideA, double* logdet, double* work, void* stream) {
     return potrf_impl(m, batch, A, lda, strideA, logdet, work, stream, 1);
+}
+int svgp_potrf_batched_refined(int m, int batch, double* A, int lda, long long strideA, double* logdet, double* work, void* stream) {
+    return potrf_impl(m, batch, A, lda, strideA, logdet, work, stream, 0, 1);
 }
 
 // ---- trsm -----------------------------------------------------------------------------------------------------

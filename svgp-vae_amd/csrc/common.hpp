@@ -45,6 +45,8 @@ int svgp_side_branch_fork(const SvgpSched& sc, void* main_stream, void** side_st
 // cholesky.hip: svgp_potrf_batched that zeroes only the 128 columns right of the diagonal (library-internal consumers)
 int svgp_potri_batched_wide(int m, int batch, double* A, const double* potrf_work, double* work, void* stream);
 int svgp_potrf_batched_band(int m, int batch, double* A, int lda, long long strideA, double* logdet, double* work, void* stream);
+// cholesky.hip: svgp_potrf_batched with one step of iterative refinement on every panel solve (64-wide block steps throughout)
+int svgp_potrf_batched_refined(int m, int batch, double* A, int lda, long long strideA, double* logdet, double* work, void* stream);
 int svgp_side_branch_join(void* main_stream, int k = 1);
 // linalg.hip: svgp_dgemm_splitk with a second factor for the result rows >= row2
 int svgp_dgemm_splitk_rows2(int ta, int tb, int M, int N, int K, double alpha, double alpha2, int row2, const double* A, int lda,

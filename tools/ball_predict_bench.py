@@ -8,7 +8,11 @@ Frames 32 x 32, hidden 500, 40 % of the frames dropped.  The GP stage is timed b
 launches only, inputs resident), `predict` by the wall clock around a call that ends in a device synchronise; medians and minima
 over --reps calls after a warm-up of each.  Information only, no threshold; needs a GPU and fails without one.
 
-    python tools/ball_predict_bench.py [--reps 30] [--out profiles/ball_predict_bench.json]
+--joint: instead, the GP stage of the marginal entries (p_m, p_v, an independent draw) against that of the joint entries (p_m, the
+full covariance, its Cholesky factor's path) at (35, 30, 15, 60) through the one-launch and through the
+workspace entries, and at (35, 30, 15, 1024) through the workspace entries, which alone take that Q.
+
+    python tools/ball_predict_bench.py [--joint] [--reps 30] [--out profiles/ball_predict_bench.json]
 """
 import argparse
 import json
@@ -24,6 +28,7 @@ sys.path.insert(0, ROOT)
 
 SHAPES = [(35, 30, 15, 30), (35, 30, 15, 240), (256, 64, 64, 512), (35, 64, 256, 128)]
 PEARCE_LONG_ONLY = [(35, 256, 512)]
+JOINT_SHAPES = [((35, 30, 15, 60), False), ((35, 30, 15, 60), True), ((35, 30, 15, 1024), True)]      # (shape, workspace entries)
 PX, HIDDEN = 32, 500
 
 
@@ -91,13 +96,60 @@ def pearce_rows(B, T, Q, reps, vid=None, observed=None):
     return row
 
 
+def joint_rows(reps):
+    """Marginal against joint GP stage, device time between events, inputs resident."""
+    from svgp_vae_amd import ball
+    from svgp_vae_amd.ball_predict import BallPredictor
+    rows = []
+    for (B, T, m, Q), large in JOINT_SHAPES:
+        rs = np.random.RandomState(0)
+        ls = min(2.0, 0.75 * (T - 1) / (m - 1))
+        params = dict(ball.truncated_normal_mlp_params(PX, PX, HIDDEN, 0))
+        params.update(ip_x=np.linspace(1, T, m), ip_y=np.linspace(1, T, m), l_x=[ls], l_y=[ls / 1.1])
+        pred = BallPredictor(params, tmax=T, m=m, hidden=HIDDEN, px=PX, py=PX, jitter=1e-9, clip_qs=True)
+        f64 = dict(dtype=torch.float64, device=pred.dev)
+        observed = rs.rand(B, T) >= 0.4
+        observed[:, 0] = True
+        mu = [torch.randn(T, B, **f64) for _ in range(2)]
+        var = [torch.rand(T, B, **f64) * 0.5 + 1e-3 for _ in range(2)]
+        eps = [torch.randn(Q, B, **f64) for _ in range(2)]
+        times, tqd = torch.arange(1, T + 1, **f64), torch.as_tensor(np.linspace(1.0, float(T), Q), **f64)
+        mask = torch.as_tensor(observed, **f64).t().contiguous()
+
+        def marginal():
+            with torch.cuda.stream(pred.stream):
+                pred._gp(mu, var, times, tqd, mask, eps, force_large=large)
+
+        def joint():
+            with torch.cuda.stream(pred.stream):
+                pred._gp_joint(mu, var, times, tqd, mask, eps, 1e-6, force_large=large)
+
+        t_m, t_j = _device_times(pred.stream, marginal, reps), _device_times(pred.stream, joint, reps)
+        row = dict(B=B, T=T, m=m, Q=Q, reps=reps, entries="workspace" if large else "one-launch",
+                   marginal_device_s=float(np.median(t_m)), marginal_device_min_s=float(np.min(t_m)),
+                   joint_device_s=float(np.median(t_j)), joint_device_min_s=float(np.min(t_j)),
+                   joint_launches=len(pred.route(B, T, Q, joint=True)) if not large else None)
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+        del pred
+        torch.cuda.empty_cache()
+    return rows
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--out", type=str, default=None)
+    ap.add_argument("--joint", action="store_true", help="time the marginal against the joint GP stage instead")
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("the timings need a GPU")
+    if args.joint:
+        rows = joint_rows(args.reps)
+        if args.out:
+            with open(args.out, "w") as f:
+                json.dump(rows, f, indent=1)
+        return rows
     from svgp_vae_amd import ball
     from svgp_vae_amd.ball_predict import BallPredictor
     rows = []
