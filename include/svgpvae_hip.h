@@ -192,7 +192,8 @@ const char* svgp_last_error(void);
  * 7 svgp_sum_job, 8 svgp_casale_cfg, 9 svgp_casale_layout, 10 svgp_ball_large_cfg, 11 svgp_mnist_cache_layout,
  * 13 svgp_ball_predict_cfg, 14 svgp_ball_predict_bufs, 15 svgp_pearce_predict_cfg, 16 svgp_pearce_predict_bufs,
  * 18 svgp_casale_cache_layout, 19 svgp_cvae_cfg, 20 svgp_cvae_ws_layout, 22 svgp_ball_predict_joint_cfg,
- * 23 svgp_ball_predict_joint_bufs; -1 otherwise (12, 17 and 21 are not assigned). */
+ * 23 svgp_ball_predict_joint_bufs, 25 svgp_ball_state_cfg, 26 svgp_ball_state_bufs; -1 otherwise (12, 17, 21 and 24 are not
+ * assigned). */
 int         svgp_struct_sizeof(int which);
 
 int svgp_mnist_param_layout_get(const svgp_mnist_cfg* cfg, svgp_mnist_param_layout* out);
@@ -1324,6 +1325,79 @@ long long svgp_ball_predict_joint_large_workspace_elems(const svgp_ball_predict_
 int svgp_ball_predict_joint_large(const svgp_ball_predict_joint_cfg* cfg, const svgp_ball_predict_joint_bufs* bufs, double* work,
                                   void* stream);
 int svgp_ball_predict_joint_route(const svgp_ball_predict_joint_cfg* cfg, int large, char* buf, int cap);
+
+/* ---- moving ball: streamed posterior state, observe once and query often (ball_state.hip) -------------
+ * The posterior of svgp_ball_predict / svgp_ball_predict_joint above with its state kept in device memory between calls.  It
+ * depends on the frames only through two additive statistics per video b and latent coordinate c (0 = x, 1 = y),
+ *   S = Kn^T diag(p) Kn  (m x m)        r = Kn^T (p mu)  (m)
+ * with p, K, Kn, k of svgp_ball_predict.  Device state, both float64, part of this ABI:
+ *   stats (B, 2, m m + m): per (b, c) the matrix S row-major, then r.  All zeros is "nothing observed", which is the prior; the
+ *         caller zeroes it, there is no init entry.  Only svgp_ball_state_update writes it.
+ *   post  (B, 2, m m + m): per (b, c) X = Si - Ki row-major, then w = Si r, with Si = ((K + S) + jitter I)^-1 and Ki = (K +
+ *         jitter I)^-1.  Written by svgp_ball_state_finalize, read by the two queries.
+ * Inducing points, length scales and jitter are not stored: pass the same ones to every entry.
+ * svgp_ball_state_update:      stats += (S, r) of the T frames mu, var, mask (T, B) at times (T); mask NULL = all ones.  Any number
+ *   of calls: no limit on the total number of frames.  Reads and writes stats only.
+ * svgp_ball_state_finalize:    post from stats.  Zero stats give X = 0 and w = 0 exactly on the fused route.
+ * svgp_ball_state_query:       p_m = k w, p_v = 1 + diag(k X k^T) (unclamped), z = p_m + eps sqrt(clamp(p_v, clip_lo, clip_hi)) at tq
+ *   (Q), (Q, B) per coordinate, from post.  eps NULL: z = p_m; z NULL: not written.
+ * svgp_ball_state_query_joint: p_m, cov, chol, z of svgp_ball_predict_joint_large from post, with its layouts, NULL rules (eps, cov,
+ *   chol, z), NaN convention and refined factorisation; m, Q <= 2048, always from the library's global-memory pieces (cfg.large is
+ *   not read): per chunk of min(64, B, max(1, 2^22 / Q^2)) videos a gather of w, svgp_se1d_kernel_matrix_fwd, svgp_dgemm_batched twice
+ *   (X read in place from post), k_bpj_cov, svgp_potrf_batched (refined), k_bpj_finish.
+ * cfg.large = 0, the fused routes, 1 <= m <= 64, ONE launch each, no workspace (work may be NULL), no atomics, fixed summation order:
+ *   update (1 <= T <= 16384 a call): a workgroup per (video, coordinate) adds the frames in order with explicit fused multiply-adds to
+ *     the elements it loaded from stats: feeding the frames in pieces gives the bits of one call, a frame with mask = 0 (whatever
+ *     its mu holds) those of the call without it, an all-dropped call leaves stats unchanged.
+ *   finalize: a workgroup per (video, coordinate), the LDS sweep of svgp_ball_predict on (K + S) + jitter I and K + jitter I.
+ *   query: grid (B, 2, S): a workgroup loads X and w into LDS and serves its slice of the query times, 16 lanes per query.
+ *     q_slices = 0: the library chooses S (about 512 workgroups, at least one round of 16 queries a slice); q_slices > 0 forces S, up
+ *     to min(ceil(Q / 16), 65535).  A query's outputs depend neither on S nor on its position in tq.
+ * cfg.large != 0, the large routes, 1 <= m <= 2048, on chunks of 64 videos with the steps of svgp_ball_predict_large:
+ *   update (1 <= T <= 2048 a call): svgp_se1d_kernel_matrix_fwd, then per chunk k_bp_scale_rows and two svgp_dgemm_batched that
+ *     accumulate into stats (beta = 1, the strides of the state layout).
+ *   finalize: svgp_se1d_kernel_matrix_fwd (K), then per chunk k_bs_gather, k_bp_add_prior, svgp_spd_inverse_batched,
+ *     svgp_dgemm_batched, k_bp_subtract, k_bs_scatter.
+ *   query: per chunk k_bs_gather, then per 4096 query rows svgp_se1d_kernel_matrix_fwd, svgp_sprites_posterior_rows, k_bp_finish.
+ * svgp_ball_state_workspace_elems(cfg, op): the doubles `work` holds for op (SVGP_BALL_STATE_*): 0 for the fused routes and for a
+ *   refused cfg; it grows with neither B beyond a chunk nor Q beyond the chunk sizes above.
+ * svgp_ball_state_route(cfg, op, buf, cap): the kernels (library entry points for the shared pieces) of one call as text, one name
+ *   per line in launch order, from the same plan as the launch code; needs no device.
+ * Each entry reads only its own fields of cfg and bufs: update B, T, m and times, mu, var, mask, stats; finalize B, m, jitter and
+ * stats, post; query B, m, Q, q_slices, clip_lo / hi and tq, eps, post, p_m, p_v, z; the joint query B, m, Q, path_jitter and tq,
+ * eps, post, p_m, cov, chol, z; all of them ip and ls.
+ * Refused with a message before any launch: a NULL cfg / bufs / needed pointer, a needed size below 1, clip_lo > clip_hi,
+ *   path_jitter < 0 or NaN, q_slices out of range, NULL work where the size is non-zero (SVGP_ERR_INVALID); m, T or Q beyond the
+ *   route's range (SVGP_ERR_UNSUPPORTED).  Explicit stream, no allocation, no synchronisation.                                  */
+#define SVGP_BALL_STATE_UPDATE      0
+#define SVGP_BALL_STATE_FINALIZE    1
+#define SVGP_BALL_STATE_QUERY       2
+#define SVGP_BALL_STATE_QUERY_JOINT 3
+typedef struct {
+    int32_t B, T, m, Q;
+    int32_t large;                            /* 0: the fused routes (m <= 64); otherwise the large routes */
+    int32_t q_slices;                         /* fused query: 0 = the library chooses */
+    double jitter, clip_lo, clip_hi, path_jitter;
+} svgp_ball_state_cfg;
+typedef struct {
+    const double *times, *tq;                 /* (T), (Q) */
+    const double *ip_x, *ip_y;                /* (m) */
+    const double *ls_x, *ls_y;                /* scalars */
+    const double *mu_x, *mu_y, *var_x, *var_y;/* (T, B) */
+    const double *mask;                       /* (T, B) or NULL */
+    const double *eps_x, *eps_y;              /* (Q, B) or NULL */
+    double *stats, *post;                     /* (B, 2, m m + m) */
+    double *p_m_x, *p_m_y, *p_v_x, *p_v_y;    /* (Q, B); p_v: the marginal query only */
+    double *cov_x, *cov_y;                    /* (B, Q, Q) or NULL; the joint query only */
+    double *chol_x, *chol_y;                  /* (B, Q, Q) or NULL; the joint query only */
+    double *z_x, *z_y;                        /* (Q, B) or NULL */
+} svgp_ball_state_bufs;
+long long svgp_ball_state_workspace_elems(const svgp_ball_state_cfg* cfg, int op);
+int svgp_ball_state_route(const svgp_ball_state_cfg* cfg, int op, char* buf, int cap);
+int svgp_ball_state_update(const svgp_ball_state_cfg* cfg, const svgp_ball_state_bufs* bufs, double* work, void* stream);
+int svgp_ball_state_finalize(const svgp_ball_state_cfg* cfg, const svgp_ball_state_bufs* bufs, double* work, void* stream);
+int svgp_ball_state_query(const svgp_ball_state_cfg* cfg, const svgp_ball_state_bufs* bufs, double* work, void* stream);
+int svgp_ball_state_query_joint(const svgp_ball_state_cfg* cfg, const svgp_ball_state_bufs* bufs, double* work, void* stream);
 
 /* ---- runtime helpers: HIP graphs and events without going through torch ---------------------*/
 int svgp_stream_create(void** stream_out);

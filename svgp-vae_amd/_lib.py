@@ -149,6 +149,22 @@ class BallPredictJointBufs(C.Structure):
                                           "eps_x", "eps_y", "p_m_x", "p_m_y", "cov_x", "cov_y", "chol_x", "chol_y", "z_x", "z_y")]
 
 
+class BallStateCfg(C.Structure):
+    """svgp_ball_state_cfg (include/svgpvae_hip.h)."""
+    _fields_ = ([(n, C.c_int32) for n in ("B", "T", "m", "Q", "large", "q_slices")]
+                + [(n, C.c_double) for n in ("jitter", "clip_lo", "clip_hi", "path_jitter")])
+
+
+class BallStateBufs(C.Structure):
+    """svgp_ball_state_bufs (include/svgpvae_hip.h)."""
+    _fields_ = [(n, C.c_void_p) for n in ("times", "tq", "ip_x", "ip_y", "ls_x", "ls_y", "mu_x", "mu_y", "var_x", "var_y", "mask",
+                                          "eps_x", "eps_y", "stats", "post", "p_m_x", "p_m_y", "p_v_x", "p_v_y", "cov_x", "cov_y",
+                                          "chol_x", "chol_y", "z_x", "z_y")]
+
+
+BALL_STATE_OPS = dict(update=0, finalize=1, query=2, query_joint=3)        # SVGP_BALL_STATE_* (include/svgpvae_hip.h)
+
+
 class PearcePredictCfg(C.Structure):
     """svgp_pearce_predict_cfg (include/svgpvae_hip.h)."""
     _fields_ = [(n, C.c_int32) for n in ("B", "T", "Q", "q_slices")]
@@ -378,6 +394,11 @@ SIGNATURES = {
     "svgp_ball_predict_joint": [C.POINTER(BallPredictJointCfg), C.POINTER(BallPredictJointBufs), _P],
     "svgp_ball_predict_joint_large": [C.POINTER(BallPredictJointCfg), C.POINTER(BallPredictJointBufs), _P, _P],
     "svgp_ball_predict_joint_route": [C.POINTER(BallPredictJointCfg), C.c_int, C.c_char_p, C.c_int],
+    "svgp_ball_state_route": [C.POINTER(BallStateCfg), C.c_int, C.c_char_p, C.c_int],
+    "svgp_ball_state_update": [C.POINTER(BallStateCfg), C.POINTER(BallStateBufs), _P, _P],
+    "svgp_ball_state_finalize": [C.POINTER(BallStateCfg), C.POINTER(BallStateBufs), _P, _P],
+    "svgp_ball_state_query": [C.POINTER(BallStateCfg), C.POINTER(BallStateBufs), _P, _P],
+    "svgp_ball_state_query_joint": [C.POINTER(BallStateCfg), C.POINTER(BallStateBufs), _P, _P],
     "svgp_pearce_predict": [C.POINTER(PearcePredictCfg), C.POINTER(PearcePredictBufs), _P],
     "svgp_pearce_predict_long": [C.POINTER(PearcePredictCfg), C.POINTER(PearcePredictBufs), _P, _P],
     "svgp_pearce_predict_route": [C.POINTER(PearcePredictCfg), C.c_int, C.c_char_p, C.c_int],
@@ -432,6 +453,7 @@ NON_STATUS = {"svgp_version": ([], C.c_int), "svgp_last_error": ([], C.c_char_p)
               "svgp_ball_predict_large_workspace_elems": ([C.POINTER(BallPredictCfg)], C.c_longlong),
               "svgp_ball_predict_joint_large_workspace_elems": ([C.POINTER(BallPredictJointCfg)], C.c_longlong),
               "svgp_pearce_predict_long_workspace_elems": ([C.POINTER(PearcePredictCfg)], C.c_longlong),
+              "svgp_ball_state_workspace_elems": ([C.POINTER(BallStateCfg), C.c_int], C.c_longlong),
               "svgp_svigp_scale_offset": ([C.c_int, C.c_int, C.c_int], C.c_longlong),
               "svgp_mnist_decoder_weff_lds_offset": ([C.c_int, C.c_int], C.c_int),
               "svgp_mnist_decoder_fused_lds_bytes": ([C.c_int], C.c_int),
@@ -470,7 +492,7 @@ def load_library(path=None):
                               CasaleCfg, CasaleLayout, BallLargeCfg, CacheLayout)))
     mirrors.update({13: BallPredictCfg, 14: BallPredictBufs, 15: PearcePredictCfg, 16: PearcePredictBufs,
                     18: CasaleCacheLayout, 19: CvaeCfg, 20: CvaeWsLayout, 22: BallPredictJointCfg,
-                    23: BallPredictJointBufs})                                         # codes 12, 17 and 21 are not assigned
+                    23: BallPredictJointBufs, 25: BallStateCfg, 26: BallStateBufs})    # codes 12, 17, 21 and 24 are not assigned
     for which, cls in mirrors.items():
         if lib.svgp_struct_sizeof(which) != C.sizeof(cls):
             raise SvgpError(f"{p}: sizeof({cls.__name__}) is {lib.svgp_struct_sizeof(which)} in the library but "

@@ -545,8 +545,9 @@ SPARSE_ENGINES = (BallStepEngine, BallLargeStepEngine)
 
 
 def __getattr__(name):
-    """BallPredictor and PearcePredictor live in ball_predict.py (which imports this module); re-exported here on first use."""
-    if name in ("BallPredictor", "PearcePredictor"):
+    """BallPredictor, BallPosteriorState and PearcePredictor live in ball_predict.py (which imports this module); re-exported here
+    on first use."""
+    if name in ("BallPredictor", "BallPosteriorState", "PearcePredictor"):
         from . import ball_predict
         return getattr(ball_predict, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

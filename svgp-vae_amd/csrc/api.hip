@@ -43,6 +43,8 @@ extern "C" int svgp_struct_sizeof(int which) {
     case 20: return (int)sizeof(svgp_cvae_ws_layout);
     case 22: return (int)sizeof(svgp_ball_predict_joint_cfg); // (21 stays unassigned: pinned to -1 by the tests)
     case 23: return (int)sizeof(svgp_ball_predict_joint_bufs);
+    case 25: return (int)sizeof(svgp_ball_state_cfg);         // (24 stays unassigned: pinned to -1 by the tests)
+    case 26: return (int)sizeof(svgp_ball_state_bufs);
     default: return -1;
     }
 }

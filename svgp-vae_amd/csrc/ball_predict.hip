@@ -29,14 +29,6 @@
 
 namespace {
 
-constexpr int BPL_QC = 4096;         // query rows of a chunk of the large form
-
-struct BpArgs : BpIn {
-    real lo, hi;
-    const real* eps[2];
-    real* p_m[2]; real* p_v[2]; real* z[2];
-};
-
 // Thread layout as in lds_spd_inverse: column j = tid & (CW - 1), row lane i0 = tid / CW; a thread owns (i0 + RL r, j).
 template <int CW>
 __global__ __launch_bounds__(256) void k_ball_predict(BpArgs a) {
@@ -202,6 +194,13 @@ BpFactorWork bp_factor_work(SvgpTake16& c16, int64_t m, int64_t T, int64_t nb) {
     return o;
 }
 
+int bp_finish_launch(const BpArgs& a, int c, int b0, int nb, int q0, int nq, const real* tpm, const real* tpv, void* stream) {
+    hipLaunchKernelGGL(k_bp_finish, dim3(svgp_blocks((long long)nq * nb)), dim3(SVGP_BLOCK), 0, (hipStream_t)stream, a, c, b0, nb, q0, nq, tpm,
+                       tpv);
+    SVGP_LAUNCH_CHECK();
+    return SVGP_OK;
+}
+
 int bp_factor_launch(const BpIn& a, const BpStep& s, const BpFactorWork& w, double* work, void* stream) {
     const int c = s.c, nb = s.nb, m = a.m, T = a.T;
     const long long mm = (long long)m * m;
@@ -295,7 +294,6 @@ extern "C" int svgp_ball_predict_large(const svgp_ball_predict_cfg* g, const svg
     SVGP_REQUIRE(work != nullptr, SVGP_ERR_INVALID, "work is NULL (B = %d, T = %d, m = %d, Q = %d needs %lld doubles)", g->B, g->T, g->m,
                  g->Q, (long long)w.total);
     const int m = a.m;
-    hipStream_t st = (hipStream_t)stream;
     return bp_walk(g, true, [&](const BpStep& s) -> int {
         const int c = s.c, nb = s.nb;
         switch (s.op) {
@@ -308,10 +306,7 @@ extern "C" int svgp_ball_predict_large(const svgp_ball_predict_cfg* g, const svg
                                                nullptr, work + w.rows, stream);
         }
         case BP_FINISH:
-            hipLaunchKernelGGL(k_bp_finish, dim3(svgp_blocks((long long)s.nq * nb)), dim3(SVGP_BLOCK), 0, st, a, c, s.b0, nb, s.q0, s.nq,
-                               work + w.tpm, work + w.tpv);
-            SVGP_LAUNCH_CHECK();
-            break;
+            return bp_finish_launch(a, c, s.b0, nb, s.q0, s.nq, work + w.tpm, work + w.tpv, stream);
         default:
             return bp_factor_launch(a, s, w.f, work, stream);
         }

@@ -33,14 +33,6 @@
 namespace {
 
 constexpr int BPJ_Q_MAX = 64;                        // query times of the fused kernel
-constexpr int BPJL_Q_MAX = 2048;
-constexpr long long BPJL_CAP = 1LL << 22;            // doubles of one chunk's covariance block in the large form (32 MiB)
-
-struct BpjArgs : BpIn {
-    real jp;
-    const real* eps[2];
-    real* p_m[2]; real* cov[2]; real* chol[2]; real* z[2];
-};
 
 // LDS beyond bp_lds_map's: kq (Q x ld), eps of the video, p_m, the query times (BPJ_Q_MAX each)
 __host__ __device__ constexpr int bpj_ldq(int Q) { return Q | 1; }          // odd row stride of C: a column walk spreads over the banks
@@ -296,6 +288,19 @@ int bpj_launch_fused(const BpjArgs& a, void* stream) {
 
 }  // namespace
 
+int bpj_cov_launch(const BpjArgs& a, int c, int b0, int nb, real* Cb, void* stream) {
+    hipLaunchKernelGGL(k_bpj_cov, dim3(svgp_blocks((long long)nb * a.Q * a.Q)), dim3(SVGP_BLOCK), 0, (hipStream_t)stream, a, c, b0, nb, Cb);
+    SVGP_LAUNCH_CHECK();
+    return SVGP_OK;
+}
+
+int bpj_finish_launch(const BpjArgs& a, int c, int b0, int nb, const real* Kq, const real* W, const real* Lb, void* stream) {
+    hipLaunchKernelGGL(k_bpj_finish, dim3((unsigned)(((long long)nb * a.Q + SVGP_BLOCK / 64 - 1) / (SVGP_BLOCK / 64))), dim3(SVGP_BLOCK), 0,
+                       (hipStream_t)stream, a, c, b0, nb, Kq, W, Lb);
+    SVGP_LAUNCH_CHECK();
+    return SVGP_OK;
+}
+
 extern "C" int svgp_ball_predict_joint_route(const svgp_ball_predict_joint_cfg* g, int large, char* buf, int cap) {
     SVGP_REQUIRE(buf && cap >= 1, SVGP_ERR_INVALID, "bad argument");
     int rc = bpj_check(g, large != 0);
@@ -331,7 +336,6 @@ extern "C" int svgp_ball_predict_joint_large(const svgp_ball_predict_joint_cfg* 
                  g->Q, (long long)w.total);
     const int m = a.m, Q = a.Q;
     const long long mm = (long long)m * m, QQ = (long long)Q * Q, Qm = (long long)Q * m;
-    hipStream_t st = (hipStream_t)stream;
     return bpj_walk(g, true, [&](const BpStep& s) -> int {
         const int c = s.c, nb = s.nb;
         switch (s.op) {
@@ -342,20 +346,14 @@ extern "C" int svgp_ball_predict_joint_large(const svgp_ball_predict_joint_cfg* 
         case BPJ_GK:        // (Q, Q) = G_l k^T
             return svgp_dgemm_batched(0, 1, Q, Q, m, 1.0, work + w.G, m, Qm, work + w.Kq, m, 0, 0.0, work + w.Cb, Q, QQ, nb, stream);
         case BPJ_COV:
-            hipLaunchKernelGGL(k_bpj_cov, dim3(svgp_blocks(nb * QQ)), dim3(SVGP_BLOCK), 0, st, a, c, s.b0, nb, work + w.Cb);
-            SVGP_LAUNCH_CHECK();
-            break;
+            return bpj_cov_launch(a, c, s.b0, nb, work + w.Cb, stream);
         case BPJ_POTRF:
             // with its panel solves refined: the residual of Lc Lc^T then stays at the level of an unblocked factorisation beyond Q = 64 too
             return svgp_potrf_batched_refined(Q, nb, work + w.Cb, Q, QQ, work + w.logdet, work + w.potrf, stream);
         case BPJ_FINISH:
-            hipLaunchKernelGGL(k_bpj_finish, dim3((unsigned)(((long long)nb * Q + SVGP_BLOCK / 64 - 1) / (SVGP_BLOCK / 64))), dim3(SVGP_BLOCK),
-                               0, st, a, c, s.b0, nb, work + w.Kq, work + w.f.W, work + w.Cb);
-            SVGP_LAUNCH_CHECK();
-            break;
+            return bpj_finish_launch(a, c, s.b0, nb, work + w.Kq, work + w.f.W, work + w.Cb, stream);
         default:
             return bp_factor_launch(a, s, w.f, work, stream);
         }
-        return (int)SVGP_OK;
     });
 }

@@ -1,12 +1,16 @@
-// What the marginal moving-ball predictor (ball_predict.hip) and the joint one (ball_predict_joint.hip,
-// section 9l) share: the inputs of a call, the fused kernels' way to K, Sig, their inverses, w and X in LDS, and the plan and
-// launches of the large form up to X and w.  Include after common.hpp and lds_spd_inverse.hpp.
+// What the marginal moving-ball predictor (ball_predict.hip), the joint one (ball_predict_joint.hip,
+// section 9l) and the streamed posterior state (ball_state.hip, section 9m) share: the inputs of a call, the fused kernels' way to
+// K, Sig, their inverses, w and X in LDS, the plan and launches of the large form up to X and w, and the launches of the large
+// forms' closing kernels.  Include after common.hpp and lds_spd_inverse.hpp.
 #pragma once
 
 constexpr int BP_TC = 16;            // frames (and query times) of a chunk of the fused kernels
 constexpr int BP_M_MAX = 64, BP_T_MAX = 16384;
 constexpr int BPL_T_MAX = 2048;
 constexpr int BPL_NB = 64;           // at most this many videos in a chunk of a large form
+constexpr int BPL_QC = 4096;         // query rows of a chunk of the marginal large form
+constexpr int BPJL_Q_MAX = 2048;     // query times of the joint large form
+constexpr long long BPJL_CAP = 1LL << 22;            // doubles of one chunk's covariance block in the joint large form (32 MiB)
 
 // the inputs of both predictors
 struct BpIn {
@@ -14,6 +18,18 @@ struct BpIn {
     real jitter;
     const real* times; const real* tq; const real* mask;
     const real* ip[2]; const real* ls[2]; const real* mu[2]; const real* var[2];
+};
+
+// the arguments of the marginal and of the joint kernels
+struct BpArgs : BpIn {
+    real lo, hi;
+    const real* eps[2];
+    real* p_m[2]; real* p_v[2]; real* z[2];
+};
+struct BpjArgs : BpIn {
+    real jp;
+    const real* eps[2];
+    real* p_m[2]; real* cov[2]; real* chol[2]; real* z[2];
 };
 
 #ifdef __HIPCC__
@@ -142,3 +158,8 @@ struct BpFactorWork { int64_t K, Kn, knn, KnP, PY, Mats, V, W, logdet, inv; };
 BpFactorWork bp_factor_work(SvgpTake16& c16, int64_t m, int64_t T, int64_t nb);
 // launches BP_KMAT or one of the seven steps (ball_predict.hip)
 int bp_factor_launch(const BpIn& a, const BpStep& s, const BpFactorWork& w, double* work, void* stream);
+// the closing kernels of the large forms, for callers outside their files: k_bp_finish (ball_predict.hip), k_bpj_cov and k_bpj_finish
+// (ball_predict_joint.hip) with exactly the arguments documented there
+int bp_finish_launch(const BpArgs& a, int c, int b0, int nb, int q0, int nq, const real* tpm, const real* tpv, void* stream);
+int bpj_cov_launch(const BpjArgs& a, int c, int b0, int nb, real* Cb, void* stream);
+int bpj_finish_launch(const BpjArgs& a, int c, int b0, int nb, const real* Kq, const real* W, const real* Lb, void* stream);

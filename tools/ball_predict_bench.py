@@ -12,7 +12,11 @@ over --reps calls after a warm-up of each.  Information only, no threshold; need
 full covariance, its Cholesky factor's path) at (35, 30, 15, 60) through the one-launch and through the
 workspace entries, and at (35, 30, 15, 1024) through the workspace entries, which alone take that Q.
 
-    python tools/ball_predict_bench.py [--joint] [--reps 30] [--out profiles/ball_predict_bench.json]
+--state: instead, the streamed posterior state against the one-shot entry, GP stage only, at (35, 30, 15, 30),
+(2, 2048, 64, 4096) and (2, 2048, 256, 4096): (a) svgp_ball_predict / svgp_ball_predict_large, (b) svgp_ball_state_update + finalize +
+query from an empty state, (c) svgp_ball_state_query alone on the finished state.
+
+    python tools/ball_predict_bench.py [--joint | --state] [--reps 30] [--out profiles/ball_predict_bench.json]
 """
 import argparse
 import json
@@ -29,6 +33,7 @@ sys.path.insert(0, ROOT)
 SHAPES = [(35, 30, 15, 30), (35, 30, 15, 240), (256, 64, 64, 512), (35, 64, 256, 128)]
 PEARCE_LONG_ONLY = [(35, 256, 512)]
 JOINT_SHAPES = [((35, 30, 15, 60), False), ((35, 30, 15, 60), True), ((35, 30, 15, 1024), True)]      # (shape, workspace entries)
+STATE_SHAPES = [(35, 30, 15, 30), (2, 2048, 64, 4096), (2, 2048, 256, 4096)]
 PX, HIDDEN = 32, 500
 
 
@@ -136,16 +141,66 @@ def joint_rows(reps):
     return rows
 
 
+def state_rows(reps):
+    """One-shot entry against update + finalize + query and against the query alone, device time between events, inputs resident."""
+    from svgp_vae_amd import ball
+    from svgp_vae_amd.ball_predict import BallPredictor
+    rows = []
+    for B, T, m, Q in STATE_SHAPES:
+        rs = np.random.RandomState(0)
+        ls = min(2.0, 0.75 * (T - 1) / (m - 1))
+        params = dict(ball.truncated_normal_mlp_params(PX, PX, HIDDEN, 0))
+        params.update(ip_x=np.linspace(1, T, m), ip_y=np.linspace(1, T, m), l_x=[ls], l_y=[ls / 1.1])
+        pred = BallPredictor(params, tmax=T, m=m, hidden=HIDDEN, px=PX, py=PX, jitter=1e-9, clip_qs=True)
+        f64 = dict(dtype=torch.float64, device=pred.dev)
+        observed = rs.rand(B, T) >= 0.4
+        observed[:, 0] = True
+        mu = [torch.randn(T, B, **f64) for _ in range(2)]
+        var = [torch.rand(T, B, **f64) * 0.5 + 1e-3 for _ in range(2)]
+        times, tqd = torch.arange(1, T + 1, **f64), torch.as_tensor(np.linspace(1.0, float(T), Q), **f64)
+        mask = torch.as_tensor(observed, **f64).t().contiguous()
+        state = pred.state(B)
+
+        def one_shot():
+            with torch.cuda.stream(pred.stream):
+                pred._gp(mu, var, times, tqd, mask, None)
+
+        def streamed():
+            with torch.cuda.stream(pred.stream):
+                state.stats.zero_()
+                state._update(mu, var, times, mask)
+                state._finalize()
+                state._query(tqd, None)
+
+        def query_only():
+            with torch.cuda.stream(pred.stream):
+                state._query(tqd, None)
+
+        t_a, t_b = _device_times(pred.stream, one_shot, reps), _device_times(pred.stream, streamed, reps)
+        t_c = _device_times(pred.stream, query_only, reps)
+        med = lambda t: float(np.median(t))
+        row = dict(B=B, T=T, m=m, Q=Q, reps=reps, one_shot_device_s=med(t_a), one_shot_device_min_s=float(np.min(t_a)),
+                   update_finalize_query_device_s=med(t_b), update_finalize_query_device_min_s=float(np.min(t_b)),
+                   query_device_s=med(t_c), query_device_min_s=float(np.min(t_c)),
+                   launches={op: len(state.route(op, T=T, Q=Q)) for op in ("update", "finalize", "query")})
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+        del pred, state
+        torch.cuda.empty_cache()
+    return rows
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--out", type=str, default=None)
     ap.add_argument("--joint", action="store_true", help="time the marginal against the joint GP stage instead")
+    ap.add_argument("--state", action="store_true", help="time the streamed posterior state against the one-shot entry instead")
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("the timings need a GPU")
-    if args.joint:
-        rows = joint_rows(args.reps)
+    if args.joint or args.state:
+        rows = joint_rows(args.reps) if args.joint else state_rows(args.reps)
         if args.out:
             with open(args.out, "w") as f:
                 json.dump(rows, f, indent=1)
