@@ -15,12 +15,16 @@
 // X = 0 and w = 0 exactly.  The query times are walked in chunks of 16: 16 lanes share a query, each takes the rows i = lane,
 // lane + 16, ... of k^T X k and of k . w, and an xor-shuffle adds the 16 partials; a query's bits do not depend on where it stands.
 // LDS at m = 64: two 64 x 65 matrices, the 16 x 65 chunk and 4 x 64 + 32 values = 77 184 bytes (two workgroups per CU).
-// The kernel's way to X and w is bp_factors of ball_predict_shared.hpp, which the joint predictor (ball_predict_joint.hip) inlines too.
+// k_ball_predict is two device pieces of ball_predict_shared.hpp: bp_factors (bp_prior, bp_accumulate from zeros, bp_invert,
+// bp_store_x in place), which the joint predictor (ball_predict_joint.hip) inlines too, and bp_query_chunks over all Q query times; the streamed
+// state (ball_state.hip) composes the same pieces around its stats and post.
 //
 // svgp_ball_predict_large (m <= 2048, T <= 2048): the same quantities from the library's global-memory pieces, walked in chunks of
 // BPL_NB videos and BPL_QC query rows so that the workspace grows with neither B nor Q (bp_walk below is the one plan both the
-// launch code and svgp_ball_predict_route follow).  svgp_sprites_posterior_rows runs with the videos of a chunk as its channels
-// (kbb = 1), an unbounded clip range and no draw: the clamp applies to the sample only and is taken in k_bp_finish.
+// launch code and svgp_ball_predict_route follow).  This file holds the factor steps (bp_factor_launch) and the marginal tail
+// (bp_tail_work, bp_tail_launch) for every caller, and bp_route_line, the route line of a step.  svgp_sprites_posterior_rows
+// runs with the videos of a chunk as its channels (kbb = 1), an unbounded clip range and no draw: the clamp applies to the sample
+// only and is taken in k_bp_finish.
 #include "common.hpp"
 #include "lds_spd_inverse.hpp"
 #include "ball_predict_shared.hpp"
@@ -29,52 +33,13 @@
 
 namespace {
 
-// Thread layout as in lds_spd_inverse: column j = tid & (CW - 1), row lane i0 = tid / CW; a thread owns (i0 + RL r, j).
 template <int CW>
 __global__ __launch_bounds__(256) void k_ball_predict(BpArgs a) {
     extern __shared__ __align__(16) real smem[];
-    constexpr int RL = 256 / CW, KS = CW + 1;
-    const int tid = threadIdx.x, j = tid & (CW - 1), i0 = tid / CW;
-    const int b = blockIdx.x, c = blockIdx.y, m = a.m, ld = m + 1, B = a.B, Q = a.Q;
-    const BpLds s = bp_lds_map<CW>(smem, m * ld, m * ld);
-    real* Sg = s.Sg; real* kt = s.kt; real* zv = s.zv; real* wv = s.wv;
-    const real* __restrict__ tq = a.tq;
-    const real* __restrict__ eps = a.eps[c];
-    real* __restrict__ o_pm = a.p_m[c];
-    real* __restrict__ o_pv = a.p_v[c];
-    real* __restrict__ o_z = a.z[c];
+    const int b = blockIdx.x, c = blockIdx.y, m = a.m;
+    const BpLds s = bp_lds_map<CW>(smem, m * (m + 1), m * (m + 1));
     const real il2 = bp_factors<CW>(a, b, c, s);          // X in Sg, w in wv
-    // ---- the query times: 16 per chunk, 16 lanes per query
-    const int qc = tid >> 4, l16 = tid & 15;
-    for (int q0 = 0; q0 < Q; q0 += BP_TC) {
-        __syncthreads();             // X is complete / the previous chunk is consumed
-#pragma unroll
-        for (int r = 0; r < BP_TC / RL; ++r) {
-            const int qq = i0 + RL * r;
-            real k = 0;
-            if (q0 + qq < Q && j < m) { const real d = tq[q0 + qq] - zv[j]; k = exp(d * d * il2); }
-            kt[qq * KS + j] = k;
-        }
-        __syncthreads();
-        const real* kr = kt + qc * KS;
-        real pm = 0, qs = 0;
-        for (int i = l16; i < m; i += 16) {
-            const real* xr = Sg + i * ld;
-            real row = 0;
-#pragma unroll 4
-            for (int k = 0; k < m; ++k) row += xr[k] * kr[k];
-            qs += kr[i] * row;
-            pm += kr[i] * wv[i];
-        }
-#pragma unroll
-        for (int o = 1; o < 16; o <<= 1) { pm += __shfl_xor(pm, o, 64); qs += __shfl_xor(qs, o, 64); }
-        if (l16 == 0 && q0 + qc < Q) {
-            const size_t e = (size_t)(q0 + qc) * B + b;
-            const real pv = real(1) + qs;
-            o_pm[e] = pm; o_pv[e] = pv;
-            if (o_z) o_z[e] = eps ? pm + eps[e] * sqrt(clip_keep_nan(pv, a.lo, a.hi)) : pm;
-        }
-    }
+    bp_query_chunks<CW>(a, b, c, s.Sg, m + 1, s.wv, s.zv, s.kt, il2, 0, a.Q);
 }
 
 inline size_t bp_lds_bytes(int m, int CW) { return ((size_t)2 * m * (m + 1) + bp_lds_tail_elems(CW)) * sizeof(real); }
@@ -131,11 +96,7 @@ int bp_walk(const svgp_ball_predict_cfg* g, bool large, F f) {
         for (int b0 = 0; b0 < g->B; b0 += BPL_NB) {
             const int nb = g->B - b0 < BPL_NB ? g->B - b0 : BPL_NB;
             if ((rc = bp_walk_factors(c, b0, nb, f))) return rc;
-            for (int q0 = 0; q0 < g->Q; q0 += BPL_QC) {
-                const int nq = g->Q - q0 < BPL_QC ? g->Q - q0 : BPL_QC;
-                for (BpOp op : {BP_KQ, BP_ROWS, BP_FINISH})
-                    if ((rc = f(BpStep{op, c, b0, nb, q0, nq}))) return rc;
-            }
+            if ((rc = bp_walk_tail(c, b0, nb, g->Q, f))) return rc;
         }
     }
     return SVGP_OK;
@@ -153,38 +114,43 @@ int bp_check(const svgp_ball_predict_cfg* g, bool large) {
 }
 
 int bp_args(const svgp_ball_predict_cfg* g, const svgp_ball_predict_bufs* q, BpArgs* a) {
-    SVGP_REQUIRE(q != nullptr, SVGP_ERR_INVALID, "bufs is NULL");
-    const void* need[] = {q->times, q->tq, q->ip_x, q->ip_y, q->ls_x, q->ls_y, q->mu_x, q->mu_y, q->var_x, q->var_y,
-                          q->p_m_x, q->p_m_y, q->p_v_x, q->p_v_y};
-    for (const void* p : need) SVGP_REQUIRE(p != nullptr, SVGP_ERR_INVALID, "NULL device pointer");
-    a->B = g->B; a->T = g->T; a->m = g->m; a->Q = g->Q; a->jitter = g->jitter; a->lo = g->clip_lo; a->hi = g->clip_hi;
-    a->times = q->times; a->tq = q->tq; a->mask = q->mask;
-    a->ip[0] = q->ip_x; a->ip[1] = q->ip_y; a->ls[0] = q->ls_x; a->ls[1] = q->ls_y; a->mu[0] = q->mu_x; a->mu[1] = q->mu_y;
-    a->var[0] = q->var_x; a->var[1] = q->var_y; a->eps[0] = q->eps_x; a->eps[1] = q->eps_y;
-    a->p_m[0] = q->p_m_x; a->p_m[1] = q->p_m_y; a->p_v[0] = q->p_v_x; a->p_v[1] = q->p_v_y; a->z[0] = q->z_x; a->z[1] = q->z_y;
+    int rc = bp_marshal(g, q, true, true, a);
+    if (rc) return rc;
+    SVGP_REQUIRE(q->p_v_x && q->p_v_y, SVGP_ERR_INVALID, "NULL device pointer");
+    a->lo = g->clip_lo; a->hi = g->clip_hi; a->p_v[0] = q->p_v_x; a->p_v[1] = q->p_v_y;
     return SVGP_OK;
 }
 
-struct BpWork { BpFactorWork f; int64_t K2, Kq, kbb, tpm, tpv, rows, total; };
+struct BpWork { BpFactorWork f; BpTailWork t; int64_t total; };
 BpWork bp_work(const svgp_ball_predict_cfg* g) {
-    const int64_t m = g->m, T = g->T, nb = g->B < BPL_NB ? g->B : BPL_NB, nq = g->Q < BPL_QC ? g->Q : BPL_QC;
+    const int64_t nb = g->B < BPL_NB ? g->B : BPL_NB;
     SvgpTake16 c16;
     BpWork o;
-    o.f = bp_factor_work(c16, m, T, nb);
-    o.K2 = c16.take(m * m); o.Kq = c16.take(nq * m); o.kbb = c16.take(nq);
-    o.tpm = c16.take(nq * nb); o.tpv = c16.take(nq * nb);
-    o.rows = c16.take(m > 256 ? 16 * nq * nb : 0);      // svgp_sprites_posterior_rows_workspace_elems: at most 16 b L, 0 up to m = 256
+    o.f = bp_factor_work(c16, g->m, g->T, nb);
+    o.t = bp_tail_work(c16, g->m, g->Q, nb);
     o.total = c16.p;
     return o;
 }
 
-}  // namespace
-
+// the route text's name of each BpOp
 const char* const BP_NAME[] = {"k_ball_predict", "svgp_se1d_kernel_matrix_fwd", "k_bp_scale_rows", "svgp_dgemm_batched", "k_bp_add_prior",
                                "svgp_dgemm_batched", "svgp_spd_inverse_batched", "svgp_dgemm_batched", "k_bp_subtract",
                                "svgp_se1d_kernel_matrix_fwd", "svgp_sprites_posterior_rows", "k_bp_finish",
                                "k_ball_predict_joint", "svgp_se1d_kernel_matrix_fwd", "svgp_dgemm_batched", "svgp_dgemm_batched", "k_bpj_cov",
                                "svgp_potrf_batched", "k_bpj_finish"};
+// the rows entry runs with the videos of a chunk as its channels, an unbounded clip range and no draw
+inline svgp_posterior_rows_cfg bp_rows_cfg(const BpStep& s, int m) { return {s.nq, m, s.nb, -INFINITY, INFINITY}; }
+
+}  // namespace
+
+int bp_route_line(const BpStep& s, int m, char* buf, int cap, int* pos) {
+    if (s.op != BP_ROWS) return svgp_route_append(buf, cap, pos, "%s\n", BP_NAME[s.op]);
+    const svgp_posterior_rows_cfg rc_ = bp_rows_cfg(s, m);
+    char sub[128];
+    int r = svgp_sprites_posterior_rows_route(&rc_, sub, (int)sizeof(sub));
+    if (r) return r;
+    return svgp_route_append(buf, cap, pos, "%s", sub);
+}
 
 BpFactorWork bp_factor_work(SvgpTake16& c16, int64_t m, int64_t T, int64_t nb) {
     BpFactorWork o;
@@ -194,10 +160,32 @@ BpFactorWork bp_factor_work(SvgpTake16& c16, int64_t m, int64_t T, int64_t nb) {
     return o;
 }
 
-int bp_finish_launch(const BpArgs& a, int c, int b0, int nb, int q0, int nq, const real* tpm, const real* tpv, void* stream) {
-    hipLaunchKernelGGL(k_bp_finish, dim3(svgp_blocks((long long)nq * nb)), dim3(SVGP_BLOCK), 0, (hipStream_t)stream, a, c, b0, nb, q0, nq, tpm,
-                       tpv);
-    SVGP_LAUNCH_CHECK();
+BpTailWork bp_tail_work(SvgpTake16& c16, int64_t m, int64_t Q, int64_t nb) {
+    const int64_t nq = Q < BPL_QC ? Q : BPL_QC;
+    BpTailWork o;
+    o.K2 = c16.take(m * m); o.Kq = c16.take(nq * m); o.kbb = c16.take(nq);
+    o.tpm = c16.take(nq * nb); o.tpv = c16.take(nq * nb);
+    o.rows = c16.take(m > 256 ? 16 * nq * nb : 0);      // svgp_sprites_posterior_rows_workspace_elems: at most 16 b L, 0 up to m = 256
+    return o;
+}
+
+int bp_tail_launch(const BpArgs& a, const BpStep& s, const BpTailWork& w, const real* X, const real* W, double* work, void* stream) {
+    switch (s.op) {
+    case BP_KQ:
+        return svgp_se1d_kernel_matrix_fwd(s.nq, a.m, a.tq + s.q0, a.ip[s.c], a.ls[s.c], work + w.K2, work + w.Kq, work + w.kbb, stream);
+    case BP_ROWS: {     // the clamp applies to the sample only and is taken in k_bp_finish
+        const svgp_posterior_rows_cfg rc_ = bp_rows_cfg(s, a.m);
+        return svgp_sprites_posterior_rows(&rc_, work + w.Kq, work + w.kbb, W, X, nullptr, work + w.tpm, work + w.tpv, nullptr, work + w.rows,
+                                           stream);
+    }
+    case BP_FINISH:
+        hipLaunchKernelGGL(k_bp_finish, dim3(svgp_blocks((long long)s.nq * s.nb)), dim3(SVGP_BLOCK), 0, (hipStream_t)stream, a, s.c, s.b0, s.nb,
+                           s.q0, s.nq, work + w.tpm, work + w.tpv);
+        SVGP_LAUNCH_CHECK();
+        break;
+    default:
+        SVGP_REQUIRE(false, SVGP_ERR_INVALID, "bp_tail_launch: op %d is not a step of the marginal tail", (int)s.op);
+    }
     return SVGP_OK;
 }
 
@@ -243,16 +231,7 @@ extern "C" int svgp_ball_predict_route(const svgp_ball_predict_cfg* g, int large
     if (rc) return rc;
     int pos = 0;
     buf[0] = 0;
-    return bp_walk(g, large != 0, [&](const BpStep& s) -> int {
-        if (s.op == BP_ROWS) {       // the rows entry prints its own one or two kernels
-            const svgp_posterior_rows_cfg rc_ = {s.nq, g->m, s.nb, -INFINITY, INFINITY};
-            char sub[128];
-            int r = svgp_sprites_posterior_rows_route(&rc_, sub, (int)sizeof(sub));
-            if (r) return r;
-            return svgp_route_append(buf, cap, &pos, "%s", sub);
-        }
-        return svgp_route_append(buf, cap, &pos, "%s\n", BP_NAME[s.op]);
-    });
+    return bp_walk(g, large != 0, [&](const BpStep& s) -> int { return bp_route_line(s, g->m, buf, cap, &pos); });
 }
 
 extern "C" int svgp_ball_predict(const svgp_ball_predict_cfg* g, const svgp_ball_predict_bufs* q, void* stream) {
@@ -293,23 +272,12 @@ extern "C" int svgp_ball_predict_large(const svgp_ball_predict_cfg* g, const svg
     const BpWork w = bp_work(g);
     SVGP_REQUIRE(work != nullptr, SVGP_ERR_INVALID, "work is NULL (B = %d, T = %d, m = %d, Q = %d needs %lld doubles)", g->B, g->T, g->m,
                  g->Q, (long long)w.total);
-    const int m = a.m;
     return bp_walk(g, true, [&](const BpStep& s) -> int {
-        const int c = s.c, nb = s.nb;
         switch (s.op) {
-        case BP_FUSED: break;
-        case BP_KQ:
-            return svgp_se1d_kernel_matrix_fwd(s.nq, m, a.tq + s.q0, a.ip[c], a.ls[c], work + w.K2, work + w.Kq, work + w.kbb, stream);
-        case BP_ROWS: {
-            const svgp_posterior_rows_cfg rc_ = {s.nq, m, nb, -INFINITY, INFINITY};
-            return svgp_sprites_posterior_rows(&rc_, work + w.Kq, work + w.kbb, work + w.f.W, work + w.f.Mats, nullptr, work + w.tpm, work + w.tpv,
-                                               nullptr, work + w.rows, stream);
-        }
-        case BP_FINISH:
-            return bp_finish_launch(a, c, s.b0, nb, s.q0, s.nq, work + w.tpm, work + w.tpv, stream);
-        default:
+        case BP_KQ: case BP_ROWS: case BP_FINISH:
+            return bp_tail_launch(a, s, w.t, work + w.f.Mats, work + w.f.W, work, stream);
+        default:            // BP_KMAT and the seven factor steps; anything else is refused there
             return bp_factor_launch(a, s, w.f, work, stream);
         }
-        return (int)SVGP_OK;
     });
 }

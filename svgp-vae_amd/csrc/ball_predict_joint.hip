@@ -8,8 +8,9 @@
 // frame dropped has X = 0 and w = 0 exactly, hence C = SE(tau, tau) and p_m = 0: paths from the prior.  A non-positive pivot gives
 // NaN in that (video, coordinate)'s chol and z only (the convention of svgp_potrf_batched: no error code, no synchronisation).
 //
-// svgp_ball_predict_joint (m <= 64, Q <= 64): ONE launch, a workgroup of 256 threads per (video, coordinate).  bp_factors leaves X
-// and w in LDS exactly as in k_ball_predict.  Then the kernel rows of all Q query times (kq), G = kq X in the slot K + j I
+// svgp_ball_predict_joint (m <= 64, Q <= 64): ONE launch, a workgroup of 256 threads per (video, coordinate).  bp_factors (the
+// pieces bp_prior, bp_accumulate, bp_invert, bp_store_x of ball_predict_shared.hpp) leaves X and w in LDS exactly as in
+// k_ball_predict.  Then the kernel rows of all Q query times (kq), G = kq X in the slot K + j I
 // occupied, and the lower triangle of C in the slot of X (which G no longer needs): element (q, r) is G[a] . kq[b] + SE(tau_q,
 // tau_r) where a is the one of q, r with the larger query time -- the pair's value, not its position, decides which row goes
 // through X, so permuting tau permutes the rows and columns of C bit for bit (equal times have equal rows).  The triangle is
@@ -23,7 +24,9 @@
 // (bp_walk_factors), svgp_se1d_kernel_matrix_fwd for k, svgp_dgemm_batched twice (k X_l, then (k X_l) k^T, k at stride 0),
 // k_bpj_cov (adds SE(tau, tau), mirrors the lower triangle, writes cov, adds jp), svgp_potrf_batched with its panel solves refined
 // once (svgp_potrf_batched_refined: beyond Q = 64 the plain routine's residual of Lc Lc^T carries the condition number of the
-// diagonal blocks, and C + jp I at jp = 1e-9 is ill conditioned), and k_bpj_finish (p_m = k w_l, z = p_m + Lc eps, the copy of chol).  bpj_walk is the one plan the launch code and svgp_ball_predict_joint_route follow.
+// diagonal blocks, and C + jp I at jp = 1e-9 is ill conditioned), and k_bpj_finish (p_m = k w_l, z = p_m + Lc eps, the copy of chol).
+// Those six steps are the joint tail (bpj_walk_tail), whose workspace and launches (bpj_tail_work, bpj_tail_launch) this file holds
+// for the streamed state's joint query too.  bpj_walk is the one plan the launch code and svgp_ball_predict_joint_route follow.
 #include "common.hpp"
 #include "lds_spd_inverse.hpp"
 #include "ball_predict_shared.hpp"
@@ -211,25 +214,18 @@ __global__ __launch_bounds__(SVGP_BLOCK) void k_bpj_finish(BpjArgs a, int c, int
 // ---------------------------------------------------------------------------------------------------------
 // one plan for the launch code and the route text
 // ---------------------------------------------------------------------------------------------------------
-inline int bpj_chunk(const svgp_ball_predict_joint_cfg* g) {
-    const long long qq = (long long)g->Q * g->Q, cap = BPJL_CAP / qq > 1 ? BPJL_CAP / qq : 1;
-    const long long nb = g->B < BPL_NB ? g->B : BPL_NB;
-    return (int)(nb < cap ? nb : cap);
-}
-
 // calls f(step) for every launch group of one call, in order; stops at the first non-zero return
 template <class F>
 int bpj_walk(const svgp_ball_predict_joint_cfg* g, bool large, F f) {
     int rc;
     if (!large) return f(BpStep{BPJ_FUSED, 0, 0, g->B, 0, g->Q});
-    const int chunk = bpj_chunk(g);
+    const int chunk = bpj_chunk(g->B, g->Q);
     for (int c = 0; c < 2; ++c) {
         if ((rc = f(BpStep{BP_KMAT, c, 0, 0, 0, 0}))) return rc;
         for (int b0 = 0; b0 < g->B; b0 += chunk) {
             const int nb = g->B - b0 < chunk ? g->B - b0 : chunk;
             if ((rc = bp_walk_factors(c, b0, nb, f))) return rc;
-            for (BpOp op : {BPJ_KQ, BPJ_G, BPJ_GK, BPJ_COV, BPJ_POTRF, BPJ_FINISH})
-                if ((rc = f(BpStep{op, c, b0, nb, 0, g->Q}))) return rc;
+            if ((rc = bpj_walk_tail(c, b0, nb, g->Q, f))) return rc;
         }
     }
     return SVGP_OK;
@@ -249,27 +245,19 @@ int bpj_check(const svgp_ball_predict_joint_cfg* g, bool large) {
 }
 
 int bpj_args(const svgp_ball_predict_joint_cfg* g, const svgp_ball_predict_joint_bufs* q, BpjArgs* a) {
-    SVGP_REQUIRE(q != nullptr, SVGP_ERR_INVALID, "bufs is NULL");
-    const void* need[] = {q->times, q->tq, q->ip_x, q->ip_y, q->ls_x, q->ls_y, q->mu_x, q->mu_y, q->var_x, q->var_y, q->p_m_x, q->p_m_y};
-    for (const void* p : need) SVGP_REQUIRE(p != nullptr, SVGP_ERR_INVALID, "NULL device pointer");
-    a->B = g->B; a->T = g->T; a->m = g->m; a->Q = g->Q; a->jitter = g->jitter; a->jp = g->path_jitter;
-    a->times = q->times; a->tq = q->tq; a->mask = q->mask;
-    a->ip[0] = q->ip_x; a->ip[1] = q->ip_y; a->ls[0] = q->ls_x; a->ls[1] = q->ls_y; a->mu[0] = q->mu_x; a->mu[1] = q->mu_y;
-    a->var[0] = q->var_x; a->var[1] = q->var_y; a->eps[0] = q->eps_x; a->eps[1] = q->eps_y;
-    a->p_m[0] = q->p_m_x; a->p_m[1] = q->p_m_y; a->cov[0] = q->cov_x; a->cov[1] = q->cov_y;
-    a->chol[0] = q->chol_x; a->chol[1] = q->chol_y; a->z[0] = q->z_x; a->z[1] = q->z_y;
+    int rc = bp_marshal(g, q, true, true, a);
+    if (rc) return rc;
+    a->jp = g->path_jitter; a->cov[0] = q->cov_x; a->cov[1] = q->cov_y; a->chol[0] = q->chol_x; a->chol[1] = q->chol_y;
     return SVGP_OK;
 }
 
-struct BpjWork { BpFactorWork f; int64_t K2, Kq, kbb, G, Cb, logdet, potrf, total; };
+struct BpjWork { BpFactorWork f; BpjTailWork t; int64_t total; };
 BpjWork bpj_work(const svgp_ball_predict_joint_cfg* g) {
-    const int64_t m = g->m, T = g->T, Q = g->Q, nb = bpj_chunk(g);
+    const int64_t nb = bpj_chunk(g->B, g->Q);
     SvgpTake16 c16;
     BpjWork o;
-    o.f = bp_factor_work(c16, m, T, nb);
-    o.K2 = c16.take(m * m); o.Kq = c16.take(Q * m); o.kbb = c16.take(Q);
-    o.G = c16.take(nb * Q * m); o.Cb = c16.take(nb * Q * Q); o.logdet = c16.take(nb);
-    o.potrf = c16.take((int64_t)svgp_potrf_workspace_elems((int)Q, (int)nb));
+    o.f = bp_factor_work(c16, g->m, g->T, nb);
+    o.t = bpj_tail_work(c16, g->m, g->Q, nb);
     o.total = c16.p;
     return o;
 }
@@ -288,16 +276,41 @@ int bpj_launch_fused(const BpjArgs& a, void* stream) {
 
 }  // namespace
 
-int bpj_cov_launch(const BpjArgs& a, int c, int b0, int nb, real* Cb, void* stream) {
-    hipLaunchKernelGGL(k_bpj_cov, dim3(svgp_blocks((long long)nb * a.Q * a.Q)), dim3(SVGP_BLOCK), 0, (hipStream_t)stream, a, c, b0, nb, Cb);
-    SVGP_LAUNCH_CHECK();
-    return SVGP_OK;
+BpjTailWork bpj_tail_work(SvgpTake16& c16, int64_t m, int64_t Q, int64_t nb) {
+    BpjTailWork o;
+    o.K2 = c16.take(m * m); o.Kq = c16.take(Q * m); o.kbb = c16.take(Q);
+    o.G = c16.take(nb * Q * m); o.Cb = c16.take(nb * Q * Q); o.logdet = c16.take(nb);
+    o.potrf = c16.take((int64_t)svgp_potrf_workspace_elems((int)Q, (int)nb));
+    return o;
 }
 
-int bpj_finish_launch(const BpjArgs& a, int c, int b0, int nb, const real* Kq, const real* W, const real* Lb, void* stream) {
-    hipLaunchKernelGGL(k_bpj_finish, dim3((unsigned)(((long long)nb * a.Q + SVGP_BLOCK / 64 - 1) / (SVGP_BLOCK / 64))), dim3(SVGP_BLOCK), 0,
-                       (hipStream_t)stream, a, c, b0, nb, Kq, W, Lb);
-    SVGP_LAUNCH_CHECK();
+int bpj_tail_launch(const BpjArgs& a, const BpStep& s, const BpjTailWork& w, const real* X, long long xstride, const real* W, double* work,
+                    void* stream) {
+    const int c = s.c, nb = s.nb, m = a.m, Q = a.Q;
+    const long long QQ = (long long)Q * Q, Qm = (long long)Q * m;
+    hipStream_t st = (hipStream_t)stream;
+    switch (s.op) {
+    case BPJ_KQ:
+        return svgp_se1d_kernel_matrix_fwd(Q, m, a.tq, a.ip[c], a.ls[c], work + w.K2, work + w.Kq, work + w.kbb, stream);
+    case BPJ_G:         // G_l (Q, m) = k X_l: the shared k has stride 0
+        return svgp_dgemm_batched(0, 0, Q, m, m, 1.0, work + w.Kq, m, 0, X, m, xstride, 0.0, work + w.G, m, Qm, nb, stream);
+    case BPJ_GK:        // (Q, Q) = G_l k^T
+        return svgp_dgemm_batched(0, 1, Q, Q, m, 1.0, work + w.G, m, Qm, work + w.Kq, m, 0, 0.0, work + w.Cb, Q, QQ, nb, stream);
+    case BPJ_COV:
+        hipLaunchKernelGGL(k_bpj_cov, dim3(svgp_blocks(nb * QQ)), dim3(SVGP_BLOCK), 0, st, a, c, s.b0, nb, work + w.Cb);
+        SVGP_LAUNCH_CHECK();
+        break;
+    case BPJ_POTRF:
+        // with its panel solves refined: the residual of Lc Lc^T then stays at the level of an unblocked factorisation beyond Q = 64 too
+        return svgp_potrf_batched_refined(Q, nb, work + w.Cb, Q, QQ, work + w.logdet, work + w.potrf, stream);
+    case BPJ_FINISH:
+        hipLaunchKernelGGL(k_bpj_finish, dim3((unsigned)(((long long)nb * Q + SVGP_BLOCK / 64 - 1) / (SVGP_BLOCK / 64))), dim3(SVGP_BLOCK), 0, st,
+                           a, c, s.b0, nb, work + w.Kq, W, work + w.Cb);
+        SVGP_LAUNCH_CHECK();
+        break;
+    default:
+        SVGP_REQUIRE(false, SVGP_ERR_INVALID, "bpj_tail_launch: op %d is not a step of the joint tail", (int)s.op);
+    }
     return SVGP_OK;
 }
 
@@ -307,7 +320,7 @@ extern "C" int svgp_ball_predict_joint_route(const svgp_ball_predict_joint_cfg* 
     if (rc) return rc;
     int pos = 0;
     buf[0] = 0;
-    return bpj_walk(g, large != 0, [&](const BpStep& s) -> int { return svgp_route_append(buf, cap, &pos, "%s\n", BP_NAME[s.op]); });
+    return bpj_walk(g, large != 0, [&](const BpStep& s) -> int { return bp_route_line(s, g->m, buf, cap, &pos); });
 }
 
 extern "C" int svgp_ball_predict_joint(const svgp_ball_predict_joint_cfg* g, const svgp_ball_predict_joint_bufs* q, void* stream) {
@@ -334,25 +347,11 @@ extern "C" int svgp_ball_predict_joint_large(const svgp_ball_predict_joint_cfg* 
     const BpjWork w = bpj_work(g);
     SVGP_REQUIRE(work != nullptr, SVGP_ERR_INVALID, "work is NULL (B = %d, T = %d, m = %d, Q = %d needs %lld doubles)", g->B, g->T, g->m,
                  g->Q, (long long)w.total);
-    const int m = a.m, Q = a.Q;
-    const long long mm = (long long)m * m, QQ = (long long)Q * Q, Qm = (long long)Q * m;
     return bpj_walk(g, true, [&](const BpStep& s) -> int {
-        const int c = s.c, nb = s.nb;
         switch (s.op) {
-        case BPJ_KQ:
-            return svgp_se1d_kernel_matrix_fwd(Q, m, a.tq, a.ip[c], a.ls[c], work + w.K2, work + w.Kq, work + w.kbb, stream);
-        case BPJ_G:         // G_l (Q, m) = k X_l: the shared k has stride 0
-            return svgp_dgemm_batched(0, 0, Q, m, m, 1.0, work + w.Kq, m, 0, work + w.f.Mats, m, mm, 0.0, work + w.G, m, Qm, nb, stream);
-        case BPJ_GK:        // (Q, Q) = G_l k^T
-            return svgp_dgemm_batched(0, 1, Q, Q, m, 1.0, work + w.G, m, Qm, work + w.Kq, m, 0, 0.0, work + w.Cb, Q, QQ, nb, stream);
-        case BPJ_COV:
-            return bpj_cov_launch(a, c, s.b0, nb, work + w.Cb, stream);
-        case BPJ_POTRF:
-            // with its panel solves refined: the residual of Lc Lc^T then stays at the level of an unblocked factorisation beyond Q = 64 too
-            return svgp_potrf_batched_refined(Q, nb, work + w.Cb, Q, QQ, work + w.logdet, work + w.potrf, stream);
-        case BPJ_FINISH:
-            return bpj_finish_launch(a, c, s.b0, nb, work + w.Kq, work + w.f.W, work + w.Cb, stream);
-        default:
+        case BPJ_KQ: case BPJ_G: case BPJ_GK: case BPJ_COV: case BPJ_POTRF: case BPJ_FINISH:
+            return bpj_tail_launch(a, s, w.t, work + w.f.Mats, (long long)a.m * a.m, work + w.f.W, work, stream);
+        default:            // BP_KMAT and the seven factor steps; anything else is refused there
             return bp_factor_launch(a, s, w.f, work, stream);
         }
     });

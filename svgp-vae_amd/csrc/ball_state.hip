@@ -8,17 +8,21 @@
 //   query     k = SE(tau, z):  p_m = k w,  p_v = 1 + diag(k X k^T),  z = p_m + eps sqrt(clamp(p_v))           (9h's tail)
 //   joint     C = SE(tau, tau) + k X k^T,  Lc = chol(C + jp I),  p_m = k w,  z = p_m + Lc eps                  (9l's tail)
 //
-// Fused routes (cfg.large = 0, m <= 64), one launch each, 256 threads, thread layout of lds_spd_inverse:
-//   k_ball_state_update<CW>    grid (B, 2).  The frame loop of bp_factors with the accumulators loaded from stats and stored back;
-//       every addition is an explicit fma in frame order, so feeding the frames in pieces gives the bits of one call, and a frame of
-//       precision 0 adds +0 to a non-negative sum.  LDS: the 16 x (CW + 1) chunk, zv, pc, pyc (9 088 bytes at CW = 64).
-//   k_ball_state_finalize<CW>  grid (B, 2).  The second half of bp_factors: (K + S) + j I beside K + j I in LDS, the one inlined
-//       two-trip sweep, then w = Si r and X = Si - Ki written straight from LDS to post.  Zero stats: the two matrices are equal bit for bit, X = 0 and w = 0 exactly.
-//   k_ball_state_query<CW>     grid (B, 2, S).  X (row stride m + 1) and w into LDS, then the workgroup's slice of the query times by
-//       the 16-lanes-per-query loop of k_ball_predict: a query's bits depend neither on S nor on its position in tq.
+// Fused routes (cfg.large = 0, m <= 64), one launch each, 256 threads, thread layout of lds_spd_inverse, each a composition of the
+// device pieces of ball_predict_shared.hpp that k_ball_predict is made of:
+//   k_ball_state_update<CW>    grid (B, 2).  The accumulators from stats, bp_accumulate, and back.  Feeding the frames in pieces gives
+//       the bits of one call because bp_accumulate adds every frame with an explicit fma in frame order onto whatever sums it is
+//       handed, here and in the one-shot entries alike; a frame of precision 0 adds +0 to a non-negative sum.
+//       LDS: the 16 x (CW + 1) chunk, zv, pc, pyc (9 088 bytes at CW = 64).
+//   k_ball_state_finalize<CW>  grid (B, 2).  S and r from stats, bp_prior (K), bp_invert ((K + S) + j I beside K + j I in LDS, the one inlined
+//       two-trip sweep, w = Si r), then bp_store_x writes X = Si - Ki straight from LDS to post, and w follows.  Zero stats: the two
+//       matrices are equal bit for bit, X = 0 and w = 0 exactly.
+//   k_ball_state_query<CW>     grid (B, 2, S).  X (row stride m + 1) and w into LDS, then bp_query_chunks on the workgroup's slice of
+//       the query times: a query's bits depend neither on S nor on its position in tq.
 // Large routes (cfg.large != 0, m <= 2048; update T <= 2048 a call): the steps of bp_factor_launch on chunks of BPL_NB videos, the
 // two GEMMs of the update accumulating into stats (beta = 1), with k_bs_gather / k_bs_scatter between the state layout and the
-// contiguous blocks those steps and svgp_sprites_posterior_rows work on.  The joint query has the large form only.
+// contiguous blocks those steps and the marginal tail (bp_tail_launch) work on; the joint tail (bpj_tail_launch) reads X in place
+// from post.  The joint query has the large form only.
 // bs_walk is the one plan the launch code and svgp_ball_state_route follow.
 #include "common.hpp"
 #include "lds_spd_inverse.hpp"
@@ -48,47 +52,22 @@ __device__ __forceinline__ real* bs_block(real* base, int m, int b, int c) { ret
 // ---------------------------------------------------------------------------------------------------------
 template <int CW>
 __global__ __launch_bounds__(256) void k_ball_state_update(BsArgs a) {
-    constexpr int RL = 256 / CW, RMAX = CW / RL, KS = CW + 1;
-    __shared__ real kt[BP_TC * KS], zv[CW], pc[BP_TC], pyc[BP_TC];
+    constexpr int RL = 256 / CW, RMAX = CW / RL;
+    __shared__ real kt[BP_TC * (CW + 1)], zv[CW], pc[BP_TC], pyc[BP_TC];
     const int tid = threadIdx.x, j = tid & (CW - 1), i0 = tid / CW;
-    const int b = blockIdx.x, c = blockIdx.y, m = a.m, B = a.B, T = a.T;
-    const real* __restrict__ times = a.times;
+    const int b = blockIdx.x, c = blockIdx.y, m = a.m;
+    BpLds s = {};                    // what bp_accumulate uses
+    s.kt = kt; s.zv = zv; s.pc = pc; s.pyc = pyc;
     real* __restrict__ S = bs_block(a.stats, m, b, c);
     real* __restrict__ rv = S + (size_t)m * m;
-    const real l = *a.ls[c], il2 = real(-0.5) / (l * l);
-    if (tid < CW) zv[tid] = tid < m ? a.ip[c][tid] : real(0);
+    bp_load_z<CW>(a, c, zv);
     real acc[RMAX], vacc = (i0 == 0 && j < m) ? rv[j] : real(0);
 #pragma unroll
     for (int r = 0; r < RMAX; ++r) {
         const int i = i0 + RL * r;
         acc[r] = (i < m && j < m) ? S[(size_t)i * m + j] : real(0);
     }
-    // ---- the frames, in order
-    for (int t0 = 0; t0 < T; t0 += BP_TC) {
-        const int cnt = T - t0 < BP_TC ? T - t0 : BP_TC;
-        __syncthreads();             // zv is complete / the previous chunk is consumed
-        if (tid < BP_TC) {
-            real p = 0, py = 0;
-            if (tid < cnt) bp_precision(a, c, (size_t)(t0 + tid) * B + b, p, py);
-            pc[tid] = p; pyc[tid] = py;
-        }
-#pragma unroll
-        for (int r = 0; r < BP_TC / RL; ++r) {
-            const int tc = i0 + RL * r;
-            real k = 0;
-            if (tc < cnt && j < m) { const real d = times[t0 + tc] - zv[j]; k = exp(d * d * il2); }
-            kt[tc * KS + j] = k;
-        }
-        __syncthreads();
-#pragma unroll 2
-        for (int tc = 0; tc < cnt; ++tc) {
-            const real* kr = kt + tc * KS;
-            const real kj = kr[j], pk = pc[tc] * kj;
-#pragma unroll
-            for (int r = 0; r < RMAX; ++r) acc[r] = fma(pk, kr[i0 + RL * r], acc[r]);
-            if (i0 == 0) vacc = fma(pyc[tc], kj, vacc);
-        }
-    }
+    bp_accumulate<CW>(a, bp_dims(a), b, c, s, bp_il2(a, c), acc, vacc);
 #pragma unroll
     for (int r = 0; r < RMAX; ++r) {
         const int i = i0 + RL * r;
@@ -102,40 +81,23 @@ __global__ __launch_bounds__(256) void k_ball_state_finalize(BsArgs a) {
     extern __shared__ __align__(16) real smem[];
     constexpr int RL = 256 / CW, RMAX = CW / RL;
     const int tid = threadIdx.x, j = tid & (CW - 1), i0 = tid / CW;
-    const int b = blockIdx.x, c = blockIdx.y, m = a.m, ld = m + 1;
-    const BpLds s = bp_lds_map<CW>(smem, m * ld, m * ld);
-    real* Km = s.Km; real* Sg = s.Sg; real* zv = s.zv; real* vv = s.vv;
+    const int b = blockIdx.x, c = blockIdx.y, m = a.m;
+    const BpLds s = bp_lds_map<CW>(smem, m * (m + 1), m * (m + 1));
     const real* __restrict__ S = bs_block(a.stats, m, b, c);
     real* __restrict__ X = bs_block(a.post, m, b, c);
-    const real l = *a.ls[c], il2 = real(-0.5) / (l * l);
-    if (tid < CW) zv[tid] = tid < m ? a.ip[c][tid] : real(0);
-    __syncthreads();
-    // (K + S) + j I beside K + j I: equal bit for bit where S is 0
+    bp_load_z<CW>(a, c, s.zv);
+    real acc[RMAX];
+    const real vacc = (i0 == 0 && j < m) ? S[(size_t)m * m + j] : real(0);
 #pragma unroll
     for (int r = 0; r < RMAX; ++r) {
         const int i = i0 + RL * r;
-        if (i < m && j < m) {
-            const real d = zv[i] - zv[j], k = exp(d * d * il2), jit = i == j ? a.jitter : real(0);
-            Sg[i * ld + j] = (k + S[(size_t)i * m + j]) + jit;
-            Km[i * ld + j] = k + jit;
-        }
+        acc[r] = (i < m && j < m) ? S[(size_t)i * m + j] : real(0);
     }
-    if (i0 == 0) vv[j] = j < m ? S[(size_t)m * m + j] : real(0);
-#pragma unroll 1
-    for (int which = 0; which < 2; ++which) lds_spd_inverse<CW>(which ? Sg : Km, ld, m, s.piv);    // one copy of the sweep's code
-    if (tid < CW) {
-        real sum = 0;
-        if (tid < m) {
-#pragma unroll 4
-            for (int k = 0; k < m; ++k) sum += Sg[tid * ld + k] * vv[k];
-            X[(size_t)m * m + tid] = sum;
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < RMAX; ++r) {
-        const int i = i0 + RL * r;
-        if (i < m && j < m) X[(size_t)i * m + j] = Sg[i * ld + j] - Km[i * ld + j];
-    }
+    __syncthreads();                 // zv is complete
+    bp_prior<CW>(s, m, bp_il2(a, c));
+    bp_invert<CW>(a, m, s, acc, vacc);
+    bp_store_x<CW>(s, m, X, m);
+    if (tid < m) X[(size_t)m * m + tid] = s.wv[tid];
 }
 
 constexpr int bsq_lds_elems(int m, int CW) { return m * (m + 1) + 2 * CW + BP_TC * (CW + 1); }
@@ -147,56 +109,20 @@ static_assert(((size_t)2 * 64 * 65 + bp_lds_tail_elems(64)) * sizeof(real) == 77
 template <int CW>
 __global__ __launch_bounds__(256) void k_ball_state_query(BsArgs a) {
     extern __shared__ __align__(16) real smem[];
-    constexpr int RL = 256 / CW, KS = CW + 1;
-    const int tid = threadIdx.x, j = tid & (CW - 1), i0 = tid / CW;
-    const int b = blockIdx.x, c = blockIdx.y, m = a.m, ld = m + 1, B = a.B, Q = a.Q;
+    const int tid = threadIdx.x;
+    const int b = blockIdx.x, c = blockIdx.y, m = a.m, ld = m + 1, Q = a.Q;
     const long long span = (long long)a.rps * BP_TC, q_lo = (long long)blockIdx.z * span;     // (64 bits: Q may be close to 2^31)
     if (q_lo >= Q) return;           // (a forced slice count may leave slices without a round)
     const long long q_hi = Q - q_lo < span ? (long long)Q : q_lo + span;
     real* Xs = smem;                 // m x ld
     real* wv = Xs + m * ld;          // CW
     real* zv = wv + CW;              // CW
-    real* kt = zv + CW;              // BP_TC x KS
+    real* kt = zv + CW;              // BP_TC x (CW + 1)
     const real* __restrict__ X = bs_block(a.post, m, b, c);
-    const real* __restrict__ tq = a.tq;
-    const real* __restrict__ eps = a.eps[c];
-    real* __restrict__ o_pm = a.p_m[c];
-    real* __restrict__ o_pv = a.p_v[c];
-    real* __restrict__ o_z = a.z[c];
-    const real l = *a.ls[c], il2 = real(-0.5) / (l * l);
     for (int e = tid; e < m * m; e += 256) { const int i = e / m; Xs[i * ld + e - i * m] = X[e]; }
-    if (tid < CW) { zv[tid] = tid < m ? a.ip[c][tid] : real(0); wv[tid] = tid < m ? X[(size_t)m * m + tid] : real(0); }
-    // ---- the query times of this slice: 16 per chunk, 16 lanes per query
-    const int qc = tid >> 4, l16 = tid & 15;
-    for (long long q0 = q_lo; q0 < q_hi; q0 += BP_TC) {
-        __syncthreads();             // X, w, zv are complete / the previous chunk is consumed
-#pragma unroll
-        for (int r = 0; r < BP_TC / RL; ++r) {
-            const int qq = i0 + RL * r;
-            real k = 0;
-            if (q0 + qq < Q && j < m) { const real d = tq[q0 + qq] - zv[j]; k = exp(d * d * il2); }
-            kt[qq * KS + j] = k;
-        }
-        __syncthreads();
-        const real* kr = kt + qc * KS;
-        real pm = 0, qs = 0;
-        for (int i = l16; i < m; i += 16) {
-            const real* xr = Xs + i * ld;
-            real row = 0;
-#pragma unroll 4
-            for (int k = 0; k < m; ++k) row += xr[k] * kr[k];
-            qs += kr[i] * row;
-            pm += kr[i] * wv[i];
-        }
-#pragma unroll
-        for (int o = 1; o < 16; o <<= 1) { pm += __shfl_xor(pm, o, 64); qs += __shfl_xor(qs, o, 64); }
-        if (l16 == 0 && q0 + qc < Q) {
-            const size_t e = (size_t)(q0 + qc) * B + b;
-            const real pv = real(1) + qs;
-            o_pm[e] = pm; o_pv[e] = pv;
-            if (o_z) o_z[e] = eps ? pm + eps[e] * sqrt(clip_keep_nan(pv, a.lo, a.hi)) : pm;
-        }
-    }
+    bp_load_z<CW>(a, c, zv);
+    if (tid < CW) wv[tid] = tid < m ? X[(size_t)m * m + tid] : real(0);
+    bp_query_chunks<CW>(a, b, c, Xs, ld, wv, zv, kt, bp_il2(a, c), q_lo, q_hi);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -230,12 +156,6 @@ enum BsStepOp { BSS_UPDATE, BSS_FINALIZE, BSS_QUERY, BSS_GATHER, BSS_SCATTER, BS
 const char* const BSS_NAME[] = {"k_ball_state_update", "k_ball_state_finalize", "k_ball_state_query", "k_bs_gather", "k_bs_scatter"};
 struct BsStep { BsStepOp own; BpStep s; };
 
-inline int bs_joint_chunk(const svgp_ball_state_cfg* g) {
-    const long long qq = (long long)g->Q * g->Q, cap = BPJL_CAP / qq > 1 ? BPJL_CAP / qq : 1;
-    const long long nb = g->B < BPL_NB ? g->B : BPL_NB;
-    return (int)(nb < cap ? nb : cap);
-}
-
 inline int bs_rounds(const svgp_ball_state_cfg* g) { return (int)(((long long)g->Q + BP_TC - 1) / BP_TC); }
 inline int bs_slices_max(const svgp_ball_state_cfg* g) { return bs_rounds(g) < BS_SLICES_MAX ? bs_rounds(g) : BS_SLICES_MAX; }
 // slices of the fused query: about BS_WG_TARGET workgroups, at least one round of BP_TC query times per slice
@@ -251,37 +171,33 @@ template <class F>
 int bs_walk(const svgp_ball_state_cfg* g, int op, F f) {
     int rc;
     auto own = [&](BsStepOp o, int c, int b0, int nb) { return f(BsStep{o, BpStep{BP_FUSED, c, b0, nb, 0, 0}}); };
-    auto bp = [&](BpOp o, int c, int b0, int nb, int q0, int nq) { return f(BsStep{BSS_BP, BpStep{o, c, b0, nb, q0, nq}}); };
+    auto step = [&](const BpStep& s) { return f(BsStep{BSS_BP, s}); };
+    auto bp = [&](BpOp o, int c, int b0, int nb) { return step(BpStep{o, c, b0, nb, 0, 0}); };
     if (!g->large && op != BS_JOINT) return own(op == BS_UPDATE ? BSS_UPDATE : op == BS_FINALIZE ? BSS_FINALIZE : BSS_QUERY, 0, 0, g->B);
-    const int chunk = op == BS_JOINT ? bs_joint_chunk(g) : BPL_NB;
+    const int chunk = op == BS_JOINT ? bpj_chunk(g->B, g->Q) : BPL_NB;
     for (int c = 0; c < 2; ++c) {
         if (op == BS_UPDATE || op == BS_FINALIZE)
-            if ((rc = bp(BP_KMAT, c, 0, 0, 0, 0))) return rc;
+            if ((rc = bp(BP_KMAT, c, 0, 0))) return rc;
         for (int b0 = 0; b0 < g->B; b0 += chunk) {
             const int nb = g->B - b0 < chunk ? g->B - b0 : chunk;
             switch (op) {
             case BS_UPDATE:
                 for (BpOp o : {BP_SCALE, BP_SIGMA, BP_V})
-                    if ((rc = bp(o, c, b0, nb, 0, 0))) return rc;
+                    if ((rc = bp(o, c, b0, nb))) return rc;
                 break;
             case BS_FINALIZE:
                 if ((rc = own(BSS_GATHER, c, b0, nb))) return rc;
                 for (BpOp o : {BP_PRIOR, BP_INVERSE, BP_W, BP_SUB})
-                    if ((rc = bp(o, c, b0, nb, 0, 0))) return rc;
+                    if ((rc = bp(o, c, b0, nb))) return rc;
                 if ((rc = own(BSS_SCATTER, c, b0, nb))) return rc;
                 break;
             case BS_QUERY:
                 if ((rc = own(BSS_GATHER, c, b0, nb))) return rc;
-                for (long long q0 = 0; q0 < g->Q; q0 += BPL_QC) {
-                    const int nq = g->Q - q0 < BPL_QC ? (int)(g->Q - q0) : BPL_QC;
-                    for (BpOp o : {BP_KQ, BP_ROWS, BP_FINISH})
-                        if ((rc = bp(o, c, b0, nb, (int)q0, nq))) return rc;
-                }
+                if ((rc = bp_walk_tail(c, b0, nb, g->Q, step))) return rc;
                 break;
             default:
                 if ((rc = own(BSS_GATHER, c, b0, nb))) return rc;
-                for (BpOp o : {BPJ_KQ, BPJ_G, BPJ_GK, BPJ_COV, BPJ_POTRF, BPJ_FINISH})
-                    if ((rc = bp(o, c, b0, nb, 0, g->Q))) return rc;
+                if ((rc = bpj_walk_tail(c, b0, nb, g->Q, step))) return rc;
             }
         }
     }
@@ -314,38 +230,23 @@ int bs_check(const svgp_ball_state_cfg* g, int op) {
 
 // the pointers an operation needs, and the kernels' arguments
 int bs_args(const svgp_ball_state_cfg* g, int op, const svgp_ball_state_bufs* q, BsArgs* a, BpjArgs* ja) {
-    SVGP_REQUIRE(q != nullptr, SVGP_ERR_INVALID, "bufs is NULL");
-    const void* always[] = {q->ip_x, q->ip_y, q->ls_x, q->ls_y};
-    for (const void* p : always) SVGP_REQUIRE(p != nullptr, SVGP_ERR_INVALID, "NULL device pointer");
-    if (op == BS_UPDATE) {
-        const void* need[] = {q->times, q->mu_x, q->mu_y, q->var_x, q->var_y, q->stats};
-        for (const void* p : need) SVGP_REQUIRE(p != nullptr, SVGP_ERR_INVALID, "NULL device pointer");
-    } else if (op == BS_FINALIZE) {
-        SVGP_REQUIRE(q->stats && q->post, SVGP_ERR_INVALID, "NULL device pointer");
-    } else {
-        const void* need[] = {q->tq, q->post, q->p_m_x, q->p_m_y};
-        for (const void* p : need) SVGP_REQUIRE(p != nullptr, SVGP_ERR_INVALID, "NULL device pointer");
-        SVGP_REQUIRE(op != BS_QUERY || (q->p_v_x && q->p_v_y), SVGP_ERR_INVALID, "NULL device pointer");
-    }
-    auto in = [&](BpIn* o) {
-        o->B = g->B; o->T = g->T; o->m = g->m; o->Q = g->Q; o->jitter = g->jitter;
-        o->times = q->times; o->tq = q->tq; o->mask = q->mask;
-        o->ip[0] = q->ip_x; o->ip[1] = q->ip_y; o->ls[0] = q->ls_x; o->ls[1] = q->ls_y; o->mu[0] = q->mu_x; o->mu[1] = q->mu_y;
-        o->var[0] = q->var_x; o->var[1] = q->var_y;
-    };
-    in(a); in(ja);
-    a->lo = g->clip_lo; a->hi = g->clip_hi; a->eps[0] = q->eps_x; a->eps[1] = q->eps_y;
-    a->p_m[0] = q->p_m_x; a->p_m[1] = q->p_m_y; a->p_v[0] = q->p_v_x; a->p_v[1] = q->p_v_y; a->z[0] = q->z_x; a->z[1] = q->z_y;
+    const bool frames = op == BS_UPDATE, query = op == BS_QUERY || op == BS_JOINT;
+    int rc = bp_marshal(g, q, frames, query, a);
+    if (!rc) rc = bp_marshal(g, q, frames, query, ja);
+    if (rc) return rc;
+    SVGP_REQUIRE(query || q->stats, SVGP_ERR_INVALID, "NULL device pointer");
+    SVGP_REQUIRE(frames || q->post, SVGP_ERR_INVALID, "NULL device pointer");
+    SVGP_REQUIRE(op != BS_QUERY || (q->p_v_x && q->p_v_y), SVGP_ERR_INVALID, "NULL device pointer");
+    a->lo = g->clip_lo; a->hi = g->clip_hi; a->p_v[0] = q->p_v_x; a->p_v[1] = q->p_v_y;
     a->stats = q->stats; a->post = q->post; a->rps = 1;
-    ja->jp = g->path_jitter; ja->eps[0] = q->eps_x; ja->eps[1] = q->eps_y; ja->p_m[0] = q->p_m_x; ja->p_m[1] = q->p_m_y;
-    ja->cov[0] = q->cov_x; ja->cov[1] = q->cov_y; ja->chol[0] = q->chol_x; ja->chol[1] = q->chol_y; ja->z[0] = q->z_x; ja->z[1] = q->z_y;
+    ja->jp = g->path_jitter; ja->cov[0] = q->cov_x; ja->cov[1] = q->cov_y; ja->chol[0] = q->chol_x; ja->chol[1] = q->chol_y;
     return SVGP_OK;
 }
 
 // workspace of the large routes: the fields of BpFactorWork an operation's steps touch, then its own
-struct BsWork { BpFactorWork f; int64_t K2, Kq, kbb, tpm, tpv, rows, G, Cb, logdet, potrf, total; };
+struct BsWork { BpFactorWork f; BpTailWork t; BpjTailWork j; int64_t total; };
 BsWork bs_work(const svgp_ball_state_cfg* g, int op) {
-    const int64_t m = g->m, T = g->T, Q = g->Q, nb = op == BS_JOINT ? bs_joint_chunk(g) : (g->B < BPL_NB ? g->B : BPL_NB);
+    const int64_t m = g->m, T = g->T, nb = op == BS_JOINT ? bpj_chunk(g->B, g->Q) : (g->B < BPL_NB ? g->B : BPL_NB);
     SvgpTake16 c16;
     BsWork o = {};
     if (!g->large && op != BS_JOINT) return o;
@@ -358,18 +259,13 @@ BsWork bs_work(const svgp_ball_state_cfg* g, int op) {
         o.f.V = c16.take(m * nb); o.f.W = c16.take(nb * m); o.f.logdet = c16.take(nb + 1);
         o.f.inv = c16.take((int64_t)svgp_spd_inverse_workspace_elems((int)m, (int)nb + 1));
         break;
-    case BS_QUERY: {
-        const int64_t nq = Q < BPL_QC ? Q : BPL_QC;
+    case BS_QUERY:
         o.f.Mats = c16.take(nb * m * m); o.f.W = c16.take(nb * m);
-        o.K2 = c16.take(m * m); o.Kq = c16.take(nq * m); o.kbb = c16.take(nq); o.tpm = c16.take(nq * nb); o.tpv = c16.take(nq * nb);
-        o.rows = c16.take(m > 256 ? 16 * nq * nb : 0);      // svgp_sprites_posterior_rows_workspace_elems: at most 16 b L, 0 up to m = 256
+        o.t = bp_tail_work(c16, m, g->Q, nb);
         break;
-    }
     default:                // X_l is read in place from post; only w_l is gathered
         o.f.W = c16.take(nb * m);
-        o.K2 = c16.take(m * m); o.Kq = c16.take(Q * m); o.kbb = c16.take(Q);
-        o.G = c16.take(nb * Q * m); o.Cb = c16.take(nb * Q * Q); o.logdet = c16.take(nb);
-        o.potrf = c16.take((int64_t)svgp_potrf_workspace_elems((int)Q, (int)nb));
+        o.j = bpj_tail_work(c16, m, g->Q, nb);
     }
     o.total = c16.p;
     return o;
@@ -411,8 +307,8 @@ int bs_run(const svgp_ball_state_cfg* g, int op, const svgp_ball_state_bufs* q, 
     const BsWork w = bs_work(g, op);
     SVGP_REQUIRE(w.total == 0 || work != nullptr, SVGP_ERR_INVALID, "work is NULL (%s: B = %d, T = %d, m = %d, Q = %d needs %lld doubles)",
                  BS_ENTRY[op], g->B, g->T, g->m, g->Q, (long long)w.total);
-    const int m = a.m, Q = a.Q;
-    const long long mm = (long long)m * m, E = bs_elems(m), QQ = (long long)Q * Q, Qm = (long long)Q * m;
+    const int m = a.m;
+    const long long mm = (long long)m * m, E = bs_elems(m);
     hipStream_t st = (hipStream_t)stream;
     BpIn one = a;                    // finalize: K from the kernel-matrix entry, its one "frame" at the first inducing point
     one.T = 1; one.times = a.ip[0];
@@ -448,27 +344,10 @@ int bs_run(const svgp_ball_state_cfg* g, int op, const svgp_ball_state_bufs* q, 
         case BP_V:          // r_l += (Kn^T PY)[:, l]: (nb, m) = PY^T Kn with the state's row stride
             return svgp_dgemm_batched(1, 0, nb, m, a.T, 1.0, work + w.f.PY, nb, 0, work + w.f.Kn, m, 0, 1.0, stats_c + mm, (int)(2 * E), 0, 1,
                                       stream);
-        case BP_KQ:
-            return svgp_se1d_kernel_matrix_fwd(s.nq, m, a.tq + s.q0, a.ip[c], a.ls[c], work + w.K2, work + w.Kq, work + w.kbb, stream);
-        case BP_ROWS: {
-            const svgp_posterior_rows_cfg rc_ = {s.nq, m, nb, -INFINITY, INFINITY};
-            return svgp_sprites_posterior_rows(&rc_, work + w.Kq, work + w.kbb, work + w.f.W, work + w.f.Mats, nullptr, work + w.tpm, work + w.tpv,
-                                               nullptr, work + w.rows, stream);
-        }
-        case BP_FINISH:
-            return bp_finish_launch(a, c, s.b0, nb, s.q0, s.nq, work + w.tpm, work + w.tpv, stream);
-        case BPJ_KQ:
-            return svgp_se1d_kernel_matrix_fwd(Q, m, a.tq, a.ip[c], a.ls[c], work + w.K2, work + w.Kq, work + w.kbb, stream);
-        case BPJ_G:         // G_l (Q, m) = k X_l, X_l in place in post
-            return svgp_dgemm_batched(0, 0, Q, m, m, 1.0, work + w.Kq, m, 0, post_c, m, 2 * E, 0.0, work + w.G, m, Qm, nb, stream);
-        case BPJ_GK:
-            return svgp_dgemm_batched(0, 1, Q, Q, m, 1.0, work + w.G, m, Qm, work + w.Kq, m, 0, 0.0, work + w.Cb, Q, QQ, nb, stream);
-        case BPJ_COV:
-            return bpj_cov_launch(ja, c, s.b0, nb, work + w.Cb, stream);
-        case BPJ_POTRF:
-            return svgp_potrf_batched_refined(Q, nb, work + w.Cb, Q, QQ, work + w.logdet, work + w.potrf, stream);
-        case BPJ_FINISH:
-            return bpj_finish_launch(ja, c, s.b0, nb, work + w.Kq, work + w.f.W, work + w.Cb, stream);
+        case BP_KQ: case BP_ROWS: case BP_FINISH:
+            return bp_tail_launch(a, s, w.t, work + w.f.Mats, work + w.f.W, work, stream);
+        case BPJ_KQ: case BPJ_G: case BPJ_GK: case BPJ_COV: case BPJ_POTRF: case BPJ_FINISH:      // X_l in place in post
+            return bpj_tail_launch(ja, s, w.j, post_c, 2 * E, work + w.f.W, work, stream);
         default:            // BP_SCALE, BP_PRIOR, BP_INVERSE, BP_W, BP_SUB as they are
             return bp_factor_launch(a, s, w.f, work, stream);
         }
@@ -490,14 +369,7 @@ extern "C" int svgp_ball_state_route(const svgp_ball_state_cfg* g, int op, char*
     buf[0] = 0;
     return bs_walk(g, op, [&](const BsStep& step) -> int {
         if (step.own != BSS_BP) return svgp_route_append(buf, cap, &pos, "%s\n", BSS_NAME[step.own]);
-        if (step.s.op == BP_ROWS) {  // the rows entry prints its own one or two kernels
-            const svgp_posterior_rows_cfg rc_ = {step.s.nq, g->m, step.s.nb, -INFINITY, INFINITY};
-            char sub[128];
-            int r = svgp_sprites_posterior_rows_route(&rc_, sub, (int)sizeof(sub));
-            if (r) return r;
-            return svgp_route_append(buf, cap, &pos, "%s", sub);
-        }
-        return svgp_route_append(buf, cap, &pos, "%s\n", BP_NAME[step.s.op]);
+        return bp_route_line(step.s, g->m, buf, cap, &pos);
     });
 }
 

@@ -184,6 +184,8 @@ def test_stats_against_the_restatement(case, large):
 
 @pytest.mark.parametrize("case,large", SC.ROUTES, ids=SC.ROUTE_IDS)
 def test_post_and_marginal_query_against_the_restatement_and_the_one_shot_entry(case, large):
+    """Against svgp_ball_predict the fused route is held to the bits: update, finalize and query run the device pieces k_ball_predict
+    is made of (bp_accumulate, bp_invert, bp_store_x, bp_query_chunks) on the same operands.  The large route keeps PATH_TOL."""
     prob, ref = SC.kernel_problem(case), dict(zip(("p_m", "p_v", "z"), SC.kernel_reference(case)))
     got, one = device_query(case, large), existing_marginal(case, large)
     bad = []
@@ -192,7 +194,7 @@ def test_post_and_marginal_query_against_the_restatement_and_the_one_shot_entry(
         print(f"{case} {'large' if large else 'fused'} {k}: restatement {e_r:.2e}, one-shot entry {e_o:.2e}")
         if not e_r <= SC.TOL:
             bad.append((k, "restatement", e_r))
-        if not e_o <= SC.PATH_TOL:
+        if not (e_o <= SC.PATH_TOL if large else np.array_equal(got[k], one[k])):
             bad.append((k, "one-shot", e_o))
     m = prob["ip"].shape[1]
     post = device_state(case, large)[1].numpy()
